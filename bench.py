@@ -16,12 +16,22 @@ torch.distributed.run on 127.0.0.1.  Two sharding modes (ofps_amd/
 `--ref-mode key`: every pair is searched against one shared key frame that rank 0 broadcasts to all ranks over RCCL
 inside the step (north_star's "RCCL broadcast of shared reference frames"); there is no other data-path collective.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps,
+writes the outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  Everything else it can
+measure or check runs only with `--full`, which adds to the line:
   roofline     -- algorithmic bytes per launch / average launch duration (HIP events on the launch stream) against
                   the 8 TB/s HBM peak, plus the packed-SAD VALU view of the same launch (the kernel is VALU-bound);
+  parity_check -- one searched pair per rank against the CPU oracle, bit for bit (a mismatch exits 3);
+  gather / D2H / pipeline timings of the strong-scaling and --pipeline steps;
   cpu_baseline -- the oracle's full search on the host cores, timed on a bounded sample of the same frames (rank 0,
                   N=1 only);
-  end_to_end   -- PCIe-inclusive rate of the Decoder::process_frame shape (N=1 only; never `value`).
+  end_to_end   -- PCIe-inclusive rate of the Decoder::process_frame shape (N=1 only; never `value`);
+  cfg3_chain / cfg4 / cfg5_stream -- the bounded legs of bench_legs.py (N=1 only).
+`--no-cpu-baseline`, `--no-end-to-end` and `--no-legs` leave parts of a `--full` run out.
+
+`--dump-outputs DIR` writes what rank 0's last timed step computed, the arrays a caller of the step receives, as
+DIR/<name>.npy in float32 / float64 (dump_outputs).  The inputs are seeded: the same arguments give the same inputs, so
+two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -65,11 +75,16 @@ def parse(argv=None):
     ap.add_argument("--block", type=int, default=16)
     ap.add_argument("--range", dest="search_range", type=int, default=16)
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline launch timing, oracle parity, gather / D2H / "
+                         "pipeline timings, and at N=1 the end-to-end leg, the bench_legs.py legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the bounded cfg3 / cfg4 / cfg5 legs (bench_legs.py) that a default N=1 run adds beside the line")
+                    help="skip the bounded cfg3 / cfg4 / cfg5 legs (bench_legs.py) that a --full N=1 run adds beside the line")
     ap.add_argument("--end-to-end-only", action="store_true",
                     help="internal: print only the end_to_end object (the main run starts this in a fresh process, whose HIP runtime "
                          "state is a decoder plugin's, not a training framework's)")
@@ -193,6 +208,41 @@ def time_steps(step, steps: int, warmup: int, sync, barrier) -> float:
 
 time_steps.gc_inside = None
 
+DUMP_LIMIT_BYTES = 60_000_000          # under the 64 MB the dump may take, with room for the sample indices
+
+
+def _as_float(a: np.ndarray) -> np.ndarray:
+    """float32 / float64 as they are; 64-bit integers (the wrapping checksums) as their two 32-bit halves in float64, every other
+    integer type as float64: exact either way."""
+    a = np.ascontiguousarray(a)
+    if a.dtype in (np.float32, np.float64):
+        return a
+    if a.dtype.itemsize == 8:
+        return a.view(np.uint32).reshape(a.shape + (2,)).astype(np.float64)
+    return a.astype(np.float64)
+
+
+def dump_outputs(path: str, outputs: dict) -> dict:
+    """Writes every array of `outputs` as path/<name>.npy (_as_float).  When they come to more than DUMP_LIMIT_BYTES, the
+    largest arrays keep a fixed sample of their rows (leading index; seeded, so every run and build keeps the same rows),
+    whose indices go to path/<name>_rows.npy.  -> {name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: _as_float(v) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for name in sorted(arrs, key=lambda k: -arrs[k].nbytes):
+        a = arrs[name]
+        if total <= DUMP_LIMIT_BYTES or a.ndim == 0 or len(a) < 2:
+            continue
+        row = a.nbytes // len(a)
+        keep = max(1, (a.nbytes - (total - DUMP_LIMIT_BYTES)) // (row + 8))
+        idx = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+        arrs[name] = a[idx]
+        arrs[name + "_rows"] = idx.astype(np.float64)
+        total += arrs[name].nbytes + idx.nbytes - a.nbytes
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
+
 
 # What each row of the hot path is pinned to (SURVEY.md 0, 8c): a reader of the line alone must not mistake "bit-exact vs the
 # oracle" on the headline kernel for parity with reference output -- the reference has no SAD search and no per-pixel flow.
@@ -207,16 +257,13 @@ PARITY_PIN = {"A6-A12 (camera + Almeida)": "reference-held mfield tables (docs/r
                                                 "integer for integer: bit-exact vs the build's C restatement and an independent NumPy one; unpinned (no OpenCV here)"}
 
 
-def build_line(args, world: int, el: float, launch_ms: float, launch_pairs: int, counts: list, nblk: int, ranks_seen: int,
+def build_line(args, world: int, el: float, launch_ms, launch_pairs: int, counts: list, nblk: int, ranks_seen: int,
                traffic_per_pair=None, traffic_stale=None) -> dict:
-    """The JSON line from measured times (pure function: tests/test_bench_contract.py feeds it synthetic timings)."""
+    """The JSON line from measured times (pure function: tests/test_bench_contract.py feeds it synthetic timings).
+    launch_ms None (a run without --full, which does not time single launches): no roofline object."""
     W, H, B, R, P = args.width, args.height, args.block, args.search_range, args.pairs
     total_pairs = sum(counts)
     ms_per_step = el / args.steps * 1e3
-    algo_bytes = launch_pairs * (2 * W * H + 16 * nblk)                 # SURVEY.md 8d, per pair x pairs in rank 0's launch
-    achieved = algo_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-    abs_diffs = launch_pairs * nblk * B * B * (2 * R + 1) ** 2
-    valu_peak = 256 * 4 * 2.4e9 * SAD_ABSDIFF_PER_CLK_PER_SIMD
     key = args.ref_mode == "key"
     geom = (W, H, B, R)
     out = {
@@ -246,24 +293,29 @@ def build_line(args, world: int, el: float, launch_ms: float, launch_pairs: int,
                    "kernel": (f"sad_strip_kernel<{B},{R}>" if args.sad_mode == "exhaustive"
                               else "sad_pde_kernel + sad_strip_kernel<16,16> on overflow strips"),
                    "sad_mode": args.sad_mode},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 5),
-                     "traffic": None if traffic_per_pair is None else traffic_per_pair * launch_pairs,
-                     "traffic_source": None if traffic_per_pair is None else "profiles/hbm_traffic.json (rocprofv3 --pmc passes of this command; not re-measured in this run)",
-                     "traffic_stale": None if traffic_per_pair is None else traffic_stale,
-                     "algorithmic_bytes_per_launch": algo_bytes, "launch_ms": round(launch_ms, 5), "pairs_per_launch": launch_pairs,
-                     "note": "full search is VALU-bound (SURVEY.md 8d): see 'valu'",
-                     "valu": {"abs_diffs_per_launch": abs_diffs,
-                              "achieved_Tops": round(abs_diffs / (launch_ms * 1e-3) / 1e12, 3) if launch_ms > 0 else 0.0,
-                              "peak_Tops": round(valu_peak / 1e12, 3),
-                              "frac": round(abs_diffs / (launch_ms * 1e-3) / valu_peak, 4) if launch_ms > 0 else 0.0,
-                              "peak_basis": "SAD unit: 64 |a-b| per clock per SIMD (v_qsad_pk_u16_u8 16 cyc, measured)"}},
     }
+    if launch_ms is not None:
+        algo_bytes = launch_pairs * (2 * W * H + 16 * nblk)             # SURVEY.md 8d, per pair x pairs in rank 0's launch
+        achieved = algo_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+        abs_diffs = launch_pairs * nblk * B * B * (2 * R + 1) ** 2
+        valu_peak = 256 * 4 * 2.4e9 * SAD_ABSDIFF_PER_CLK_PER_SIMD
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 5),
+                           "traffic": None if traffic_per_pair is None else traffic_per_pair * launch_pairs,
+                           "traffic_source": None if traffic_per_pair is None else "profiles/hbm_traffic.json (rocprofv3 --pmc passes of this command; not re-measured in this run)",
+                           "traffic_stale": None if traffic_per_pair is None else traffic_stale,
+                           "algorithmic_bytes_per_launch": algo_bytes, "launch_ms": round(launch_ms, 5), "pairs_per_launch": launch_pairs,
+                           "note": "full search is VALU-bound (SURVEY.md 8d): see 'valu'",
+                           "valu": {"abs_diffs_per_launch": abs_diffs,
+                                    "achieved_Tops": round(abs_diffs / (launch_ms * 1e-3) / 1e12, 3) if launch_ms > 0 else 0.0,
+                                    "peak_Tops": round(valu_peak / 1e12, 3),
+                                    "frac": round(abs_diffs / (launch_ms * 1e-3) / valu_peak, 4) if launch_ms > 0 else 0.0,
+                                    "peak_basis": "SAD unit: 64 |a-b| per clock per SIMD (v_qsad_pk_u16_u8 16 cyc, measured)"}}
     out["parity_pin"] = PARITY_PIN
     if getattr(args, "device_map", None) and len(set(args.device_map)) != len(args.device_map):
         out["rehearsal"] = (f"{world} ranks on devices {args.device_map} over gloo: real HIP steps, host-side collectives -- a plumbing "
                             "rehearsal of the N-GPU run on fewer GPUs, NOT a scaling measurement")
-    if args.sad_mode == "pruned":
+    if args.sad_mode == "pruned" and "roofline" in out:
         out["roofline"]["valu"]["note"] = ("exhaustive-equivalent rate: the pruned search returns the same winners but "
                                            "evaluates fewer |a-b|, so this fraction can exceed 1")
         out["roofline"]["traffic"] = None             # the committed PMC traffic figure belongs to the exhaustive kernel
@@ -600,8 +652,22 @@ def run_rank(args) -> int:
     el = D.max_over_ranks(el_local, device=dev)
     el_min = -D.max_over_ranks(-el_local, device=dev)
 
+    # ---- what the last timed step computed, as its caller receives it (rank 0's pairs; with strong scaling also the gathered tables)
+    if args.dump_outputs and rank == 0:
+        if args.stub:
+            outs = {"checksum": d_sum}
+        else:
+            outs = {"records": d_out[:count]}
+            if args.pipeline:
+                outs.update(detect=d_res[:count], block_field=d_field[:count], quat=d_quat[:count])
+        if args.scaling == "strong":
+            outs.update({"gathered_" + k: v for k, v in gathered.items()})
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()})
+
     # ---- per-launch duration of the dominant kernel with HIP events on the launch stream (roofline leg)
-    if args.stub:
+    if not args.full:
+        launch_ms = None
+    elif args.stub:
         launch_ms = el / args.steps * 1e3
     else:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -612,7 +678,7 @@ def run_rank(args) -> int:
 
     # ---- the gather alone (strong scaling): HIP events around K gathers, nothing else on the stream
     gather_ms = None
-    if args.scaling == "strong" and not args.stub and D.active() and world > 1:
+    if args.full and args.scaling == "strong" and not args.stub and D.active() and world > 1:
         local = pair_checksums(d_out[:count], ctx, d_chk)
         ga, gb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         D.gather_results(local, P)
@@ -629,7 +695,7 @@ def run_rank(args) -> int:
     # buffers in turn and the copy runs on a side stream behind an event, so the D2H of step k overlaps the search of step k+1;
     # a buffer is searched into again only after its previous copy finished.  Never `value` (the metric is device-resident).
     d2h_ms = None
-    if args.scaling == "strong" and not args.stub and count:
+    if args.full and args.scaling == "strong" and not args.stub and count:
         side = torch.cuda.Stream(device=dev)
         host = [torch.empty((count, nblk, 4), dtype=torch.float32).pin_memory() for _ in range(2)]
         outs = [d_out, torch.empty_like(d_out)]
@@ -662,7 +728,7 @@ def run_rank(args) -> int:
     out = None
     if rank == 0:
         out = build_line(args, world, el, launch_ms, count, counts, nblk, seen,
-                         *((None, None) if args.stub else committed_traffic_per_pair(W, H, B, R)))
+                         *((None, None) if args.stub or launch_ms is None else committed_traffic_per_pair(W, H, B, R)))
         out["launcher"] = (("torchrun (one process per GPU, RCCL)" if args.backend == "nccl" else
                             "torchrun (one process per rank, gloo: host-side collectives)") if D.active() else "single process")
         out["per_rank_ms_per_step"] = {"min": round(el_min / args.steps * 1e3, 4), "max": round(el / args.steps * 1e3, 4)}
@@ -678,7 +744,7 @@ def run_rank(args) -> int:
                                "Mvectors_per_s": round(sum(counts) * nblk * args.steps / (d2h_ms * 1e-3 * args.steps) / 1e6, 3),
                                "host_copy_equals_device_records": d2h_same}
 
-    if args.pipeline and not args.stub:
+    if args.full and args.pipeline and not args.stub:
         def full():
             kernel_only(); tail()
         for _ in range(2):
@@ -697,56 +763,58 @@ def run_rank(args) -> int:
     # ---- outside the timed region: parity.  Every rank checks one pair it searched against the CPU oracle (the oracle
     # is the checker here, never the thing measured); with strong scaling rank 0 also checks the gathered table: the
     # checksum of a pair searched by the LAST rank must equal the checksum of the oracle's records for that pair
-    ok = None
-    gather_ok = None
-    if args.stub:
-        ok = 1
-        if args.stub_parity:
-            v = args.stub_parity.split(",")[rank]
-            ok = None if v == "skip" else int(v)
-        if args.scaling == "strong":
-            base = 36 if key_mode else 0                     # sum(1..8): the key frame reached every rank
-            gather_ok = int(gathered["checksum"].tolist() == [k * 1000 + base for k in range(P)])
-    elif count:
-        try:
-            import oracle
+    mismatch = False
+    if args.full:
+        ok = None
+        gather_ok = None
+        if args.stub:
+            ok = 1
+            if args.stub_parity:
+                v = args.stub_parity.split(",")[rank]
+                ok = None if v == "skip" else int(v)
+            if args.scaling == "strong":
+                base = 36 if key_mode else 0                     # sum(1..8): the key frame reached every rank
+                gather_ok = int(gathered["checksum"].tolist() == [k * 1000 + base for k in range(P)])
+        elif count:
+            try:
+                import oracle
 
-            def host_pair(k):                                # global pair k -> (prev, cur) as the spec defines them
-                a = frames[walk[0]] if key_mode else frames[walk[k]]
-                return np.ascontiguousarray(a[:, :W]), np.ascontiguousarray(frames[walk[k + 1]][:, :W])
-            if key_mode and args.scaling == "weak" and rank != 0:
-                from ofps_amd import synth
-                key = synth.luma_sequence(1, W, H, seed=synth.SEED0, stride=stride,
-                                          **(dict(max_step=R) if args.content == "regions" else dict(max_step=min(R, 12), region=1 << 14, noise=1)))[0]
-            else:
-                key = None
-            kl = (3 * rank + 1) % count                          # a different local pair on every rank
-            prev, cur = host_pair(first + kl)
-            if key is not None:
-                prev = np.ascontiguousarray(key[:, :W])
-            ent_o, _ = oracle.sad_flow(prev, cur, B, R, threads=4)
-            ok = int((d_out[kl].cpu().numpy().view(np.uint32) == ent_o.view(np.uint32)).all())
-            if args.scaling == "strong" and rank == 0:
-                kg = P - 1                                       # searched by the last rank that holds pairs
-                ent_g, _ = oracle.sad_flow(*host_pair(kg), B, R, threads=4)
-                with np.errstate(over="ignore"):
-                    want = int(np.ascontiguousarray(ent_g).view(np.int64).sum(dtype=np.int64))   # wrapping, like the device sum
-                gather_ok = int(int(gathered["checksum"][kg].item()) == want)
-        except ImportError as e:                                 # no oracle on this machine: report "not checked"
-            print(f"[bench] parity check skipped on rank {rank}: {e}", file=sys.stderr)
-    # mismatches and skips are reduced separately: a rank that had nothing to check (no pairs, no oracle) must not hide
-    # another rank's mismatch
-    ok_min = D.min_over_ranks(1 if ok is None else ok, dev)                 # 0 = at least one rank saw a mismatch
-    skipped = world - int(round(D.sum_over_ranks(0 if ok is None else 1, dev)))
-    mismatch = ok_min == 0 or gather_ok == 0
-    if out is not None:
-        out["parity_check"] = {"what": "one searched pair per rank vs the CPU oracle, bit for bit", "ranks": world,
-                               "ranks_checked": world - skipped, "ranks_skipped": skipped,
-                               "ok": False if ok_min == 0 else (True if skipped < world else None)}
-        if args.scaling == "strong":
-            out["parity_check"]["gathered_checksum_of_last_pair_matches_oracle"] = None if gather_ok is None else bool(gather_ok)
+                def host_pair(k):                                # global pair k -> (prev, cur) as the spec defines them
+                    a = frames[walk[0]] if key_mode else frames[walk[k]]
+                    return np.ascontiguousarray(a[:, :W]), np.ascontiguousarray(frames[walk[k + 1]][:, :W])
+                if key_mode and args.scaling == "weak" and rank != 0:
+                    from ofps_amd import synth
+                    key = synth.luma_sequence(1, W, H, seed=synth.SEED0, stride=stride,
+                                              **(dict(max_step=R) if args.content == "regions" else dict(max_step=min(R, 12), region=1 << 14, noise=1)))[0]
+                else:
+                    key = None
+                kl = (3 * rank + 1) % count                          # a different local pair on every rank
+                prev, cur = host_pair(first + kl)
+                if key is not None:
+                    prev = np.ascontiguousarray(key[:, :W])
+                ent_o, _ = oracle.sad_flow(prev, cur, B, R, threads=4)
+                ok = int((d_out[kl].cpu().numpy().view(np.uint32) == ent_o.view(np.uint32)).all())
+                if args.scaling == "strong" and rank == 0:
+                    kg = P - 1                                       # searched by the last rank that holds pairs
+                    ent_g, _ = oracle.sad_flow(*host_pair(kg), B, R, threads=4)
+                    with np.errstate(over="ignore"):
+                        want = int(np.ascontiguousarray(ent_g).view(np.int64).sum(dtype=np.int64))   # wrapping, like the device sum
+                    gather_ok = int(int(gathered["checksum"][kg].item()) == want)
+            except ImportError as e:                                 # no oracle on this machine: report "not checked"
+                print(f"[bench] parity check skipped on rank {rank}: {e}", file=sys.stderr)
+        # mismatches and skips are reduced separately: a rank that had nothing to check (no pairs, no oracle) must not hide
+        # another rank's mismatch
+        ok_min = D.min_over_ranks(1 if ok is None else ok, dev)                 # 0 = at least one rank saw a mismatch
+        skipped = world - int(round(D.sum_over_ranks(0 if ok is None else 1, dev)))
+        mismatch = ok_min == 0 or gather_ok == 0
+        if out is not None:
+            out["parity_check"] = {"what": "one searched pair per rank vs the CPU oracle, bit for bit", "ranks": world,
+                                   "ranks_checked": world - skipped, "ranks_skipped": skipped,
+                                   "ok": False if ok_min == 0 else (True if skipped < world else None)}
+            if args.scaling == "strong":
+                out["parity_check"]["gathered_checksum_of_last_pair_matches_oracle"] = None if gather_ok is None else bool(gather_ok)
 
-    if rank == 0 and world == 1 and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.stub:
         if not args.no_end_to_end:
             import subprocess
             try:
@@ -817,18 +885,24 @@ def run_threads(args) -> int:
         t0 = time.perf_counter()
         md.run_resident(B, R, args.steps)
         el = time.perf_counter() - t0
-        ms = md.run_resident(B, R, args.steps, timed=True)              # per-worker HIP events (roofline leg)
-        got = md.fetch(B)
+        got = md.fetch(B) if args.full or args.dump_outputs else None      # every worker's records of the last timed step
+        ms = md.run_resident(B, R, args.steps, timed=True) if args.full else None      # per-worker HIP events (roofline leg)
     finally:
         md.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"records": got})
     counts = [MultiDevice.pair_range(total, N, k)[1] for k in range(N)]
     args_line = argparse.Namespace(**vars(args))
     args_line.pairs = total if args.scaling == "strong" else P
-    out = build_line(args_line, N, el, float(ms[0]) / args.steps, counts[0], counts, nblk, N, *committed_traffic_per_pair(W, H, B, R))
+    out = build_line(args_line, N, el, None if ms is None else float(ms[0]) / args.steps, counts[0], counts, nblk, N,
+                     *((None, None) if ms is None else committed_traffic_per_pair(W, H, B, R)))
     out["launcher"] = "threads (one process, ofps_hip_multi_*: one worker thread + context per GPU, no collective)"
     if len(set(devices)) != len(devices):
         out["rehearsal"] = (f"{N} workers on devices {devices}: real HIP steps through the in-process dispatcher, several workers per GPU -- "
                             "a plumbing rehearsal of the N-GPU run on fewer GPUs, NOT a scaling measurement")
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return 0
     out["per_rank_ms_per_step"] = {"min": round(float(ms[ms > 0].min()) / args.steps, 4) if (ms > 0).any() else 0.0,
                                    "max": round(float(ms.max()) / args.steps, 4), "what": "HIP events per worker"}
     # ---- PCIe-inclusive stream form through the same dispatcher (ofps_hip_multi_push_frames_async: batches of 16 frames dealt to

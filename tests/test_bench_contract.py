@@ -101,3 +101,35 @@ def test_traffic_is_flagged_stale_when_the_kernel_source_changed(tmp_path, monke
     assert bench.committed_traffic_per_pair(1920, 1080, 16, 16)[1] is True
     _, line = _line([], 1, 1.0, 1.0, [256])
     assert "traffic_stale" in line["roofline"]
+
+
+def test_plain_line_keeps_the_headline_fields_without_the_full_runs_objects():
+    """Without --full nothing times single launches: the line has the same headline fields, no roofline."""
+    args = bench.parse(["--steps", "7"])
+    assert args.full is False and args.dump_outputs is None and bench.parse(["--full"]).full is True
+    d = json.loads(json.dumps(bench.build_line(args, 1, 7 * 4.1e-3, None, 256, [256], 8040, 1)))
+    assert abs(d["value"] - 256 * 8040 / 4.1e-3 / 1e6) < 1e-2 and abs(d["ms_per_step"] - 4.1) < 1e-9 and d["steps"] == 7
+    assert d["unit"] == "Mvectors/s" and d["higher_is_better"] is True and d["dtype"] == "u8" and d["metric"].startswith("Mvectors/s")
+    assert "roofline" not in d
+
+
+def test_dump_outputs_writes_exact_floats_and_a_seeded_sample_of_large_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    rec = rng.standard_normal((40, 100, 4)).astype(np.float32)
+    chk = rng.integers(-2**63, 2**63 - 1, size=40, dtype=np.int64)
+    det = rng.integers(-5, 1000, size=(40, 4)).astype(np.int32)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"records": rec, "checksum": chk, "detect": det})
+    assert shapes == {"records": [40, 100, 4], "checksum": [40, 2], "detect": [40, 4]}
+    r = np.load(tmp_path / "a" / "records.npy"); c = np.load(tmp_path / "a" / "checksum.npy"); t = np.load(tmp_path / "a" / "detect.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, rec)
+    assert c.dtype == np.float64 and np.array_equal(c.astype(np.uint32).view(np.int64).reshape(-1), chk)     # both halves, exact
+    assert t.dtype == np.float64 and np.array_equal(t, det)
+    # over the limit: the largest array keeps a fixed sample of its rows, listed beside it; the same rows every time
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", rec.nbytes // 2)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), {"records": rec, "detect": det})
+    rows = np.load(tmp_path / "b" / "records_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "records_rows.npy")) and 0 < len(rows) < 40
+    assert np.array_equal(np.load(tmp_path / "b" / "records.npy"), rec[rows])
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b")) <= rec.nbytes // 2

@@ -59,7 +59,7 @@ def test_time_steps_runs_exactly_w_plus_k_steps_inside_the_brackets():
 
 
 def test_gpus_2_self_launches_two_ranks_strong():
-    p, d = _run("--gpus", "2", "--stub", "--scaling", "strong", "--pairs", "5", "--steps", "2", "--warmup", "1")
+    p, d = _run("--gpus", "2", "--stub", "--scaling", "strong", "--pairs", "5", "--steps", "2", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["scaling"] == "strong" and d["data"] == "stub"
     assert d["config"]["pairs_per_rank"] == [3, 2] and d["config"]["pairs_per_step"] == 5
@@ -67,7 +67,7 @@ def test_gpus_2_self_launches_two_ranks_strong():
 
 
 def test_gpus_2_key_frame_broadcast_reaches_every_rank():
-    p, d = _run("--gpus", "2", "--stub", "--scaling", "strong", "--pairs", "4", "--ref-mode", "key", "--steps", "1", "--warmup", "1")
+    p, d = _run("--gpus", "2", "--stub", "--scaling", "strong", "--pairs", "4", "--ref-mode", "key", "--steps", "1", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     # the stubbed step folds the key frame's bytes into every pair's checksum: true only if the broadcast delivered them
     assert d["parity_check"]["gathered_checksum_of_last_pair_matches_oracle"] is True and d["ranks_seen"] == 2
@@ -83,12 +83,12 @@ def test_gpus_2_weak_reports_whole_job_pairs():
 def test_a_skipping_rank_cannot_hide_another_ranks_mismatch_and_a_mismatch_fails_the_run():
     """Mismatches and skips are reduced separately; any mismatch makes the process exit non-zero (a driver that looks
     only at the return code and `value` must not accept wrong vectors)."""
-    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,0")
+    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,0", "--full")
     assert p.returncode != 0 and "PARITY MISMATCH" in p.stderr
     assert d["parity_check"]["ok"] is False and d["parity_check"]["ranks_skipped"] == 1 and d["parity_check"]["ranks_checked"] == 1
-    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,1")
+    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,1", "--full")
     assert p.returncode == 0 and d["parity_check"]["ok"] is True and d["parity_check"]["ranks_skipped"] == 1
-    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,skip")
+    p, d = _run("--gpus", "2", "--stub", "--pairs", "4", "--steps", "1", "--warmup", "0", "--stub-parity", "skip,skip", "--full")
     assert p.returncode == 0 and d["parity_check"]["ok"] is None and d["parity_check"]["ranks_skipped"] == 2
 
 
@@ -188,3 +188,15 @@ def test_quiet_gc_counts_what_still_runs_and_restores_the_collector():
     assert s["collections"] >= 1 and s["oldest_generation"] is not None
     assert gc.get_freeze_count() == 0 and q._cb not in gc.callbacks
     assert median_min_max([3.0, 1.0, 2.0, 10.0, 2.5]) == {"median": 2.5, "min": 1.0, "max": 10.0, "repeats": 5}
+
+
+def test_plain_run_times_exactly_the_steps_asked_for_and_dumps_the_last_steps_outputs(tmp_path):
+    """A run without --full: the line carries no parity or roofline object; --dump-outputs writes what the last timed step
+    computed (the stub's per-pair table), the same on every run."""
+    for sub in ("a", "b"):
+        p, d = _run("--stub", "--pairs", "6", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / sub))
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["ms_per_step"] >= 0 and "parity_check" not in d and "roofline" not in d
+    a = np.load(tmp_path / "a" / "checksum.npy")
+    assert a.dtype == np.float64 and a.shape == (6, 2) and np.array_equal(a, np.load(tmp_path / "b" / "checksum.npy"))
+    assert np.array_equal(a.astype(np.uint32).view(np.int64).reshape(-1), np.arange(6) * 1000)

@@ -18,7 +18,7 @@ def _run(*argv, timeout=900):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE"):
         e.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv, "--no-cpu-baseline", "--no-end-to-end", "--no-legs"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv, "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-legs"],
                        capture_output=True, text=True, timeout=timeout, env=e)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p, (json.loads(lines[-1]) if lines else None)
@@ -110,7 +110,7 @@ def test_eight_worker_threads_on_one_gpu_resident_batch_and_the_stream_dispatche
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE"):
         e.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--launcher", "threads", "--device-map", "0,0,0,0,0,0,0,0",
-                        "--config", "cfg4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-legs"],
+                        "--config", "cfg4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-legs"],
                        capture_output=True, text=True, timeout=1500, env=e)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -134,7 +134,7 @@ def test_rccl_process_group_of_one_rank_initialises_and_runs_the_collectives():
     from ofps_amd.distributed import free_port
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                         "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--config", "cfg4",
-                        "--pairs", "4", "--gen-pairs", "2", "--ref-mode", "key", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--pairs", "4", "--gen-pairs", "2", "--ref-mode", "key", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-end-to-end", "--no-legs"], capture_output=True, text=True, timeout=900, env=e)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -10,18 +10,18 @@ bash tools/prof_counters.sh r04p/sad_strip_cfg4 --config cfg4 --steps 10 > /dev/
 mkdir -p profiles/r04
 for p in sad_strip sad_strip_cfg4; do python tools/pack_profile.py $O/$p profiles/r04/$p; done
 python tools/make_hbm_traffic.py > /dev/null && cp profiles/hbm_traffic.json $O/hbm_traffic.json
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 > $O/bench_cfg4_strong_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 --pairs 8 > $O/bench_cfg4_strong_8pairs_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-legs --launcher threads > $O/bench_threads_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --launcher threads --config cfg4 > $O/bench_threads_cfg4_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --pipeline > $O/bench_pipeline_n1.json 2>/dev/null
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/bench_torchrun_world1.json
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 > $O/bench_cfg4_strong_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 --pairs 8 > $O/bench_cfg4_strong_8pairs_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-legs --launcher threads > $O/bench_threads_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --launcher threads --config cfg4 > $O/bench_threads_cfg4_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --pipeline > $O/bench_pipeline_n1.json 2>/dev/null
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/bench_torchrun_world1.json
 # the N-rank run rehearsed on this one GPU: two and four ranks, real HIP steps, gloo collectives through host tensors
-python bench.py --gpus 2 --backend gloo --device-map 0,0 --config cfg4 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_cfg4_strong.json
-python bench.py --gpus 4 --backend gloo --device-map 0,0,0,0 --config cfg4 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_4ranks_cfg4_strong.json
-python bench.py --gpus 2 --backend gloo --device-map 0,0 --scaling strong --pairs 64 --ref-mode key --pipeline --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_key_pipeline.json
-python bench.py --gpus 2 --backend gloo --device-map 0,0 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_weak.json
+python bench.py --full --gpus 2 --backend gloo --device-map 0,0 --config cfg4 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_cfg4_strong.json
+python bench.py --full --gpus 4 --backend gloo --device-map 0,0,0,0 --config cfg4 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_4ranks_cfg4_strong.json
+python bench.py --full --gpus 2 --backend gloo --device-map 0,0 --scaling strong --pairs 64 --ref-mode key --pipeline --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_key_pipeline.json
+python bench.py --full --gpus 2 --backend gloo --device-map 0,0 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | tail -n 1 > $O/rehearsal_2ranks_weak.json
 bash tools/cfg3_profile.sh r04p/cfg3_chain 20 3 > /dev/null 2>&1
 bash tools/cfg3_profile.sh r04p/cfg3_chain_pm16 20 16 > /dev/null 2>&1
 python tools/cfg3_time.py > $O/cfg3_chain/stage_times.json 2>/dev/null

@@ -10,11 +10,11 @@ bash tools/prof_counters.sh r06p/sad_strip_cfg4 --config cfg4 --steps 10 > /dev/
 mkdir -p profiles/r06
 for p in sad_strip sad_strip_cfg4; do python tools/pack_profile.py $O/$p profiles/r06/$p; done
 python tools/make_hbm_traffic.py > /dev/null && cp profiles/hbm_traffic.json $O/hbm_traffic.json
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 python tools/perf_gate.py $O/bench_n1.json > $O/perf_gate.txt 2>&1
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 > $O/bench_cfg4_strong_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-legs --launcher threads > $O/bench_threads_n1.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-end-to-end --no-legs --pipeline > $O/bench_pipeline_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --config cfg4 > $O/bench_cfg4_strong_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-legs --launcher threads > $O/bench_threads_n1.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-end-to-end --no-legs --pipeline > $O/bench_pipeline_n1.json 2>/dev/null
 bash tools/cfg3_profile.sh r06p/cfg3_chain 20 3 > /dev/null 2>&1
 bash tools/cfg3_profile.sh r06p/cfg3_chain_pm16 20 16 > /dev/null 2>&1
 python tools/cfg3_time.py > $O/cfg3_chain/stage_times.json 2>/dev/null

@@ -6,7 +6,7 @@ once per round, when the round starts -- never to a line of the round that is be
 inside one run.
 
   python tools/perf_gate.py <bench_line.json> [--baseline profiles/r05/bench_n1.json] [--tolerance 0.05]
-  python tools/perf_gate.py --run                      runs `python bench.py` itself (N = 1, a few minutes)
+  python tools/perf_gate.py --run                      runs `python bench.py --full` itself (N = 1, a few minutes)
 
 Checks (each prints PASS / FAIL with both numbers; exit code 1 on any FAIL):
   against the baseline, slower-only, 5 %:  headline Mvectors/s, cfg4 Mvectors/s, Farneback ms, the
@@ -145,7 +145,7 @@ def main():
     ap.add_argument("--save", help="write the line that was gated here")
     args = ap.parse_args()
     if args.run:
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")], capture_output=True, text=True, timeout=1500)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"], capture_output=True, text=True, timeout=1500)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
         if p.returncode != 0 or not lines:
             print(p.stdout[-2000:], p.stderr[-2000:], file=sys.stderr)

@@ -10,7 +10,7 @@ for v in 0 1 2; do
     cp build/ab/colkeys$v/libofps_hip.so ofps_amd/libofps_hip.so
     python -m pytest tests/test_gpu_parity.py tests/test_golden.py tests/test_gpu_properties.py -m gpu -q -k "sad or golden or SAD" 2>&1 | tail -2 > $OUT/parity_$v.txt
     for rep in 1 2 3; do python bench_legs.py cfg4 2>/dev/null | tail -1 >> $OUT/cfg4_$v.jsonl; done
-    for rep in 1 2; do python bench.py --no-legs --no-end-to-end --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/cfg2_$v.jsonl; done
+    for rep in 1 2; do python bench.py --full --no-legs --no-end-to-end --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/cfg2_$v.jsonl; done
     (cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY \
         --output-format csv -d $OUT/pmc1_$v -o k -- python $GRAFT_REPO_ROOT/bench_legs.py cfg4 > $OUT/pmc1_$v.txt 2>&1
      rocprofv3 --pmc SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE \
