@@ -104,9 +104,30 @@ int ofps_hip_set_sad_mode(ofps_hip_ctx* ctx, int mode);
 /* Diagnostics: how many strips of the last PRUNED call overflowed their survivor lists and were redone by the
  * exhaustive kernel (synchronises the stream). */
 int ofps_hip_sad_pruned_overflow_strips(ofps_hip_ctx* ctx, uint32_t* count);
+/* ---- N1q: quarter-pel vectors (AVMotionVector.motion_scale = 4, H.264's; av-decoder/src/lib.rs:412-417 divides by it) ----
+ * scale 1 (the default): the full-pel vectors above, byte for byte.  scale 4: every ofps_hip_sad_flow* call and every
+ * ofps_hip_push_frame* search is followed by a refinement launch around each block's integer winner (dx,dy), unchanged:
+ *   candidates D = (4*dx + fx, 4*dy + fy), fx, fy in [-3,3], in quarter-pel units; valid when every sample position of
+ *   the block lies inside the frame: 0 <= 4*x0 + Dx and 4*(x0 + B - 1) + Dx <= 4*(W - 1), the same in y (f = 0 always is);
+ *   cost = sum |cur - ref_q| over the block, ref_q = the previous frame at quarter-pel positions by H.264's luma
+ *   interpolation (ITU-T H.264 8.4.2.2.1), taps outside the frame edge-replicated:
+ *     half-pel in one direction: b1 = E - 5F + 20G + 20H - 5I + J over the six nearest integer samples of the row (the
+ *       column for h1), b = clip255((b1 + 16) >> 5); half-pel in both: j1 = the same taps over the unrounded b1 of six
+ *       rows, j = clip255((j1 + 512) >> 10);
+ *     quarter-pel: (p + q + 1) >> 1 of two samples of the half-pel grid (integer samples included): fx odd, fy even: the
+ *       left and right neighbours; fx even, fy odd: the upper and lower; both odd: of the four surrounding half-grid
+ *       points the two that are half-pel in exactly one direction (H.264's e, g, p, r);
+ *   winner = min of (SAD, Dx*Dx + Dy*Dy, Dy + 4*range + 3, Dx + 4*range + 3), lexicographic (a flat block keeps D = 4*d);
+ *   entry: pos.x = ((float)(4*cx + Dx) * 0.25f) * nx, motion.x = ((float)Dx / 4.0f) * (-nx), cx = x0 + B/2,
+ *   nx = 1.0f / (float)W; y alike.  out_best holds (Dx, Dy, SAD) in quarter-pel units while the scale is 4.
+ * Build-defined like N1 (no encoder's search is anybody's contract: parity with FFmpeg's vectors is unpinned by
+ * construction); all-integer, bit-exact against the NumPy restatement tests/indep_sad_qpel.py.  Any scale other than
+ * 1 or 4 is OFPS_HIP_EINVAL.  The option OFPS_HIP_SAD_MOTION_SCALE (environment / ofps_hip_set_option) sets the same field. */
+int ofps_hip_set_sad_motion_scale(ofps_hip_ctx* ctx, int scale);
+int ofps_hip_get_sad_motion_scale(ofps_hip_ctx* ctx);
 int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur,
                       int W, int H, int stride, int block, int range,
-                      float* out_entries /* 4*nblk */, int32_t* out_best /* 3*nblk (dx,dy,sad) or NULL */,
+                      float* out_entries /* 4*nblk */, int32_t* out_best /* 3*nblk (dx,dy,sad); with motion scale 4: (Dx,Dy,SAD) in quarter-pel units; or NULL */,
                       size_t* n_out);
 /* Batched, device-resident: n_frames luma frames at d_frames + k*frame_pitch (bytes).
  * ref_mode 0: pairs (k, k+1); ref_mode 1: pairs (0, k+1) (shared key frame).  n_frames-1 pairs.

@@ -36,6 +36,7 @@ struct ofps_hip_ctx {
         int lk_prof = 0;                 // OFPS_HIP_LK_PROF
         int fb_prepare_ahead = 1;        // OFPS_HIP_FB_PREPARE_AHEAD: a hip_flow stream's new frame is expanded on the upload's stream when it is pushed (0: inside the pair's flow, round 5's order)
         int lk_serial = 0;               // OFPS_HIP_LK_SERIAL: one launch per pyramid level instead of one for the pyramid
+        int sad_motion_scale = 1;        // OFPS_HIP_SAD_MOTION_SCALE / ofps_hip_set_sad_motion_scale: 1 full-pel vectors, 4 quarter-pel refinement (sad_qpel.hip)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -156,6 +157,7 @@ enum ScratchSlot {
     S_FB_FLOW,              // hip_flow streams with OFPS_HIP_FLOW_USE_PREVIOUS: the last pair's flow (the next pair's initial flow)
     S_XMAJOR,               // densify.hip, raster producers: the field + visited flag in (x, y)-sorted cell order (the record order)
     S_LK_MASKS,             // dense decoders, stream forms: one contrast mask per ticket in flight (made on the upload's stream, beside the previous pair's flow)
+    S_SAD_QBEST,            // sad_qpel.hip: the integer winners when the caller of a quarter-pel search passes no out_best
     S_FE_RAW,               // frontend.hip: the frames as they arrive (colour and / or full size) when the decoder resizes / converts them: one per ticket in flight
     S_FE_RAW_PAIR           // ... of the stateless calls (ofps_hip_lk_decode, ofps_hip_cv_frontend, ofps_hip_resize_linear): never the stream's staging, whose
                             // upload + front-end may still be running on the upload stream when such a call comes in
@@ -183,6 +185,9 @@ void* scratch(ofps_hip_ctx* ctx, int slot, size_t bytes);
 int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
                      size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
                      void* d_out_best);
+int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
+                           int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
+                           void* d_out_best);
 int densify_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
                    uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end);
 int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,

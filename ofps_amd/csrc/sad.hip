@@ -1106,6 +1106,12 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
     OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // motion scale 4: the refinement (sad_qpel.hip) starts from the integer winners, so they are kept even when the caller wants none
+    const bool qpel = ctx->opt.sad_motion_scale == 4;
+    if (qpel && !p.out_best) {
+        p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
+        if (!p.out_best) return OFPS_HIP_ENOMEM;
+    }
     hipStream_t s = ctx->stream;
     const int key = block * 1000 + range;
     const bool force_block = ctx->opt.sad_force_block != 0;     // OFPS_HIP_SAD_KERNEL=block (A/B profiling)
@@ -1152,6 +1158,9 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
         }
     }
     OFPS_HIP_TRY(ctx, hipGetLastError());
+    if (qpel)
+        return ofps::sad_qpel_refine_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block, range, d_out_entries,
+                                            p.out_best, d_out_best);
     return OFPS_HIP_OK;
 }
 }  // namespace ofps

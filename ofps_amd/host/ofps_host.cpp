@@ -140,6 +140,7 @@ bool HipSadDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_f
     prm.range = (int)range_;
     ofps_hip_frame_result res{};
     ctx_.check(ofps_hip_set_sad_mode(ctx_.get(), pruned_ ? OFPS_HIP_SAD_PRUNED : OFPS_HIP_SAD_EXHAUSTIVE));
+    ctx_.check(ofps_hip_set_sad_motion_scale(ctx_.get(), quarter_pel_ ? 4 : 1));
     ctx_.check(ofps_hip_push_frame(ctx_.get(), frame_, (int)w_, (int)h_, (int)w_, &prm, &res, out_.data(), nullptr));
     if (!res.have_vectors) return false;                              // first frame: no pair yet
     const size_t base = field.size();
@@ -150,7 +151,8 @@ bool HipSadDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_f
 
 std::vector<std::pair<std::string, PropertyMut>> HipSadDecoder::props_mut() {
     return {{"Block size", PropertyMut::usize(&block_, 8, 16)}, {"Search range", PropertyMut::usize(&range_, 8, 32)},
-            {"Exact pruning", PropertyMut::boolean(&pruned_)}};       // same vectors; faster on smooth camera motion
+            {"Exact pruning", PropertyMut::boolean(&pruned_)},        // same vectors; faster on smooth camera motion
+            {"Quarter pel", PropertyMut::boolean(&quarter_pel_)}};    // motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
 }
 
 // ------------------------------------------------------------------ hip_lk

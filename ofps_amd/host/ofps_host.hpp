@@ -150,6 +150,7 @@ private:
     std::unique_ptr<std::istream> in_;
     size_t w_, h_, block_ = 16, range_ = 16;
     bool pruned_ = false;                  // OFPS_HIP_SAD_PRUNED: identical vectors, content-dependent run time
+    bool quarter_pel_ = false;             // ofps_hip_set_sad_motion_scale(4): quarter-pel refinement of every block vector
     std::optional<double> fps_;
     uint8_t* frame_ = nullptr;             // page-locked staging buffer for the frame being read
     std::vector<float> out_;

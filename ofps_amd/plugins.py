@@ -69,13 +69,15 @@ class HipSadDecoder(Properties):
     """Decoder (ofps/src/decoder.rs:45-73) over an iterator / raw stream of luma frames: full-search SAD
     block vectors in av-decoder's record convention (av-decoder/src/lib.rs:404-419)."""
     _PROPS = (("Block size", "usize", "block", 8, 16), ("Search range", "usize", "range", 8, 32),
-              ("Exact pruning", "bool", "pruned", None, None))      # same vectors; faster on smooth camera motion (16x16, +-16)
+              ("Exact pruning", "bool", "pruned", None, None),      # same vectors; faster on smooth camera motion (16x16, +-16)
+              ("Quarter pel", "bool", "quarter_pel", None, None))   # motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
 
     def __init__(self, frames: Iterable[np.ndarray], framerate: Optional[float] = None, device: int = 0):
         self.ctx = HipContext(device)
         self._it: Iterator[np.ndarray] = iter(frames)
         self.block, self.range = 16, 16
         self.pruned = False
+        self.quarter_pel = False
         self._prev: Optional[np.ndarray] = None
         self._cur: Optional[np.ndarray] = None
         self._fps = framerate
@@ -112,6 +114,7 @@ class HipSadDecoder(Properties):
         if out_frame is not None:
             out_frame[:] = [self._cur.copy()]
         self.ctx.set_sad_mode(self.ctx.SAD_PRUNED if self.pruned else self.ctx.SAD_EXHAUSTIVE)
+        self.ctx.set_sad_motion_scale(4 if self.quarter_pel else 1)
         r = self.ctx.push_frame(self._cur, self.block, self.range, detector=False, estimator=False, want_entries=True)
         if not r["have_vectors"]:                          # first frame of the stream / geometry change
             return False

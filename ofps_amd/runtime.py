@@ -107,6 +107,13 @@ class HipContext:
         """0 = exhaustive (default), 1 = exact search with partial-distortion elimination (content-dependent run time)."""
         self._check(self._lib.ofps_hip_set_sad_mode(self._h, mode))
 
+    def set_sad_motion_scale(self, scale: int):
+        """1 = full-pel vectors (default); 4 = quarter-pel refinement of every block's integer winner (H.264's motion_scale)."""
+        self._check(self._lib.ofps_hip_set_sad_motion_scale(self._h, scale))
+
+    def get_sad_motion_scale(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_motion_scale(self._h))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))

@@ -11,6 +11,7 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
   decoders    hip_sad (16x16 blocks, +-16)  |  hip_lk (3-level pyramid, r = 4, 3 steps, contrast mask, 150 x 84 records)  |  hip_lk5 (the same
               with "Pyramid levels" = 5, the reference's Farneback depth)  |  hip_flow (Farneback's polynomial-expansion flow with
               cv-decoder's own arguments: levels 5, winsize 13, 3 iterations, poly_n 7, poly_sigma 1.5; same mask and records)
+              with --quarter-pel also hip_sad_q: hip_sad with its "Quarter pel" property on (motion scale 4, include/ofps_hip.h N1q)
   estimators  hip_almeida LSQ  |  hip_almeida RANSAC (the reference's default: 200 hypotheses x 1000 samples, 0.05 degree inliers)
 Per clip and combination: mean and max of angle_to(planted q_k, estimated r_k) over the frames, that mean relative to the clip's mean
 rotation per frame (the reference's own test bound is 10 %: almeida-estimator/src/lib.rs:347-348), and the pose drift after the
@@ -113,7 +114,7 @@ def stats(est, truth):
             "drift_deg": synth.quat_angle_deg(accumulate(est), accumulate(truth))}
 
 
-def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print):
+def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -122,6 +123,8 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print):
               ("hip_lk5", HipLkDecoder, False, {"Pyramid levels": 5}), ("hip_lk5", HipLkDecoder, True, {"Pyramid levels": 5}),
               # Farneback's flow itself with cv-decoder's arguments (the hip_flow decoder)
               ("hip_flow", HipFlowDecoder, False, {}), ("hip_flow", HipFlowDecoder, True, {})]
+    if quarter_pel:     # hip_sad with its "Quarter pel" property on (motion_scale 4: include/ofps_hip.h N1q); off by default: the -m gpu test's run time
+        combos[2:2] = [("hip_sad_q", HipSadDecoder, False, {"Quarter pel": True}), ("hip_sad_q", HipSadDecoder, True, {"Quarter pel": True})]
     res = {}
     for name, (W, H, fov, eul, dis) in clip_table(quick).items():
         if only and name not in only:
@@ -162,6 +165,8 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print):
 def table(res):
     cols = ["hip_sad+lsq", "hip_sad+ransac", "hip_lk+lsq", "hip_lk+ransac", "hip_lk5+lsq", "hip_lk5+ransac", "hip_flow+lsq", "hip_flow+ransac",
             "cpu_oracle:sad+lsq"]
+    if any("hip_sad_q+lsq" in r for r in res.values()):
+        cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
     lines = []
     lines.append("mean rotation error per frame, degrees (docs/statistics/err_av.csv's unit); clip rows, decoder+estimator columns")
     lines.append("clip,geometry,mean_rot_deg_per_frame,px_per_deg," + ",".join(cols))
@@ -201,8 +206,9 @@ def main():
     ap.add_argument("--oracle-lk-pairs", type=int, default=3)
     ap.add_argument("--no-oracle", action="store_true")
     ap.add_argument("--only", nargs="*")
+    ap.add_argument("--quarter-pel", action="store_true", help="add the hip_sad_q columns: hip_sad with \"Quarter pel\" on")
     args = ap.parse_args()
-    res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True))
+    res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel)
     txt = table(res)
     print(txt)
     if args.out:
