@@ -86,6 +86,50 @@ def refine(prev, cur, B, R, best_int, W=None):
     return entries(best, B, W, H), best
 
 
+def candidate_is_valid(x0, y0, B, W, H, Dx, Dy):
+    """every sample of the block displaced by (Dx, Dy) quarter pels lies inside the frame"""
+    return 4 * x0 + Dx >= 0 and 4 * (x0 + B - 1) + Dx <= 4 * (W - 1) and 4 * y0 + Dy >= 0 and 4 * (y0 + B - 1) + Dy <= 4 * (H - 1)
+
+
+def refine_by_tuples(prev, cur, B, R, best_int, W=None):
+    """refine() once more, slowly and without the packed 64-bit key: per block Python's min over the tuples
+    (SAD, Dx*Dx + Dy*Dy, Dy, Dx) of the valid candidates (Python integers: no field can run into its neighbour).
+    The 49 SADs of every block are gathered from quarter_plane(); nothing else is shared with refine().
+    -> (entries, best, n_valid [nblk]: how many of the 49 candidates passed the validity rule)"""
+    prev = np.asarray(prev, np.uint8); cur = np.asarray(cur, np.uint8)
+    H = prev.shape[0]
+    W = prev.shape[1] if W is None else W
+    prev = prev[:, :W]; cur = cur[:, :W]
+    nbx, nby = W // B, H // B
+    n = nbx * nby
+    if n == 0:
+        return np.zeros((0, 4), np.float32), np.zeros((0, 3), np.int32), np.zeros(0, np.int32)
+    q = quarter_plane(prev)
+    d = np.asarray(best_int, np.int64).reshape(n, 3)
+    x0 = (np.arange(n) % nbx) * B
+    y0 = (np.arange(n) // nbx) * B
+    cblk = cur[(y0[:, None, None] + np.arange(B)[None, :, None]), (x0[:, None, None] + np.arange(B)[None, None, :])].astype(np.int64)
+    sads = {}
+    for fy in range(-3, 4):
+        for fx in range(-3, 4):
+            # positions of an invalid candidate may leave the plane: clamp them, the candidate is dropped below
+            qy = np.clip(4 * (y0[:, None, None] + np.arange(B)[None, :, None]) + (4 * d[:, 1] + fy)[:, None, None], 0, q.shape[0] - 1)
+            qx = np.clip(4 * (x0[:, None, None] + np.arange(B)[None, None, :]) + (4 * d[:, 0] + fx)[:, None, None], 0, q.shape[1] - 1)
+            sads[(fx, fy)] = np.abs(cblk - q[qy, qx]).sum(axis=(1, 2)).tolist()
+    best = np.zeros((n, 3), np.int32)
+    n_valid = np.zeros(n, np.int32)
+    for k in range(n):
+        cands = []
+        for (fx, fy), s in sads.items():
+            Dx, Dy = 4 * int(d[k, 0]) + fx, 4 * int(d[k, 1]) + fy
+            if candidate_is_valid(int(x0[k]), int(y0[k]), B, W, H, Dx, Dy):
+                cands.append((s[k], Dx * Dx + Dy * Dy, Dy, Dx))
+        sad, _, Dy, Dx = min(cands)                                           # f = 0 is always valid: never empty
+        best[k] = (Dx, Dy, sad)
+        n_valid[k] = len(cands)
+    return entries(best, B, W, H), best, n_valid
+
+
 def entries(best, B, W, H):
     """(Dx, Dy, .) -> the decoder's records, in the kernel's f32 operation order"""
     best = np.asarray(best, np.int64)

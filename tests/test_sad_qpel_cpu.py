@@ -10,6 +10,7 @@ import oracle
 from ofps_amd import synth
 
 import indep_sad_qpel as iq
+import sad_qpel_cases as cases
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sad_qpel.npz")
 
@@ -58,6 +59,20 @@ def test_saturation_at_0_and_255():
     assert hg[2 * 3 + 1, 2 * 3 + 1] == 64           # 16 * 16 * 255 = 65280, (65280 + 512) >> 10 = 64
     assert hg[2 * 2 + 1, 2 * 2 + 1] == 4            # (-4) * (-4) * 255 = 4080, (4080 + 512) >> 10 = 4
     assert hg[2 * 2 + 1, 2 * 4 + 1] == 0            # (-4) * 36 * 255 < 0 -> 0
+
+
+def test_binary_frames_take_both_clip_branches_of_b_h_and_j():
+    """The sweeps' `binary` kind (only 0 and 255) drives every half-pel formula past both clip limits: shown on the UNCLIPPED
+    intermediates, so the GPU sweep that replays those frames provably runs clip255's two branches in b, h and j."""
+    a = cases.frames(64, 64, 64, 64, 1000, "binary")[0].astype(np.int64)
+    b1, h1 = iq._tap6(a, 1), iq._tap6(a, 0)
+    j1 = iq._tap6(b1, 0)
+    assert b1.max() <= 10710 and b1.min() >= -2550                 # (1 + 20 + 20 + 1) * 255 and -(5 + 5) * 255: int16 holds b1
+    for name, v in (("b", (b1 + 16) >> 5), ("h", (h1 + 16) >> 5), ("j", (j1 + 512) >> 10)):
+        assert (v < 0).any() and (v > 255).any(), name
+        assert v.min() < -30 and v.max() > 300, name               # well past the limits, not by a rounding step
+    hg = iq.half_plane(a.astype(np.uint8))
+    assert hg.min() == 0 and hg.max() == 255
 
 
 def test_linear_ramp_is_reproduced_exactly():
@@ -198,6 +213,44 @@ def test_known_quarter_pel_shift_is_recovered(D0):
     assert (reach & interior).sum() >= 0.9 * interior.sum()
     np.testing.assert_array_equal(best[reach & interior, 2], 0)
     np.testing.assert_array_equal(best[reach & interior, :2], np.tile(D0, ((reach & interior).sum(), 1)))
+
+
+def test_sweep_refine_equals_the_plain_tuple_minimum_and_the_sweep_covers_the_domain():
+    """The whole accepted domain (blocks 1..64, ranges 0..64, frames from 1x1, five kinds of content; tests/sad_qpel_cases.py)
+    through oracle.sad_flow -> refine: the packed-key winner == Python's min over (SAD, Dx^2 + Dy^2, Dy, Dx) tuples, and the
+    refinement's rules hold.  Then the coverage conditions over the whole run, from the restatement's output alone: the GPU
+    sweeps replay these examples (and assert the same conditions), so they cannot be vacuous."""
+    obs = []
+
+    @cases.sweep
+    def run(case):
+        w, h, b, r, _, _ = case
+        fr = cases.frames(*case)
+        _, best_i = oracle.sad_flow(fr[0], fr[1], b, r)
+        ent, best = iq.refine(fr[0], fr[1], b, r, best_i)
+        ent_t, best_t, n_valid = iq.refine_by_tuples(fr[0], fr[1], b, r, best_i)
+        assert len(best) == (w // b) * (h // b)
+        np.testing.assert_array_equal(best, best_t)
+        np.testing.assert_array_equal(ent.view(np.uint32), ent_t.view(np.uint32))
+        obs.append(cases.observe(case, best, n_valid))
+        if not len(best):
+            return
+        assert (best[:, 2] <= best_i[:, 2]).all()                              # f = 0 is always a candidate
+        assert (np.abs(best[:, :2] - 4 * best_i[:, :2]) <= 3).all()
+        nbx = w // b
+        x0 = (np.arange(len(best)) % nbx) * b; y0 = (np.arange(len(best)) // nbx) * b
+        assert (4 * x0 + best[:, 0] >= 0).all() and (4 * (x0 + b - 1) + best[:, 0] <= 4 * (w - 1)).all()
+        assert (4 * y0 + best[:, 1] >= 0).all() and (4 * (y0 + b - 1) + best[:, 1] <= 4 * (h - 1)).all()
+        assert (n_valid >= 1).all() and (n_valid <= 49).all()
+        # at f = 0 the quarter plane gives the integer search's SAD
+        q = iq.quarter_plane(fr[0]).astype(np.int64)
+        yy, xx = np.meshgrid(np.arange(b), np.arange(b), indexing="ij")
+        ref = q[4 * (y0 + best_i[:, 1])[:, None, None] + 4 * yy, 4 * (x0 + best_i[:, 0])[:, None, None] + 4 * xx]
+        cblk = fr[1][y0[:, None, None] + yy, x0[:, None, None] + xx].astype(np.int64)
+        np.testing.assert_array_equal(np.abs(cblk - ref).sum(axis=(1, 2)), best_i[:, 2])
+
+    run()
+    cases.coverage(obs)                                                        # prints the measured values (pytest -s)
 
 
 def test_records_follow_the_spec_formula():

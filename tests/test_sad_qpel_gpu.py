@@ -1,6 +1,12 @@
 """-m gpu: the quarter-pel refinement (N1q, ofps_hip_set_sad_motion_scale(ctx, 4)) through the C ABI against the NumPy restatement
 tests/indep_sad_qpel.py on the CPU oracle's integer winners.  All-integer arithmetic: (Dx, Dy, SAD) equal as integers, the records
-as f32 bit patterns, on every search path (strip, per-block, pruned, generic) and every entry point that runs a search."""
+as f32 bit patterns, on every search path (strip, per-block, pruned, generic) and every single-context entry point that runs a
+search: ofps_hip_sad_flow, _sad_flow_dev (both reference modes, with and without out_best, growing and shrinking geometries and
+batches), push_frame / push_frame_async / push_frames_async with the detector and the estimator off and on (LSQ and RANSAC, the scale
+flipped mid-stream), the Python decoder and the C++ host.  Elsewhere: the whole block / range domain and frames smaller than the
+refinement's window in tests/test_sad_qpel_properties_gpu.py, the multi-device dispatcher in tests/test_multi_device_qpel.py.
+Left out: the batched and the multi-device streams return no detector field, so there only the island's id and the field's side
+are compared; the LK / Farneback decoders have no motion scale."""
 import ctypes as C
 import json
 import os
@@ -198,6 +204,165 @@ def test_push_frame_sync_async_and_batched_equal_the_stage_wise_call(ctx):
     assert [r["have_vectors"] for r in res] == [False] + [True] * (n - 1)
     for k in range(1, n):
         np.testing.assert_array_equal(out[k].view(np.uint32), want[k - 1].view(np.uint32))
+
+
+# ------------------------------------------------------------------ the fused per-frame path with the detector and the estimator on
+FW, FH, FB, FR, FN = 640, 360, 16, 8, 5
+FASPECT, FFOV = 16 / 9, 22.275
+
+
+def _fused_sequences():
+    return {"seq": synth.luma_sequence(FN, FW, FH, max_step=8), "pan": _frames(FW, FH, FR, "pan", n=FN)}
+
+
+def _fused_expect(fr, scales):
+    """per frame k >= 1: (records, detector result, LSQ quaternion) of the stage-wise CPU chain at that frame's motion scale"""
+    cam = oracle.camera(FASPECT, FFOV)
+    out = [None]
+    for k in range(1, len(fr)):
+        ent, best_i = oracle.sad_flow(fr[k - 1], fr[k], FB, FR, threads=8)
+        if scales[k] == 4:
+            ent, _ = iq.refine(fr[k - 1], fr[k], FB, FR, best_i)
+        out.append((ent, oracle.detect_motion(ent), oracle.solve_ypr_given(ent, cam)))
+    return out
+
+
+def _check_fused(k, exp, have_vectors, entries, motion, field, quat):
+    """motion: None | (area, dim or None); field: the detector's field, or None where the entry point returns none"""
+    if exp is None:
+        assert not have_vectors and motion is None, k
+        return
+    ent_e, det_e, quat_e = exp
+    assert have_vectors, k
+    np.testing.assert_array_equal(entries.view(np.uint32), ent_e.view(np.uint32), err_msg=f"frame {k}")
+    assert (motion is None) == (det_e is None), k
+    if det_e is not None:
+        assert motion[0] == det_e[0], k                                            # island id
+        if motion[1] is not None:
+            assert motion[1] == det_e[1].shape[0], k
+        if field is not None:
+            np.testing.assert_array_equal(field.view(np.uint32), det_e[1].view(np.uint32), err_msg=f"frame {k}")
+    np.testing.assert_allclose(quat, quat_e, atol=2e-6, rtol=0, err_msg=f"frame {k}")
+
+
+def _push_sync(ctx, fr, scales, **kw):
+    ctx.reset_frames()
+    res = []
+    for k in range(len(fr)):
+        ctx.set_sad_motion_scale(scales[k])
+        r = ctx.push_frame(fr[k], block=FB, search_range=FR, aspect=FASPECT, fov_y_deg=FFOV, want_entries=True, want_field=True, **kw)
+        mo = r["motion"]
+        res.append((r["have_vectors"], r["entries"], None if mo is None else (mo[0], None), None if mo is None else mo[1], r["quat"]))
+    return res
+
+
+def _push_async(ctx, fr, scales, **kw):
+    """two tickets in flight; detector and estimator on, so the detector is forked onto the auxiliary stream behind the search"""
+    ctx.reset_frames()
+    nblk = (FW // FB) * (FH // FB)
+    dim = ctx.block_dim(0.05, 3)
+    pinned = [ctx.pinned_frame(FH, FW) for _ in range(2)]
+    ents = [ctx.pinned_array((nblk, 4)) for _ in range(2)]
+    flds = [ctx.pinned_array((dim, dim, 2)) for _ in range(2)]
+    res, tickets = [], []
+
+    def collect():
+        t, j = tickets.pop(0)
+        r = ctx.frame_wait(t)
+        mo = r["motion"]
+        res.append((r["have_vectors"], ents[j % 2].copy(), mo, None if mo is None else flds[j % 2].copy(), r["quat"]))
+
+    try:
+        for k in range(len(fr)):
+            if len(tickets) == 2:
+                collect()
+            np.copyto(pinned[k % 2], fr[k])
+            ctx.set_sad_motion_scale(scales[k])
+            tickets.append((ctx.push_frame_async(pinned[k % 2], block=FB, search_range=FR, aspect=FASPECT, fov_y_deg=FFOV,
+                                                 out_entries=ents[k % 2], out_field=flds[k % 2], **kw), k))
+        while tickets:
+            collect()
+    finally:
+        for a in pinned + ents + flds:
+            ctx.free_pinned(a)
+    return res
+
+
+def _push_batched(ctx, fr, scales, **kw):
+    """one batch: the entry point returns the island's id and the field's side, not the field"""
+    assert len(set(scales)) == 1
+    ctx.reset_frames()
+    ctx.set_sad_motion_scale(scales[0])
+    out = np.zeros((len(fr), (FW // FB) * (FH // FB), 4), np.float32)
+    t = ctx.push_frames_async(np.ascontiguousarray(fr), block=FB, search_range=FR, aspect=FASPECT, fov_y_deg=FFOV, out_entries=out, **kw)
+    return [(r["have_vectors"], out[k], r["motion"], None, r["quat"]) for k, r in enumerate(ctx.frames_wait(t))]
+
+
+@pytest.mark.parametrize("push", [_push_sync, _push_async, _push_batched], ids=["push_frame", "push_frame_async", "push_frames_async"])
+@pytest.mark.parametrize("name", ["seq", "pan"])
+def test_push_frame_at_scale_four_matches_the_stagewise_chain_with_detector_and_estimator_on(ctx, name, push):
+    """tests/test_gpu_parity.py::test_push_frame_matches_stagewise_oracle at motion scale 4: the refinement is a second launch
+    between the search and the fork of the detector's stream, and writes the records both stages read."""
+    fr = _fused_sequences()[name]
+    scales = [4] * FN
+    exp = _fused_expect(fr, scales)
+    if name == "pan":
+        assert ((np.round(exp[1][0][:, 2] * FW * 4).astype(int) % 4) != 0).any()   # sub-pel motion is in the records
+    for k, got in enumerate(push(ctx, fr, scales)):
+        _check_fused(k, exp[k], *got)
+
+
+def test_push_frame_async_with_ransac_at_scale_four(ctx):
+    fr = _fused_sequences()["pan"]
+    scales = [4] * FN
+    kw = dict(use_ransac=True, num_iters=200, seed=12345)
+    got_a = _push_async(ctx, fr, scales, **kw)
+    got_s = _push_sync(ctx, fr, scales, **kw)
+    exp = _fused_expect(fr, scales)
+    cam = oracle.camera(FASPECT, FFOV)
+    for k in range(1, FN):
+        np.testing.assert_array_equal(got_a[k][1].view(np.uint32), exp[k][0].view(np.uint32))
+        np.testing.assert_array_equal(got_s[k][1].view(np.uint32), exp[k][0].view(np.uint32))
+        # the same seed on the same records: the same bits, forked or not
+        np.testing.assert_array_equal(got_a[k][4].view(np.uint32), got_s[k][4].view(np.uint32), err_msg=f"frame {k}")
+        # HIP and CPU RANSAC agree to 1e-4 per component (tests/test_sad_qpel_accuracy_gpu.py)
+        q_o = oracle.solve_ypr_ransac(exp[k][0], cam, num_iters=200, seed=12345)
+        np.testing.assert_allclose(got_a[k][4], q_o, atol=1e-4, rtol=0, err_msg=f"frame {k}")
+
+
+@pytest.mark.parametrize("push", [_push_sync, _push_async], ids=["push_frame", "push_frame_async"])
+def test_scale_flips_between_frames_of_one_stream_with_detector_and_estimator_on(ctx, push):
+    fr = _fused_sequences()["pan"]
+    scales = [4, 4, 1, 4, 1]                                                       # frames 1..4 are searched at 4, 1, 4, 1
+    exp = _fused_expect(fr, scales)
+    for k, got in enumerate(push(ctx, fr, scales)):
+        _check_fused(k, exp[k], *got)
+
+
+# ------------------------------------------------------------------ scratch regrowth, a batch after a batch
+def test_geometry_grows_and_shrinks_on_one_context(ctx):
+    """ofps_hip_sad_flow (its own result buffers regrow) and ofps_hip_sad_flow_dev without out_best (the integer winners live in the
+    context's S_SAD_QBEST scratch, sized by the call): small, large, small, large with another block size."""
+    order = [(64, 48, 16), (1920, 1080, 8), (64, 48, 16), (1920, 1080, 16)]
+    frames = {(W, H): _frames(W, H, 16, "pan") for W, H, _ in order}
+    expect = {g: _expect(frames[g[:2]][0], frames[g[:2]][1], g[2], 16)[0] for g in set(order)}
+    for W, H, B in order:
+        fr = frames[(W, H)]
+        np.testing.assert_array_equal(ctx.sad_flow(fr[0], fr[1], B, 16).view(np.uint32), expect[(W, H, B)].view(np.uint32))
+    for W, H, B in order:
+        ent, _ = _dev_run(ctx, frames[(W, H)], (W + 63) // 64 * 64, 0, B, 16, False)
+        np.testing.assert_array_equal(ent[0].view(np.uint32), expect[(W, H, B)].view(np.uint32))
+
+
+def test_a_larger_batch_behind_a_smaller_one_and_scratch_alternating_with_a_caller_buffer(ctx):
+    fr = _frames(256, 144, 16, "pan", n=6)
+    want = [_expect(fr[k], fr[k + 1], 16, 16) for k in range(5)]
+    for n, with_best in ((2, False), (6, False), (2, False), (6, True), (3, False), (6, True), (6, False)):
+        ent, best = _dev_run(ctx, fr[:n], 256, 0, 16, 16, with_best)
+        for k in range(n - 1):
+            np.testing.assert_array_equal(ent[k].view(np.uint32), want[k][0].view(np.uint32), err_msg=f"n={n} with_best={with_best} pair {k}")
+            if with_best:
+                np.testing.assert_array_equal(best[k], want[k][1])
 
 
 def test_golden_fixture(ctx):
