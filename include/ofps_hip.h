@@ -203,7 +203,7 @@ int ofps_hip_contrast_mask_dev(ofps_hip_ctx* ctx, const void* d_gray, int W, int
  * OFPS_HIP_LK_REDUCED is set, as in the reference. */
 #define OFPS_HIP_FRAME_FORMAT(fmt) ((unsigned)(fmt) << 8)
 #define OFPS_HIP_FRAME_FORMAT_MASK 0x300u
-/* One Decoder::process_frame of a "hip_lk" plugin (cv-decoder/src/lib.rs:82-294): flow -> per-pixel records
+/* (csrc/dense_decoder.hip)  One Decoder::process_frame of a "hip_lk" plugin (cv-decoder/src/lib.rs:82-294): flow -> per-pixel records
  * [-> contrast mask] -> down-sampled through the densifier to the (max_w, max_h)-capped grid of :98-121 (defaults
  * 150 x 150 -> 150 x 84 at 16:9) -> one record per visited cell in (x, y)-sorted order.  out_entries capacity:
  * 4 * min(max_w,W) * min(max_h,H) floats (4 * W * H with OFPS_HIP_LK_FULLRES_RECORDS).  out_w/out_h: the record grid (with

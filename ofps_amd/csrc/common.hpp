@@ -11,6 +11,144 @@
 
 #include "../../include/ofps_hip.h"
 
+namespace ofps {
+
+// The streaming front doors (pipeline.hip, dense_decoder.hip, multi.hip) number their tickets 0, 1, 2, ... and keep the newest N in a
+// ring; the caller sees the low 31 bits of the number.
+inline int ticket_id(long number) { return (int)(number & 0x7FFFFFFF); }
+// the number of the ticket with this id among the newest `n` handed out (numbers next - n .. next - 1), or -1
+inline long ticket_number(long next, int n, int id) {
+    for (long k = next - 1; k >= 0 && k >= next - n; --k) if (ticket_id(k) == id) return k;
+    return -1;
+}
+
+// Ticket: { bool pending; hipEvent_t done; ... }.  pending: pushed, not yet collected; done: everything of the ticket, read-backs included.
+template <class Ticket, int N>
+struct TicketRing {
+    Ticket entry[N]; long next = 0;      // next: the number the next push gets
+    Ticket& at(long number) { return entry[number % N]; }
+    Ticket* find(int id) { const long k = ticket_number(next, N, id); return k < 0 ? nullptr : &at(k); }
+    bool any_pending(const Ticket* but = nullptr) const { for (const Ticket& t : entry) if (t.pending && &t != but) return true; return false; }
+    bool other_pending() const { return any_pending(&entry[next % N]); }     // ... but the one the next push would take
+    hipError_t drain(bool forget = true) {       // waits for everything in flight [and marks it collected]
+        for (Ticket& t : entry) {
+            const hipError_t e = t.pending && t.done ? hipEventSynchronize(t.done) : hipSuccess;
+            if (e != hipSuccess) return e;
+            if (forget) t.pending = false;
+        }
+        return hipSuccess;
+    }
+    int commit() { at(next).pending = true; return ticket_id(next++); }      // the LAST thing a push does: one that failed half-way changed nothing here
+};
+
+inline void destroy(hipEvent_t e) { if (e) (void)hipEventDestroy(e); }
+inline void destroy(hipStream_t s) { if (s) (void)hipStreamDestroy(s); }
+inline void free_host(void* p) { if (p) (void)hipHostFree(p); }
+
+// Farneback's state across calls (farneback.hip).  hip_flow in the stream forms: the pyramid + polynomial expansion of a pair's second
+// frame is the next pair's first, and the NEW frame's is made on the upload's stream beside the previous pair's flow.  Frames of the
+// stream carry ids (never reused); `cache.id[i]` is the frame whose expansion planes are in R slot i of the S_FB_WORK allocation of
+// generation `gen`, made with these parameters.
+struct FarnebackState {
+    static constexpr int kSlots = 3;     // expansion-plane slots per layer: the frames of two pairs in flight (k - 1, k, k + 1)
+    struct Cache {
+        uint64_t id[kSlots] = {0, 0, 0}; // the stream frame whose planes a slot holds (0 = none)
+        int W = 0, H = 0, K = 0, poly_n = 0;
+        double poly_sigma = 0;
+        uint64_t gen = 0;
+    } cache;
+    hipEvent_t prep_done = nullptr;      // the last pyramid + expansion of this context (its T / I temporaries are shared; prepares may run on two streams)
+    bool prep_recorded = false;          // a prepare has been enqueued (on prep_stream) since the context was made
+    hipStream_t prep_stream = nullptr;
+    hipStream_t prep_synced = nullptr;   // a stream that has been ordered behind the latest prepare by its caller (the stream forms' `uploaded` event)
+    uint64_t cache_hits = 0;             // (tests: how many calls skipped the first frame's pyramid + expansion)
+    struct PrevFlow { bool valid = false; int W = 0, H = 0; uint64_t id = 0, gen = 0; } prev_flow;     // S_FB_FLOW holds the flow of the pair whose second frame has this id
+    void release() { destroy(prep_done); }
+};
+
+// ---- the three streaming front doors' state: a ring of device frame slots, two tickets in flight, the new frame uploaded on a copy stream
+// beside the previous ticket's work.  release(): for ofps_hip_destroy; sync_side_streams(): before the context moves to another compute stream.
+// per-frame SAD pipeline (pipeline.hip: ofps_hip_push_frame[_async] / ofps_hip_frame_wait): frame k lives in slot k % 3 of S_PIPE_FRAMES
+struct PipeStream {
+    static constexpr int kSlots = 3, kTickets = 2;
+    int w = 0, h = 0;
+    long frames = 0;                     // frames pushed since the last reset
+    hipStream_t copy_stream = nullptr;
+    hipStream_t aux_stream = nullptr;    // the detector runs here beside the estimator (both read the same vectors)
+    hipEvent_t fork = nullptr, join = nullptr;
+    hipEvent_t uploaded[kSlots] = {};    // H2D of the frame in this slot finished (recorded on the copy stream)
+    hipEvent_t slot_read[kSlots] = {};   // last search that reads this slot finished (recorded on the compute stream)
+    bool slot_read_valid[kSlots] = {};
+    bool uploaded_on_compute[kSlots] = {};   // the upload was enqueued on the compute stream (ordered by it)
+    struct Ticket {
+        bool pending = false; hipEvent_t done = nullptr;
+        void* pinned = nullptr;          // page-locked PipeOut block for the result read-back
+        int have_vectors = 0, run_detector = 0, run_estimator = 0;
+        size_t n_vectors = 0;
+    };
+    TicketRing<Ticket, kTickets> ring;
+    void release() {
+        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); }
+        for (int k = 0; k < kSlots; ++k) { destroy(uploaded[k]); destroy(slot_read[k]); }
+        destroy(copy_stream); destroy(aux_stream); destroy(fork); destroy(join);
+    }
+    hipError_t sync_side_streams() {
+        const hipError_t e = copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess;
+        return e == hipSuccess && aux_stream ? hipStreamSynchronize(aux_stream) : e;
+    }
+};
+
+// batched form of the same pipeline (ofps_hip_push_frames_async / ofps_hip_frames_wait): n frames per ticket, ONE upload, ONE search
+// launch over the batch's pairs, ONE read-back.  Two batch buffers of (capacity + 1) frames alternate in S_BATCH_FRAMES: slot 0 holds the
+// last frame of the previous batch (the first pair's previous frame).  Its stream of frames is separate from the single-frame calls';
+// its uploads run on the per-frame pipeline's copy stream.
+struct BatchStream {
+    static constexpr int kTickets = 2;
+    int w = 0, h = 0;
+    void* last_frame = nullptr;          // device address of the newest frame of the batched stream
+    struct Ticket {
+        bool pending = false;
+        hipEvent_t done = nullptr, uploaded = nullptr, prev_copied = nullptr;
+        bool prev_copied_valid = false;
+        void* pinned = nullptr; size_t pinned_cap = 0;       // n x {result[4], quat[4]}
+        int n = 0, first_has_prev = 0, run_detector = 0, run_estimator = 0;
+        size_t n_vectors = 0;
+    };
+    TicketRing<Ticket, kTickets> ring;
+    void release() { for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); destroy(t.prev_copied); } }
+};
+
+// dense decoders, hip_lk and hip_flow (dense_decoder.hip: ofps_hip_lk_push_frame[_async] / ofps_hip_lk_frame_wait): frame k lives in
+// slot k % 3 of S_LK_FRAMES; each ticket has a page-locked block [count, pad x 3][records] that its last kernels write directly
+struct DenseStream {
+    static constexpr int kSlots = 3, kTickets = 2;
+    int w = 0, h = 0;                    // the arriving frames' size
+    int fw = 0, fh = 0, fmt = 0;         // the size of the frames in the ring (reduced with OFPS_HIP_LK_REDUCED) and the arriving frames' format
+    long frames = 0;
+    uint64_t frames_gen = 0;             // generation of the S_LK_FRAMES allocation the count refers to
+    bool fb_params_valid = false; int fb_levels = 0, fb_radius = 0;     // the hip_flow stream's last Farneback parameters (a change with a ticket in flight is refused)
+    uint64_t frame_serial = 0;           // frames of the stream carry ids (FarnebackState::cache); the id of the frame in each slot
+    uint64_t slot_id[kSlots] = {0, 0, 0};
+    hipStream_t copy_stream = nullptr;
+    struct Ticket {
+        bool pending = false;
+        hipEvent_t done = nullptr, uploaded = nullptr;
+        void* pinned = nullptr; size_t pinned_cap = 0;
+        int have_vectors = 0, gw = 0, gh = 0;
+        size_t max_records = 0;
+    };
+    TicketRing<Ticket, kTickets> ring;
+    void* decode_pinned = nullptr; size_t decode_pinned_cap = 0;     // ofps_hip_lk_decode's block: a pair's records + their count (one wait)
+    void release() {
+        free_host(decode_pinned);
+        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); }
+        destroy(copy_stream);
+    }
+    hipError_t sync_side_streams() { return copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess; }
+};
+
+}  // namespace ofps
+
 struct ofps_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -46,88 +184,12 @@ struct ofps_hip_ctx {
         int test_lk_order = 0;           // OFPS_HIP_LK_TEST_ORDER: the one-launch pyramid's blocks take their positions 1: in reverse, 2: permuted, after random delays
     } opt;
 
-    // hip_lk stream state (lk.hip: ofps_hip_lk_push_frame): frame k of the stream lives in slot k % 2 of S_FRAMES
-    int lk_w = 0, lk_h = 0;              // the arriving frames' size
-    int lk_fw = 0, lk_fh = 0, lk_fmt = 0; // the size of the frames in the ring (reduced with OFPS_HIP_LK_REDUCED) and the arriving frames' format
-    long lk_frames = 0;
-    bool lk_fb_params_valid = false; int lk_fb_levels = 0, lk_fb_radius = 0;     // the hip_flow stream's last Farneback parameters (a change with a ticket in flight is refused)
-    uint64_t lk_frames_gen = 0;          // generation of the S_LK_FRAMES allocation the count refers to
+    ofps::PipeStream pipe;
+    ofps::BatchStream batch;
+    ofps::DenseStream dense;
+    ofps::FarnebackState fb;
     uint32_t lk_epoch = 0;               // lk_levels_kernel: tag of the last launch in the tile flags (S_LK_FLAGS)
     uint64_t lk_flags_gen = 0;           // generation of the flag buffer the tags refer to
-    void* lk_pinned = nullptr;           // page-locked staging for a frame's records + their count (one D2H, one wait)
-    size_t lk_pinned_cap = 0;
-    // read-ahead form (ofps_hip_lk_push_frame_async / ofps_hip_lk_frame_wait): a ring of three device frame slots, the new frame
-    // uploaded on a copy stream while the previous pair's flow runs, two tickets in flight, each with a page-locked block
-    // [count, pad x 3][records] that the last kernels of the ticket write directly
-    static constexpr int kLkSlots = 3, kLkTickets = 2;
-    hipStream_t lk_copy_stream = nullptr;
-    struct LkTicket {
-        bool pending = false;
-        hipEvent_t done = nullptr, uploaded = nullptr;
-        void* pinned = nullptr; size_t pinned_cap = 0;
-        int have_vectors = 0, gw = 0, gh = 0;
-        size_t max_records = 0;
-        long fixed_count = -1;           // >= 0: the record count is known on the host (per-pixel output without a mask)
-    } lk_ticket[kLkTickets];
-    long lk_next_ticket = 0;
-    // hip_flow in the stream forms (farneback.hip): the pyramid + polynomial expansion of a pair's second frame is the next pair's
-    // first, and the NEW frame's is made on the upload's stream beside the previous pair's flow.  Frames of the stream carry ids (never
-    // reused); `fb_cache.id[i]` is the frame whose expansion planes are in R slot i of the S_FB_WORK allocation of generation `gen`, made
-    // with these parameters.
-    uint64_t lk_frame_serial = 0;
-    uint64_t lk_slot_id[kLkSlots] = {0, 0, 0};
-    static constexpr int kFbSlots = 3;   // expansion-plane slots per layer: the frames of two pairs in flight (k - 1, k, k + 1)
-    struct FbCache {
-        uint64_t id[kFbSlots] = {0, 0, 0};   // the stream frame whose planes a slot holds (0 = none)
-        int W = 0, H = 0, K = 0, poly_n = 0;
-        double poly_sigma = 0;
-        uint64_t gen = 0;
-    } fb_cache;
-    hipEvent_t fb_prep_done = nullptr;   // the last pyramid + expansion of this context (its T / I temporaries are shared; prepares may run on two streams)
-    bool fb_prep_recorded = false;       // a prepare has been enqueued (on fb_prep_stream) since the context was made
-    hipStream_t fb_prep_stream = nullptr;
-    hipStream_t fb_prep_synced = nullptr; // a stream that has been ordered behind the latest prepare by its caller (the stream forms' `uploaded` event)
-    uint64_t fb_cache_hits = 0;          // (tests: how many calls skipped the first frame's pyramid + expansion)
-    struct FbPrevFlow { bool valid = false; int W = 0, H = 0; uint64_t id = 0, gen = 0; } fb_prev_flow;     // S_FB_FLOW holds the flow of the pair whose second frame has this id
-
-    // per-frame pipeline state (pipeline.hip): a ring of three device frame slots (the new frame is uploaded on the copy
-    // stream while the previous pair is still being searched), two tickets in flight
-    static constexpr int kPipeSlots = 3, kPipeTickets = 2;
-    int pipe_w = 0, pipe_h = 0, pipe_stride = 0;
-    long pipe_frames = 0;                // frames pushed since the last reset; frame k lives in slot k % 3
-    hipStream_t pipe_copy_stream = nullptr;
-    hipStream_t pipe_aux_stream = nullptr;       // the detector runs here beside the estimator (both read the same vectors)
-    hipEvent_t pipe_fork = nullptr, pipe_join = nullptr;
-    hipEvent_t pipe_uploaded[kPipeSlots] = {};   // H2D of the frame in this slot finished (recorded on the copy stream)
-    hipEvent_t pipe_slot_read[kPipeSlots] = {};  // last search that reads this slot finished (recorded on the compute stream)
-    bool pipe_slot_read_valid[kPipeSlots] = {};
-    bool pipe_uploaded_on_compute[kPipeSlots] = {};   // the upload was enqueued on the compute stream (ordered by it)
-    struct PipeTicket {
-        bool pending = false;            // pushed, not yet collected by ofps_hip_frame_wait
-        hipEvent_t done = nullptr;       // everything of this ticket, read-backs included
-        void* pinned = nullptr;          // page-locked PipeOut block for the result read-back
-        int have_vectors = 0, run_detector = 0, run_estimator = 0;
-        size_t n_vectors = 0;
-    } pipe_ticket[kPipeTickets];
-    long pipe_next_ticket = 0;
-
-    // batched form of the same pipeline (ofps_hip_push_frames_async): n frames per ticket, ONE upload, ONE search launch
-    // over the batch's pairs, ONE read-back.  Two batch buffers of (capacity + 1) frames alternate: slot 0 holds the last
-    // frame of the previous batch (the first pair's previous frame).  Its stream of frames is separate from the
-    // single-frame calls'.
-    static constexpr int kBatchTickets = 2;
-    struct BatchTicket {
-        bool pending = false;
-        hipEvent_t done = nullptr, uploaded = nullptr, prev_copied = nullptr;
-        bool prev_copied_valid = false;
-        void* pinned = nullptr; size_t pinned_cap = 0;       // n x {result[4], quat[4]}
-        int n = 0, first_has_prev = 0, run_detector = 0, run_estimator = 0;
-        size_t n_vectors = 0;
-    } batch_ticket[kBatchTickets];
-    long batch_next_ticket = 0;
-    long batch_frames = 0;               // frames pushed through the batched form since the last reset
-    int batch_w = 0, batch_h = 0;
-    void* batch_last_frame = nullptr;    // device address of the newest frame of the batched stream
 
     // cluster Almeida solver (almeida.hip): granule exchange buffer state.  Tags are unique per call (tag base advances
     // by 32 per launch), so the buffer is zeroed only when (re)allocated or when the 32-bit tag space wraps.
@@ -213,7 +275,7 @@ int detect_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batc
                   float target_motion, int* d_result, float2* d_out_field, int* out_dim);
 int farneback_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int winsize,
                           int iters, int poly_n, double poly_sigma, const float2* d_init, float2* d_flow, float4* d_entries,
-                          uint64_t prev_id = 0, uint64_t cur_id = 0);     // ids != 0: frames of a stream (ofps_hip_ctx::fb_cache)
+                          uint64_t prev_id = 0, uint64_t cur_id = 0);     // ids != 0: frames of a stream (FarnebackState::cache)
 void farneback_mark_ordered(ofps_hip_ctx* ctx, hipStream_t s);
 int farneback_prepare_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int H, int stride, int levels, int winsize, int poly_n, double poly_sigma,
                              uint64_t id, hipStream_t st);          // a stream frame's pyramid + expansion ahead of its pair's flow, on stream st
@@ -223,11 +285,19 @@ void cluster_gate_context_destroyed(int device);
 int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
                    int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
 
-// device -> host: by a copy KERNEL when the destination is page-locked (device-addressable) -- a D2H DMA would queue behind the
-// next frame's H2D --, by hipMemcpyAsync otherwise (pipeline.hip).  bytes % 4 == 0.
+// ---- transfers (transfer.hip)
+bool device_address_of(const void* host_ptr, void** dev_ptr);        // the device address of page-locked host memory, or false for pageable memory
+// device -> host: by a copy KERNEL when the destination is page-locked (device-addressable), by hipMemcpyAsync otherwise.  bytes % 4 == 0.
 int read_back_device(ofps_hip_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes, hipStream_t s);
-// the device address of page-locked host memory, or false for pageable memory
-bool device_address_of(const void* host_ptr, void** dev_ptr);
+int copy_words_device(ofps_hip_ctx* ctx, void* dst, const void* src, size_t words, unsigned blocks, hipStream_t s);     // that kernel, `blocks` workgroups
+// dense bytes, host -> device on stream s; by_kernel: through the upload kernel when the source is page-locked (else the DMA engine)
+int upload_dense_device(ofps_hip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s, bool by_kernel);
+// a page-locked block that kernels write and the host reads after an event, of at least `bytes`; grows, never shrinks
+int host_block_reserve(ofps_hip_ctx* ctx, void** p, size_t* cap, size_t bytes);
+
+// lk.hip: the iterative LK flow of a pair of device frames (d_flow and / or d_entries; d_init: the initial flow or null)
+int lk_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                   float2* d_flow, float4* d_entries, const float2* d_init = nullptr);
 
 // the batched read-ahead push with the previous frame supplied by the caller (pipeline.hip; multi.hip deals batches to workers)
 int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int H, int stride, size_t frame_pitch,

@@ -205,32 +205,7 @@ void ofps_hip_destroy(ofps_hip_ctx* ctx) {
     (void)hipDeviceSynchronize();
     for (auto& s : ctx->scratch)
         if (s.p) (void)hipFree(s.p);
-    for (auto& t : ctx->pipe_ticket) {
-        if (t.pinned) (void)hipHostFree(t.pinned);
-        if (t.done) (void)hipEventDestroy(t.done);
-    }
-    for (auto& t : ctx->batch_ticket) {
-        if (t.pinned) (void)hipHostFree(t.pinned);
-        if (t.done) (void)hipEventDestroy(t.done);
-        if (t.uploaded) (void)hipEventDestroy(t.uploaded);
-        if (t.prev_copied) (void)hipEventDestroy(t.prev_copied);
-    }
-    for (int k = 0; k < ofps_hip_ctx::kPipeSlots; ++k) {
-        if (ctx->pipe_uploaded[k]) (void)hipEventDestroy(ctx->pipe_uploaded[k]);
-        if (ctx->pipe_slot_read[k]) (void)hipEventDestroy(ctx->pipe_slot_read[k]);
-    }
-    if (ctx->lk_pinned) (void)hipHostFree(ctx->lk_pinned);
-    for (auto& t : ctx->lk_ticket) {
-        if (t.pinned) (void)hipHostFree(t.pinned);
-        if (t.done) (void)hipEventDestroy(t.done);
-        if (t.uploaded) (void)hipEventDestroy(t.uploaded);
-    }
-    if (ctx->lk_copy_stream) (void)hipStreamDestroy(ctx->lk_copy_stream);
-    if (ctx->pipe_copy_stream) (void)hipStreamDestroy(ctx->pipe_copy_stream);
-    if (ctx->pipe_aux_stream) (void)hipStreamDestroy(ctx->pipe_aux_stream);
-    if (ctx->fb_prep_done) (void)hipEventDestroy(ctx->fb_prep_done);
-    if (ctx->pipe_fork) (void)hipEventDestroy(ctx->pipe_fork);
-    if (ctx->pipe_join) (void)hipEventDestroy(ctx->pipe_join);
+    ctx->pipe.release(); ctx->batch.release(); ctx->dense.release(); ctx->fb.release();
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -256,9 +231,8 @@ static int switch_stream(ofps_hip_ctx* ctx, hipStream_t next) {
     if (next == ctx->stream) return OFPS_HIP_OK;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pipe_copy_stream) OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe_copy_stream));
-    if (ctx->pipe_aux_stream) OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe_aux_stream));
-    if (ctx->lk_copy_stream) OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->lk_copy_stream));
+    OFPS_HIP_TRY(ctx, ctx->pipe.sync_side_streams());
+    OFPS_HIP_TRY(ctx, ctx->dense.sync_side_streams());
     ctx->stream = next;
     ctx->stream_cus = stream_cu_count(ctx, next);
     return OFPS_HIP_OK;

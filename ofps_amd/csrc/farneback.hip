@@ -18,7 +18,7 @@
 //                        order) -> LDS; then per pixel the column-window sums, the 2 x 2 solve, and -- except in a layer's last update --
 //                        the NEXT update's matrices for its own pixels, written where the flow they depend on is produced; the flow
 //                        itself is stored only when somebody reads it (next layer, caller).  Tiles are dealt to the XCDs in contiguous runs.
-// Stream forms keep the second frame's pyramid + expansion for the next pair (ofps_hip_ctx::fb_cache).
+// Stream forms keep the second frame's pyramid + expansion for the next pair (FarnebackState::cache).
 // All streaming: the honest roofline of this path is HBM (R0 + R1 + M in / out per update); measured numbers: DESIGN.md "N2b".
 #include "common.hpp"
 
@@ -759,7 +759,7 @@ struct FbPlan {
     float2* Fp[2];
     uint64_t gen;
     // expansion planes of layer k in R slot `slot` (three slots per layer: the frames of a stream's two pairs in flight)
-    float* Rk(int k, int slot) const { return R + (size_t)ofps_hip_ctx::kFbSlots * 5 * r_off[k] + (size_t)slot * 5 * Y.w[k] * Y.h[k]; }
+    float* Rk(int k, int slot) const { return R + (size_t)FarnebackState::kSlots * 5 * r_off[k] + (size_t)slot * 5 * Y.w[k] * Y.h[k]; }
 };
 
 int fb_plan(ofps_hip_ctx* ctx, int W, int H, int levels, int winsize, int poly_n, double poly_sigma, FbPlan* pl) {
@@ -798,15 +798,15 @@ int fb_plan(ofps_hip_ctx* ctx, int W, int H, int levels, int winsize, int poly_n
     Y.blk0[K + 1] = q.vblocks;
     q.px = (size_t)W * H;
     // T | I (layers >= 1) | R [layer][3 slots][5][h][w] | M x 2 [5][H][W] | two flow planes [H][W] float2
-    const size_t floats = t_floats + i_floats + (size_t)ofps_hip_ctx::kFbSlots * 5 * q.r_px + 2 * 5 * q.px + 2 * 2 * q.px;
+    const size_t floats = t_floats + i_floats + (size_t)FarnebackState::kSlots * 5 * q.r_px + 2 * 5 * q.px + 2 * 2 * q.px;
     auto* base = static_cast<float*>(scratch(ctx, S_FB_WORK, floats * sizeof(float)));
     if (!base) return OFPS_HIP_ENOMEM;
     q.T = base; q.I = q.T + t_floats; q.R = q.I + i_floats;
-    q.Mb[0] = q.R + (size_t)ofps_hip_ctx::kFbSlots * 5 * q.r_px; q.Mb[1] = q.Mb[0] + 5 * q.px;
+    q.Mb[0] = q.R + (size_t)FarnebackState::kSlots * 5 * q.r_px; q.Mb[1] = q.Mb[0] + 5 * q.px;
     q.Fp[0] = reinterpret_cast<float2*>(q.Mb[1] + 5 * q.px); q.Fp[1] = q.Fp[0] + q.px;
     q.gen = ctx->scratch[S_FB_WORK].gen;
     // the cache of expanded frames belongs to one workspace, geometry and parameter set
-    ofps_hip_ctx::FbCache& fc = ctx->fb_cache;
+    FarnebackState::Cache& fc = ctx->fb.cache;
     if (fc.gen != q.gen || fc.W != W || fc.H != H || fc.K != K || fc.poly_n != poly_n || fc.poly_sigma != poly_sigma) {
         for (auto& id : fc.id) id = 0;
         fc.gen = q.gen; fc.W = W; fc.H = H; fc.K = K; fc.poly_n = poly_n; fc.poly_sigma = poly_sigma;
@@ -819,11 +819,11 @@ int fb_plan(ofps_hip_ctx* ctx, int W, int H, int levels, int winsize, int poly_n
 // on the previous prepare's stream (a record covers everything enqueued before it); prepares that follow each other on one stream, the
 // steady state of both the read-ahead and the synchronous forms, cost no event at all.
 static int fb_order_behind_last_prepare(ofps_hip_ctx* ctx, hipStream_t st) {
-    if (!ctx->fb_prep_recorded || ctx->fb_prep_stream == st || ctx->fb_prep_synced == st) return OFPS_HIP_OK;
-    if (!ctx->fb_prep_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fb_prep_done, hipEventDisableTiming));
-    OFPS_HIP_TRY(ctx, hipEventRecord(ctx->fb_prep_done, ctx->fb_prep_stream));
-    OFPS_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->fb_prep_done, 0));
-    ctx->fb_prep_synced = st;
+    if (!ctx->fb.prep_recorded || ctx->fb.prep_stream == st || ctx->fb.prep_synced == st) return OFPS_HIP_OK;
+    if (!ctx->fb.prep_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fb.prep_done, hipEventDisableTiming));
+    OFPS_HIP_TRY(ctx, hipEventRecord(ctx->fb.prep_done, ctx->fb.prep_stream));
+    OFPS_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->fb.prep_done, 0));
+    ctx->fb.prep_synced = st;
     return OFPS_HIP_OK;
 }
 int fb_prepare(ofps_hip_ctx* ctx, const FbPlan& pl, const uint8_t* const* imgs, const int* slots, int n_img, int stride, hipStream_t st) {
@@ -875,21 +875,21 @@ int fb_prepare(ofps_hip_ctx* ctx, const FbPlan& pl, const uint8_t* const* imgs, 
         else hipLaunchKernelGGL((fb_polyexp_kernel<0>), dim3(blk), dim3(256), lds, st, E, pl.P, t_c, t_s);
     }
     OFPS_HIP_TRY(ctx, hipGetLastError());
-    ctx->fb_prep_recorded = true; ctx->fb_prep_stream = st; ctx->fb_prep_synced = nullptr;
+    ctx->fb.prep_recorded = true; ctx->fb.prep_stream = st; ctx->fb.prep_synced = nullptr;
     return OFPS_HIP_OK;
 }
 
 // which R slot holds the expansion of the stream frame `id` (0 = none does)
-int fb_find_slot(const ofps_hip_ctx::FbCache& fc, uint64_t id) {
+int fb_find_slot(const FarnebackState::Cache& fc, uint64_t id) {
     if (id == 0) return -1;
-    for (int i = 0; i < ofps_hip_ctx::kFbSlots; ++i)
+    for (int i = 0; i < FarnebackState::kSlots; ++i)
         if (fc.id[i] == id) return i;
     return -1;
 }
 // a slot to overwrite: an empty one, else the one with the oldest frame -- never `keep` (the other frame of the pair being computed)
-int fb_victim_slot(const ofps_hip_ctx::FbCache& fc, int keep) {
+int fb_victim_slot(const FarnebackState::Cache& fc, int keep) {
     int best = -1;
-    for (int i = 0; i < ofps_hip_ctx::kFbSlots; ++i) {
+    for (int i = 0; i < FarnebackState::kSlots; ++i) {
         if (i == keep) continue;
         if (best < 0 || fc.id[i] < fc.id[best]) best = i;
     }
@@ -906,7 +906,7 @@ int farneback_prepare_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int
     FbPlan pl;
     int rc = fb_plan(ctx, W, H, levels, winsize, poly_n, poly_sigma, &pl);
     if (rc != OFPS_HIP_OK) return rc;
-    ofps_hip_ctx::FbCache& fc = ctx->fb_cache;
+    FarnebackState::Cache& fc = ctx->fb.cache;
     if (fb_find_slot(fc, id) >= 0) return OFPS_HIP_OK;
     const int slot = fb_victim_slot(fc, -1);
     fc.id[slot] = 0;
@@ -918,7 +918,7 @@ int farneback_prepare_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int
 
 // the caller has made `s` wait for everything enqueued so far on the stream of the latest prepare (the stream forms' `uploaded` event):
 // the flow on `s` needs no event of its own
-void farneback_mark_ordered(ofps_hip_ctx* ctx, hipStream_t s) { ctx->fb_prep_synced = s; }
+void farneback_mark_ordered(ofps_hip_ctx* ctx, hipStream_t s) { ctx->fb.prep_synced = s; }
 
 int farneback_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int winsize,
                           int iters, int poly_n, double poly_sigma, const float2* d_init, float2* d_flow, float4* d_entries,
@@ -938,15 +938,15 @@ int farneback_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_
     // the first frame's from the previous pair (its second frame), the second frame's from farneback_prepare_device on the upload's
     // stream -- if they were made for the same frame id, geometry and parameters and the workspace has not moved since (fb_plan).
     // Whatever is missing goes through the pyramid and the expansion here, on ctx->stream.
-    ofps_hip_ctx::FbCache& fc = ctx->fb_cache;
+    FarnebackState::Cache& fc = ctx->fb.cache;
     int slot_prev = fb_find_slot(fc, prev_id), slot_cur = fb_find_slot(fc, cur_id);
-    if (slot_prev >= 0) ctx->fb_cache_hits += 1;
+    if (slot_prev >= 0) ctx->fb.cache_hits += 1;
     {
         const uint8_t* imgs[2]; int slots[2]; int n = 0;
         if (slot_prev < 0) { slot_prev = fb_victim_slot(fc, slot_cur); fc.id[slot_prev] = 0; imgs[n] = d_prev; slots[n++] = slot_prev; }
         if (slot_cur < 0) {
             int v = -1;                                            // not the first frame's slot
-            for (int i = 0; i < ofps_hip_ctx::kFbSlots; ++i)
+            for (int i = 0; i < FarnebackState::kSlots; ++i)
                 if (i != slot_prev && (v < 0 || fc.id[i] < fc.id[v])) v = i;
             slot_cur = v; fc.id[slot_cur] = 0; imgs[n] = d_cur; slots[n++] = slot_cur;
         }
@@ -1015,7 +1015,7 @@ extern "C" {
 
 int ofps_hip_flow_cache_hits(ofps_hip_ctx* ctx, uint64_t* count) {
     if (!ctx || !count) return OFPS_HIP_EINVAL;
-    *count = ctx->fb_cache_hits;
+    *count = ctx->fb.cache_hits;
     return OFPS_HIP_OK;
 }
 

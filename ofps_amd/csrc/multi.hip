@@ -545,7 +545,7 @@ int ofps_hip_multi_push_frames_async(ofps_hip_multi* m, const uint8_t* frames, i
     });
     m->stream_frames += n;
     m->next_ticket = g + 1;
-    *ticket = (int)(g & 0x7FFFFFFF);
+    *ticket = ofps::ticket_id(g);
     return OFPS_HIP_OK;
 }
 
@@ -555,10 +555,7 @@ int ofps_hip_multi_frames_wait(ofps_hip_multi* m, int ticket, ofps_hip_frame_res
     {
         std::lock_guard<std::recursive_mutex> api(m->api);
         const int nw = (int)m->w.size();
-        const long newest = m->next_ticket - 1;
-        long g = -1;
-        for (long k = newest; k >= 0 && k > newest - 2 * nw; --k)
-            if ((int)(k & 0x7FFFFFFF) == ticket) { g = k; break; }
+        const long g = ofps::ticket_number(m->next_ticket, 2 * nw, ticket);
         if (g < 0 || m->tickets.empty()) return multi_error(m, OFPS_HIP_EINVAL, "multi_frames_wait: ticket %d is not in flight", ticket);
         int ts;
         ofps_hip_multi_stream_plan(g, nw, nullptr, nullptr, &ts);

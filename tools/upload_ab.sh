@@ -9,11 +9,14 @@ variant() {
     local name=$1; shift
     local d=build/ab/up_$name
     mkdir -p $d
-    $HIPCC $FLAGS "$@" -c ofps_amd/csrc/pipeline.hip -o $d/pipeline.o
+    # OFPS_HIP_UPLOAD_WGS is read by transfer.hip (the upload kernel), OFPS_HIP_UPLOAD_KERNEL_SINGLE by pipeline.hip (the single-frame upload)
     objs=""
     for src in ofps_amd/csrc/*.hip; do
         stem=$(basename $src .hip)
-        if [ $stem = pipeline ]; then objs="$objs $d/pipeline.o"; else objs="$objs ofps_amd/csrc/$stem.o"; fi
+        if [ $stem = pipeline ] || [ $stem = transfer ]; then
+            $HIPCC $FLAGS "$@" -c $src -o $d/$stem.o
+            objs="$objs $d/$stem.o"
+        else objs="$objs ofps_amd/csrc/$stem.o"; fi
     done
     $HIPCC --offload-arch=gfx950 -shared -fPIC -o $d/libofps_hip.so $objs -Wl,-rpath,/opt/rocm/lib
     cp ofps_amd/host/ofps_hip_tool $d/
