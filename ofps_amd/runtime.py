@@ -327,13 +327,19 @@ class HipContext:
         """forget the stream's frames, keep its last flow as the next pair's initial flow (a decoder that skipped frames)"""
         self._check(self._lib.ofps_hip_lk_rewind(self._h))
 
-    def contrast_mask(self, gray: np.ndarray) -> np.ndarray:
-        """cv-decoder's Sobel/threshold/dilate mask (cv-decoder/src/lib.rs:203-237) -> u8[H, W], 1 = keep."""
-        g = np.ascontiguousarray(gray, np.uint8)
+    def contrast_mask(self, gray: np.ndarray, stride: int | None = None) -> np.ndarray:
+        """cv-decoder's Sobel/threshold/dilate mask (cv-decoder/src/lib.rs:203-237) -> u8[H, W], 1 = keep (dense: W bytes per row).
+        stride: `gray` is a u8 view [H, W] whose rows lie `stride` >= W bytes apart (e.g. buf[:, :W]); it is passed as it is."""
+        if stride is None:
+            g = np.ascontiguousarray(gray, np.uint8)
+            stride = g.shape[1]
+        else:
+            g = gray
+            assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
         H, W = g.shape
         out = np.zeros((H, W), np.uint8)
         u8 = C.POINTER(C.c_uint8)
-        self._check(self._lib.ofps_hip_contrast_mask(self._h, g.ctypes.data_as(u8), W, H, W, out.ctypes.data_as(u8)))
+        self._check(self._lib.ofps_hip_contrast_mask(self._h, C.cast(C.c_void_p(g.ctypes.data), u8), W, H, stride, out.ctypes.data_as(u8)))
         return out
 
     def contrast_mask_dev(self, d_gray: int, W: int, H: int, stride: int, d_out_mask: int):
