@@ -355,6 +355,28 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
                               const ofps_hip_frame_params* params, float* out_entries /* 4*nblk or NULL */,
                               float* out_field /* 2*dim*dim or NULL */, int* ticket);
 int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* out);
+/* The dense decoders ("hip_lk", "hip_flow") in the same shape: one ticket = frame -> records -> island + quaternion, the records and their
+ * COUNT staying on the device between the decoder and its tail (the count of a dense decoder -- mask survivors, visited cells -- is only
+ * known there: detector and estimator read it from device memory, every launch is sized from the records' capacity, nothing is read back
+ * or synchronised between push and wait).  Arguments up to `flags` as for ofps_hip_lk_push_frame_async; `tail` is the
+ * ofps_hip_frame_params of ofps_hip_push_frame with `block` / `range` ignored.  The wait fills `out` (n_vectors = the record count; a
+ * stream's first frame: have_vectors = 0, identity, no motion), copies the records to out_entries (capacity as for ofps_hip_lk_decode)
+ * and the island's field to out_field when given, and returns the record grid in out_w / out_h.  These calls and
+ * ofps_hip_lk_push_frame[_async] are ONE stream of frames -- same ring (2 tickets in flight), same ofps_hip_lk_reset / _rewind, same kept
+ * Farneback expansion and OFPS_HIP_FLOW_USE_PREVIOUS flow -- and may be mixed freely: ofps_hip_lk_frame_wait collects a fused ticket (the
+ * tail's results are dropped), the fused wait a plain one (identity, no motion).  The records are bit for bit the plain form's; the
+ * detector's result equals ofps_hip_detect on them bit for bit, the quaternion ofps_hip_almeida's to the solver's parity bound (2e-6
+ * least squares: the launch partitions the capacity, not the count -- another fixed summation order; RANSAC draws the same samples).
+ * OFPS_HIP_LK_FULLRES_RECORDS has no fused form (OFPS_HIP_EUNSUPPORTED): ofps_hip_lk_flow_dev -> ofps_hip_almeida_dev is that chain. */
+int ofps_hip_lk_push_frame_fused_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride,
+                                       int levels, int radius, int iters, int max_w, int max_h, unsigned flags,
+                                       const ofps_hip_frame_params* tail, int* ticket);
+int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* out, float* out_entries /* or NULL */,
+                                 float* out_field /* 2*dim*dim or NULL */, int* out_w, int* out_h);
+int ofps_hip_lk_push_frame_fused(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride,
+                                 int levels, int radius, int iters, int max_w, int max_h, unsigned flags,
+                                 const ofps_hip_frame_params* tail, ofps_hip_frame_result* out, float* out_entries /* or NULL */,
+                                 float* out_field /* 2*dim*dim or NULL */, int* out_w, int* out_h);
 /* Batched read-ahead form: n consecutive frames of a stream per ticket (a decoder running n frames ahead).  `frames` holds
  * them frame_pitch bytes apart; ONE upload, one search launch over the batch's pairs, one detector chain and one
  * estimator launch over the batch, one read-back: a handful of HIP calls per batch instead of ~9 per frame.  Frame j is

@@ -113,6 +113,12 @@ PROTOTYPES["ofps_hip_frame_wait"] = (C.c_int, [_ctx, C.c_int, C.POINTER(FrameRes
 PROTOTYPES["ofps_hip_push_frames_async"] = (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(FrameParams), _f32p,
                                                       C.POINTER(C.c_int)])
 PROTOTYPES["ofps_hip_frames_wait"] = (C.c_int, [_ctx, C.c_int, C.POINTER(FrameResult)])
+_ip = C.POINTER(C.c_int)
+PROTOTYPES["ofps_hip_lk_push_frame_fused_async"] = (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                              C.c_uint, C.POINTER(FrameParams), _ip])
+PROTOTYPES["ofps_hip_lk_frame_fused_wait"] = (C.c_int, [_ctx, C.c_int, C.POINTER(FrameResult), _f32p, _f32p, _ip, _ip])
+PROTOTYPES["ofps_hip_lk_push_frame_fused"] = (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.c_uint, C.POINTER(FrameParams), C.POINTER(FrameResult), _f32p, _f32p, _ip, _ip])
 
 _multi = C.c_void_p
 PROTOTYPES["ofps_hip_checksum_dev"] = (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, _vp])

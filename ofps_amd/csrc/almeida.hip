@@ -578,7 +578,8 @@ __global__ __launch_bounds__(1024) void almeida_lsq_wg_kernel(const float4* __re
     __shared__ Quat rot_sh[2];
     __shared__ float4 plds[P_LDS ? EPT * 1024 : 1];     // (roll.x, roll.y, pitch.x, pitch.y) per entry
     const size_t item = blockIdx.x;
-    const size_t n = n_dev ? (size_t)n_dev[item] : n_fixed;
+    size_t n = n_dev ? (size_t)n_dev[item] : n_fixed;
+    if (n > n_fixed) n = n_fixed;                      // a device-side count never reaches past the n_fixed records the launch was sized for
     const float eps = almeida_eps();
     if (n < min_n) {                                   // lib.rs:247-251: fewer than 3 inliers -> identity
         if (threadIdx.x == 0) out_quat[item] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
@@ -668,7 +669,8 @@ template <bool FAST>
 __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __restrict__ entries, size_t n, int it,
                                                                 Camera cam, const float* __restrict__ part_prev,
                                                                 float* __restrict__ part_out, Quat* __restrict__ state,
-                                                                int batch, float4* __restrict__ out_quat) {
+                                                                int batch, float4* __restrict__ out_quat,
+                                                                const uint32_t* __restrict__ n_dev, uint32_t min_n) {
     // dense variant: the first PRE entries of every thread are loaded, and everything about them that does not need the
     // new rotation (unprojection, the three prototypes, the A sums) is computed, BEFORE the workgroup waits for the
     // fold + update of the previous step -- that prologue is a chain of dependent global loads and ~400 serial
@@ -681,6 +683,10 @@ __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __
     __shared__ float4 plds[FAST ? PRE * 1024 : 1];
     const size_t item = blockIdx.y;
     const int nblk = gridDim.x;
+    // n_dev (optional): the record count lives on the device -- the launch partitions the n records it was sized for, the workgroup reads
+    // the count once and works on the first min(*n_dev, n) of them
+    const float4* __restrict__ ent = entries + item * n;
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     const float eps = almeida_eps();
     const Mat3 mroll = mat3_from_euler(0.0f, eps, 0.0f);
     const Mat3 mpitch = mat3_from_euler(eps, 0.0f, 0.0f);
@@ -706,7 +712,7 @@ __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __
 #pragma unroll
             for (int k = 0; k < PRE; ++k) {
                 const size_t i = i0 + (size_t)k * istride;
-                pre[k] = i < n ? entries[item * n + i] : make_float4(0.5f, 0.5f, 0.0f, 0.0f);
+                pre[k] = i < n ? ent[i] : make_float4(0.5f, 0.5f, 0.0f, 0.0f);
             }
 #pragma unroll
             for (int k = 0; k < PRE; ++k) {
@@ -750,7 +756,8 @@ __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __
     const Quat rotation = rot_sh;
     if (it == kIters) {                                  // epilogue launch: publish the result
         if (blockIdx.x == 0 && threadIdx.x == 0)
-            out_quat[item] = make_float4(rotation.w, -rotation.i, -rotation.j, -rotation.k);
+            out_quat[item] = n < min_n ? make_float4(1.0f, 0.0f, 0.0f, 0.0f)                    // lib.rs:247-251: fewer than 3 inliers -> identity
+                                       : make_float4(rotation.w, -rotation.i, -rotation.j, -rotation.k);
         return;
     }
     const Mat3 rotm = quat_to_mat3(rotation);
@@ -769,7 +776,7 @@ __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __
         }
     }
     for (size_t i = i0 + (size_t)PRE * istride; i < n; i += istride) {
-        const float4 e = entries[item * n + i];
+        const float4 e = ent[i];
         const Unproj un = cam_unproject<FAST>(cam, e.x, e.y);
         const float2 d = cam_delta_w<FAST>(cam, e.x, e.y, un, rotm);
         const float2 pr = cam_delta_w<FAST>(cam, e.x, e.y, un, mroll);
@@ -1041,8 +1048,18 @@ __global__ __launch_bounds__(BLOCK) void almeida_lsq_cluster_kernel(const float4
                                                                    const DeltaConsts dk, gran_u4* gran, uint32_t tag_base,
                                                                    float4* __restrict__ out_quat,
                                                                    unsigned long long* __restrict__ prof, uint32_t fault_arg, int hier_mode,
-                                                                   unsigned long long* __restrict__ recoveries, int spread) {
+                                                                   unsigned long long* __restrict__ recoveries, int spread,
+                                                                   const uint32_t* __restrict__ n_dev, uint32_t min_n) {
     if (spread > 1 && (blockIdx.x % (unsigned)spread) != 0) return;     // one-XCD launch: the workgroups dealt to the other XCDs
+    // n_dev (optional): the record count lives on the device.  The launch -- workgroups, records per thread, arithmetic -- was sized from
+    // n alone; every workgroup reads the count ONCE (a scalar load, uniform) and the slots past min(*n_dev, n) are the all-zero dummies
+    // a ragged last workgroup already has: workgroups without a record publish exact zeros and take part in every exchange.
+    const float4* __restrict__ ent_item = entries + (size_t)blockIdx.y * n;
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
+    if (n < min_n) {                                                    // lib.rs:247-251: fewer than 3 inliers -> identity (uniform over the launch: nobody waits for anybody)
+        if (blockIdx.x == 0 && threadIdx.x == 0) out_quat[blockIdx.y] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
     // fault (libofps_hip_testhooks.so only; compiled out of the product library): workgroup fault-1 withholds its step-3
     // granule, which is what a workgroup that never became resident looks like to the others -- exercises the timeout
     // and the in-kernel recovery (almeida_solo_solve)
@@ -1098,7 +1115,7 @@ __global__ __launch_bounds__(BLOCK) void almeida_lsq_cluster_kernel(const float4
     float s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (threadIdx.x == 0) {                              // slot 1 = rotation entering step 0
         fail_sh = 0; hier_sh = 0; rot_sh[1] = Quat{1.0f, 0.0f, 0.0f, 0.0f};
-        cold_sh.entries = entries + item * n; cold_sh.n = n; cold_sh.cam = cam; cold_sh.out = out_quat + item;
+        cold_sh.entries = ent_item; cold_sh.n = n; cold_sh.cam = cam; cold_sh.out = out_quat + item;
         cold_sh.recoveries = recoveries; cold_sh.flag = ff.p; cold_sh.tag = ff.tag;
         if (hier_mode) {
             const uint32_t me = (((tag_base + 1u) & 0xFFFFu) << 16) | ((uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFFu);   // HW_REG_XCC_ID
@@ -1110,7 +1127,7 @@ __global__ __launch_bounds__(BLOCK) void almeida_lsq_cluster_kernel(const float4
     for (int t = 0; t < EPT; ++t) {
         const size_t i = ((size_t)blk * EPT + t) * BLOCK + threadIdx.x;
         ok[t] = i < n;
-        e[t] = ok[t] ? entries[item * n + i] : make_float4(0.5f, 0.5f, 0.0f, 0.0f);
+        e[t] = ok[t] ? ent_item[i] : make_float4(0.5f, 0.5f, 0.0f, 0.0f);
     }
 #pragma unroll
     for (int t = 0; t < EPT; ++t) {
@@ -1421,9 +1438,13 @@ __device__ __forceinline__ Quat almeida_update_quad_lu(const Quat& rotation, con
 
 constexpr int kHypPerWave = 16;
 
+// n_dev (optional, all three RANSAC kernels): the record count lives on the device -- n is then the capacity the launches were sized
+// for, and n = min(*n_dev, n), ns = min(ns, n) are formed here, so the sampler draws what a host-n call with that n draws
 __global__ __launch_bounds__(64) void ransac_hyp_kernel(const float4* __restrict__ entries, uint32_t n, uint32_t iters,
-                                                        uint64_t seed, Camera cam, Mat3* __restrict__ hyp) {
+                                                        uint64_t seed, Camera cam, Mat3* __restrict__ hyp, const uint32_t* __restrict__ n_dev) {
     const size_t item = blockIdx.y;
+    const float4* __restrict__ ent = entries + item * n;
+    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; if (n == 0) return; }      // (no record to draw: the count kernel finds no inlier)
     const int q = threadIdx.x & 3;
     const uint32_t it_raw = blockIdx.x * kHypPerWave + (threadIdx.x >> 2);
     const bool live = it_raw < iters;
@@ -1435,7 +1456,7 @@ __global__ __launch_bounds__(64) void ransac_hyp_kernel(const float4* __restrict
                myaw = mat3_from_euler(0.0f, 0.0f, -eps);
     // this lane's sample (lane 3 of a quad, and lanes past n3, carry a harmless copy of sample 0: their terms are never added)
     const uint32_t j = (uint32_t)q < n3 ? (uint32_t)q : 0u;
-    const float4 e = entries[item * n + sample_index(sk, j, n)];
+    const float4 e = ent[sample_index(sk, j, n)];
     const float2 pr = cam_delta(cam, e.x, e.y, mroll);
     const float2 pp = cam_delta(cam, e.x, e.y, mpitch);
     const float2 py = cam_delta(cam, e.x, e.y, myaw);
@@ -1479,9 +1500,11 @@ constexpr int kCountThreads = 1024;
 __global__ __launch_bounds__(kCountThreads) void ransac_count_kernel(const float4* __restrict__ entries, uint32_t n, uint32_t ns,
                                                            uint32_t iters, uint64_t seed, Camera cam, float fx, float fy,
                                                            float thr2, const Mat3* __restrict__ hyp,
-                                                           uint32_t* __restrict__ counts) {
+                                                           uint32_t* __restrict__ counts, const uint32_t* __restrict__ n_dev) {
     __shared__ uint32_t total;
     const size_t item = blockIdx.y;
+    const float4* __restrict__ ent = entries + item * n;
+    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
     const uint32_t it = blockIdx.x;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
@@ -1489,7 +1512,7 @@ __global__ __launch_bounds__(kCountThreads) void ransac_count_kernel(const float
     const SampleKey sk = sample_key(seed + item, it, 1, n);
     uint32_t c = 0;
     for (uint32_t j = threadIdx.x; j < ns; j += kCountThreads) {
-        const float4 e = entries[item * n + sample_index(sk, j, n)];
+        const float4 e = ent[sample_index(sk, j, n)];
         c += ransac_is_inlier(cam, fx, fy, mat, e, thr2) ? 1u : 0u;
     }
 #pragma unroll
@@ -1506,10 +1529,13 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float4* __res
                                                              float thr2, const Mat3* __restrict__ hyp,
                                                              const uint32_t* __restrict__ counts,
                                                              float4* __restrict__ sel, uint32_t* __restrict__ sel_idx,
-                                                             uint32_t* __restrict__ sel_n) {
+                                                             uint32_t* __restrict__ sel_n, const uint32_t* __restrict__ n_dev) {
     __shared__ unsigned long long best;
     __shared__ uint32_t base;
     const size_t item = blockIdx.x;
+    const float4* __restrict__ ent = entries + item * n;
+    const size_t sel_stride = ns;                  // sel[item][0 .. ns): the capacity, whatever the count turns out to be
+    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
     if (threadIdx.x == 0) { best = 0; base = 0; }
     __syncthreads();
     unsigned long long k = 0;
@@ -1540,7 +1566,7 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float4* __res
         float4 e = make_float4(0, 0, 0, 0);
         if (j < ns) {
             idx = sample_index(sk, j, n);
-            e = entries[item * n + idx];
+            e = ent[idx];
             in = ransac_is_inlier(cam, fx, fy, mat, e, thr2);
         }
         const unsigned long long bal = __ballot(in);
@@ -1551,8 +1577,8 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float4* __res
         for (int k = 0; k < 16; ++k) { const uint32_t v = wave_cnt[par][k]; total += v; before += k < wave ? v : 0u; }
         if (in) {
             const uint32_t pos = run + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            sel[item * ns + pos] = e;
-            if (sel_idx) sel_idx[item * ns + pos] = idx;
+            sel[item * sel_stride + pos] = e;
+            if (sel_idx) sel_idx[item * sel_stride + pos] = idx;
         }
         run += total;
     }
@@ -1590,7 +1616,8 @@ void cluster_gate_context_destroyed(int device) {
 
 template <bool FAST, int EPT, int BLOCK = 1024>
 static void launch_cluster(ofps_hip_ctx* ctx, hipStream_t s, int nblk, int items, const float4* d_entries, size_t n, const Camera& cam,
-                           gran_u4* gran, uint32_t tag_base, float4* d_quat, unsigned long long* prof, unsigned long long* recoveries) {
+                           gran_u4* gran, uint32_t tag_base, float4* d_quat, unsigned long long* prof, unsigned long long* recoveries,
+                           const uint32_t* d_n, uint32_t min_n) {
     const uint32_t fault = (uint32_t)ctx->opt.test_almeida_fault;   // always 0 in the product library (ofps_hip_set_option refuses it)
     int hier_mode = ctx->opt.almeida_hier;                    // 0 never, 1 when it pays (>= kHierMinBlocks workgroups), 2 always (A/B, tests)
     if (hier_mode == 1 && nblk < kHierMinBlocks) hier_mode = 0;     // few workgroups: the flat gather is as fast and needs no XCC_ID round
@@ -1603,11 +1630,13 @@ static void launch_cluster(ofps_hip_ctx* ctx, hipStream_t s, int nblk, int items
         ctx->stream_cus >= ctx->num_cus) { spread = 8; hier_mode = 3; }
     hipLaunchKernelGGL((almeida_lsq_cluster_kernel<FAST, EPT, BLOCK>), dim3(nblk * spread, items), dim3(BLOCK), 0, s, d_entries, n, cam,
                        delta_consts(cam), gran,
-                       tag_base, d_quat, prof, fault, hier_mode, recoveries, spread);
+                       tag_base, d_quat, prof, fault, hier_mode, recoveries, spread, d_n, min_n);
 }
 
 // -> 1 launched, 0 not applicable (caller falls back to the launch-per-step kernel), < 0 error
-static int lsq_cluster(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const Camera& cam, float4* d_quat) {
+// d_n (optional, batch == 1): the record count on the device; everything below is chosen from n, the capacity
+static int lsq_cluster(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const Camera& cam, float4* d_quat,
+                       const uint32_t* d_n = nullptr, uint32_t min_n = 0) {
     // records per thread: fewer = less arithmetic per step on the critical path, more = fewer workgroups to gather from
     // and -- for batches -- more items whose workgroups are co-resident in one launch.  Cost model fitted to
     // tools/almeida_prof.py (ms per launch ~ 0.11 + 0.004 * ept + 0.00001 * workgroups per item, + 0.006 when the gather has
@@ -1688,16 +1717,16 @@ static int lsq_cluster(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int
             else if (last != s) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ev, 0));  // (a barrier packet costs ~4 us in front of the kernel)
             last = s;
         }
-        if (block == 256 && ept >= 4) launch_cluster<false, 4, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (block == 256 && ept == 2) launch_cluster<false, 2, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (block == 256) launch_cluster<false, 1, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (dense && ept == 8) launch_cluster<true, 8>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (dense && ept == 4) launch_cluster<true, 4>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (dense && ept == 2) launch_cluster<true, 2>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (dense) launch_cluster<true, 1>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (ept == 4) launch_cluster<false, 4>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else if (ept == 2) launch_cluster<false, 2>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
-        else launch_cluster<false, 1>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries);
+        if (block == 256 && ept >= 4) launch_cluster<false, 4, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (block == 256 && ept == 2) launch_cluster<false, 2, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (block == 256) launch_cluster<false, 1, 256>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (dense && ept == 8) launch_cluster<true, 8>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (dense && ept == 4) launch_cluster<true, 4>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (dense && ept == 2) launch_cluster<true, 2>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (dense) launch_cluster<true, 1>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (ept == 4) launch_cluster<false, 4>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else if (ept == 2) launch_cluster<false, 2>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
+        else launch_cluster<false, 1>(ctx, s, nblk, items, ent, n, cam, gran, tag_base, q, prof, recoveries, d_n, min_n);
         OFPS_HIP_TRY(ctx, hipGetLastError());
         if (gated) OFPS_HIP_TRY(ctx, hipEventRecord(ev, s));
     }
@@ -1736,7 +1765,8 @@ static int lsq_cluster(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int
     return 1;
 }
 
-static int lsq_stepped(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, int batch, const Camera& cam, float4* d_quat) {
+static int lsq_stepped(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, int batch, const Camera& cam, float4* d_quat,
+                       const uint32_t* d_n = nullptr, uint32_t min_n = 0) {
     hipStream_t s = ctx->stream;
     // enough workgroups to fill the chip, few enough that the fixed-order fold stays short
     const size_t per_wg = n_max > 65536 ? 8 * 1024 : 1024;
@@ -1753,18 +1783,21 @@ static int lsq_stepped(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max,
     for (int it = 0; it <= kIters; ++it) {
         if (dense)
             hipLaunchKernelGGL(almeida_lsq_step_kernel<true>, dim3(nblk, batch), dim3(1024), 0, s, d_entries, n_max, it, cam,
-                               pa, pb, state, batch, d_quat);
+                               pa, pb, state, batch, d_quat, d_n, min_n);
         else
             hipLaunchKernelGGL(almeida_lsq_step_kernel<false>, dim3(nblk, batch), dim3(1024), 0, s, d_entries, n_max, it, cam,
-                               pa, pb, state, batch, d_quat);
+                               pa, pb, state, batch, d_quat, d_n, min_n);
         float* t = pa; pa = pb; pb = t;
     }
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
 
+// multi: a device-side count (d_n) may take the cluster and the launch-per-step solver too -- one problem, every choice below made from
+// n_max alone.  Without it a device-side count keeps to the one-workgroup solver, as the RANSAC refit of a host-n call always has.
 static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride, size_t n_max, const uint32_t* d_n,
-                      uint32_t min_n, int batch, const Camera& cam, float4* d_quat) {
+                      uint32_t min_n, int batch, const Camera& cam, float4* d_quat, bool multi = false) {
+    const bool any_path = d_n == nullptr || (multi && batch == 1);
     hipStream_t s = ctx->stream;
     // One-workgroup solver: one launch, 30 steps at 2.5-6 us each on a single CU (0.076 ms at N = 576, 0.185 ms at
     // N = 8,040, flat up to 256 items) -- the path for batches of block-vector sized problems and mandatory when the
@@ -1772,14 +1805,14 @@ static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride,
     // the cluster solver (one launch, granule exchange between co-resident workgroups); what it cannot hold
     // (N > 256 x 8192) or a forced A/B run takes one launch per step.
     bool wg_path = n_max <= 8192;
-    bool cluster = d_n == nullptr && stride == n_max;
+    bool cluster = any_path && stride == n_max;
     size_t cluster_min = batch == 1 ? 1536 : 8192;                       // lone problems above this size use the cluster (one XCD: 0.061 ms at any size up to 8,040; the
                                                                          // one-workgroup solver: 1,280 vectors 0.055, 1,600 0.062, 2,048 0.066 -- tools/almeida_threshold_ab.py)
-    if (ctx->opt.almeida_path == 1 && d_n == nullptr) { wg_path = false; cluster = false; }   // A/B experiments only (OFPS_HIP_ALMEIDA_PATH)
+    if (ctx->opt.almeida_path == 1 && any_path) { wg_path = false; cluster = false; }   // A/B experiments only (OFPS_HIP_ALMEIDA_PATH)
     if (ctx->opt.almeida_path == 2) cluster = false;
     if (ctx->opt.almeida_path == 3) cluster_min = 0;
     if (cluster && n_max > cluster_min && n_max > 0) {
-        const int rc = lsq_cluster(ctx, d_entries, n_max, batch, cam, d_quat);
+        const int rc = lsq_cluster(ctx, d_entries, n_max, batch, cam, d_quat, d_n, min_n);
         if (rc != 0) return rc < 0 ? rc : OFPS_HIP_OK;
     }
     if (wg_path) {
@@ -1791,19 +1824,22 @@ static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride,
         OFPS_HIP_TRY(ctx, hipGetLastError());
         return OFPS_HIP_OK;
     }
-    OFPS_REQUIRE(ctx, d_n == nullptr && stride == n_max, "almeida: device-side counts need n <= 8192");
-    return lsq_stepped(ctx, d_entries, n_max, batch, cam, d_quat);
+    OFPS_REQUIRE(ctx, any_path && stride == n_max, "almeida: per-item device-side counts need n <= 8192");
+    return lsq_stepped(ctx, d_entries, n_max, batch, cam, d_quat, d_n, min_n);
 }
 
-int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
-                          int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed,
-                          float4* d_quat) {
+// d_n == nullptr: n records per item, known to the host.  d_n != nullptr (batch == 1): the estimate over the first min(*d_n, n) of n
+// records, the count read on the device -- no launch, grid or path depends on it, nothing is read back.
+static int almeida_impl(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, const uint32_t* d_n, int batch, float aspect, float fov_y_deg,
+                        int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed,
+                        float4* d_quat) {
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "almeida: batch %d out of range", batch);
+    OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "almeida: a device-side count is for one problem (batch %d)", batch);
     OFPS_REQUIRE(ctx, n < (1ull << 31), "almeida: too many entries");
     OFPS_REQUIRE(ctx, aspect > 0.0f && fov_y_deg > 0.0f && fov_y_deg < 180.0f, "almeida: bad camera (aspect=%g fov_y=%g)",
                  (double)aspect, (double)fov_y_deg);
     const Camera cam = camera_new(aspect, fov_y_deg);
-    if (!use_ransac) return lsq_device(ctx, d_entries, n, n, nullptr, 0, batch, cam, d_quat);
+    if (!use_ransac) return lsq_device(ctx, d_entries, n, n, d_n, 0, batch, cam, d_quat, /*multi=*/true);
 
     OFPS_REQUIRE(ctx, num_iters >= 1 && num_iters <= 65535, "almeida: ransac iters %zu out of range", num_iters);
     OFPS_REQUIRE(ctx, num_samples >= 1, "almeida: ransac samples must be >= 1");
@@ -1823,15 +1859,17 @@ int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
         OFPS_HIP_TRY(ctx, hipMemsetAsync(sel_n, 0, (size_t)batch * sizeof(uint32_t), s));
     } else {
         hipLaunchKernelGGL(ransac_hyp_kernel, dim3((iters + kHypPerWave - 1) / kHypPerWave, batch), dim3(64), 0, s, d_entries, (uint32_t)n, iters,
-                           seed, cam, hyp);
+                           seed, cam, hyp, d_n);
         hipLaunchKernelGGL(ransac_count_kernel, dim3(iters, batch), dim3(kCountThreads), 0, s, d_entries, (uint32_t)n, ns, iters, seed,
-                           cam, fx, fy, thr2, hyp, counts);
+                           cam, fx, fy, thr2, hyp, counts, d_n);
         hipLaunchKernelGGL(ransac_select_kernel, dim3(batch), dim3(1024), 0, s, d_entries, (uint32_t)n, ns, iters, seed, cam,
-                           fx, fy, thr2, hyp, counts, sel, (uint32_t*)nullptr, sel_n);
+                           fx, fy, thr2, hyp, counts, sel, (uint32_t*)nullptr, sel_n, d_n);
     }
     OFPS_HIP_TRY(ctx, hipGetLastError());
     const size_t cap = ns ? ns : 1;
     if (cap <= 8192) return lsq_device(ctx, sel, cap, cap, sel_n, 3, batch, cam, d_quat);
+    // (the device-count form never reads anything back: its refit takes the cluster / launch-per-step solver with the inlier count on the device)
+    if (d_n) return lsq_device(ctx, sel, cap, cap, sel_n, 3, 1, cam, d_quat, /*multi=*/true);
     // "Ransac samples" can reach 16000 (lib.rs:92-95): refit sets above 8192 need their size on the
     // host to pick the multi-launch path -- one small read-back per item.
     for (int b = 0; b < batch; ++b) {
@@ -1844,6 +1882,17 @@ int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
         if (rc != OFPS_HIP_OK) return rc;
     }
     return OFPS_HIP_OK;
+}
+
+int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
+                   int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat) {
+    return almeida_impl(ctx, d_entries, n, nullptr, batch, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat);
+}
+
+int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
+                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat) {
+    OFPS_REQUIRE(ctx, d_n, "almeida: null device count");
+    return almeida_impl(ctx, d_entries, n_max, d_n, 1, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat);
 }
 
 }  // namespace ofps

@@ -136,6 +136,9 @@ struct DenseStream {
         void* pinned = nullptr; size_t pinned_cap = 0;
         int have_vectors = 0, gw = 0, gh = 0;
         size_t max_records = 0;
+        // fused form (ofps_hip_lk_push_frame_fused[_async]): the tail's results sit behind the records, at tail_off of the block
+        int fused = 0, run_detector = 0, run_estimator = 0, dim = 0;
+        size_t tail_off = 0;
     };
     TicketRing<Ticket, kTickets> ring;
     void* decode_pinned = nullptr; size_t decode_pinned_cap = 0;     // ofps_hip_lk_decode's block: a pair's records + their count (one wait)
@@ -199,7 +202,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 40;
+    static constexpr int kNumScratch = 44;
     Scratch scratch[kNumScratch];
 };
 
@@ -221,10 +224,11 @@ enum ScratchSlot {
     S_LK_MASKS,             // dense decoders, stream forms: one contrast mask per ticket in flight (made on the upload's stream, beside the previous pair's flow)
     S_SAD_QBEST,            // sad_qpel.hip: the integer winners when the caller of a quarter-pel search passes no out_best
     S_FE_RAW,               // frontend.hip: the frames as they arrive (colour and / or full size) when the decoder resizes / converts them: one per ticket in flight
-    S_FE_RAW_PAIR           // ... of the stateless calls (ofps_hip_lk_decode, ofps_hip_cv_frontend, ofps_hip_resize_linear): never the stream's staging, whose
+    S_FE_RAW_PAIR,          // ... of the stateless calls (ofps_hip_lk_decode, ofps_hip_cv_frontend, ofps_hip_resize_linear): never the stream's staging, whose
                             // upload + front-end may still be running on the upload stream when such a call comes in
+    S_DENSE_REC             // dense decoders, fused stream form: [count, pad x 3][records] of the newest pair, in device memory for the detector + estimator
 };
-static_assert(S_FE_RAW_PAIR < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_DENSE_REC < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -250,11 +254,13 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);
+// d_n (densify_device, densify_device_raw, detect_device; optional, batch == 1): the entry count lives in device memory -- n is the capacity,
+// the first min(*d_n, n) entries count, and nothing about the launches depends on the count
 int densify_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
-                   uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end);
+                   uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, const uint32_t* d_n = nullptr);
 int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
                        uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, float2* d_sum, float* d_cnt,
-                       const float* d_weights);
+                       const float* d_weights, const uint32_t* d_n = nullptr);
 int densify_entries_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int w, int h, float2* d_field,
                            float4* d_out_entries, uint32_t* d_count);
 int densify_raster_device(ofps_hip_ctx* ctx, const float4* d_entries, const uint8_t* d_mask, int W, int H, int w, int h,
@@ -272,7 +278,7 @@ int compact_entries_device(ofps_hip_ctx* ctx, const float4* d_in, const uint8_t*
 constexpr size_t kCompactSmallMax = 32768;          // record sets up to this size are compacted by one workgroup, straight to their destination (mask.hip)
 int compact_small_device(ofps_hip_ctx* ctx, const float4* d_in, const uint8_t* d_mask, size_t n, float4* d_out, uint32_t* d_count);
 int detect_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float min_size, size_t subdivide,
-                  float target_motion, int* d_result, float2* d_out_field, int* out_dim);
+                  float target_motion, int* d_result, float2* d_out_field, int* out_dim, const uint32_t* d_n = nullptr);
 int farneback_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int winsize,
                           int iters, int poly_n, double poly_sigma, const float2* d_init, float2* d_flow, float4* d_entries,
                           uint64_t prev_id = 0, uint64_t cur_id = 0);     // ids != 0: frames of a stream (FarnebackState::cache)
@@ -284,6 +290,9 @@ void cluster_gate_context_created(int device);      // almeida.hip: the cluster 
 void cluster_gate_context_destroyed(int device);
 int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
                    int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
+// one problem whose record count lives in device memory: the estimate over the first min(*d_n, n_max) records; every launch is sized from n_max
+int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
+                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
 
 // ---- transfers (transfer.hip)
 bool device_address_of(const void* host_ptr, void** dev_ptr);        // the device address of page-locked host memory, or false for pageable memory

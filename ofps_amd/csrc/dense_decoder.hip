@@ -1,5 +1,7 @@
 // dense_decoder.hip -- the dense decoders ("hip_lk" and "hip_flow", full-resolution and reduced) as a stage chain and as a read-ahead stream
-// (ofps_hip_lk_decode / ofps_hip_lk_push_frame[_async] / ofps_hip_lk_frame_wait; state: common.hpp DenseStream).  No flow kernel lives here.
+// (ofps_hip_lk_decode / ofps_hip_lk_push_frame[_async] / ofps_hip_lk_frame_wait; state: common.hpp DenseStream), and the same stream with the
+// detector and the estimator behind the decoder in the same ticket (ofps_hip_lk_push_frame_fused[_async] / ofps_hip_lk_frame_fused_wait).
+// No flow kernel lives here.
 //
 // The body of a Decoder::process_frame (cv-decoder/src/lib.rs:82-294): dense flow (lk.hip, or farneback.hip with OFPS_HIP_FLOW_FARNEBACK),
 // per-pixel records, optionally filtered by the contrast mask of :203-237 (OFPS_HIP_LK_CONTRAST_MASK, computed on `cur` like the
@@ -88,7 +90,11 @@ __global__ __launch_bounds__(256) void dense_copy_records_kernel(const float4* _
 // block (the kernels store there directly: no read-back launch of their own).
 int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int levels, int radius, int iters,
                      const DenseGrid& g, float4* rec_dst, uint32_t* cnt_dst, uint64_t prev_id = 0,
-                     uint64_t cur_id = 0, const uint8_t* d_mask_ready = nullptr) {
+                     uint64_t cur_id = 0, const uint8_t* d_mask_ready = nullptr, const float4** tail_rec = nullptr,
+                     const uint32_t** tail_cnt = nullptr) {
+    // tail_rec / tail_cnt (fused form): where a tail finds the records and their count in DEVICE memory -- rec_dst / cnt_dst, which the
+    // caller then points at device scratch, or the compaction's own output, which is then not copied to rec_dst at all
+    if (tail_rec) { *tail_rec = rec_dst; *tail_cnt = cnt_dst; }
     const size_t px = (size_t)W * H, cells = g.per_pixel ? 1 : (size_t)g.gw * g.gh;
     auto* d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_ENTRIES, px * sizeof(float4)));
     auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_FIELD, cells * sizeof(float2)));
@@ -138,6 +144,7 @@ int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t*
             rc = ofps::compact_entries_device(ctx, d_ent, d_mask, px, d_ent2, d_cnt + 1);
             if (rc != OFPS_HIP_OK) return rc;
             d_rec = d_ent2; d_n = d_cnt + 1;
+            if (tail_rec) { *tail_rec = d_ent2; *tail_cnt = d_cnt + 1; return OFPS_HIP_OK; }      // (the caller's one copy fills the block from here)
         }
         hipLaunchKernelGGL(dense_copy_records_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_rec, rec_dst, d_n, px, cnt_dst);
         OFPS_HIP_TRY(ctx, hipGetLastError());
@@ -148,7 +155,9 @@ int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t*
     return ofps::densify_raster_entries_device(ctx, d_ent, d_mask, W, H, g.gw, g.gh, d_field, rec_dst, cnt_dst);
 }
 
-constexpr size_t kBlockHeader = 16;             // a page-locked result block: [count, pad x 3][records]
+constexpr size_t kBlockHeader = 16;             // a page-locked result block: [count, pad x 3][records]; a fused ticket's goes on behind
+                                                // the records' capacity with [has_motion, area, dim, 0][quaternion][detector field 2 * dim * dim]
+constexpr size_t kTailResult = 0, kTailQuat = 16, kTailField = 32;
 
 // count + records of a finished block -> the caller's buffer
 void dense_collect(const void* pinned, size_t max_records, float* out_entries, size_t* n_out) {
@@ -178,51 +187,35 @@ int dense_stream_drain(ofps_hip_ctx* ctx) {
     return OFPS_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ofps_hip_lk_decode(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels,
-                       int radius, int iters, int max_w, int max_h, unsigned flags, float* out_entries, size_t* n_out,
-                       int* out_w, int* out_h) {
+// One frame of the dense decoders' stream.  tail == nullptr: ofps_hip_lk_push_frame_async, the records go straight to the ticket's block.
+// tail != nullptr: ofps_hip_lk_push_frame_fused_async -- the records and their count are kept in device memory (S_DENSE_REC), copied to
+// the block from there, and the detector and / or the estimator run on them behind the decoder, the count staying on the device.
+// Everything of a ticket is enqueued on the compute stream: ticket k's tail has read the records (and detect_device's / almeida's workspaces
+// are free again) before ticket k + 1's output stage writes them -- stream order is the join, no per-ticket copy of the tail's inputs.
+int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters, int max_w, int max_h,
+               unsigned flags, const ofps_hip_frame_params* tail, int* ticket, const char* who) {
     if (!ctx) return OFPS_HIP_EINVAL;
-    OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "lk_decode: null host pointer");
-    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "lk_decode: bad geometry");
-    OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "lk_decode: unknown flags 0x%x", flags);
-    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DenseGrid g;
-    int rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, "lk_decode", &g);
-    if (rc != OFPS_HIP_OK) return rc;
-    const size_t px = (size_t)g.fw * g.fh, raw_bytes = g.raw_row * (size_t)H;
-    auto* d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * px));
-    auto* d_raw = g.frontend ? static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FE_RAW_PAIR, 2 * raw_bytes)) : nullptr;
-    if (!d_frames || (g.frontend && !d_raw)) return OFPS_HIP_ENOMEM;
-    rc = dense_upload_frame(ctx, g, prev, W, H, stride, d_raw, d_frames, ctx->stream);
-    if (rc != OFPS_HIP_OK) return rc;
-    rc = dense_upload_frame(ctx, g, cur, W, H, stride, d_raw ? d_raw + raw_bytes : nullptr, d_frames + px, ctx->stream);
-    if (rc != OFPS_HIP_OK) return rc;
-    // the count and the records come back in ONE page-locked block and one wait; only the visited cells' records reach the
-    // caller's buffer
-    rc = ofps::host_block_reserve(ctx, &ctx->dense.decode_pinned, &ctx->dense.decode_pinned_cap, kBlockHeader + g.max_records * sizeof(float4));
-    if (rc != OFPS_HIP_OK) return rc;
-    void* mapped = nullptr;
-    OFPS_REQUIRE(ctx, ofps::device_address_of(ctx->dense.decode_pinned, &mapped), "lk_decode: page-locked block is not device-addressable");
-    rc = dense_enqueue_frame(ctx, d_frames, d_frames + px, g.fw, g.fh, levels, radius, iters, g, reinterpret_cast<float4*>(static_cast<char*>(mapped) + kBlockHeader),
-                             static_cast<uint32_t*>(mapped));
-    if (rc != OFPS_HIP_OK) return rc;
-    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    dense_collect(ctx->dense.decode_pinned, g.max_records, out_entries, n_out);
-    if (out_w) *out_w = g.gw;
-    if (out_h) *out_h = g.gh;
-    return OFPS_HIP_OK;
-}
-
-int ofps_hip_lk_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters,
-                                 int max_w, int max_h, unsigned flags, int* ticket) {
-    if (!ctx) return OFPS_HIP_EINVAL;
-    OFPS_REQUIRE(ctx, frame && ticket, "lk_push_frame_async: null pointer");
-    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "lk_push_frame_async: bad geometry");
-    OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "lk_push_frame_async: unknown flags 0x%x", flags);
+    OFPS_REQUIRE(ctx, frame && ticket, "%s: null pointer", who);
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "%s: bad geometry", who);
+    OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "%s: unknown flags 0x%x", who, flags);
+    int dim = 0;
+    if (tail) {
+        // refused before anything is uploaded, the stream's first frame (which runs no tail) included
+        if (flags & OFPS_HIP_LK_FULLRES_RECORDS)
+            return ofps::set_error(ctx, OFPS_HIP_EUNSUPPORTED, "%s: OFPS_HIP_LK_FULLRES_RECORDS has no fused form (ofps_hip_lk_flow_dev -> "
+                                   "ofps_hip_almeida_dev / ofps_hip_densify_raster_dev is that chain, with a count the host knows)", who);
+        if (tail->run_detector) {
+            dim = ofps_hip_block_dim(tail->min_size, tail->subdivide);
+            OFPS_REQUIRE(ctx, dim >= 1 && dim <= 160, "%s: detector block_dim %d outside [1,160] (min_size=%g subdivide=%zu)", who, dim,
+                         (double)tail->min_size, tail->subdivide);
+        }
+        if (tail->run_estimator) {
+            OFPS_REQUIRE(ctx, tail->aspect > 0.0f && tail->fov_y_deg > 0.0f && tail->fov_y_deg < 180.0f, "%s: bad camera (aspect=%g fov_y=%g)", who,
+                         (double)tail->aspect, (double)tail->fov_y_deg);
+            OFPS_REQUIRE(ctx, !tail->use_ransac || (tail->num_iters >= 1 && tail->num_iters <= 65535 && tail->num_samples >= 1),
+                         "%s: ransac iters %zu / samples %zu out of range", who, tail->num_iters, tail->num_samples);
+        }
+    }
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = dense_stream_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
@@ -230,11 +223,11 @@ int ofps_hip_lk_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W,
     constexpr int kSlots = ofps::DenseStream::kSlots, kTickets = ofps::DenseStream::kTickets;
     DenseGrid g;
     // (a stream's first frame runs no flow: the flow's parameters -- Farneback's own limits included -- are refused here, not one frame later)
-    rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, "lk_push_frame_async", &g);
+    rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, who, &g);
     if (rc != OFPS_HIP_OK) return rc;
     const long tno = ds.ring.next;
     auto& t = ds.ring.at(tno);
-    OFPS_REQUIRE(ctx, !t.pending, "lk_push_frame_async: ticket %ld has not been collected (at most %d frames in flight)",
+    OFPS_REQUIRE(ctx, !t.pending, "%s: ticket %ld has not been collected (at most %d frames in flight)", who,
                  tno - kTickets, kTickets);
     const size_t px = (size_t)g.fw * g.fh, raw_bytes = g.raw_row * (size_t)H;      // the ring holds the frames the flow reads (reduced / converted)
     // A new geometry restarts the stream and may reallocate the ring.  With a ticket in flight that would throw its records away
@@ -246,13 +239,13 @@ int ofps_hip_lk_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W,
     const bool restart = ds.w != W || ds.h != H || ds.fw != g.fw || ds.fh != g.fh || ds.fmt != g.fmt ||
                          ctx->scratch[ofps::S_LK_FRAMES].cap < kSlots * px ||
                          (g.frontend && ctx->scratch[ofps::S_FE_RAW].cap < kTickets * raw_bytes);
-    OFPS_REQUIRE(ctx, !(restart && other_pending), "lk_push_frame_async: geometry change %dx%d -> %dx%d with a ticket in flight "
-                 "(collect it with ofps_hip_lk_frame_wait first)", ds.w, ds.h, W, H);
+    OFPS_REQUIRE(ctx, !(restart && other_pending), "%s: geometry change %dx%d -> %dx%d with a ticket in flight "
+                 "(collect it with ofps_hip_lk_frame_wait first)", who, ds.w, ds.h, W, H);
     // hip_flow expands a new frame ahead of its pair, into the plane slot of the oldest frame of THIS parameter set: other Farneback parameters
     // re-plan the workspace (other layers), which a flow still in flight would be reading -- refused like a geometry change
     const bool fb_params_changed = g.farneback && ds.fb_params_valid && (ds.fb_levels != levels || ds.fb_radius != radius);
-    OFPS_REQUIRE(ctx, !(fb_params_changed && other_pending), "lk_push_frame_async: Farneback parameters changed (levels %d -> %d, radius %d -> %d) with a "
-                 "ticket in flight (collect it with ofps_hip_lk_frame_wait first)", ds.fb_levels, levels, ds.fb_radius, radius);
+    OFPS_REQUIRE(ctx, !(fb_params_changed && other_pending), "%s: Farneback parameters changed (levels %d -> %d, radius %d -> %d) with a "
+                 "ticket in flight (collect it with ofps_hip_lk_frame_wait first)", who, ds.fb_levels, levels, ds.fb_radius, radius);
     if (g.farneback) { ds.fb_params_valid = true; ds.fb_levels = levels; ds.fb_radius = radius; }
     if (restart) {
         rc = dense_stream_drain(ctx);
@@ -310,23 +303,105 @@ int ofps_hip_lk_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W,
     // frame's slot is simply uploaded again by the next push) -- ADVICE r4
     const long frames_after = ds.frames + 1;
     int have_vectors = 0;
+    size_t tail_off = 0;
     if (frames_after >= 2) {                                        // cv-decoder/src/lib.rs:156-158: flow needs two frames
-        rc = ofps::host_block_reserve(ctx, &t.pinned, &t.pinned_cap, kBlockHeader + g.max_records * sizeof(float4));
+        const size_t rec_bytes = kBlockHeader + g.max_records * sizeof(float4);
+        tail_off = rec_bytes;
+        rc = ofps::host_block_reserve(ctx, &t.pinned, &t.pinned_cap, rec_bytes + (tail ? kTailField + (size_t)dim * dim * sizeof(float2) : 0));
         if (rc != OFPS_HIP_OK) return rc;
         void* mapped = nullptr;
-        OFPS_REQUIRE(ctx, ofps::device_address_of(t.pinned, &mapped), "lk_push_frame_async: page-locked block is not device-addressable");
+        OFPS_REQUIRE(ctx, ofps::device_address_of(t.pinned, &mapped), "%s: page-locked block is not device-addressable", who);
+        char* blk = static_cast<char*>(mapped);
         const int prev_slot = (int)((frames_after - 2) % kSlots);
+        float4* rec_dst = reinterpret_cast<float4*>(blk + kBlockHeader);
+        uint32_t* cnt_dst = reinterpret_cast<uint32_t*>(blk);
+        char* d_rec_blk = nullptr;
+        if (tail) {
+            // the tail reads records and count from DEVICE memory, not back over PCIe: the output stage stores there, and one copy kernel
+            // (bounded by the count it reads on the device) fills the block
+            d_rec_blk = static_cast<char*>(ofps::scratch(ctx, ofps::S_DENSE_REC, rec_bytes));
+            if (!d_rec_blk) return OFPS_HIP_ENOMEM;
+            rec_dst = reinterpret_cast<float4*>(d_rec_blk + kBlockHeader);
+            cnt_dst = reinterpret_cast<uint32_t*>(d_rec_blk);
+        }
+        const float4* d_rec = nullptr;                       // fused form: the records and their count in device memory
+        const uint32_t* d_cnt = nullptr;
         rc = dense_enqueue_frame(ctx, d_frames + (size_t)prev_slot * px, d_frames + (size_t)slot * px, g.fw, g.fh, levels, radius, iters, g,
-                                 reinterpret_cast<float4*>(static_cast<char*>(mapped) + kBlockHeader), static_cast<uint32_t*>(mapped),
-                                 ds.slot_id[prev_slot], ds.slot_id[slot], d_mask_ready);
+                                 rec_dst, cnt_dst, ds.slot_id[prev_slot], ds.slot_id[slot], d_mask_ready, tail ? &d_rec : nullptr,
+                                 tail ? &d_cnt : nullptr);
         if (rc != OFPS_HIP_OK) return rc;
+        if (tail) {
+            const unsigned copy_blocks = (unsigned)((g.max_records + 255) / 256 < 1024 ? (g.max_records + 255) / 256 : 1024);
+            hipLaunchKernelGGL(dense_copy_records_kernel, dim3(copy_blocks ? copy_blocks : 1), dim3(256), 0, s, d_rec,
+                               reinterpret_cast<float4*>(blk + kBlockHeader), d_cnt, g.max_records, reinterpret_cast<uint32_t*>(blk));
+            OFPS_HIP_TRY(ctx, hipGetLastError());
+            // the 32 bytes the caller waits for -- island result, quaternion -- and the island's field are stored by the detector's and the
+            // estimator's last kernels straight into the ticket's block, as pipeline.hip does (one stream: their order is of no consequence)
+            if (tail->run_estimator) {
+                rc = ofps::almeida_device_n(ctx, d_rec, g.max_records, d_cnt, tail->aspect, tail->fov_y_deg, tail->use_ransac, tail->num_iters,
+                                            tail->inlier_deg, tail->num_samples, tail->seed, reinterpret_cast<float4*>(blk + tail_off + kTailQuat));
+                if (rc != OFPS_HIP_OK) return rc;
+            }
+            if (tail->run_detector) {
+                rc = ofps::detect_device(ctx, d_rec, g.max_records, 1, tail->min_size, tail->subdivide, tail->target_motion,
+                                         reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float2*>(blk + tail_off + kTailField),
+                                         nullptr, d_cnt);
+                if (rc != OFPS_HIP_OK) return rc;
+            }
+        }
         have_vectors = 1;
     }
     OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
     ds.frames = frames_after;
     t.have_vectors = have_vectors; t.gw = g.gw; t.gh = g.gh; t.max_records = g.max_records;
+    t.fused = tail ? 1 : 0; t.run_detector = tail ? tail->run_detector : 0; t.run_estimator = tail ? tail->run_estimator : 0;
+    t.dim = dim; t.tail_off = tail_off;
     *ticket = ds.ring.commit();
     return OFPS_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofps_hip_lk_decode(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels,
+                       int radius, int iters, int max_w, int max_h, unsigned flags, float* out_entries, size_t* n_out,
+                       int* out_w, int* out_h) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "lk_decode: null host pointer");
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "lk_decode: bad geometry");
+    OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "lk_decode: unknown flags 0x%x", flags);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DenseGrid g;
+    int rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, "lk_decode", &g);
+    if (rc != OFPS_HIP_OK) return rc;
+    const size_t px = (size_t)g.fw * g.fh, raw_bytes = g.raw_row * (size_t)H;
+    auto* d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * px));
+    auto* d_raw = g.frontend ? static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FE_RAW_PAIR, 2 * raw_bytes)) : nullptr;
+    if (!d_frames || (g.frontend && !d_raw)) return OFPS_HIP_ENOMEM;
+    rc = dense_upload_frame(ctx, g, prev, W, H, stride, d_raw, d_frames, ctx->stream);
+    if (rc != OFPS_HIP_OK) return rc;
+    rc = dense_upload_frame(ctx, g, cur, W, H, stride, d_raw ? d_raw + raw_bytes : nullptr, d_frames + px, ctx->stream);
+    if (rc != OFPS_HIP_OK) return rc;
+    // the count and the records come back in ONE page-locked block and one wait; only the visited cells' records reach the
+    // caller's buffer
+    rc = ofps::host_block_reserve(ctx, &ctx->dense.decode_pinned, &ctx->dense.decode_pinned_cap, kBlockHeader + g.max_records * sizeof(float4));
+    if (rc != OFPS_HIP_OK) return rc;
+    void* mapped = nullptr;
+    OFPS_REQUIRE(ctx, ofps::device_address_of(ctx->dense.decode_pinned, &mapped), "lk_decode: page-locked block is not device-addressable");
+    rc = dense_enqueue_frame(ctx, d_frames, d_frames + px, g.fw, g.fh, levels, radius, iters, g, reinterpret_cast<float4*>(static_cast<char*>(mapped) + kBlockHeader),
+                             static_cast<uint32_t*>(mapped));
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    dense_collect(ctx->dense.decode_pinned, g.max_records, out_entries, n_out);
+    if (out_w) *out_w = g.gw;
+    if (out_h) *out_h = g.gh;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_lk_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters,
+                                 int max_w, int max_h, unsigned flags, int* ticket) {
+    return dense_push(ctx, frame, W, H, stride, levels, radius, iters, max_w, max_h, flags, nullptr, ticket, "lk_push_frame_async");
 }
 
 int ofps_hip_lk_frame_wait(ofps_hip_ctx* ctx, int ticket, float* out_entries, size_t* n_out, int* out_w, int* out_h, int* have_vectors) {
@@ -356,6 +431,58 @@ int ofps_hip_lk_push_frame(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H
     const int rc = ofps_hip_lk_push_frame_async(ctx, frame, W, H, stride, levels, radius, iters, max_w, max_h, flags, &ticket);
     if (rc != OFPS_HIP_OK) return rc;
     return ofps_hip_lk_frame_wait(ctx, ticket, out_entries, n_out, out_w, out_h, have_vectors);     // the caller may reuse `frame` right away
+}
+
+int ofps_hip_lk_push_frame_fused_async(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters,
+                                       int max_w, int max_h, unsigned flags, const ofps_hip_frame_params* tail, int* ticket) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, tail, "lk_push_frame_fused_async: null parameters");
+    return dense_push(ctx, frame, W, H, stride, levels, radius, iters, max_w, max_h, flags, tail, ticket, "lk_push_frame_fused_async");
+}
+
+int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* out, float* out_entries, float* out_field, int* out_w,
+                                 int* out_h) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, out, "lk_frame_fused_wait: null pointer");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto* t = ctx->dense.ring.find(ticket);
+    OFPS_REQUIRE(ctx, t, "lk_frame_fused_wait: ticket %d is not in flight", ticket);
+    OFPS_REQUIRE(ctx, t->pending, "lk_frame_fused_wait: ticket %d has already been collected", ticket);
+    OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
+    t->pending = false;
+    memset(out, 0, sizeof(*out));
+    out->quat[0] = 1.0f;                                   // identity / no motion: a stream's first frame, a plain ticket, a stage that did not run
+    out->have_vectors = t->have_vectors;
+    if (out_w) *out_w = t->gw;
+    if (out_h) *out_h = t->gh;
+    if (!t->have_vectors) return OFPS_HIP_OK;
+    const char* blk = static_cast<const char*>(t->pinned);
+    uint32_t cnt = 0;
+    memcpy(&cnt, blk, sizeof(cnt));
+    if (cnt > t->max_records) cnt = (uint32_t)t->max_records;
+    out->n_vectors = cnt;
+    if (out_entries && cnt) memcpy(out_entries, blk + kBlockHeader, (size_t)cnt * sizeof(float4));
+    if (!t->fused) return OFPS_HIP_OK;
+    if (t->run_detector) {
+        int res[4];
+        memcpy(res, blk + t->tail_off + kTailResult, sizeof(res));
+        out->has_motion = res[0]; out->area = (size_t)res[1]; out->dim = res[2];
+        if (out_field) memcpy(out_field, blk + t->tail_off + kTailField, (size_t)t->dim * t->dim * sizeof(float2));
+    }
+    if (t->run_estimator) memcpy(out->quat, blk + t->tail_off + kTailQuat, sizeof(out->quat));
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_lk_push_frame_fused(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters,
+                                 int max_w, int max_h, unsigned flags, const ofps_hip_frame_params* tail, ofps_hip_frame_result* out,
+                                 float* out_entries, float* out_field, int* out_w, int* out_h) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, frame && tail && out, "lk_push_frame_fused: null pointer");
+    OFPS_REQUIRE(ctx, !ctx->dense.ring.any_pending(), "lk_push_frame_fused: a read-ahead ticket is in flight (collect it with ofps_hip_lk_frame_fused_wait first)");
+    int ticket = 0;
+    const int rc = dense_push(ctx, frame, W, H, stride, levels, radius, iters, max_w, max_h, flags, tail, &ticket, "lk_push_frame_fused");
+    if (rc != OFPS_HIP_OK) return rc;
+    return ofps_hip_lk_frame_fused_wait(ctx, ticket, out, out_entries, out_field, out_w, out_h);     // the caller may reuse `frame` right away
 }
 
 int ofps_hip_lk_reset(ofps_hip_ctx* ctx) {

@@ -39,7 +39,10 @@ __device__ __forceinline__ void densifier_cell(float px, float py, int w, int h,
 __global__ __launch_bounds__(256) void cell_kernel(const float4* __restrict__ entries, size_t n, int w, int h,
                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                    uint32_t* __restrict__ out_cells, uint32_t* __restrict__ begin,
-                                                   uint32_t* __restrict__ end, size_t cells) {
+                                                   uint32_t* __restrict__ end, size_t cells, const uint32_t* __restrict__ n_dev) {
+    // n_dev (optional; this and the kernels below): the entry count lives on the device.  The launches are sized for n, the capacity, and
+    // work on the first min(*n_dev, n) entries; such calls have one item, so the item * n offsets below are 0 either way.
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     const size_t item = blockIdx.y;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     // clear the per-cell [begin, end) tables bounds_kernel fills later on this stream (saves two memset launches)
@@ -58,8 +61,9 @@ __global__ __launch_bounds__(256) void cell_kernel(const float4* __restrict__ en
 
 // per-tile digit histogram -> hist[item][digit][tile]
 __global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t* __restrict__ keys, size_t n, int shift,
-                                                         int ntiles, uint32_t* __restrict__ hist) {
+                                                         int ntiles, uint32_t* __restrict__ hist, const uint32_t* __restrict__ n_dev) {
     __shared__ uint32_t cnt[256];
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     const size_t item = blockIdx.y;
     const int tile = blockIdx.x;
     cnt[threadIdx.x] = 0;
@@ -117,7 +121,8 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
                                                            int ntiles, const uint32_t* __restrict__ hist,
                                                            const uint32_t* __restrict__ digit_total,
                                                            uint32_t* __restrict__ keys_out,
-                                                           uint32_t* __restrict__ vals_out) {
+                                                           uint32_t* __restrict__ vals_out, const uint32_t* __restrict__ n_dev) {
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     __shared__ uint32_t slot_cnt[16][256];      // [round*4 + wave][digit]
     __shared__ uint32_t dbase[256];             // exclusive prefix over the digit totals of this item
     const size_t item = blockIdx.y;
@@ -173,7 +178,9 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
 
 // cell_begin / cell_end from the sorted keys (arrays pre-zeroed: empty cell <=> begin == end)
 __global__ __launch_bounds__(256) void bounds_kernel(const uint32_t* __restrict__ keys, size_t n, size_t cells,
-                                                     uint32_t* __restrict__ cell_begin, uint32_t* __restrict__ cell_end) {
+                                                     uint32_t* __restrict__ cell_begin, uint32_t* __restrict__ cell_end,
+                                                     const uint32_t* __restrict__ n_dev) {
+    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     const size_t item = blockIdx.y;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -239,7 +246,8 @@ constexpr size_t kSmallLds = (size_t)kSmallMaxN * sizeof(float2) + (size_t)kSmal
 
 __global__ __launch_bounds__(1024) void densify_small_kernel(const float4* __restrict__ entries, uint32_t n, int w, int h,
                                                              float2* __restrict__ out_field, uint32_t* __restrict__ cell_begin,
-                                                             uint32_t* __restrict__ cell_end) {
+                                                             uint32_t* __restrict__ cell_end, const uint32_t* __restrict__ n_dev) {
+    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; }               // (one item: see cell_kernel)
     extern __shared__ __attribute__((aligned(16))) uint8_t small_lds[];
     float2* mot = reinterpret_cast<float2*>(small_lds);                          // [kSmallMaxN] motion of entry i
     uint16_t* sorted = reinterpret_cast<uint16_t*>(mot + kSmallMaxN);            // [kSmallMaxN] entry index by (cell, input order)
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(1024) void densify_small_kernel(const float4* __res
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {                                           // all of a thread's entries requested at once: the
         const uint32_t i = (uint32_t)(wave * ROUNDS + r) * 64u + (uint32_t)lane;  // ballots below would expose one round trip per round
-        ent[r] = entries[item * n + (i < n ? i : n - 1)];
+        ent[r] = entries[item * n + (i < n ? i : (n ? n - 1 : 0))];      // (n == 0: a device-side count; nothing of the record is used)
     }
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
@@ -647,13 +655,15 @@ __global__ __launch_bounds__(256) void interpolate_kernel(float2* __restrict__ s
 // Shared by detect.hip: densify `batch` items of n entries into (w x h) fields.  Leaves the
 // per-cell [begin,end) tables in S_WORK3 (begin) / S_WORK4 (end).
 int densify_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
-                   uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end) {
-    return densify_device_raw(ctx, d_entries, n, batch, w, h, d_field, d_cells, out_begin, out_end, nullptr, nullptr, nullptr);
+                   uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, const uint32_t* d_n) {
+    return densify_device_raw(ctx, d_entries, n, batch, w, h, d_field, d_cells, out_begin, out_end, nullptr, nullptr, nullptr, d_n);
 }
 
 int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
                        uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, float2* d_sum, float* d_cnt,
-                       const float* d_weights) {
+                       const float* d_weights, const uint32_t* d_n) {
+    // d_n (optional, batch == 1): the entry count on the device; n is then the capacity, and the path and every grid are chosen from it
+    OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "densify: a device-side count is for one item (batch %d)", batch);
     const size_t cells = (size_t)w * (size_t)h;
     OFPS_REQUIRE(ctx, w >= 1 && h >= 1 && cells <= 65536, "densify: grid %dx%d unsupported (1..65536 cells)", w, h);
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "densify: batch %d out of range", batch);
@@ -677,7 +687,7 @@ int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallLds));
             attr_set[ctx->device & 63] = true;
         }
-        hipLaunchKernelGGL(densify_small_kernel, dim3(batch), dim3(1024), kSmallLds, s, d_entries, (uint32_t)n, w, h, d_field, begin, end);
+        hipLaunchKernelGGL(densify_small_kernel, dim3(batch), dim3(1024), kSmallLds, s, d_entries, (uint32_t)n, w, h, d_field, begin, end, d_n);
         OFPS_HIP_TRY(ctx, hipGetLastError());
         return OFPS_HIP_OK;
     }
@@ -691,19 +701,19 @@ int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int
         uint32_t* digit_total = hist + (size_t)batch * 256 * ntiles;
         uint32_t *keys_a = k0, *vals_a = k0 + tot, *keys_b = k1, *vals_b = k1 + tot;
         const dim3 ge((unsigned)((n + 255) / 256), batch), gt(ntiles, batch);
-        hipLaunchKernelGGL(cell_kernel, ge, dim3(256), 0, s, d_entries, n, w, h, keys_a, vals_a, d_cells, begin, end, cells);
+        hipLaunchKernelGGL(cell_kernel, ge, dim3(256), 0, s, d_entries, n, w, h, keys_a, vals_a, d_cells, begin, end, cells, d_n);
         const int passes = cells <= 256 ? 1 : 2;
         for (int p = 0; p < passes; ++p) {
             const int shift = 8 * p;
-            hipLaunchKernelGGL(sort_count_kernel, gt, dim3(256), 0, s, keys_a, n, shift, ntiles, hist);
+            hipLaunchKernelGGL(sort_count_kernel, gt, dim3(256), 0, s, keys_a, n, shift, ntiles, hist, d_n);
             hipLaunchKernelGGL(sort_scan_kernel, dim3(256, batch), dim3(256), 0, s, hist, ntiles, digit_total);
             hipLaunchKernelGGL(sort_scatter_kernel, gt, dim3(256), 0, s, keys_a, vals_a, n, shift, ntiles, hist, digit_total,
-                               keys_b, vals_b);
+                               keys_b, vals_b, d_n);
             uint32_t* t;
             t = keys_a; keys_a = keys_b; keys_b = t;
             t = vals_a; vals_a = vals_b; vals_b = t;
         }
-        hipLaunchKernelGGL(bounds_kernel, ge, dim3(256), 0, s, keys_a, n, cells, begin, end);
+        hipLaunchKernelGGL(bounds_kernel, ge, dim3(256), 0, s, keys_a, n, cells, begin, end, d_n);
         sorted_vals = vals_a;
     }
     hipLaunchKernelGGL(cell_sum_kernel, dim3((unsigned)((cells + 3) / 4), batch), dim3(256), 0, s, d_entries, n,

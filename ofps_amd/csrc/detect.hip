@@ -102,8 +102,9 @@ static int block_dim_host(float min_size, size_t subdivide) {          // lib.rs
     return (int)d;
 }
 
+// d_n (optional, batch == 1): the entry count on the device -- n is the capacity (densify.hip)
 int detect_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float min_size, size_t subdivide,
-                  float target_motion, int* d_result, float2* d_out_field, int* out_dim) {
+                  float target_motion, int* d_result, float2* d_out_field, int* out_dim, const uint32_t* d_n) {
     const int dim = block_dim_host(min_size, subdivide);
     if (out_dim) *out_dim = dim;
     OFPS_REQUIRE(ctx, dim >= 1 && dim <= 160, "detect: block_dim %d outside [1,160] (min_size=%g subdivide=%zu)", dim,
@@ -111,7 +112,7 @@ int detect_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batc
     const size_t cells = (size_t)dim * dim;
     auto* d_field = static_cast<float2*>(scratch(ctx, S_FIELD, cells * batch * sizeof(float2)));
     if (!d_field) return OFPS_HIP_ENOMEM;
-    int rc = densify_device(ctx, d_entries, n, batch, dim, dim, d_field, nullptr, nullptr, nullptr);
+    int rc = densify_device(ctx, d_entries, n, batch, dim, dim, d_field, nullptr, nullptr, nullptr, d_n);
     if (rc != OFPS_HIP_OK) return rc;
     const size_t lds = cells * sizeof(uint32_t) + ((cells * sizeof(uint16_t) + 15) & ~size_t(15));
     if (lds > 48 * 1024)

@@ -311,6 +311,7 @@ class HipContext:
         """-> None for the first frame of a stream, else (entries[n,4], (grid_w, grid_h)).  `out`: a caller buffer of the
         capacity lk_decode documents (the result is then a view of it)."""
         cap = getattr(self, "_lk_cap", {}).pop(ticket, 1)    # an unknown ticket: the library says so
+        getattr(self, "_lk_dim", {}).pop(ticket, None)       # (a fused ticket collected here: its tail is dropped)
         if out is None:
             out = np.zeros((cap, 4), np.float32)
         assert out.dtype == np.float32 and out.size >= 4 * cap and out.flags["C_CONTIGUOUS"]
@@ -319,6 +320,67 @@ class HipContext:
         if not have.value:
             return None
         return out.reshape(-1, 4)[:n.value], (gw.value, gh.value)
+
+    # ---- the dense decoders with detector + estimator behind them in the same ticket (ofps_hip_lk_push_frame_fused[_async])
+    def _fused_result(self, res, ent, fld, grid):
+        have = bool(res.have_vectors)
+        n = int(res.n_vectors)
+        motion = (int(res.area), fld) if res.has_motion else None
+        return {"have_vectors": have, "n_vectors": n, "motion": motion, "quat": np.array(list(res.quat), np.float32),
+                "entries": ent[:n] if (ent is not None and have) else None, "grid": grid}
+
+    def lk_push_frame_fused_async(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
+                                  farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True,
+                                  min_size=0.05, subdivide=3, target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16,
+                                  use_ransac=False, num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0) -> int:
+        """Read-ahead form of lk_push_frame_fused: -> ticket once upload, flow, output stage, detector and estimator are enqueued.
+        `frame` as for lk_push_frame_async; collect with lk_frame_fused_wait (or lk_frame_wait: the records alone)."""
+        assert frame.dtype == np.uint8 and frame.flags["C_CONTIGUOUS"]
+        W, H, pitch = self._frame_geometry(frame, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        prm = self._frame_params(0, 0, detector, min_size, subdivide, target_motion, estimator, aspect, fov_y_deg, use_ransac, num_iters,
+                                 inlier_deg, num_samples, seed)
+        t = C.c_int(0)
+        self._check(self._lib.ofps_hip_lk_push_frame_fused_async(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels,
+                                                                 radius, iters, max_w, max_h, flags, C.byref(prm), C.byref(t)))
+        self._lk_cap = getattr(self, "_lk_cap", {})
+        self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records)
+        self._lk_dim = getattr(self, "_lk_dim", {})
+        self._lk_dim[t.value] = self.block_dim(min_size, subdivide) if detector else 0
+        return t.value
+
+    def lk_frame_fused_wait(self, ticket: int, want_entries=True, want_field=True) -> dict:
+        """-> dict(have_vectors, n_vectors, motion=None|(area, field|None), quat, entries|None, grid): push_frame's shape plus the record
+        grid.  A ticket of the plain lk_push_frame_async comes back with the identity and no motion."""
+        cap = getattr(self, "_lk_cap", {}).pop(ticket, 1)
+        dim = getattr(self, "_lk_dim", {}).pop(ticket, 0)
+        ent = np.zeros((cap, 4), np.float32) if want_entries else None
+        fld = np.zeros((dim, dim, 2), np.float32) if (want_field and dim) else None
+        res = _lib.FrameResult(); gw = C.c_int(0); gh = C.c_int(0)
+        self._check(self._lib.ofps_hip_lk_frame_fused_wait(self._h, ticket, C.byref(res), _fp(ent) if ent is not None else None,
+                                                           _fp(fld) if fld is not None else None, C.byref(gw), C.byref(gh)))
+        return self._fused_result(res, ent, fld, (gw.value, gh.value))
+
+    def lk_push_frame_fused(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
+                            farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True, min_size=0.05,
+                            subdivide=3, target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16, use_ransac=False,
+                            num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, want_entries=True, want_field=True) -> dict:
+        """One frame of a hip_lk / hip_flow stream -> records -> island + rotation in one call, the records staying on the device in
+        between (ofps_hip_lk_push_frame_fused).  The same stream of frames as lk_push_frame."""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        W, H, pitch = self._frame_geometry(frame, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        prm = self._frame_params(0, 0, detector, min_size, subdivide, target_motion, estimator, aspect, fov_y_deg, use_ransac, num_iters,
+                                 inlier_deg, num_samples, seed)
+        dim = self.block_dim(min_size, subdivide) if detector else 0
+        ent = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records), 4), np.float32) if want_entries else None
+        fld = np.zeros((dim, dim, 2), np.float32) if (want_field and dim) else None
+        res = _lib.FrameResult(); gw = C.c_int(0); gh = C.c_int(0)
+        self._check(self._lib.ofps_hip_lk_push_frame_fused(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels, radius,
+                                                           iters, max_w, max_h, flags, C.byref(prm), C.byref(res),
+                                                           _fp(ent) if ent is not None else None, _fp(fld) if fld is not None else None,
+                                                           C.byref(gw), C.byref(gh)))
+        return self._fused_result(res, ent, fld, (gw.value, gh.value))
 
     def lk_reset(self):
         self._check(self._lib.ofps_hip_lk_reset(self._h))
