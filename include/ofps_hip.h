@@ -320,6 +320,39 @@ int ofps_hip_almeida_dev(ofps_hip_ctx* ctx, const void* d_entries, size_t n_per_
                          void* d_out_quat /* 4 f32 per item */);
 int ofps_hip_almeida_recoveries(ofps_hip_ctx* ctx, uint64_t* count);
 
+/* ---- A6c: camera compensation -- what moves relative to the camera (csrc/compensate.hip) ----
+ * The residual of the reference's RANSAC inlier test, vec - camera.delta(pos, fit.inverse().to_homogeneous())
+ * (almeida-estimator/src/lib.rs:224-231; delta: ofps/src/camera.rs:115-117), as an output.  Per record, in f32 without contraction:
+ *   M = to_homogeneous(inverse(q)), q = (w,i,j,k) as ofps_hip_almeida returns it (oracle/ofps_oracle.c: orc_quat_inverse,
+ *       orc_quat_to_homogeneous);
+ *   d = camera.delta(pos, M), camera = (aspect, fov_y_deg) as for ofps_hip_almeida;
+ *   out.pos = pos, the same bits; out.motion = motion - d.
+ * ONE regime: the exact delta with IEEE divisions at every record count -- the estimator's reciprocal-quotient regime above 65,536
+ * records has no counterpart here, a record's result does not depend on how many records there are.  n == 0 is valid; out_entries may
+ * be entries (in place).  The _dev form takes `batch` items of n_per_item records and ONE quaternion per item from DEVICE memory
+ * (4 f32 each -- what ofps_hip_almeida_dev wrote, no host copy or synchronisation in between), enqueues and returns.
+ *
+ * Detect-compensation mode of the fused per-frame entry points -- ofps_hip_push_frame[_async], ofps_hip_push_frames_async,
+ * ofps_hip_lk_push_frame_fused[_async]; the option OFPS_HIP_DETECT_COMPENSATE (environment / ofps_hip_set_option) sets the same field:
+ *   0 (the default): the detector reads the decoder's raw records -- the launches, streams and bytes of a build without this stage;
+ *   1: when a ticket runs detector AND estimator, its detector reads that frame's records compensated with that frame's quaternion
+ *      (LSQ or RANSAC as the parameters say, camera = the parameters' aspect / fov_y_deg): has_motion, area, dim and out_field describe
+ *      the compensated field and equal ofps_hip_detect(ofps_hip_compensate(out_entries, quat)) bit for bit.  The vectors handed back in
+ *      out_entries stay the raw decoder records and the quaternion is unchanged, both bit for bit.  The detector's chain then runs
+ *      BEHIND the estimator and one compensation launch instead of beside the estimator.  A ticket whose estimator does not run has
+ *      the raw detector, with no compensation launch and no error: camera.delta(pos, identity) is not exactly zero in f32, so
+ *      "compensated with the identity" is NOT the definition.  A ticket follows the mode the context has when it is pushed.
+ *   Any other value is OFPS_HIP_EINVAL.  ofps_hip_frame_params / ofps_hip_frame_result are unchanged (API version 2).
+ * Out of scope: the worker contexts of ofps_hip_multi_* (always mode 0, also with the variable in the environment), the Python
+ * plugins (ofps_amd/plugins.py) and the C++ host loops (ofps_amd/host) keep the default. */
+int ofps_hip_compensate(ofps_hip_ctx* ctx, const float* entries, size_t n, float aspect, float fov_y_deg,
+                        const float quat[4], float* out_entries /* 4*n */);
+int ofps_hip_compensate_dev(ofps_hip_ctx* ctx, const void* d_entries, size_t n_per_item, int batch,
+                            float aspect, float fov_y_deg, const void* d_quat /* 4 f32 per item, device memory */,
+                            void* d_out_entries /* may equal d_entries */);
+int ofps_hip_set_detect_compensation(ofps_hip_ctx* ctx, int mode);
+int ofps_hip_get_detect_compensation(ofps_hip_ctx* ctx);
+
 /* ---- fused per-frame path (live streams): decoder -> detector + estimator, vectors stay on the device ----
  * One call per arriving luma frame = one iteration of the reference's worker loops
  * (ofps-suite/src/app/detection.rs:111-148, tracking/worker.rs:328-361).  The context keeps the previous

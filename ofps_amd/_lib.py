@@ -84,6 +84,10 @@ PROTOTYPES = {
                                    C.c_float, C.c_size_t, C.c_uint64, _f32p, _f32p]),
     "ofps_hip_almeida_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.c_size_t,
                                        C.c_float, C.c_size_t, C.c_uint64, _vp]),
+    "ofps_hip_compensate": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_float, C.c_float, _f32p, _f32p]),
+    "ofps_hip_compensate_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_float, _vp, _vp]),
+    "ofps_hip_set_detect_compensation": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_detect_compensation": (C.c_int, [_ctx]),
 }
 
 

@@ -178,6 +178,7 @@ struct ofps_hip_ctx {
         int fb_prepare_ahead = 1;        // OFPS_HIP_FB_PREPARE_AHEAD: a hip_flow stream's new frame is expanded on the upload's stream when it is pushed (0: inside the pair's flow, round 5's order)
         int lk_serial = 0;               // OFPS_HIP_LK_SERIAL: one launch per pyramid level instead of one for the pyramid
         int sad_motion_scale = 1;        // OFPS_HIP_SAD_MOTION_SCALE / ofps_hip_set_sad_motion_scale: 1 full-pel vectors, 4 quarter-pel refinement (sad_qpel.hip)
+        int detect_compensate = 0;       // OFPS_HIP_DETECT_COMPENSATE / ofps_hip_set_detect_compensation: 0 the fused entry points' detector reads the raw vectors, 1 the vectors compensated with the frame's own quaternion (compensate.hip)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -226,9 +227,11 @@ enum ScratchSlot {
     S_FE_RAW,               // frontend.hip: the frames as they arrive (colour and / or full size) when the decoder resizes / converts them: one per ticket in flight
     S_FE_RAW_PAIR,          // ... of the stateless calls (ofps_hip_lk_decode, ofps_hip_cv_frontend, ofps_hip_resize_linear): never the stream's staging, whose
                             // upload + front-end may still be running on the upload stream when such a call comes in
-    S_DENSE_REC             // dense decoders, fused stream form: [count, pad x 3][records] of the newest pair, in device memory for the detector + estimator
+    S_DENSE_REC,            // dense decoders, fused stream form: [count, pad x 3][records] of the newest pair, in device memory for the detector + estimator
+    S_COMP                  // detect-compensation mode 1 (compensate.hip): [quaternion, 16 bytes][compensated records] -- the detector's input; the slots the
+                            // record copy and the estimator read are never overwritten.  Written and read on the compute stream only
 };
-static_assert(S_DENSE_REC < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_COMP < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -293,6 +296,12 @@ int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
 // one problem whose record count lives in device memory: the estimate over the first min(*d_n, n_max) records; every launch is sized from n_max
 int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
                      int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
+
+// compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
+// are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.
+// d_quat_echo (optional): the quaternions are stored there as well (a ticket's result block)
+int compensate_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const uint32_t* d_n, float aspect, float fov_y_deg,
+                      const float4* d_quat, float4* d_out, float4* d_quat_echo);
 
 // ---- transfers (transfer.hip)
 bool device_address_of(const void* host_ptr, void** dev_ptr);        // the device address of page-locked host memory, or false for pageable memory

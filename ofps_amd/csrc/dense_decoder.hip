@@ -337,13 +337,28 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
             OFPS_HIP_TRY(ctx, hipGetLastError());
             // the 32 bytes the caller waits for -- island result, quaternion -- and the island's field are stored by the detector's and the
             // estimator's last kernels straight into the ticket's block, as pipeline.hip does (one stream: their order is of no consequence)
-            if (tail->run_estimator) {
+            // detect-compensation mode 1 (compensate.hip; the mode is the context's at this push): the estimator writes its quaternion to
+            // device memory, the compensation launch -- in its device-count form, sized from the capacity -- reads it there, passes it on to
+            // the block and leaves the compensated records in a slot of their own for the detector; d_rec is what the copy above reads
+            const bool compensate = ctx->opt.detect_compensate == 1 && tail->run_detector && tail->run_estimator;
+            float4* quat_blk = reinterpret_cast<float4*>(blk + tail_off + kTailQuat);
+            const float4* d_det_in = d_rec;
+            if (compensate) {
+                auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, (1 + g.max_records) * sizeof(float4)));    // [quaternion][records]
+                if (!d_comp) return OFPS_HIP_ENOMEM;
                 rc = ofps::almeida_device_n(ctx, d_rec, g.max_records, d_cnt, tail->aspect, tail->fov_y_deg, tail->use_ransac, tail->num_iters,
-                                            tail->inlier_deg, tail->num_samples, tail->seed, reinterpret_cast<float4*>(blk + tail_off + kTailQuat));
+                                            tail->inlier_deg, tail->num_samples, tail->seed, d_comp);
+                if (rc != OFPS_HIP_OK) return rc;
+                rc = ofps::compensate_device(ctx, d_rec, g.max_records, 1, d_cnt, tail->aspect, tail->fov_y_deg, d_comp, d_comp + 1, quat_blk);
+                if (rc != OFPS_HIP_OK) return rc;
+                d_det_in = d_comp + 1;
+            } else if (tail->run_estimator) {
+                rc = ofps::almeida_device_n(ctx, d_rec, g.max_records, d_cnt, tail->aspect, tail->fov_y_deg, tail->use_ransac, tail->num_iters,
+                                            tail->inlier_deg, tail->num_samples, tail->seed, quat_blk);
                 if (rc != OFPS_HIP_OK) return rc;
             }
             if (tail->run_detector) {
-                rc = ofps::detect_device(ctx, d_rec, g.max_records, 1, tail->min_size, tail->subdivide, tail->target_motion,
+                rc = ofps::detect_device(ctx, d_det_in, g.max_records, 1, tail->min_size, tail->subdivide, tail->target_motion,
                                          reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float2*>(blk + tail_off + kTailField),
                                          nullptr, d_cnt);
                 if (rc != OFPS_HIP_OK) return rc;

@@ -183,18 +183,35 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     // detector and estimator read the same device-resident vectors and share no workspace: with both enabled the
     // detector's chain of small launches runs on an auxiliary stream beside the estimator (fork after the search, join
     // before the read-back) instead of in front of it
-    const bool fork = prm->run_detector && prm->run_estimator;
+    // detect-compensation mode 1 (compensate.hip; the mode is the context's at this push): the detector reads this frame's vectors
+    // compensated with this frame's quaternion, so its chain cannot run beside the estimator -- estimator, compensation and detector are
+    // enqueued on the compute stream in that order.  The estimator writes the quaternion to device memory (the compensation launch reads it
+    // there and passes it on to the ticket's block); the compensated records have a slot of their own: d_ent is what the caller gets.
+    const bool compensate = ctx->opt.detect_compensate == 1 && prm->run_detector && prm->run_estimator;
+    const bool fork = prm->run_detector && prm->run_estimator && !compensate;
     if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.slot_read[prev_slot], 0));
+    const float4* d_det_in = d_ent;
+    if (compensate) {
+        auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, nblk * sizeof(float4)));
+        if (!d_comp) return OFPS_HIP_ENOMEM;
+        float4* d_quat_dev = reinterpret_cast<float4*>(d_out + 16);
+        rc = ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
+                                  prm->inlier_deg, prm->num_samples, prm->seed, d_quat_dev);
+        if (rc != OFPS_HIP_OK) return rc;
+        rc = ofps::compensate_device(ctx, d_ent, nblk, 1, nullptr, prm->aspect, prm->fov_y_deg, d_quat_dev, d_comp, direct ? d_quat : nullptr);
+        if (rc != OFPS_HIP_OK) return rc;
+        d_det_in = d_comp;
+    }
     // the estimator is enqueued first: it is the long pole (0.1 ms of dependent steps against the detector's seven small
     // launches), and whatever is enqueued second starts a host-enqueue time later
-    if (prm->run_estimator) {
+    if (prm->run_estimator && !compensate) {
         rc = ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
                                   prm->inlier_deg, prm->num_samples, prm->seed, d_quat);
         if (rc != OFPS_HIP_OK) return rc;
     }
     if (prm->run_detector) {
         if (fork) ctx->stream = ctx->pipe.aux_stream;           // the stage entry points enqueue on ctx->stream
-        rc = ofps::detect_device(ctx, d_ent, nblk, 1, prm->min_size, prm->subdivide, prm->target_motion, d_res, d_field, &dim);
+        rc = ofps::detect_device(ctx, d_det_in, nblk, 1, prm->min_size, prm->subdivide, prm->target_motion, d_res, d_field, &dim);
         if (fork) {
             ctx->stream = s;
             if (rc == OFPS_HIP_OK) OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.join, ctx->pipe.aux_stream));
@@ -381,7 +398,18 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
             int dim = 0;
             auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_BATCH_FIELD, (size_t)pairs * 160 * 160 * sizeof(float2)));   // its own slot: the densifier works in S_WORK*
             if (!d_field) return OFPS_HIP_ENOMEM;
-            rc = ofps::detect_device(ctx, ent0, nblk, pairs, prm->min_size, prm->subdivide, prm->target_motion, d_res + 4 * first, d_field, &dim);
+            // detect-compensation mode 1: ONE compensation launch over the batch, item j with the quaternion the estimator's launch above left
+            // for it in device memory, into a slot of its own; then the batched detector chain as it is.  The multi-device dispatcher's
+            // worker contexts (halo_mode 1) keep the raw detector.
+            const float4* det_in = ent0;
+            if (ctx->opt.detect_compensate == 1 && prm->run_estimator && !halo_mode) {
+                auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, (size_t)pairs * nblk * sizeof(float4)));
+                if (!d_comp) return OFPS_HIP_ENOMEM;
+                rc = ofps::compensate_device(ctx, ent0, nblk, pairs, nullptr, prm->aspect, prm->fov_y_deg, d_quat + first, d_comp, nullptr);
+                if (rc != OFPS_HIP_OK) return rc;
+                det_in = d_comp;
+            }
+            rc = ofps::detect_device(ctx, det_in, nblk, pairs, prm->min_size, prm->subdivide, prm->target_motion, d_res + 4 * first, d_field, &dim);
             if (rc != OFPS_HIP_OK) return rc;
         }
         if (prm->run_detector || prm->run_estimator) {

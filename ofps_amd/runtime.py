@@ -491,6 +491,27 @@ class HipContext:
                                                    int(use_ransac), num_iters, inlier_deg, num_samples, seed,
                                                    C.c_void_p(d_out_quat)))
 
+    # ---- A6c: camera compensation (include/ofps_hip.h; csrc/compensate.hip)
+    def compensate(self, entries, aspect: float, fov_y_deg: float, quat) -> np.ndarray:
+        """records [n, 4] and the estimator's quaternion (w, i, j, k) -> [n, 4]: pos as it is, motion - camera.delta(pos, inverse(quat))"""
+        e = np.ascontiguousarray(entries, np.float32).reshape(-1, 4)
+        q = np.ascontiguousarray(quat, np.float32).reshape(4)
+        out = np.zeros((max(e.shape[0], 1), 4), np.float32)
+        self._check(self._lib.ofps_hip_compensate(self._h, _fp(e), e.shape[0], aspect, fov_y_deg, _fp(q), _fp(out)))
+        return out[:e.shape[0]]
+
+    def compensate_dev(self, d_entries: int, n_per_item: int, batch: int, aspect: float, fov_y_deg: float, d_quat: int, d_out_entries: int):
+        """Device form: one quaternion per item in device memory (what almeida_dev wrote); d_out_entries may be d_entries.  Enqueue only."""
+        self._check(self._lib.ofps_hip_compensate_dev(self._h, C.c_void_p(d_entries), n_per_item, batch, aspect, fov_y_deg,
+                                                      C.c_void_p(d_quat), C.c_void_p(d_out_entries)))
+
+    def set_detect_compensation(self, mode: int):
+        """0 = the fused entry points' detector reads the raw vectors (default); 1 = the vectors compensated with the frame's own quaternion
+        when detector and estimator both run: "what moves relative to the camera"."""
+        self._check(self._lib.ofps_hip_set_detect_compensation(self._h, mode))
+
+    def get_detect_compensation(self) -> int:
+        return int(self._lib.ofps_hip_get_detect_compensation(self._h))
 
     def checksum_dev(self, d_data: int, bytes_per_item: int, batch: int, d_out_u64: int):
         """Per-item wrapping u64 sum of device-resident data (ofps_hip_checksum_dev); enqueue only."""
