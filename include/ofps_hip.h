@@ -136,6 +136,44 @@ int ofps_hip_sad_flow_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames,
                           int W, int H, int stride, size_t frame_pitch, int ref_mode,
                           int block, int range, void* d_out_entries, void* d_out_best);
 
+/* ---- N1g: hip_sad's contrast gate -- a block that tells nothing yields no record (csrc/sad_gate.hip) ----
+ * av-decoder, whose record convention hip_sad copies, yields a vector only for the blocks the encoder chose to predict
+ * (av-decoder/src/lib.rs:396-419); the dense decoders drop the pixels outside cv-decoder's contrast mask.  The gate is hip_sad's form of
+ * both.  Build-defined, like N1 and N1q.  The contrast gate of a frame pair (prev, cur) with lattice `block` = B:
+ *   M = cv-decoder's contrast mask of the CURRENT frame's luma: exactly what ofps_hip_contrast_mask(cur) returns;
+ *   count(bx, by) = the number of set pixels of M inside [bx*B, bx*B + B) x [by*B, by*B + B).  Only full lattice blocks are counted, as in
+ *     ofps_hip_sad_block_count; mask pixels in the ragged right / bottom margin belong to no block;
+ *   a block is KEPT iff count >= min_pixels, min_pixels in [1, B*B];
+ *   the kept blocks' records keep raster order (block row outer, block column inner): the ungated order with the dropped ones removed.
+ *     The records themselves are the ungated ones bit for bit, quarter-pel refined or not; out_best triples are compacted the same way.
+ * Gate value 0 = off, the default: every entry point then uses the launches, streams and bytes of a build without the gate.  A negative
+ * value is OFPS_HIP_EINVAL at the setter; a value > B*B for the block size of a call is OFPS_HIP_EINVAL at that call.  The option
+ * OFPS_HIP_SAD_GATE (environment / ofps_hip_set_option) sets the same field.
+ * ofps_hip_block_contrast[_dev]: the counts alone, uint32 per block in raster order, any block <= 64, any stride >= W; they equal the
+ *   per-block sums of ofps_hip_contrast_mask's output (the kernel runs the mask's arithmetic and never writes the pixel mask).
+ * With the gate on:
+ *   ofps_hip_sad_flow: *n_out = the kept count; out_entries / out_best hold the kept records first (capacity nblk, as without the gate;
+ *     what lies behind the kept ones is unspecified).
+ *   ofps_hip_push_frame[_async] / ofps_hip_frame_wait: the count stays on the device -- the keep flags are made beside the search on a
+ *     second stream, one compaction launch behind it, and estimator, compensation (mode 1) and detector read the count from device memory
+ *     (launches sized from the capacity nblk).  n_vectors = the kept count; have_vectors stays 1 for every frame that ran a search, also
+ *     with 0 kept (Ok(true) with an empty list: av-decoder on an all-intra frame); out_entries receives the kept records first.  The
+ *     detector's result equals ofps_hip_detect on the kept records bit for bit, the quaternion ofps_hip_almeida's to the solver's parity
+ *     bound (2e-6, as for the dense decoders' fused form below).  Fewer than 3 kept records -> identity, with either solver (the
+ *     reference's rule for RANSAC inliers, almeida-estimator/src/lib.rs:246-250); none kept -> no motion.  A ticket follows the gate the
+ *     context has when it is pushed.
+ * ofps_hip_sad_flow_gated_dev: one pair of device frames with an explicit min_pixels in [1, B*B] (the context's gate is not looked at);
+ *   d_out_entries / d_out_best have capacity nblk, d_out_count is one uint32 in device memory; enqueues only.
+ * Out of scope: the batched forms -- ofps_hip_sad_flow_dev, ofps_hip_push_frames_async, the ofps_hip_multi_* workers -- ignore the gate and
+ * always produce nblk records per pair (the device-count forms of the tail are one-item forms); a second criterion on the SAD surface
+ * (best against second best) is not part of this. */
+int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_counts /* nblk */);
+int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts);
+int ofps_hip_set_sad_gate(ofps_hip_ctx* ctx, int min_pixels);   /* 0 = off (default) */
+int ofps_hip_get_sad_gate(ofps_hip_ctx* ctx);
+int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
+                                int min_pixels, void* d_out_entries, void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
+
 /* ---- N2: dense per-pixel flow, pyramidal Lucas-Kanade ("hip_lk" Decoder) ----
  * The reference's only per-pixel flow is OpenCV's Farneback inside cv-decoder (cv-decoder/src/lib.rs:188-199); this
  * is a build-defined algorithm (oracle/ofps_oracle.c:orc_lk_flow) with cv-decoder's conventions: prev(x,y) ~

@@ -1761,14 +1761,14 @@ static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride,
 // records, the count read on the device -- no launch, grid or path depends on it, nothing is read back.
 static int almeida_impl(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, const uint32_t* d_n, int batch, float aspect, float fov_y_deg,
                         int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed,
-                        float4* d_quat) {
+                        float4* d_quat, uint32_t lsq_min_n = 0) {
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "almeida: batch %d out of range", batch);
     OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "almeida: a device-side count is for one problem (batch %d)", batch);
     OFPS_REQUIRE(ctx, n < (1ull << 31), "almeida: too many entries");
     OFPS_REQUIRE(ctx, aspect > 0.0f && fov_y_deg > 0.0f && fov_y_deg < 180.0f, "almeida: bad camera (aspect=%g fov_y=%g)",
                  (double)aspect, (double)fov_y_deg);
     const Camera cam = camera_new(aspect, fov_y_deg);
-    if (!use_ransac) return lsq_device(ctx, d_entries, n, n, d_n, 0, batch, cam, d_quat, /*multi=*/true);
+    if (!use_ransac) return lsq_device(ctx, d_entries, n, n, d_n, lsq_min_n, batch, cam, d_quat, /*multi=*/true);
 
     OFPS_REQUIRE(ctx, num_iters >= 1 && num_iters <= 65535, "almeida: ransac iters %zu out of range", num_iters);
     OFPS_REQUIRE(ctx, num_samples >= 1, "almeida: ransac samples must be >= 1");
@@ -1819,9 +1819,10 @@ int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
 }
 
 int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
-                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat) {
+                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat,
+                     uint32_t lsq_min_n) {
     OFPS_REQUIRE(ctx, d_n, "almeida: null device count");
-    return almeida_impl(ctx, d_entries, n_max, d_n, 1, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat);
+    return almeida_impl(ctx, d_entries, n_max, d_n, 1, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat, lsq_min_n);
 }
 
 }  // namespace ofps

@@ -84,13 +84,15 @@ struct PipeStream {
         bool pending = false; hipEvent_t done = nullptr;
         void* pinned = nullptr;          // page-locked PipeOut block for the result read-back
         int have_vectors = 0, run_detector = 0, run_estimator = 0;
+        int gated = 0;                   // pushed with the contrast gate on: n_vectors is the kept count in the page-locked block
         size_t n_vectors = 0;
     };
+    hipEvent_t gate_done = nullptr;      // contrast gate (sad_gate.hip): the keep flags of the newest frame, made on aux_stream beside the search (created with the first gated push)
     TicketRing<Ticket, kTickets> ring;
     void release() {
         for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); }
         for (int k = 0; k < kSlots; ++k) { destroy(uploaded[k]); destroy(slot_read[k]); }
-        destroy(copy_stream); destroy(aux_stream); destroy(fork); destroy(join);
+        destroy(copy_stream); destroy(aux_stream); destroy(fork); destroy(join); destroy(gate_done);
     }
     hipError_t sync_side_streams() {
         const hipError_t e = copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess;
@@ -179,6 +181,7 @@ struct ofps_hip_ctx {
         int lk_serial = 0;               // OFPS_HIP_LK_SERIAL: one launch per pyramid level instead of one for the pyramid
         int sad_motion_scale = 1;        // OFPS_HIP_SAD_MOTION_SCALE / ofps_hip_set_sad_motion_scale: 1 full-pel vectors, 4 quarter-pel refinement (sad_qpel.hip)
         int detect_compensate = 0;       // OFPS_HIP_DETECT_COMPENSATE / ofps_hip_set_detect_compensation: 0 the fused entry points' detector reads the raw vectors, 1 the vectors compensated with the frame's own quaternion (compensate.hip)
+        int sad_gate = 0;                // OFPS_HIP_SAD_GATE / ofps_hip_set_sad_gate: 0 one record per lattice block, N >= 1 only blocks with at least N contrast-mask pixels of the current frame (sad_gate.hip)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -203,7 +206,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 44;
+    static constexpr int kNumScratch = 48;
     Scratch scratch[kNumScratch];
 };
 
@@ -228,6 +231,9 @@ enum ScratchSlot {
     S_FE_RAW_PAIR,          // ... of the stateless calls (ofps_hip_lk_decode, ofps_hip_cv_frontend, ofps_hip_resize_linear): never the stream's staging, whose
                             // upload + front-end may still be running on the upload stream when such a call comes in
     S_DENSE_REC,            // dense decoders, fused stream form: [count, pad x 3][records] of the newest pair, in device memory for the detector + estimator
+    S_GATE_RAW,             // hip_sad's contrast gate (sad_gate.hip): the search's one-record-per-block output, in front of the compaction
+    S_GATE_BEST,            // ... and its (dx, dy, SAD) triples
+    S_GATE_FLAGS,           // ... [counts, u32 per block][kept count, 16 bytes][keep flags, u8 per block], one per ticket in flight in the fused path
     S_COMP                  // detect-compensation mode 1 (compensate.hip): [quaternion, 16 bytes][compensated records] -- the detector's input; the slots the
                             // record copy and the estimator read are never overwritten.  Written and read on the compute stream only
 };
@@ -293,9 +299,26 @@ void cluster_gate_context_created(int device);      // almeida.hip: the cluster 
 void cluster_gate_context_destroyed(int device);
 int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
                    int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
-// one problem whose record count lives in device memory: the estimate over the first min(*d_n, n_max) records; every launch is sized from n_max
+// one problem whose record count lives in device memory: the estimate over the first min(*d_n, n_max) records; every launch is sized from n_max.
+// lsq_min_n: the least-squares fit of fewer records than this is the identity (RANSAC has its own rule: fewer than 3 inliers)
 int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
-                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
+                     int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat,
+                     uint32_t lsq_min_n = 0);
+
+// sad_gate.hip: hip_sad's contrast gate.  The flags buffer of a frame: [counts][kept count][keep flags]
+inline size_t gate_flags_bytes(size_t nblk) { return ((nblk * sizeof(uint32_t) + 15) & ~size_t(15)) + 16 + ((nblk + 15) & ~size_t(15)); }
+inline uint32_t* gate_counts(char* flags) { return reinterpret_cast<uint32_t*>(flags); }
+inline uint32_t* gate_kept(char* flags, size_t nblk) { return reinterpret_cast<uint32_t*>(flags + ((nblk * sizeof(uint32_t) + 15) & ~size_t(15))); }
+inline uint8_t* gate_keep(char* flags, size_t nblk) { return reinterpret_cast<uint8_t*>(gate_kept(flags, nblk)) + 16; }
+int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const char* who);          // min_pixels in [1, block * block]
+// counts and keep flags of `cur` on stream st (they depend on that frame only)
+int sad_gate_flags_device(ofps_hip_ctx* ctx, const uint8_t* d_cur, int W, int H, int stride, int block, int min_pixels, uint32_t* d_counts,
+                          uint8_t* d_keep, hipStream_t st);
+// the kept records [and triples] in raster order and their count, on ctx->stream; d_out may not alias d_raw
+int sad_gate_compact_device(ofps_hip_ctx* ctx, const float4* d_raw, const int* d_raw_best, const uint8_t* d_keep, size_t nblk, float4* d_out,
+                            int* d_out_best, uint32_t* d_count);
+int sad_flow_gated_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                          int min_pixels, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.

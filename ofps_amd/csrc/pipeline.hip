@@ -18,7 +18,9 @@ namespace {
 struct PipeOut {                 // layout of the pinned read-back block
     int result[4];               // has_motion, area, dim, 0
     float quat[4];
+    uint32_t kept[4];            // contrast gate on: the kept record count (sad_gate.hip); not read back, not looked at, with the gate off
 };
+constexpr size_t kPipeOutPlain = offsetof(PipeOut, kept);       // what a ticket without the gate reads back
 constexpr int kSlots = ofps::PipeStream::kSlots;
 
 #ifndef OFPS_HIP_UPLOAD_KERNEL_SINGLE
@@ -122,6 +124,12 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     auto& t = ctx->pipe.ring.at(tno);
     OFPS_REQUIRE(ctx, !t.pending, "push_frame_async: ticket %ld has not been collected (at most %d frames in flight)",
                  tno - kTickets, kTickets);
+    // contrast gate (sad_gate.hip; the gate is the context's at this push): 0 = every launch, stream and byte below is the ungated build's
+    const int gate = ctx->opt.sad_gate;
+    if (gate > 0) {
+        rc = ofps::sad_gate_check(ctx, prm->block, gate, "push_frame_async");
+        if (rc != OFPS_HIP_OK) return rc;
+    }
     hipStream_t s = ctx->stream;
     uint8_t* slots; size_t pitch; int dstride;
     const bool overlap = ctx->pipe.ring.other_pending();               // the other ticket is in flight
@@ -129,7 +137,7 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     if (rc != OFPS_HIP_OK) return rc;
     const long frame_no = ctx->pipe.frames - 1;                       // the frame just enqueued
     const int cur_slot = (int)(frame_no % kSlots);
-    t.have_vectors = 0; t.n_vectors = 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator;
+    t.have_vectors = 0; t.n_vectors = 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.gated = 0;
     const size_t nblk = ofps_hip_sad_block_count(W, H, prm->block);
     if (frame_no == 0) {                                             // first frame of a stream: Ok(false), no vectors yet
         if (!ctx->pipe.uploaded_on_compute[cur_slot]) {
@@ -151,20 +159,53 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     // the search needs both frames on the device: the previous frame's upload was waited for by the previous ticket
     // (or by the stage_frame that made it), this frame's by the event
     // (uploads made on the compute stream itself are ordered by the stream; one wait per upload is enough)
+    const bool cur_by_event = !ctx->pipe.uploaded_on_compute[cur_slot];      // this frame's upload is on the copy stream and has an event of its own
     for (int slot : {prev_slot, cur_slot}) {
         if (!ctx->pipe.uploaded_on_compute[slot]) {
             OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.uploaded[slot], 0));
             ctx->pipe.uploaded_on_compute[slot] = true;
         }
     }
+    // gate on: the keep flags depend on the new frame only -- they are made on the auxiliary stream, forked on that frame's upload, beside
+    // the search (never in front of it on the compute stream); the search writes one record per block into the gate's own slot and the
+    // compaction behind the join leaves the kept records, in raster order, in d_ent and their count in device memory (d_kept)
+    float4* d_raw = d_ent;
+    char* d_flags = nullptr;
+    uint32_t* d_kept = nullptr;
+    if (gate > 0) {
+        const size_t fbytes = ofps::gate_flags_bytes(nblk);
+        d_raw = static_cast<float4*>(ofps::scratch(ctx, ofps::S_GATE_RAW, nblk * sizeof(float4)));
+        auto* d_flags_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_GATE_FLAGS, kTickets * fbytes));
+        if (!d_raw || !d_flags_all) return OFPS_HIP_ENOMEM;
+        d_flags = d_flags_all + (size_t)tix * fbytes;
+        d_kept = ofps::gate_kept(d_flags, nblk);
+        if (!ctx->pipe.gate_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe.gate_done, hipEventDisableTiming));
+        // fork on the upload: its own event when it ran on the copy stream (the flags are then made beside the previous ticket's tail as
+        // well), else the compute stream's position, which is right behind the upload
+        if (cur_by_event) {
+            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.uploaded[cur_slot], 0));
+        } else {
+            OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.fork, s));
+            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.fork, 0));
+        }
+        rc = ofps::sad_gate_flags_device(ctx, slots + (size_t)cur_slot * pitch, W, H, dstride, prm->block, gate, ofps::gate_counts(d_flags),
+                                         ofps::gate_keep(d_flags, nblk), ctx->pipe.aux_stream);
+        if (rc != OFPS_HIP_OK) return rc;
+        OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.gate_done, ctx->pipe.aux_stream));
+    }
     rc = ofps::sad_pairs_device(ctx, slots + (size_t)prev_slot * pitch, 0, slots + (size_t)cur_slot * pitch, 0, 1, W, H, dstride,
-                                prm->block, prm->range, d_ent, nullptr);
+                                prm->block, prm->range, d_raw, nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     // the older slot may be overwritten once this search is through; the same event forks the detector's stream below
     // (one barrier packet between the search and the estimator instead of two)
     OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.slot_read[prev_slot], s));
     ctx->pipe.slot_read_valid[prev_slot] = true;
-    t.have_vectors = 1; t.n_vectors = nblk;
+    t.have_vectors = 1; t.n_vectors = nblk; t.gated = gate > 0;
+    if (gate > 0) {
+        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.gate_done, 0));
+        rc = ofps::sad_gate_compact_device(ctx, d_raw, nullptr, ofps::gate_keep(d_flags, nblk), nblk, d_ent, nullptr, d_kept);
+        if (rc != OFPS_HIP_OK) return rc;
+    }
 
     int dim = 0;
     int* d_res = reinterpret_cast<int*>(d_out);
@@ -189,29 +230,38 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     // there and passes it on to the ticket's block); the compensated records have a slot of their own: d_ent is what the caller gets.
     const bool compensate = ctx->opt.detect_compensate == 1 && prm->run_detector && prm->run_estimator;
     const bool fork = prm->run_detector && prm->run_estimator && !compensate;
-    if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.slot_read[prev_slot], 0));
+    if (fork && gate > 0) {                                      // the detector's stream starts behind the compaction, not behind the search
+        OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.fork, s));
+        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.fork, 0));
+    } else if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.slot_read[prev_slot], 0));
+    // gate on: estimator, compensation and detector in their device-count forms -- every launch sized from the capacity nblk, the first
+    // *d_kept records count; fewer than 3 kept records -> identity (both solvers), none -> no motion
+    auto estimate = [&](float4* d_q) {
+        return gate > 0 ? ofps::almeida_device_n(ctx, d_ent, nblk, d_kept, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
+                                                 prm->inlier_deg, prm->num_samples, prm->seed, d_q, /*lsq_min_n=*/3)
+                        : ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
+                                               prm->inlier_deg, prm->num_samples, prm->seed, d_q);
+    };
     const float4* d_det_in = d_ent;
     if (compensate) {
         auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, nblk * sizeof(float4)));
         if (!d_comp) return OFPS_HIP_ENOMEM;
         float4* d_quat_dev = reinterpret_cast<float4*>(d_out + 16);
-        rc = ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
-                                  prm->inlier_deg, prm->num_samples, prm->seed, d_quat_dev);
+        rc = estimate(d_quat_dev);
         if (rc != OFPS_HIP_OK) return rc;
-        rc = ofps::compensate_device(ctx, d_ent, nblk, 1, nullptr, prm->aspect, prm->fov_y_deg, d_quat_dev, d_comp, direct ? d_quat : nullptr);
+        rc = ofps::compensate_device(ctx, d_ent, nblk, 1, d_kept, prm->aspect, prm->fov_y_deg, d_quat_dev, d_comp, direct ? d_quat : nullptr);
         if (rc != OFPS_HIP_OK) return rc;
         d_det_in = d_comp;
     }
     // the estimator is enqueued first: it is the long pole (0.1 ms of dependent steps against the detector's seven small
     // launches), and whatever is enqueued second starts a host-enqueue time later
     if (prm->run_estimator && !compensate) {
-        rc = ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
-                                  prm->inlier_deg, prm->num_samples, prm->seed, d_quat);
+        rc = estimate(d_quat);
         if (rc != OFPS_HIP_OK) return rc;
     }
     if (prm->run_detector) {
         if (fork) ctx->stream = ctx->pipe.aux_stream;           // the stage entry points enqueue on ctx->stream
-        rc = ofps::detect_device(ctx, d_det_in, nblk, 1, prm->min_size, prm->subdivide, prm->target_motion, d_res, d_field, &dim);
+        rc = ofps::detect_device(ctx, d_det_in, nblk, 1, prm->min_size, prm->subdivide, prm->target_motion, d_res, d_field, &dim, d_kept);
         if (fork) {
             ctx->stream = s;
             if (rc == OFPS_HIP_OK) OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.join, ctx->pipe.aux_stream));
@@ -220,7 +270,11 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     }
     if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.join, 0));
     if ((prm->run_detector || prm->run_estimator) && !direct) {
-        rc = ofps::read_back_device(ctx, t.pinned, d_out, sizeof(PipeOut), s);
+        rc = ofps::read_back_device(ctx, t.pinned, d_out, kPipeOutPlain, s);
+        if (rc != OFPS_HIP_OK) return rc;
+    }
+    if (gate > 0) {                                              // the kept count travels in the ticket's page-locked block
+        rc = ofps::read_back_device(ctx, static_cast<char*>(t.pinned) + offsetof(PipeOut, kept), d_kept, sizeof(uint32_t), s);
         if (rc != OFPS_HIP_OK) return rc;
     }
     if (out_entries && nblk) {
@@ -265,6 +319,7 @@ int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* ou
     out->n_vectors = t->n_vectors;
     if (t->have_vectors) {
         const auto* host = static_cast<const PipeOut*>(t->pinned);
+        if (t->gated) out->n_vectors = host->kept[0] < t->n_vectors ? host->kept[0] : t->n_vectors;
         if (t->run_detector) {
             out->has_motion = host->result[0];
             out->area = (size_t)host->result[1];

@@ -1,0 +1,204 @@
+// sad_gate.hip -- hip_sad's contrast gate (include/ofps_hip.h N1g): a lattice block whose pixels hold fewer than `min_pixels` set pixels
+// of cv-decoder's contrast mask of the CURRENT frame yields no record -- what av-decoder does with a block the encoder did not predict
+// (av-decoder/src/lib.rs:396-419) and what the dense decoders do per pixel (mask.hip).
+//
+// block_contrast_kernel: the mask's arithmetic (mask_tile.hpp: 64x16 tile, halo 7, reflect-101, separable Sobel, threshold, ballot-packed
+// rows, ellipse by 128-bit window extraction) WITHOUT the pixel mask: each wave ballots its dilated rows into 16 row masks of the tile,
+// and the row masks are popcounted per lattice block.  HBM traffic: the mask kernel's reads, 4 bytes per BLOCK written instead of one
+// per pixel.  For block 8 and 16 the tile origin lies on the lattice and a block lies in one tile: one writer per count, plain stores.
+// Any other block size <= 64: a block straddles tiles, the partial counts are added with atomicAdd to a zeroed buffer (integer sums: the
+// result does not depend on the order).
+// block_keep_kernel: count >= min_pixels -> one byte per block, the flag the ordered compactions of mask.hip take.
+// compact_best_kernel: the (dx, dy, SAD) triples compacted by the same flags in the same order.
+#include "common.hpp"
+#include "mask_tile.hpp"
+
+namespace ofps {
+
+__global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx,
+                                                             int nby, int lattice, uint32_t* __restrict__ counts) {
+    __shared__ uint8_t g[MG_H][MG_W + 2];
+    __shared__ short hx[MG_H][MS_W + 2];
+    __shared__ unsigned long long rowbits[MS_H][2];          // thresholded window, one bit per column
+    __shared__ unsigned long long drow[MT_H];                // the tile's mask rows, one bit per column (pixels outside the frame: 0)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = blockIdx.x * MT_W, y0 = blockIdx.y * MT_H;
+    mask_tile_rowbits(gray, W, H, stride, x0, y0, g, hx, rowbits);
+#pragma unroll
+    for (int k = 0; k < MT_H / 4; ++k) {
+        const int ly = wave + 4 * k;
+        const bool m = mask_tile_dilated(rowbits, lane, ly);
+        const unsigned long long bal = __ballot(m && x0 + lane < W && y0 + ly < H);
+        if (lane == 0) drow[ly] = bal;
+    }
+    __syncthreads();
+    // thread j: the j-th block column that meets the tile, clipped to the tile: bits [lo, hi) of every row mask
+    if (tid >= MT_W) return;
+    const int bx = x0 / block + tid;
+    if (bx >= nbx) return;
+    const int lo = max(bx * block, x0) - x0, hi = min(bx * block + block, x0 + MT_W) - x0;
+    if (lo >= MT_W) return;
+    const unsigned long long seg = hi - lo == 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull);
+    uint32_t c = 0;
+    int by = y0 / block;
+    for (int r = 0; r < MT_H; ++r) {
+        const int b = (y0 + r) / block;
+        if (b != by) {                                        // a block row ends inside the tile
+            if (lattice) counts[(size_t)by * nbx + bx] = c; else if (c) atomicAdd(&counts[(size_t)by * nbx + bx], c);
+            c = 0; by = b;
+        }
+        if (by >= nby) return;                                // the ragged bottom margin belongs to no block
+        c += (uint32_t)__popcll((drow[r] >> lo) & seg);
+    }
+    // lattice: MT_H is a multiple of the block size, the last block row ends with the tile
+    if (lattice) counts[(size_t)by * nbx + bx] = c; else if (c) atomicAdd(&counts[(size_t)by * nbx + bx], c);
+}
+
+__global__ __launch_bounds__(256) void block_keep_kernel(const uint32_t* __restrict__ counts, uint32_t n, uint32_t min_pixels,
+                                                         uint8_t* __restrict__ keep) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) keep[i] = counts[i] >= min_pixels ? 1 : 0;
+}
+
+// compact_small_kernel's scheme (mask.hip) for 12-byte triples, any n: one workgroup, 1,024 triples per round
+__global__ __launch_bounds__(1024) void compact_best_kernel(const int* __restrict__ in, const uint8_t* __restrict__ keep_flags, uint32_t n,
+                                                            int* __restrict__ out) {
+    __shared__ uint32_t wtot[16];
+    __shared__ uint32_t base_sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) base_sh = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < n; i0 += 1024) {
+        const uint32_t i = i0 + tid;
+        const bool keep = i < n && keep_flags[i];
+        int v0 = 0, v1 = 0, v2 = 0;
+        if (keep) { v0 = in[3 * (size_t)i]; v1 = in[3 * (size_t)i + 1]; v2 = in[3 * (size_t)i + 2]; }
+        const unsigned long long bal = __ballot(keep);
+        const uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base_sh;
+        for (int k = 0; k < wave; ++k) off += wtot[k];
+        if (keep) { int* o = out + 3 * (size_t)(off + rank); o[0] = v0; o[1] = v1; o[2] = v2; }
+        __syncthreads();
+        if (tid == 0) { uint32_t t = 0; for (int k = 0; k < 16; ++k) t += wtot[k]; base_sh += t; }
+        __syncthreads();
+    }
+}
+
+int block_contrast_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, int W, int H, int stride, int block, uint32_t* d_counts, hipStream_t st) {
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
+    OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
+    const int nbx = W / block, nby = H / block;
+    if (nbx == 0 || nby == 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "block_contrast: too many blocks");
+    const int lattice = block == 8 || block == 16;
+    if (!lattice) OFPS_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)nbx * nby * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(block_contrast_kernel, dim3((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H), dim3(256), 0, st, d_luma, W, H, stride,
+                       block, nbx, nby, lattice, d_counts);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const char* who) {
+    OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "%s: block=%d outside [1,64]", who, block);
+    OFPS_REQUIRE(ctx, min_pixels >= 1 && min_pixels <= block * block, "%s: contrast gate %d outside [1, %d] for block %d", who, min_pixels,
+                 block * block, block);
+    return OFPS_HIP_OK;
+}
+
+int sad_gate_flags_device(ofps_hip_ctx* ctx, const uint8_t* d_cur, int W, int H, int stride, int block, int min_pixels, uint32_t* d_counts,
+                          uint8_t* d_keep, hipStream_t st) {
+    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
+    if (!nblk) return OFPS_HIP_OK;
+    const int rc = block_contrast_device(ctx, d_cur, W, H, stride, block, d_counts, st);
+    if (rc != OFPS_HIP_OK) return rc;
+    hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_counts, (uint32_t)nblk, (uint32_t)min_pixels, d_keep);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+int sad_gate_compact_device(ofps_hip_ctx* ctx, const float4* d_raw, const int* d_raw_best, const uint8_t* d_keep, size_t nblk, float4* d_out,
+                            int* d_out_best, uint32_t* d_count) {
+    if (nblk == 0) {
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
+        return OFPS_HIP_OK;
+    }
+    const int rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_keep, nblk, d_out, d_count)
+                                            : compact_entries_device(ctx, d_raw, d_keep, nblk, d_out, d_count);
+    if (rc != OFPS_HIP_OK) return rc;
+    if (d_out_best) {
+        hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_raw_best, d_keep, (uint32_t)nblk, d_out_best);
+        OFPS_HIP_TRY(ctx, hipGetLastError());
+    }
+    return OFPS_HIP_OK;
+}
+
+// One pair, everything on ctx->stream: search into the gate's own slots, flags of `cur`, compaction into the caller's buffers.
+int sad_flow_gated_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                          int min_pixels, float4* d_out, int* d_out_best, uint32_t* d_count) {
+    int rc = sad_gate_check(ctx, block, min_pixels, "sad_flow");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
+    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
+    auto* d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, nblk * sizeof(float4)));
+    auto* d_raw_best = d_out_best ? static_cast<int*>(scratch(ctx, S_GATE_BEST, nblk * 3 * sizeof(int))) : nullptr;
+    auto* d_flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, gate_flags_bytes(nblk)));
+    if (!d_raw || !d_flags || (d_out_best && !d_raw_best)) return OFPS_HIP_ENOMEM;
+    rc = sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, d_raw_best);
+    if (rc != OFPS_HIP_OK) return rc;
+    rc = sad_gate_flags_device(ctx, d_cur, W, H, stride, block, min_pixels, gate_counts(d_flags), gate_keep(d_flags, nblk), ctx->stream);
+    if (rc != OFPS_HIP_OK) return rc;
+    return sad_gate_compact_device(ctx, d_raw, d_raw_best, gate_keep(d_flags, nblk), nblk, d_out, d_out_best, d_count);
+}
+
+}  // namespace ofps
+
+extern "C" {
+
+int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_luma && d_out_counts, "block_contrast_dev: null device pointer");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ofps::block_contrast_device(ctx, static_cast<const uint8_t*>(d_luma), W, H, stride, block, static_cast<uint32_t*>(d_out_counts), ctx->stream);
+}
+
+int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_counts) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, luma && out_counts, "block_contrast: null host pointer");
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
+    OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
+    if (!nblk) return OFPS_HIP_OK;
+    auto* d_gray = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)W * H));
+    auto* d_flags = static_cast<char*>(ofps::scratch(ctx, ofps::S_GATE_FLAGS, ofps::gate_flags_bytes(nblk)));
+    if (!d_gray || !d_flags) return OFPS_HIP_ENOMEM;
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_gray, W, luma, stride, W, H, ctx->stream));
+    const int rc = ofps::block_contrast_device(ctx, d_gray, W, H, W, block, ofps::gate_counts(d_flags), ctx->stream);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, ofps::gate_counts(d_flags), nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_set_sad_gate(ofps_hip_ctx* ctx, int min_pixels) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, min_pixels >= 0, "set_sad_gate: %d is negative", min_pixels);
+    ctx->opt.sad_gate = min_pixels;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_sad_gate(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.sad_gate : OFPS_HIP_EINVAL; }
+
+int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
+                                int min_pixels, void* d_out_entries, void* d_out_best, void* d_out_count) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "sad_flow_gated_dev: null device pointer");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ofps::sad_flow_gated_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
+                                       min_pixels, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                       static_cast<uint32_t*>(d_out_count));
+}
+
+}  // extern "C"

@@ -70,7 +70,11 @@ class HipSadDecoder(Properties):
     block vectors in av-decoder's record convention (av-decoder/src/lib.rs:404-419)."""
     _PROPS = (("Block size", "usize", "block", 8, 16), ("Search range", "usize", "range", 8, 32),
               ("Exact pruning", "bool", "pruned", None, None),      # same vectors; faster on smooth camera motion (16x16, +-16)
-              ("Quarter pel", "bool", "quarter_pel", None, None))   # motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
+              ("Quarter pel", "bool", "quarter_pel", None, None),   # motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
+              # build-defined like "Quarter pel": 0 = one vector per block; N = only blocks with at least N contrast-mask pixels of the
+              # current frame (include/ofps_hip.h N1g).  The upper bound is the largest block's area; a value above Block size^2 is refused
+              # by the call
+              ("Contrast gate", "usize", "contrast_gate", 0, 256))
 
     def __init__(self, frames: Iterable[np.ndarray], framerate: Optional[float] = None, device: int = 0):
         self.ctx = HipContext(device)
@@ -78,6 +82,7 @@ class HipSadDecoder(Properties):
         self.block, self.range = 16, 16
         self.pruned = False
         self.quarter_pel = False
+        self.contrast_gate = 0
         self._prev: Optional[np.ndarray] = None
         self._cur: Optional[np.ndarray] = None
         self._fps = framerate
@@ -115,6 +120,7 @@ class HipSadDecoder(Properties):
             out_frame[:] = [self._cur.copy()]
         self.ctx.set_sad_mode(self.ctx.SAD_PRUNED if self.pruned else self.ctx.SAD_EXHAUSTIVE)
         self.ctx.set_sad_motion_scale(4 if self.quarter_pel else 1)
+        self.ctx.set_sad_gate(self.contrast_gate)
         r = self.ctx.push_frame(self._cur, self.block, self.range, detector=False, estimator=False, want_entries=True)
         if not r["have_vectors"]:                          # first frame of the stream / geometry change
             return False

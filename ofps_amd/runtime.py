@@ -114,12 +114,47 @@ class HipContext:
     def get_sad_motion_scale(self) -> int:
         return int(self._lib.ofps_hip_get_sad_motion_scale(self._h))
 
+    def set_sad_gate(self, min_pixels: int):
+        """hip_sad's contrast gate (include/ofps_hip.h N1g): 0 = one record per lattice block (default); N >= 1 = only the blocks that hold
+        at least N set pixels of the current frame's contrast mask yield a record (sad_flow, push_frame[_async])."""
+        self._check(self._lib.ofps_hip_set_sad_gate(self._h, min_pixels))
+
+    def get_sad_gate(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_gate(self._h))
+
+    def block_contrast(self, luma: np.ndarray, block: int, stride: int | None = None) -> np.ndarray:
+        """Set pixels of the contrast mask of `luma` per full lattice block -> uint32 [H // block, W // block].  stride: as for contrast_mask."""
+        if stride is None:
+            g = np.ascontiguousarray(luma, np.uint8)
+            stride = g.shape[1]
+        else:
+            g = luma
+            assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
+        H, W = g.shape
+        out = np.zeros((H // block, W // block), np.uint32)
+        buf = out if out.size else np.zeros(1, np.uint32)
+        self._check(self._lib.ofps_hip_block_contrast(self._h, C.cast(C.c_void_p(g.ctypes.data), C.POINTER(C.c_uint8)), W, H, stride, block,
+                                                      buf.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def block_contrast_dev(self, d_luma: int, W: int, H: int, stride: int, block: int, d_out_counts: int):
+        self._check(self._lib.ofps_hip_block_contrast_dev(self._h, C.c_void_p(d_luma), W, H, stride, block, C.c_void_p(d_out_counts)))
+
+    def sad_flow_gated_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, search_range: int, min_pixels: int,
+                           d_out_entries: int, d_out_best: int | None, d_out_count: int):
+        """One pair of device frames through the contrast gate: the kept records first (capacity nblk), their count in *d_out_count (u32).
+        Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_gated_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, search_range,
+                                                          min_pixels, C.c_void_p(d_out_entries), C.c_void_p(d_out_best or 0),
+                                                          C.c_void_p(d_out_count)))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))
         return int(n.value)
 
     def sad_flow(self, prev: np.ndarray, cur: np.ndarray, block: int, search_range: int, want_best=False):
+        """-> records [n, 4] (and (dx, dy, SAD) triples [n, 3]): n = one per lattice block, or the kept blocks with the contrast gate on"""
         prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
         assert prev.shape == cur.shape and prev.ndim == 2
         H, W = prev.shape
@@ -131,8 +166,9 @@ class HipContext:
         self._check(self._lib.ofps_hip_sad_flow(self._h, prev.ctypes.data_as(u8), cur.ctypes.data_as(u8), W, H, W,
                                                 block, search_range, _fp(ent),
                                                 best.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out)))
-        assert n_out.value == nb
-        return (ent[:nb], best[:nb]) if want_best else ent[:nb]
+        n = int(n_out.value)
+        assert n <= nb
+        return (ent[:n], best[:n]) if want_best else ent[:n]
 
     def sad_flow_dev(self, d_frames: int, n_frames: int, W: int, H: int, stride: int, frame_pitch: int, ref_mode: int,
                      block: int, search_range: int, d_out_entries: int, d_out_best: int | None = None):
@@ -618,7 +654,8 @@ class HipContext:
                                                   _fp(fld) if want_field else None))
         motion = (int(res.area), fld) if res.has_motion else None
         return {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors), "motion": motion,
-                "quat": np.array(list(res.quat), np.float32), "entries": ent[:nb] if (want_entries and res.have_vectors) else None}
+                "quat": np.array(list(res.quat), np.float32),
+                "entries": ent[:min(nb, int(res.n_vectors))] if (want_entries and res.have_vectors) else None}      # (the kept records with the contrast gate on)
 
 
 def device_count() -> int:

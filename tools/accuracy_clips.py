@@ -114,7 +114,16 @@ def stats(est, truth):
             "drift_deg": synth.quat_angle_deg(accumulate(est), accumulate(truth))}
 
 
-def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False):
+def flat_third(frames, seed=5):
+    """the clip with its right third replaced by constant 128 plus {0, 1} noise, fresh per frame: texture-free blocks under sensor noise"""
+    out = np.array(frames, np.uint8)
+    x0 = out.shape[2] * 2 // 3
+    rng = np.random.default_rng(seed)
+    out[:, :, x0:] = (128 + rng.integers(0, 2, out[:, :, x0:].shape)).astype(np.uint8)
+    return out
+
+
+def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -125,12 +134,22 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
               ("hip_flow", HipFlowDecoder, False, {}), ("hip_flow", HipFlowDecoder, True, {})]
     if quarter_pel:     # hip_sad with its "Quarter pel" property on (motion_scale 4: include/ofps_hip.h N1q); off by default: the -m gpu test's run time
         combos[2:2] = [("hip_sad_q", HipSadDecoder, False, {"Quarter pel": True}), ("hip_sad_q", HipSadDecoder, True, {"Quarter pel": True})]
+    if sad_gate:        # hip_sad with its "Contrast gate" property at N (include/ofps_hip.h N1g), and every clip once more with a flat noisy third
+        combos[2:2] = [("hip_sad_g", HipSadDecoder, False, {"Contrast gate": sad_gate}), ("hip_sad_g", HipSadDecoder, True, {"Contrast gate": sad_gate})]
     res = {}
-    for name, (W, H, fov, eul, dis) in clip_table(quick).items():
+    clips = []
+    for name, geom in clip_table(quick).items():
         if only and name not in only:
             continue
+        clip_seed = 21 + sum(1 for c in clips if not c[3])         # the n-th clip that runs renders with seed 21 + n
+        clips.append((name, geom, clip_seed, False))
+        if sad_gate:
+            clips.append((name + "_flat_third", geom, clip_seed, True))
+    for name, (W, H, fov, eul, dis), clip_seed, flat in clips:
         t0 = time.perf_counter()
-        frames, truth = synth.rotation_clip(eul, W, H, fov, seed=21 + len(res), distractor=dis)
+        frames, truth = synth.rotation_clip(eul, W, H, fov, seed=clip_seed, distractor=dis)
+        if flat:
+            frames = flat_third(frames)
         t_render = time.perf_counter() - t0
         cam = StandardCamera(W / H, fov)
         row = {"geometry": f"{W}x{H}", "fov_y_deg": fov, "frames": len(frames), "px_per_deg_at_centre": round(H / 2 / np.tan(np.radians(fov) / 2) * np.radians(1.0), 2),
@@ -167,6 +186,8 @@ def table(res):
             "cpu_oracle:sad+lsq"]
     if any("hip_sad_q+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
+    if any("hip_sad_g+lsq" in r for r in res.values()):
+        cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
     lines = []
     lines.append("mean rotation error per frame, degrees (docs/statistics/err_av.csv's unit); clip rows, decoder+estimator columns")
     lines.append("clip,geometry,mean_rot_deg_per_frame,px_per_deg," + ",".join(cols))
@@ -207,8 +228,11 @@ def main():
     ap.add_argument("--no-oracle", action="store_true")
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--quarter-pel", action="store_true", help="add the hip_sad_q columns: hip_sad with \"Quarter pel\" on")
+    ap.add_argument("--sad-gate", type=int, default=0, metavar="N",
+                    help="add the hip_sad_g columns (hip_sad with \"Contrast gate\" = N) and a variant of every clip with a flat noisy right third")
     args = ap.parse_args()
-    res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel)
+    res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
+              sad_gate=args.sad_gate)
     txt = table(res)
     print(txt)
     if args.out:
