@@ -166,13 +166,60 @@ int ofps_hip_sad_flow_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames,
  *   d_out_entries / d_out_best have capacity nblk, d_out_count is one uint32 in device memory; enqueues only.
  * Out of scope: the batched forms -- ofps_hip_sad_flow_dev, ofps_hip_push_frames_async, the ofps_hip_multi_* workers -- ignore the gate and
  * always produce nblk records per pair (the device-count forms of the tail are one-item forms); a second criterion on the SAD surface
- * (best against second best) is not part of this. */
+ * (best against second best) is not part of this (the forward-backward check, N1c below, is the second criterion this build has). */
 int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_counts /* nblk */);
 int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts);
 int ofps_hip_set_sad_gate(ofps_hip_ctx* ctx, int min_pixels);   /* 0 = off (default) */
 int ofps_hip_get_sad_gate(ofps_hip_ctx* ctx);
 int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
                                 int min_pixels, void* d_out_entries, void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
+
+/* ---- N1c: hip_sad's forward-backward consistency check -- a winner that does not come back yields no record (csrc/sad_consistency.hip) ----
+ * The round-trip test of flow and stereo pipelines: search forward, search backward, drop what does not return.  It drops what the contrast
+ * gate keeps: blocks whose content left the frame or was occluded, repeated texture, noise that trips the mask's threshold, the block column
+ * the mask's dilation carries across a texture edge.  Build-defined, like N1, N1q and N1g.  For a frame pair (prev, cur), lattice `block`
+ * = B, nbx = W / B, nby = H / B:
+ *   F[k] = (dx, dy): the forward winner of block k -- what ofps_hip_sad_flow(prev, cur) reports in out_best at motion scale 1: the block of
+ *     cur at (x0, y0) matched prev at (x0 + dx, y0 + dy);
+ *   G[k'] = (ex, ey): the winner of the same search with the frames exchanged, sad(prev := cur, cur := prev), same block and range;
+ *   the partner of block k = (bx, by): cx = bx*B + B/2 + dx, cy = by*B + B/2 + dy (the integer numerators of the record's pos; never
+ *     negative: the matched block lies inside the frame); bx' = min(cx / B, nbx - 1), by' = min(cy / B, nby - 1), integer division (the
+ *     clamp catches centres in the ragged right / bottom margin); k' = by'*nbx + bx';
+ *   residual(k) = max(|dx + ex|, |dy + ey|) with (ex, ey) = G[k']: an integer in [0, 2*range];
+ *   a block is KEPT iff residual < limit, limit in [1, 129]: 1 = an exact round trip.  A limit above 2*range + 1 is valid and keeps every block.
+ *   The check always uses the INTEGER winners of both directions: at motion scale 4 the backward search is never refined and the forward
+ *     refinement is unchanged.
+ *   Kept records and out_best triples keep raster order and are the unchecked call's records and triples bit for bit, quarter-pel or not.
+ *   With the contrast gate (N1g) on as well a block is kept iff both criteria keep it: one compaction, one count.
+ * Limit 0 = off, the default: every entry point then uses the launches, streams and bytes of a build without the check.  Negative values and
+ * values above 129 are OFPS_HIP_EINVAL at the setter.  The option OFPS_HIP_SAD_CONSISTENCY (environment / ofps_hip_set_option) sets the
+ * same field.
+ * The check says nothing about a clean flat block: both directions return 0 and the round trip is exact -- that is the contrast gate's job.
+ * ofps_hip_sad_consistency[_dev]: residuals and / or keep bytes from two arrays of (dx, dy, sad) triples in integer units (only dx and dy are
+ *   read), limit in [1, 129]; either output may be NULL.  The triples are the caller's responsibility: |d| above 64 gives an unspecified
+ *   flag, never an access out of bounds (k' is clamped on both sides).  The _dev form enqueues only.
+ * With the context's limit > 0:
+ *   ofps_hip_sad_flow: *n_out = the kept count, the kept records first (capacity nblk, as for the gate); the contrast gate is applied as well
+ *     when it is on.
+ *   ofps_hip_push_frame[_async] / ofps_hip_frame_wait: the gate's path with one more producer of keep flags -- the backward search runs on the
+ *     two resident frames right behind the forward one on the compute stream, then (behind the join with the contrast flags, if any) the
+ *     check, ONE compaction and the count in device memory; estimator, compensation (mode 1) and detector in their device-count forms.
+ *     n_vectors = the kept count; have_vectors stays 1 for every frame that ran a search; fewer than 3 kept -> identity, none -> no motion,
+ *     as N1g documents them.  A ticket follows the limit the context has when it is pushed.
+ * ofps_hip_sad_flow_checked_dev: one pair of device frames with an explicit min_pixels (0 = no contrast gate, else [1, B*B]) and limit in
+ *   [1, 129] (the context's values are not looked at); capacities and count as ofps_hip_sad_flow_gated_dev; enqueues only.
+ * In PRUNED mode ofps_hip_sad_pruned_overflow_strips then reports the backward search, the last one of the call.
+ * Out of scope, as for N1g: ofps_hip_sad_flow_dev, ofps_hip_push_frames_async and the ofps_hip_multi_* workers ignore the limit and always
+ * produce nblk records per pair. */
+int ofps_hip_sad_consistency(ofps_hip_ctx* ctx, const int32_t* fwd_best, const int32_t* bwd_best, int W, int H, int block, int limit,
+                             uint32_t* out_residual /* nblk or NULL */, uint8_t* out_keep /* nblk or NULL */);
+int ofps_hip_sad_consistency_dev(ofps_hip_ctx* ctx, const void* d_fwd_best, const void* d_bwd_best, int W, int H, int block, int limit,
+                                 void* d_out_residual /* or NULL */, void* d_out_keep /* or NULL */);
+int ofps_hip_set_sad_consistency(ofps_hip_ctx* ctx, int limit);   /* 0 = off (default) */
+int ofps_hip_get_sad_consistency(ofps_hip_ctx* ctx);
+int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
+                                  int min_pixels /* 0 = no contrast gate */, int limit /* >= 1 */, void* d_out_entries,
+                                  void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
 
 /* ---- N2: dense per-pixel flow, pyramidal Lucas-Kanade ("hip_lk" Decoder) ----
  * The reference's only per-pixel flow is OpenCV's Farneback inside cv-decoder (cv-decoder/src/lib.rs:188-199); this

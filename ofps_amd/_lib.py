@@ -50,6 +50,11 @@ PROTOTYPES = {
     "ofps_hip_set_sad_gate": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_gate": (C.c_int, [_ctx]),
     "ofps_hip_sad_flow_gated_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_sad_consistency": (C.c_int, [_ctx, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _u32p, _u8p]),
+    "ofps_hip_sad_consistency_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ofps_hip_set_sad_consistency": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_consistency": (C.c_int, [_ctx]),
+    "ofps_hip_sad_flow_checked_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "ofps_hip_lk_flow": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     "ofps_hip_farneback_flow": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _f32p, _f32p]),
     "ofps_hip_farneback_flow_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp]),

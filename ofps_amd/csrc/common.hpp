@@ -84,7 +84,7 @@ struct PipeStream {
         bool pending = false; hipEvent_t done = nullptr;
         void* pinned = nullptr;          // page-locked PipeOut block for the result read-back
         int have_vectors = 0, run_detector = 0, run_estimator = 0;
-        int gated = 0;                   // pushed with the contrast gate on: n_vectors is the kept count in the page-locked block
+        int gated = 0;                   // pushed with the contrast gate or the consistency check on: n_vectors is the kept count in the page-locked block
         size_t n_vectors = 0;
     };
     hipEvent_t gate_done = nullptr;      // contrast gate (sad_gate.hip): the keep flags of the newest frame, made on aux_stream beside the search (created with the first gated push)
@@ -182,6 +182,7 @@ struct ofps_hip_ctx {
         int sad_motion_scale = 1;        // OFPS_HIP_SAD_MOTION_SCALE / ofps_hip_set_sad_motion_scale: 1 full-pel vectors, 4 quarter-pel refinement (sad_qpel.hip)
         int detect_compensate = 0;       // OFPS_HIP_DETECT_COMPENSATE / ofps_hip_set_detect_compensation: 0 the fused entry points' detector reads the raw vectors, 1 the vectors compensated with the frame's own quaternion (compensate.hip)
         int sad_gate = 0;                // OFPS_HIP_SAD_GATE / ofps_hip_set_sad_gate: 0 one record per lattice block, N >= 1 only blocks with at least N contrast-mask pixels of the current frame (sad_gate.hip)
+        int sad_consistency = 0;         // OFPS_HIP_SAD_CONSISTENCY / ofps_hip_set_sad_consistency: 0 off, N in [1, 129] only blocks whose forward-backward residual is below N (sad_consistency.hip)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -234,10 +235,13 @@ enum ScratchSlot {
     S_GATE_RAW,             // hip_sad's contrast gate (sad_gate.hip): the search's one-record-per-block output, in front of the compaction
     S_GATE_BEST,            // ... and its (dx, dy, SAD) triples
     S_GATE_FLAGS,           // ... [counts, u32 per block][kept count, 16 bytes][keep flags, u8 per block], one per ticket in flight in the fused path
-    S_COMP                  // detect-compensation mode 1 (compensate.hip): [quaternion, 16 bytes][compensated records] -- the detector's input; the slots the
+    S_COMP,                 // detect-compensation mode 1 (compensate.hip): [quaternion, 16 bytes][compensated records] -- the detector's input; the slots the
                             // record copy and the estimator read are never overwritten.  Written and read on the compute stream only
+    S_CONS_FWD,             // hip_sad's consistency check (sad_consistency.hip): the forward search's integer winners, kept through a quarter-pel refinement
+    S_CONS_BWD,             // ... the backward search's integer winners
+    S_CONS_BWD_ENT          // ... and its records, which nobody reads (the search kernels always write them).  All three: compute stream only
 };
-static_assert(S_COMP < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_CONS_BWD_ENT < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -257,9 +261,12 @@ int check_hip(ofps_hip_ctx* ctx, hipError_t e, const char* what);
 void* scratch(ofps_hip_ctx* ctx, int slot, size_t bytes);
 
 // ---- device-side stage entry points shared between translation units (all enqueue on ctx->stream)
+// integer_only: no quarter-pel refinement whatever the context's motion scale (the consistency check's backward search).
+// d_int_best (motion scale 4 only): the integer winners are written here, not to S_SAD_QBEST / d_out_best, and are still there behind the
+// refinement, which then writes its triples to d_out_best (or nowhere)
 int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
                      size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
-                     void* d_out_best);
+                     void* d_out_best, bool integer_only = false, void* d_int_best = nullptr);
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);
@@ -319,6 +326,18 @@ int sad_gate_compact_device(ofps_hip_ctx* ctx, const float4* d_raw, const int* d
                             int* d_out_best, uint32_t* d_count);
 int sad_flow_gated_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
                           int min_pixels, float4* d_out, int* d_out_best, uint32_t* d_count);
+
+// sad_consistency.hip: hip_sad's forward-backward consistency check (include/ofps_hip.h N1c)
+constexpr int kSadConsistencyMax = 129;                     // 2 * 64 + 1: above every residual of the largest search range
+int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);        // limit in [1, 129]
+// residual and / or keep byte per block from the two directions' integer winners, on stream st; d_keep_in (optional, may be d_out_keep) is ANDed in
+int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
+                                 const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st);
+// the forward search into d_raw and the backward search behind it, both on ctx->stream -> the integer winners of both and the records' triples
+int sad_consistency_searches_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                                    float4* d_raw, bool want_triples, const int** d_fwd, const int** d_bwd, const int** d_triples);
+int sad_flow_checked_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                            int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.

@@ -18,7 +18,7 @@ namespace {
 struct PipeOut {                 // layout of the pinned read-back block
     int result[4];               // has_motion, area, dim, 0
     float quat[4];
-    uint32_t kept[4];            // contrast gate on: the kept record count (sad_gate.hip); not read back, not looked at, with the gate off
+    uint32_t kept[4];            // contrast gate or consistency check on: the kept record count (sad_gate.hip, sad_consistency.hip); not read back, not looked at, with both off
 };
 constexpr size_t kPipeOutPlain = offsetof(PipeOut, kept);       // what a ticket without the gate reads back
 constexpr int kSlots = ofps::PipeStream::kSlots;
@@ -130,6 +130,14 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
         rc = ofps::sad_gate_check(ctx, prm->block, gate, "push_frame_async");
         if (rc != OFPS_HIP_OK) return rc;
     }
+    // consistency check (sad_consistency.hip; the limit is the context's at this push): one more producer of keep flags on the gate's path.
+    // `filtered`: either criterion is on; with only the gate on, everything enqueued below is what it was before the check existed
+    const int limit = ctx->opt.sad_consistency;
+    if (limit > 0) {
+        rc = ofps::sad_consistency_check(ctx, prm->block, limit, "push_frame_async");
+        if (rc != OFPS_HIP_OK) return rc;
+    }
+    const bool filtered = gate > 0 || limit > 0;
     hipStream_t s = ctx->stream;
     uint8_t* slots; size_t pitch; int dstride;
     const bool overlap = ctx->pipe.ring.other_pending();               // the other ticket is in flight
@@ -172,13 +180,15 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     float4* d_raw = d_ent;
     char* d_flags = nullptr;
     uint32_t* d_kept = nullptr;
-    if (gate > 0) {
+    if (filtered) {
         const size_t fbytes = ofps::gate_flags_bytes(nblk);
         d_raw = static_cast<float4*>(ofps::scratch(ctx, ofps::S_GATE_RAW, nblk * sizeof(float4)));
         auto* d_flags_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_GATE_FLAGS, kTickets * fbytes));
         if (!d_raw || !d_flags_all) return OFPS_HIP_ENOMEM;
         d_flags = d_flags_all + (size_t)tix * fbytes;
         d_kept = ofps::gate_kept(d_flags, nblk);
+    }
+    if (gate > 0) {
         if (!ctx->pipe.gate_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe.gate_done, hipEventDisableTiming));
         // fork on the upload: its own event when it ran on the copy stream (the flags are then made beside the previous ticket's tail as
         // well), else the compute stream's position, which is right behind the upload
@@ -193,16 +203,28 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
         if (rc != OFPS_HIP_OK) return rc;
         OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.gate_done, ctx->pipe.aux_stream));
     }
-    rc = ofps::sad_pairs_device(ctx, slots + (size_t)prev_slot * pitch, 0, slots + (size_t)cur_slot * pitch, 0, 1, W, H, dstride,
-                                prm->block, prm->range, d_raw, nullptr);
+    // check on: the forward search keeps its integer winners, the backward search runs on the same two resident slots right behind it on the
+    // compute stream (one context's searches share scratch: never two at once) -- both read prev_slot, so its event is recorded behind both
+    const int *d_fwd = nullptr, *d_bwd = nullptr;
+    if (limit > 0)
+        rc = ofps::sad_consistency_searches_device(ctx, slots + (size_t)prev_slot * pitch, slots + (size_t)cur_slot * pitch, W, H, dstride,
+                                                   prm->block, prm->range, d_raw, false, &d_fwd, &d_bwd, nullptr);
+    else
+        rc = ofps::sad_pairs_device(ctx, slots + (size_t)prev_slot * pitch, 0, slots + (size_t)cur_slot * pitch, 0, 1, W, H, dstride,
+                                    prm->block, prm->range, d_raw, nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     // the older slot may be overwritten once this search is through; the same event forks the detector's stream below
     // (one barrier packet between the search and the estimator instead of two)
     OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.slot_read[prev_slot], s));
     ctx->pipe.slot_read_valid[prev_slot] = true;
-    t.have_vectors = 1; t.n_vectors = nblk; t.gated = gate > 0;
-    if (gate > 0) {
-        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.gate_done, 0));
+    t.have_vectors = 1; t.n_vectors = nblk; t.gated = filtered;
+    if (filtered) {
+        if (gate > 0) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.gate_done, 0));
+        if (limit > 0) {                                         // behind the join: the contrast flags, when there are any, are ANDed in in place
+            uint8_t* d_keep = ofps::gate_keep(d_flags, nblk);
+            rc = ofps::sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, prm->block, limit, gate > 0 ? d_keep : nullptr, nullptr, d_keep, s);
+            if (rc != OFPS_HIP_OK) return rc;
+        }
         rc = ofps::sad_gate_compact_device(ctx, d_raw, nullptr, ofps::gate_keep(d_flags, nblk), nblk, d_ent, nullptr, d_kept);
         if (rc != OFPS_HIP_OK) return rc;
     }
@@ -230,14 +252,14 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     // there and passes it on to the ticket's block); the compensated records have a slot of their own: d_ent is what the caller gets.
     const bool compensate = ctx->opt.detect_compensate == 1 && prm->run_detector && prm->run_estimator;
     const bool fork = prm->run_detector && prm->run_estimator && !compensate;
-    if (fork && gate > 0) {                                      // the detector's stream starts behind the compaction, not behind the search
+    if (fork && filtered) {                                      // the detector's stream starts behind the compaction, not behind the search
         OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.fork, s));
         OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.fork, 0));
     } else if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.slot_read[prev_slot], 0));
-    // gate on: estimator, compensation and detector in their device-count forms -- every launch sized from the capacity nblk, the first
+    // gate or check on: estimator, compensation and detector in their device-count forms -- every launch sized from the capacity nblk, the first
     // *d_kept records count; fewer than 3 kept records -> identity (both solvers), none -> no motion
     auto estimate = [&](float4* d_q) {
-        return gate > 0 ? ofps::almeida_device_n(ctx, d_ent, nblk, d_kept, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
+        return filtered ? ofps::almeida_device_n(ctx, d_ent, nblk, d_kept, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
                                                  prm->inlier_deg, prm->num_samples, prm->seed, d_q, /*lsq_min_n=*/3)
                         : ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
                                                prm->inlier_deg, prm->num_samples, prm->seed, d_q);
@@ -273,7 +295,7 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
         rc = ofps::read_back_device(ctx, t.pinned, d_out, kPipeOutPlain, s);
         if (rc != OFPS_HIP_OK) return rc;
     }
-    if (gate > 0) {                                              // the kept count travels in the ticket's page-locked block
+    if (filtered) {                                              // the kept count travels in the ticket's page-locked block
         rc = ofps::read_back_device(ctx, static_cast<char*>(t.pinned) + offsetof(PipeOut, kept), d_kept, sizeof(uint32_t), s);
         if (rc != OFPS_HIP_OK) return rc;
     }

@@ -1088,7 +1088,7 @@ namespace ofps {
 // pair k between prev_base + k*prev_pitch and cur_base + k*cur_pitch.
 int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
                      size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
-                     void* d_out_best) {
+                     void* d_out_best, bool integer_only, void* d_int_best) {
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
     OFPS_REQUIRE(ctx, stride % 4 == 0 && ((uintptr_t)prev_base % 4) == 0 && ((uintptr_t)cur_base % 4) == 0 &&
                           prev_pitch % 4 == 0 && cur_pitch % 4 == 0,
@@ -1107,8 +1107,10 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // motion scale 4: the refinement (sad_qpel.hip) starts from the integer winners, so they are kept even when the caller wants none
-    const bool qpel = ctx->opt.sad_motion_scale == 4;
-    if (qpel && !p.out_best) {
+    // (consistency check, sad_consistency.hip: its backward search is integer_only; its forward search keeps the integer winners in d_int_best)
+    const bool qpel = ctx->opt.sad_motion_scale == 4 && !integer_only;
+    if (qpel && d_int_best) p.out_best = static_cast<int*>(d_int_best);
+    else if (qpel && !p.out_best) {
         p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
         if (!p.out_best) return OFPS_HIP_ENOMEM;
     }
@@ -1196,12 +1198,15 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (!d_frames || !d_ent || !d_best) return OFPS_HIP_ENOMEM;
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames, dstride, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames + pitch, dstride, cur, stride, W, H, ctx->stream));
-    if (ctx->opt.sad_gate > 0) {
-        // contrast gate (sad_gate.hip): the kept records first, their count from the device with them
+    if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0) {
+        // contrast gate (sad_gate.hip) and / or consistency check (sad_consistency.hip): the kept records first, their count from the device with them
         auto* d_kept = static_cast<uint32_t*>(ofps::scratch(ctx, ofps::S_RESULT, sizeof(uint32_t)));
         if (!d_kept) return OFPS_HIP_ENOMEM;
-        int rc = ofps::sad_flow_gated_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate,
-                                             reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept);
+        int rc = ctx->opt.sad_consistency > 0
+                     ? ofps::sad_flow_checked_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate,
+                                                     ctx->opt.sad_consistency, reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept)
+                     : ofps::sad_flow_gated_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate,
+                                                   reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept);
         if (rc != OFPS_HIP_OK) return rc;
         uint32_t kept = 0;
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));

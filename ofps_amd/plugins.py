@@ -74,7 +74,10 @@ class HipSadDecoder(Properties):
               # build-defined like "Quarter pel": 0 = one vector per block; N = only blocks with at least N contrast-mask pixels of the
               # current frame (include/ofps_hip.h N1g).  The upper bound is the largest block's area; a value above Block size^2 is refused
               # by the call
-              ("Contrast gate", "usize", "contrast_gate", 0, 256))
+              ("Contrast gate", "usize", "contrast_gate", 0, 256),
+              # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
+              # include/ofps_hip.h N1c).  Costs a second search per frame
+              ("Consistency check", "usize", "consistency", 0, 129))
 
     def __init__(self, frames: Iterable[np.ndarray], framerate: Optional[float] = None, device: int = 0):
         self.ctx = HipContext(device)
@@ -83,6 +86,7 @@ class HipSadDecoder(Properties):
         self.pruned = False
         self.quarter_pel = False
         self.contrast_gate = 0
+        self.consistency = 0
         self._prev: Optional[np.ndarray] = None
         self._cur: Optional[np.ndarray] = None
         self._fps = framerate
@@ -121,6 +125,7 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_mode(self.ctx.SAD_PRUNED if self.pruned else self.ctx.SAD_EXHAUSTIVE)
         self.ctx.set_sad_motion_scale(4 if self.quarter_pel else 1)
         self.ctx.set_sad_gate(self.contrast_gate)
+        self.ctx.set_sad_consistency(self.consistency)
         r = self.ctx.push_frame(self._cur, self.block, self.range, detector=False, estimator=False, want_entries=True)
         if not r["have_vectors"]:                          # first frame of the stream / geometry change
             return False

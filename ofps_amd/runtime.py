@@ -148,13 +148,50 @@ class HipContext:
                                                           min_pixels, C.c_void_p(d_out_entries), C.c_void_p(d_out_best or 0),
                                                           C.c_void_p(d_out_count)))
 
+    def set_sad_consistency(self, limit: int):
+        """hip_sad's forward-backward consistency check (include/ofps_hip.h N1c): 0 = off (default); N in [1, 129] = only the blocks whose
+        round-trip residual max(|dx + ex|, |dy + ey|) is below N yield a record (sad_flow, push_frame[_async]); 1 = an exact round trip."""
+        self._check(self._lib.ofps_hip_set_sad_consistency(self._h, limit))
+
+    def get_sad_consistency(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_consistency(self._h))
+
+    def sad_consistency(self, fwd_best: np.ndarray, bwd_best: np.ndarray, W: int, H: int, block: int, limit: int, want_residual=True,
+                        want_keep=True):
+        """The check alone on two [nblk, 3] arrays of (dx, dy, sad) integer winners (forward, backward) -> (residual uint32 [nblk] or None,
+        keep uint8 [nblk] or None)."""
+        f = np.ascontiguousarray(fwd_best, np.int32); b = np.ascontiguousarray(bwd_best, np.int32)
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        assert f.shape == b.shape == (nb, 3)
+        res = np.zeros(max(nb, 1), np.uint32) if want_residual else None
+        keep = np.zeros(max(nb, 1), np.uint8) if want_keep else None
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_sad_consistency(self._h, f.ctypes.data_as(i32), b.ctypes.data_as(i32), W, H, block, limit,
+                                                       res.ctypes.data_as(C.POINTER(C.c_uint32)) if want_residual else None,
+                                                       keep.ctypes.data_as(C.POINTER(C.c_uint8)) if want_keep else None))
+        return (res[:nb] if want_residual else None), (keep[:nb] if want_keep else None)
+
+    def sad_consistency_dev(self, d_fwd_best: int, d_bwd_best: int, W: int, H: int, block: int, limit: int, d_out_residual: int | None,
+                            d_out_keep: int | None):
+        self._check(self._lib.ofps_hip_sad_consistency_dev(self._h, C.c_void_p(d_fwd_best), C.c_void_p(d_bwd_best), W, H, block, limit,
+                                                           C.c_void_p(d_out_residual or 0), C.c_void_p(d_out_keep or 0)))
+
+    def sad_flow_checked_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, search_range: int, min_pixels: int,
+                             limit: int, d_out_entries: int, d_out_best: int | None, d_out_count: int):
+        """One pair of device frames through the consistency check (and the contrast gate when min_pixels > 0): the kept records first
+        (capacity nblk), their count in *d_out_count (u32).  Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_checked_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, search_range,
+                                                            min_pixels, limit, C.c_void_p(d_out_entries), C.c_void_p(d_out_best or 0),
+                                                            C.c_void_p(d_out_count)))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))
         return int(n.value)
 
     def sad_flow(self, prev: np.ndarray, cur: np.ndarray, block: int, search_range: int, want_best=False):
-        """-> records [n, 4] (and (dx, dy, SAD) triples [n, 3]): n = one per lattice block, or the kept blocks with the contrast gate on"""
+        """-> records [n, 4] (and (dx, dy, SAD) triples [n, 3]): n = one per lattice block, or the kept blocks with the contrast gate and / or
+        the consistency check on"""
         prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
         assert prev.shape == cur.shape and prev.ndim == 2
         H, W = prev.shape

@@ -12,6 +12,7 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               with "Pyramid levels" = 5, the reference's Farneback depth)  |  hip_flow (Farneback's polynomial-expansion flow with
               cv-decoder's own arguments: levels 5, winsize 13, 3 iterations, poly_n 7, poly_sigma 1.5; same mask and records)
               with --quarter-pel also hip_sad_q: hip_sad with its "Quarter pel" property on (motion scale 4, include/ofps_hip.h N1q)
+              with --sad-consistency N also hip_sad_c: hip_sad with its "Consistency check" property at N (include/ofps_hip.h N1c)
   estimators  hip_almeida LSQ  |  hip_almeida RANSAC (the reference's default: 200 hypotheses x 1000 samples, 0.05 degree inliers)
 Per clip and combination: mean and max of angle_to(planted q_k, estimated r_k) over the frames, that mean relative to the clip's mean
 rotation per frame (the reference's own test bound is 10 %: almeida-estimator/src/lib.rs:347-348), and the pose drift after the
@@ -123,7 +124,7 @@ def flat_third(frames, seed=5):
     return out
 
 
-def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0):
+def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -136,6 +137,12 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         combos[2:2] = [("hip_sad_q", HipSadDecoder, False, {"Quarter pel": True}), ("hip_sad_q", HipSadDecoder, True, {"Quarter pel": True})]
     if sad_gate:        # hip_sad with its "Contrast gate" property at N (include/ofps_hip.h N1g), and every clip once more with a flat noisy third
         combos[2:2] = [("hip_sad_g", HipSadDecoder, False, {"Contrast gate": sad_gate}), ("hip_sad_g", HipSadDecoder, True, {"Contrast gate": sad_gate})]
+    if sad_consistency:  # hip_sad with its "Consistency check" property at N (include/ofps_hip.h N1c); with --quarter-pel also on top of "Quarter pel"
+        props_c = {"Consistency check": sad_consistency}
+        combos[2:2] = [("hip_sad_c", HipSadDecoder, False, props_c), ("hip_sad_c", HipSadDecoder, True, props_c)]
+        if quarter_pel:
+            props_qc = {"Quarter pel": True, "Consistency check": sad_consistency}
+            combos[2:2] = [("hip_sad_qc", HipSadDecoder, False, props_qc), ("hip_sad_qc", HipSadDecoder, True, props_qc)]
     res = {}
     clips = []
     for name, geom in clip_table(quick).items():
@@ -188,6 +195,9 @@ def table(res):
         cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
     if any("hip_sad_g+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
+    for tag in ("hip_sad_c", "hip_sad_qc"):
+        if any(tag + "+lsq" in r for r in res.values()):
+            cols[2:2] = [tag + "+lsq", tag + "+ransac"]
     lines = []
     lines.append("mean rotation error per frame, degrees (docs/statistics/err_av.csv's unit); clip rows, decoder+estimator columns")
     lines.append("clip,geometry,mean_rot_deg_per_frame,px_per_deg," + ",".join(cols))
@@ -230,9 +240,11 @@ def main():
     ap.add_argument("--quarter-pel", action="store_true", help="add the hip_sad_q columns: hip_sad with \"Quarter pel\" on")
     ap.add_argument("--sad-gate", type=int, default=0, metavar="N",
                     help="add the hip_sad_g columns (hip_sad with \"Contrast gate\" = N) and a variant of every clip with a flat noisy right third")
+    ap.add_argument("--sad-consistency", type=int, default=0, metavar="N",
+                    help="add the hip_sad_c columns (hip_sad with \"Consistency check\" = N; with --quarter-pel also hip_sad_qc: on top of \"Quarter pel\")")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
-              sad_gate=args.sad_gate)
+              sad_gate=args.sad_gate, sad_consistency=args.sad_consistency)
     txt = table(res)
     print(txt)
     if args.out:
