@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -12,6 +13,8 @@
 #include "../../include/ofps_hip.h"
 
 namespace ofps {
+
+int set_error(ofps_hip_ctx* ctx, int code, const char* fmt, ...);
 
 // The streaming front doors (pipeline.hip, dense_decoder.hip, multi.hip) number their tickets 0, 1, 2, ... and keep the newest N in a
 // ring; the caller sees the low 31 bits of the number.
@@ -38,8 +41,26 @@ struct TicketRing {
         }
         return hipSuccess;
     }
+    // a wait entry point's ticket: in flight and not yet collected -- else nullptr, the error set in that entry point's own words
+    Ticket* claim(ofps_hip_ctx* ctx, int id, const char* who, const char* collected) {
+        Ticket* t = find(id);
+        if (!t) set_error(ctx, OFPS_HIP_EINVAL, "%s: ticket %d is not in flight", who, id);
+        else if (!t->pending) { set_error(ctx, OFPS_HIP_EINVAL, "%s: ticket %d %s collected", who, id, collected); t = nullptr; }
+        return t;
+    }
     int commit() { at(next).pending = true; return ticket_id(next++); }      // the LAST thing a push does: one that failed half-way changed nothing here
 };
+
+// What a fused ticket answers per frame, as the detector's and the estimator's last kernels store it (tail.hip).  The per-frame SAD
+// ticket (pipeline.hip: PipeOut) and the dense decoders' ticket (dense_decoder.hip: behind the records) hold one; a batch ticket holds
+// n results followed by n quaternions.
+struct TailRecord {
+    int result[4];                       // has_motion, area, dim, 0
+    float quat[4];                       // (w, i, j, k)
+};
+static_assert(sizeof(TailRecord) == 32 && offsetof(TailRecord, quat) == 16 && sizeof(TailRecord::quat) == sizeof(float4), "result record layout");
+constexpr int kMaxDetectDim = 160;       // the detector's field is at most 160 x 160 vectors
+constexpr size_t kMaxFieldBytes = (size_t)kMaxDetectDim * kMaxDetectDim * sizeof(float2);
 
 inline void destroy(hipEvent_t e) { if (e) (void)hipEventDestroy(e); }
 inline void destroy(hipStream_t s) { if (s) (void)hipStreamDestroy(s); }
@@ -235,7 +256,7 @@ enum ScratchSlot {
     S_GATE_RAW,             // hip_sad's contrast gate (sad_gate.hip): the search's one-record-per-block output, in front of the compaction
     S_GATE_BEST,            // ... and its (dx, dy, SAD) triples
     S_GATE_FLAGS,           // ... [counts, u32 per block][kept count, 16 bytes][keep flags, u8 per block], one per ticket in flight in the fused path
-    S_COMP,                 // detect-compensation mode 1 (compensate.hip): [quaternion, 16 bytes][compensated records] -- the detector's input; the slots the
+    S_COMP,                 // detect-compensation mode 1 (tail.hip): [quaternion per item][compensated records] -- the detector's input; the slots the
                             // record copy and the estimator read are never overwritten.  Written and read on the compute stream only
     S_CONS_FWD,             // hip_sad's consistency check (sad_consistency.hip): the forward search's integer winners, kept through a quarter-pel refinement
     S_CONS_BWD,             // ... the backward search's integer winners
@@ -255,7 +276,6 @@ static_assert(S_CONS_BWD_ENT < ofps_hip_ctx::kNumScratch, "scratch table too sma
 #define OFPS_HIP_FRAME_WAIT_SPIN_US 500
 #endif
 
-int set_error(ofps_hip_ctx* ctx, int code, const char* fmt, ...);
 int check_hip(ofps_hip_ctx* ctx, hipError_t e, const char* what);
 // returns nullptr (and sets the error) on failure
 void* scratch(ofps_hip_ctx* ctx, int slot, size_t bytes);
@@ -317,15 +337,6 @@ inline size_t gate_flags_bytes(size_t nblk) { return ((nblk * sizeof(uint32_t) +
 inline uint32_t* gate_counts(char* flags) { return reinterpret_cast<uint32_t*>(flags); }
 inline uint32_t* gate_kept(char* flags, size_t nblk) { return reinterpret_cast<uint32_t*>(flags + ((nblk * sizeof(uint32_t) + 15) & ~size_t(15))); }
 inline uint8_t* gate_keep(char* flags, size_t nblk) { return reinterpret_cast<uint8_t*>(gate_kept(flags, nblk)) + 16; }
-int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const char* who);          // min_pixels in [1, block * block]
-// counts and keep flags of `cur` on stream st (they depend on that frame only)
-int sad_gate_flags_device(ofps_hip_ctx* ctx, const uint8_t* d_cur, int W, int H, int stride, int block, int min_pixels, uint32_t* d_counts,
-                          uint8_t* d_keep, hipStream_t st);
-// the kept records [and triples] in raster order and their count, on ctx->stream; d_out may not alias d_raw
-int sad_gate_compact_device(ofps_hip_ctx* ctx, const float4* d_raw, const int* d_raw_best, const uint8_t* d_keep, size_t nblk, float4* d_out,
-                            int* d_out_best, uint32_t* d_count);
-int sad_flow_gated_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                          int min_pixels, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // sad_consistency.hip: hip_sad's forward-backward consistency check (include/ofps_hip.h N1c)
 constexpr int kSadConsistencyMax = 129;                     // 2 * 64 + 1: above every residual of the largest search range
@@ -333,17 +344,51 @@ int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* w
 // residual and / or keep byte per block from the two directions' integer winners, on stream st; d_keep_in (optional, may be d_out_keep) is ANDed in
 int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
                                  const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st);
-// the forward search into d_raw and the backward search behind it, both on ctx->stream -> the integer winners of both and the records' triples
-int sad_consistency_searches_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                                    float4* d_raw, bool want_triples, const int** d_fwd, const int** d_bwd, const int** d_triples);
-int sad_flow_checked_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                            int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count);
+
+// sad_gate.hip: one pair's filtered search -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device -- in the
+// steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  The one-pair entry points run them all on ctx->stream
+// (sad_flow_filtered_device); the fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  With gate == 0 and
+// limit == 0 search() is the plain search into d_out and no other step reserves or enqueues anything.
+struct SadFilter {
+    int W, H, stride, block, range;
+    int gate, limit;                     // the contrast gate's min_pixels, the consistency check's limit; 0 = off
+    bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
+    size_t nblk = 0;
+    float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
+    char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
+    int *d_fwd = nullptr, *d_bwd = nullptr;      // S_CONS_FWD, S_CONS_BWD: the two directions' integer winners (limit > 0)
+    float4* d_bwd_ent = nullptr;         // S_CONS_BWD_ENT
+    int* d_triples = nullptr;            // the triples that belong to d_raw: S_GATE_BEST, or d_fwd itself (limit > 0 at motion scale 1)
+    bool on() const { return gate > 0 || limit > 0; }
+    uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk) : nullptr; }
+    uint8_t* keep() const { return gate_keep(d_flags, nblk); }
+    int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
+    // the scratch slots; S_GATE_FLAGS holds `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
+    int reserve(ofps_hip_ctx* ctx, int tix = 0, int tickets = 1);
+    int search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out);      // on ctx->stream; d_out: the unfiltered search's records
+    int contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st);                    // gate > 0: counts and keep flags of `cur`, which they depend on alone
+    // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] kept records [and triples] in raster order -> count
+    int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
+};
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                             int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.
 // d_quat_echo (optional): the quaternions are stored there as well (a ticket's result block)
 int compensate_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const uint32_t* d_n, float aspect, float fov_y_deg,
                       const float4* d_quat, float4* d_out, float4* d_quat_echo);
+
+// tail.hip: estimator -> [compensation ->] detector over `batch` items of n records, the one tail of every fused entry point.
+// TailSide: the detector's chain runs on `stream` beside the estimator -- forked on `fork_on` (recorded on the compute stream here unless it
+// `recorded` a point there already), joined through `join`.  Only when both stages run and nothing is compensated.
+struct TailSide { hipStream_t stream; hipEvent_t fork_on; bool recorded; hipEvent_t join; };
+// d_n (optional, batch == 1): the record count lives in device memory, n is the capacity, and the estimator takes its device-count form
+// (lsq_min_n: almeida_device_n).  seed0: item 0's seed, item j gets seed0 + j.  may_compensate: the context's detect-compensation mode
+// counts here.  d_result [batch][4], d_quat [batch], d_field: device memory or a ticket's device-addressable block.  -> *out_dim (optional)
+int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batch, const uint32_t* d_n, uint32_t lsq_min_n,
+                      const ofps_hip_frame_params* prm, uint64_t seed0, bool may_compensate, int* d_result, float4* d_quat, float2* d_field,
+                      const TailSide* side, int* out_dim);
 
 // ---- transfers (transfer.hip)
 bool device_address_of(const void* host_ptr, void** dev_ptr);        // the device address of page-locked host memory, or false for pageable memory

@@ -156,8 +156,9 @@ int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t*
 }
 
 constexpr size_t kBlockHeader = 16;             // a page-locked result block: [count, pad x 3][records]; a fused ticket's goes on behind
-                                                // the records' capacity with [has_motion, area, dim, 0][quaternion][detector field 2 * dim * dim]
-constexpr size_t kTailResult = 0, kTailQuat = 16, kTailField = 32;
+                                                // the records' capacity with [TailRecord][detector field 2 * dim * dim]
+constexpr size_t kTailResult = offsetof(ofps::TailRecord, result), kTailQuat = offsetof(ofps::TailRecord, quat), kTailField = sizeof(ofps::TailRecord);
+static_assert(kBlockHeader % sizeof(float4) == 0 && kTailField % sizeof(float4) == 0, "records, quaternion and field stay 16-byte aligned");
 
 // count + records of a finished block -> the caller's buffer
 void dense_collect(const void* pinned, size_t max_records, float* out_entries, size_t* n_out) {
@@ -206,7 +207,7 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
                                    "ofps_hip_almeida_dev / ofps_hip_densify_raster_dev is that chain, with a count the host knows)", who);
         if (tail->run_detector) {
             dim = ofps_hip_block_dim(tail->min_size, tail->subdivide);
-            OFPS_REQUIRE(ctx, dim >= 1 && dim <= 160, "%s: detector block_dim %d outside [1,160] (min_size=%g subdivide=%zu)", who, dim,
+            OFPS_REQUIRE(ctx, dim >= 1 && dim <= ofps::kMaxDetectDim, "%s: detector block_dim %d outside [1,160] (min_size=%g subdivide=%zu)", who, dim,
                          (double)tail->min_size, tail->subdivide);
         }
         if (tail->run_estimator) {
@@ -336,33 +337,13 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
                                reinterpret_cast<float4*>(blk + kBlockHeader), d_cnt, g.max_records, reinterpret_cast<uint32_t*>(blk));
             OFPS_HIP_TRY(ctx, hipGetLastError());
             // the 32 bytes the caller waits for -- island result, quaternion -- and the island's field are stored by the detector's and the
-            // estimator's last kernels straight into the ticket's block, as pipeline.hip does (one stream: their order is of no consequence)
-            // detect-compensation mode 1 (compensate.hip; the mode is the context's at this push): the estimator writes its quaternion to
-            // device memory, the compensation launch -- in its device-count form, sized from the capacity -- reads it there, passes it on to
-            // the block and leaves the compensated records in a slot of their own for the detector; d_rec is what the copy above reads
-            const bool compensate = ctx->opt.detect_compensate == 1 && tail->run_detector && tail->run_estimator;
-            float4* quat_blk = reinterpret_cast<float4*>(blk + tail_off + kTailQuat);
-            const float4* d_det_in = d_rec;
-            if (compensate) {
-                auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, (1 + g.max_records) * sizeof(float4)));    // [quaternion][records]
-                if (!d_comp) return OFPS_HIP_ENOMEM;
-                rc = ofps::almeida_device_n(ctx, d_rec, g.max_records, d_cnt, tail->aspect, tail->fov_y_deg, tail->use_ransac, tail->num_iters,
-                                            tail->inlier_deg, tail->num_samples, tail->seed, d_comp);
-                if (rc != OFPS_HIP_OK) return rc;
-                rc = ofps::compensate_device(ctx, d_rec, g.max_records, 1, d_cnt, tail->aspect, tail->fov_y_deg, d_comp, d_comp + 1, quat_blk);
-                if (rc != OFPS_HIP_OK) return rc;
-                d_det_in = d_comp + 1;
-            } else if (tail->run_estimator) {
-                rc = ofps::almeida_device_n(ctx, d_rec, g.max_records, d_cnt, tail->aspect, tail->fov_y_deg, tail->use_ransac, tail->num_iters,
-                                            tail->inlier_deg, tail->num_samples, tail->seed, quat_blk);
-                if (rc != OFPS_HIP_OK) return rc;
-            }
-            if (tail->run_detector) {
-                rc = ofps::detect_device(ctx, d_det_in, g.max_records, 1, tail->min_size, tail->subdivide, tail->target_motion,
-                                         reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float2*>(blk + tail_off + kTailField),
-                                         nullptr, d_cnt);
-                if (rc != OFPS_HIP_OK) return rc;
-            }
+            // estimator's last kernels straight into the ticket's block, as pipeline.hip does.  The tail (tail.hip) in its device-count form,
+            // sized from the capacity, on this one stream; with detect-compensation 1 its detector reads compensated records in a slot of
+            // their own: d_rec is what the copy above reads
+            rc = ofps::frame_tail_device(ctx, d_rec, g.max_records, 1, d_cnt, /*lsq_min_n=*/0, tail, tail->seed, /*may_compensate=*/true,
+                                         reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float4*>(blk + tail_off + kTailQuat),
+                                         reinterpret_cast<float2*>(blk + tail_off + kTailField), nullptr, nullptr);
+            if (rc != OFPS_HIP_OK) return rc;
         }
         have_vectors = 1;
     }
@@ -423,9 +404,8 @@ int ofps_hip_lk_frame_wait(ofps_hip_ctx* ctx, int ticket, float* out_entries, si
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, out_entries && n_out && have_vectors, "lk_frame_wait: null pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto* t = ctx->dense.ring.find(ticket);
-    OFPS_REQUIRE(ctx, t, "lk_frame_wait: ticket %d is not in flight", ticket);
-    OFPS_REQUIRE(ctx, t->pending, "lk_frame_wait: ticket %d has already been collected", ticket);
+    auto* t = ctx->dense.ring.claim(ctx, ticket, "lk_frame_wait", "has already been");
+    if (!t) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
     *n_out = 0;
@@ -460,9 +440,8 @@ int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_r
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, out, "lk_frame_fused_wait: null pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto* t = ctx->dense.ring.find(ticket);
-    OFPS_REQUIRE(ctx, t, "lk_frame_fused_wait: ticket %d is not in flight", ticket);
-    OFPS_REQUIRE(ctx, t->pending, "lk_frame_fused_wait: ticket %d has already been collected", ticket);
+    auto* t = ctx->dense.ring.claim(ctx, ticket, "lk_frame_fused_wait", "has already been");
+    if (!t) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
     memset(out, 0, sizeof(*out));

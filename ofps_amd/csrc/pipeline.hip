@@ -15,13 +15,19 @@
 #include <chrono>
 
 namespace {
-struct PipeOut {                 // layout of the pinned read-back block
-    int result[4];               // has_motion, area, dim, 0
-    float quat[4];
-    uint32_t kept[4];            // contrast gate or consistency check on: the kept record count (sad_gate.hip, sad_consistency.hip); not read back, not looked at, with both off
+using ofps::PipeStream;
+using ofps::TailRecord;
+struct PipeOut {                 // a ticket's result block: page-locked, and in device scratch at the head of its kPipeOutBytes
+    TailRecord r;
+    uint32_t kept[4];            // contrast gate or consistency check on: the kept record count (sad_gate.hip); not read back, not looked at, with both off
 };
 constexpr size_t kPipeOutPlain = offsetof(PipeOut, kept);       // what a ticket without the gate reads back
-constexpr int kSlots = ofps::PipeStream::kSlots;
+constexpr size_t kPipeField = 4096;                             // the detector's field in the device copy, behind the block
+constexpr size_t kPipeOutBytes = kPipeField + ofps::kMaxFieldBytes;
+static_assert(offsetof(PipeOut, r) == 0 && kPipeOutPlain == sizeof(TailRecord) && sizeof(PipeOut) == 48 && sizeof(PipeOut) <= kPipeField, "PipeOut layout");
+constexpr int kSlots = PipeStream::kSlots, kTickets = PipeStream::kTickets;
+constexpr size_t kBatchResult = sizeof(TailRecord::result);     // a batch ticket's block: [n results][n quaternions]
+static_assert(kBatchResult + sizeof(TailRecord::quat) == sizeof(TailRecord), "batch block layout");
 
 #ifndef OFPS_HIP_UPLOAD_KERNEL_SINGLE
 #define OFPS_HIP_UPLOAD_KERNEL_SINGLE 0          // A/B (tools/upload_ab.sh): the single-frame form through the upload kernel as well (transfer.hip)
@@ -87,6 +93,117 @@ int pipe_upload(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride
     *slots_out = slots; *pitch_out = pitch; *dstride_out = dstride;
     return OFPS_HIP_OK;
 }
+
+// One ofps_hip_push_frame_async call, step by step.  Every step enqueues or returns an error; none touches the ring (commit does, last).
+struct Push {
+    ofps_hip_ctx* ctx;
+    const ofps_hip_frame_params* prm;
+    ofps::SadFilter f;                   // contrast gate and consistency check as the context has them at this push; both 0: the plain search
+    PipeStream::Ticket* t = nullptr;
+    int tix = 0;
+    long frame_no = 0;                   // the frame this push uploads
+    int cur_slot = 0, prev_slot = 0;
+    bool cur_by_event = false;           // this frame's upload ran on the copy stream and has an event of its own
+    const uint8_t *prev = nullptr, *cur = nullptr;
+    float4* d_ent = nullptr;             // this ticket's records: what the caller gets
+    char* d_out = nullptr;               // ... and its kPipeOutBytes
+    PipeOut* out = nullptr;              // where the tail stores result and quaternion: the ticket's page-locked block, or d_out
+    int dim = 0;
+
+    int claim() {
+        const long tno = ctx->pipe.ring.next;
+        t = &ctx->pipe.ring.at(tno);
+        tix = (int)(tno % kTickets);
+        OFPS_REQUIRE(ctx, !t->pending, "push_frame_async: ticket %ld has not been collected (at most %d frames in flight)", tno - kTickets, kTickets);
+        return f.plan(ctx, "push_frame_async");
+    }
+
+    // The H2D of the frame, and the compute stream behind the uploads of both frames of the pair: the previous frame's was waited for by the
+    // previous ticket (or by the stage_frame that made it), this frame's by its event.  Uploads made on the compute stream itself are ordered
+    // by the stream; one wait per upload is enough
+    int upload(const uint8_t* luma, int stride) {
+        PipeStream& ps = ctx->pipe;
+        uint8_t* slots; size_t pitch; int dstride;
+        const int rc = pipe_upload(ctx, luma, f.W, f.H, stride, /*overlap=*/ps.ring.other_pending(), &slots, &pitch, &dstride);
+        if (rc != OFPS_HIP_OK) return rc;
+        frame_no = ps.frames - 1;
+        cur_slot = (int)(frame_no % kSlots); prev_slot = (int)((frame_no + kSlots - 1) % kSlots);
+        cur = slots + (size_t)cur_slot * pitch; prev = slots + (size_t)prev_slot * pitch;
+        cur_by_event = !ps.uploaded_on_compute[cur_slot];
+        for (int slot : {prev_slot, cur_slot}) {
+            if (ps.uploaded_on_compute[slot] || (frame_no == 0 && slot == prev_slot)) continue;
+            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ps.uploaded[slot], 0));
+            ps.uploaded_on_compute[slot] = true;
+        }
+        return OFPS_HIP_OK;
+    }
+
+    // The search of pair (prev, cur) -> the [kept] records in d_ent [and their count in device memory, f.kept()].  Gate on: the keep flags
+    // depend on the new frame only -- they are made on the auxiliary stream, forked on that frame's upload, beside the search (never in front
+    // of it on the compute stream).  Check on: both searches read prev_slot, so its event is recorded behind both.
+    int search() {
+        PipeStream& ps = ctx->pipe;
+        hipStream_t s = ctx->stream;
+        d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_PIPE_ENTRIES, kTickets * f.nblk * sizeof(float4)));
+        d_out = static_cast<char*>(ofps::scratch(ctx, ofps::S_PIPE_OUT, kTickets * kPipeOutBytes));
+        if (!d_ent || !d_out) return OFPS_HIP_ENOMEM;
+        d_ent += (size_t)tix * f.nblk; d_out += (size_t)tix * kPipeOutBytes;
+        int rc = f.reserve(ctx, tix, kTickets);          // S_GATE_FLAGS per ticket: the detector may still read ticket k's count while ticket k + 1 compacts
+        if (rc != OFPS_HIP_OK) return rc;
+        if (f.gate > 0) {
+            if (!ps.gate_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ps.gate_done, hipEventDisableTiming));
+            // fork on the upload: its own event when it ran on the copy stream (the flags are then made beside the previous ticket's tail as
+            // well), else the compute stream's position, which is right behind the upload
+            if (!cur_by_event) OFPS_HIP_TRY(ctx, hipEventRecord(ps.fork, s));
+            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ps.aux_stream, cur_by_event ? ps.uploaded[cur_slot] : ps.fork, 0));
+            rc = f.contrast_flags(ctx, cur, ps.aux_stream);
+            if (rc != OFPS_HIP_OK) return rc;
+            OFPS_HIP_TRY(ctx, hipEventRecord(ps.gate_done, ps.aux_stream));
+        }
+        rc = f.search(ctx, prev, cur, d_ent);
+        if (rc != OFPS_HIP_OK) return rc;
+        // the older slot may be overwritten once this search is through; the same event forks the unfiltered tail's detector
+        // (one barrier packet between the search and the estimator instead of two)
+        OFPS_HIP_TRY(ctx, hipEventRecord(ps.slot_read[prev_slot], s));
+        ps.slot_read_valid[prev_slot] = true;
+        if (f.gate > 0) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ps.gate_done, 0));
+        return f.finish(ctx, d_ent, nullptr, f.kept());
+    }
+
+    // The 32 bytes the caller waits for (island result, quaternion) are written by the detector's and the estimator's last kernels STRAIGHT
+    // into the ticket's page-locked block -- it is device-addressable, each is one thread's store at the end of a kernel -- instead of into
+    // device scratch and from there by a copy launch behind the join: that launch and the gap in front of it were 14 us of a 170 us frame
+    // (rocprofv3 kernel trace, tools/trace_stream.sh).  Filtered: the tail's device-count forms, fewer than 3 kept records -> identity, and
+    // the detector's stream starts behind the compaction, not behind the search.
+    int tail() {
+        PipeStream& ps = ctx->pipe;
+        void* mapped = nullptr;
+        out = ofps::device_address_of(t->pinned, &mapped) ? static_cast<PipeOut*>(mapped) : reinterpret_cast<PipeOut*>(d_out);
+        const ofps::TailSide side{ps.aux_stream, f.on() ? ps.fork : ps.slot_read[prev_slot], /*recorded=*/!f.on(), ps.join};
+        return ofps::frame_tail_device(ctx, d_ent, f.nblk, 1, f.kept(), /*lsq_min_n=*/3, prm, prm->seed, /*may_compensate=*/true, out->r.result,
+                                       reinterpret_cast<float4*>(out->r.quat), reinterpret_cast<float2*>(d_out + kPipeField), &side, &dim);
+    }
+
+    int read_back(float* out_entries, float* out_field) {
+        hipStream_t s = ctx->stream;
+        int rc = OFPS_HIP_OK;
+        if ((prm->run_detector || prm->run_estimator) && out == reinterpret_cast<PipeOut*>(d_out)) rc = ofps::read_back_device(ctx, t->pinned, d_out, kPipeOutPlain, s);
+        if (rc == OFPS_HIP_OK && f.on())                             // the kept count travels in the ticket's page-locked block
+            rc = ofps::read_back_device(ctx, static_cast<PipeOut*>(t->pinned)->kept, f.kept(), sizeof(uint32_t), s);
+        if (rc == OFPS_HIP_OK && out_entries && f.nblk) rc = ofps::read_back_device(ctx, out_entries, d_ent, f.nblk * sizeof(float4), s);
+        if (rc == OFPS_HIP_OK && out_field && prm->run_detector)
+            rc = ofps::read_back_device(ctx, out_field, d_out + kPipeField, (size_t)dim * dim * sizeof(float2), s);
+        return rc;
+    }
+
+    int commit(int* ticket) {
+        OFPS_HIP_TRY(ctx, hipEventRecord(t->done, ctx->stream));
+        t->have_vectors = frame_no > 0; t->n_vectors = frame_no > 0 ? f.nblk : 0; t->gated = frame_no > 0 && f.on();
+        t->run_detector = prm->run_detector; t->run_estimator = prm->run_estimator;
+        *ticket = ctx->pipe.ring.commit();
+        return OFPS_HIP_OK;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -119,206 +236,23 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    constexpr int kTickets = ofps::PipeStream::kTickets;
-    const long tno = ctx->pipe.ring.next;
-    auto& t = ctx->pipe.ring.at(tno);
-    OFPS_REQUIRE(ctx, !t.pending, "push_frame_async: ticket %ld has not been collected (at most %d frames in flight)",
-                 tno - kTickets, kTickets);
-    // contrast gate (sad_gate.hip; the gate is the context's at this push): 0 = every launch, stream and byte below is the ungated build's
-    const int gate = ctx->opt.sad_gate;
-    if (gate > 0) {
-        rc = ofps::sad_gate_check(ctx, prm->block, gate, "push_frame_async");
-        if (rc != OFPS_HIP_OK) return rc;
+    Push p{ctx, prm, {W, H, (W + 63) & ~63, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency, /*want_triples=*/false}};
+    rc = p.claim();                                     // refused before anything is uploaded
+    if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
+    if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)
+        rc = p.search();
+        if (rc == OFPS_HIP_OK) rc = p.tail();
+        if (rc == OFPS_HIP_OK) rc = p.read_back(out_entries, out_field);
     }
-    // consistency check (sad_consistency.hip; the limit is the context's at this push): one more producer of keep flags on the gate's path.
-    // `filtered`: either criterion is on; with only the gate on, everything enqueued below is what it was before the check existed
-    const int limit = ctx->opt.sad_consistency;
-    if (limit > 0) {
-        rc = ofps::sad_consistency_check(ctx, prm->block, limit, "push_frame_async");
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    const bool filtered = gate > 0 || limit > 0;
-    hipStream_t s = ctx->stream;
-    uint8_t* slots; size_t pitch; int dstride;
-    const bool overlap = ctx->pipe.ring.other_pending();               // the other ticket is in flight
-    rc = pipe_upload(ctx, luma, W, H, stride, overlap, &slots, &pitch, &dstride);
-    if (rc != OFPS_HIP_OK) return rc;
-    const long frame_no = ctx->pipe.frames - 1;                       // the frame just enqueued
-    const int cur_slot = (int)(frame_no % kSlots);
-    t.have_vectors = 0; t.n_vectors = 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.gated = 0;
-    const size_t nblk = ofps_hip_sad_block_count(W, H, prm->block);
-    if (frame_no == 0) {                                             // first frame of a stream: Ok(false), no vectors yet
-        if (!ctx->pipe.uploaded_on_compute[cur_slot]) {
-            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.uploaded[cur_slot], 0));
-            ctx->pipe.uploaded_on_compute[cur_slot] = true;
-        }
-        OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
-        *ticket = ctx->pipe.ring.commit();
-        return OFPS_HIP_OK;
-    }
-    const int prev_slot = (int)((frame_no - 1) % kSlots);
-    const int tix = (int)(tno % kTickets);
-    auto* d_ent_all = static_cast<float4*>(ofps::scratch(ctx, ofps::S_PIPE_ENTRIES, kTickets * nblk * sizeof(float4)));
-    constexpr size_t kOutBytes = 4096 + (size_t)160 * 160 * sizeof(float2);
-    auto* d_out_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_PIPE_OUT, kTickets * kOutBytes));
-    if (!d_ent_all || !d_out_all) return OFPS_HIP_ENOMEM;
-    float4* d_ent = d_ent_all + (size_t)tix * nblk;
-    char* d_out = d_out_all + (size_t)tix * kOutBytes;
-    // the search needs both frames on the device: the previous frame's upload was waited for by the previous ticket
-    // (or by the stage_frame that made it), this frame's by the event
-    // (uploads made on the compute stream itself are ordered by the stream; one wait per upload is enough)
-    const bool cur_by_event = !ctx->pipe.uploaded_on_compute[cur_slot];      // this frame's upload is on the copy stream and has an event of its own
-    for (int slot : {prev_slot, cur_slot}) {
-        if (!ctx->pipe.uploaded_on_compute[slot]) {
-            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.uploaded[slot], 0));
-            ctx->pipe.uploaded_on_compute[slot] = true;
-        }
-    }
-    // gate on: the keep flags depend on the new frame only -- they are made on the auxiliary stream, forked on that frame's upload, beside
-    // the search (never in front of it on the compute stream); the search writes one record per block into the gate's own slot and the
-    // compaction behind the join leaves the kept records, in raster order, in d_ent and their count in device memory (d_kept)
-    float4* d_raw = d_ent;
-    char* d_flags = nullptr;
-    uint32_t* d_kept = nullptr;
-    if (filtered) {
-        const size_t fbytes = ofps::gate_flags_bytes(nblk);
-        d_raw = static_cast<float4*>(ofps::scratch(ctx, ofps::S_GATE_RAW, nblk * sizeof(float4)));
-        auto* d_flags_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_GATE_FLAGS, kTickets * fbytes));
-        if (!d_raw || !d_flags_all) return OFPS_HIP_ENOMEM;
-        d_flags = d_flags_all + (size_t)tix * fbytes;
-        d_kept = ofps::gate_kept(d_flags, nblk);
-    }
-    if (gate > 0) {
-        if (!ctx->pipe.gate_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe.gate_done, hipEventDisableTiming));
-        // fork on the upload: its own event when it ran on the copy stream (the flags are then made beside the previous ticket's tail as
-        // well), else the compute stream's position, which is right behind the upload
-        if (cur_by_event) {
-            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.uploaded[cur_slot], 0));
-        } else {
-            OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.fork, s));
-            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.fork, 0));
-        }
-        rc = ofps::sad_gate_flags_device(ctx, slots + (size_t)cur_slot * pitch, W, H, dstride, prm->block, gate, ofps::gate_counts(d_flags),
-                                         ofps::gate_keep(d_flags, nblk), ctx->pipe.aux_stream);
-        if (rc != OFPS_HIP_OK) return rc;
-        OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.gate_done, ctx->pipe.aux_stream));
-    }
-    // check on: the forward search keeps its integer winners, the backward search runs on the same two resident slots right behind it on the
-    // compute stream (one context's searches share scratch: never two at once) -- both read prev_slot, so its event is recorded behind both
-    const int *d_fwd = nullptr, *d_bwd = nullptr;
-    if (limit > 0)
-        rc = ofps::sad_consistency_searches_device(ctx, slots + (size_t)prev_slot * pitch, slots + (size_t)cur_slot * pitch, W, H, dstride,
-                                                   prm->block, prm->range, d_raw, false, &d_fwd, &d_bwd, nullptr);
-    else
-        rc = ofps::sad_pairs_device(ctx, slots + (size_t)prev_slot * pitch, 0, slots + (size_t)cur_slot * pitch, 0, 1, W, H, dstride,
-                                    prm->block, prm->range, d_raw, nullptr);
-    if (rc != OFPS_HIP_OK) return rc;
-    // the older slot may be overwritten once this search is through; the same event forks the detector's stream below
-    // (one barrier packet between the search and the estimator instead of two)
-    OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.slot_read[prev_slot], s));
-    ctx->pipe.slot_read_valid[prev_slot] = true;
-    t.have_vectors = 1; t.n_vectors = nblk; t.gated = filtered;
-    if (filtered) {
-        if (gate > 0) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.gate_done, 0));
-        if (limit > 0) {                                         // behind the join: the contrast flags, when there are any, are ANDed in in place
-            uint8_t* d_keep = ofps::gate_keep(d_flags, nblk);
-            rc = ofps::sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, prm->block, limit, gate > 0 ? d_keep : nullptr, nullptr, d_keep, s);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
-        rc = ofps::sad_gate_compact_device(ctx, d_raw, nullptr, ofps::gate_keep(d_flags, nblk), nblk, d_ent, nullptr, d_kept);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-
-    int dim = 0;
-    int* d_res = reinterpret_cast<int*>(d_out);
-    float4* d_quat = reinterpret_cast<float4*>(d_out + 16);
-    float2* d_field = reinterpret_cast<float2*>(d_out + 4096);
-    // The 32 bytes the caller waits for (island result, quaternion) are written by the detector's and the estimator's last
-    // kernels STRAIGHT into the ticket's page-locked block -- it is device-addressable, each is one thread's store at the
-    // end of a kernel -- instead of into device scratch and from there by a copy launch behind the join: that launch and
-    // the gap in front of it were 14 us of a 170 us frame (rocprofv3 kernel trace, tools/trace_stream.sh).
-    void* mapped_out = nullptr;
-    const bool direct = ofps::device_address_of(t.pinned, &mapped_out);
-    if (direct) {
-        d_res = reinterpret_cast<int*>(static_cast<char*>(mapped_out) + offsetof(PipeOut, result));
-        d_quat = reinterpret_cast<float4*>(static_cast<char*>(mapped_out) + offsetof(PipeOut, quat));
-    }
-    // detector and estimator read the same device-resident vectors and share no workspace: with both enabled the
-    // detector's chain of small launches runs on an auxiliary stream beside the estimator (fork after the search, join
-    // before the read-back) instead of in front of it
-    // detect-compensation mode 1 (compensate.hip; the mode is the context's at this push): the detector reads this frame's vectors
-    // compensated with this frame's quaternion, so its chain cannot run beside the estimator -- estimator, compensation and detector are
-    // enqueued on the compute stream in that order.  The estimator writes the quaternion to device memory (the compensation launch reads it
-    // there and passes it on to the ticket's block); the compensated records have a slot of their own: d_ent is what the caller gets.
-    const bool compensate = ctx->opt.detect_compensate == 1 && prm->run_detector && prm->run_estimator;
-    const bool fork = prm->run_detector && prm->run_estimator && !compensate;
-    if (fork && filtered) {                                      // the detector's stream starts behind the compaction, not behind the search
-        OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.fork, s));
-        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.fork, 0));
-    } else if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.aux_stream, ctx->pipe.slot_read[prev_slot], 0));
-    // gate or check on: estimator, compensation and detector in their device-count forms -- every launch sized from the capacity nblk, the first
-    // *d_kept records count; fewer than 3 kept records -> identity (both solvers), none -> no motion
-    auto estimate = [&](float4* d_q) {
-        return filtered ? ofps::almeida_device_n(ctx, d_ent, nblk, d_kept, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
-                                                 prm->inlier_deg, prm->num_samples, prm->seed, d_q, /*lsq_min_n=*/3)
-                        : ofps::almeida_device(ctx, d_ent, nblk, 1, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters,
-                                               prm->inlier_deg, prm->num_samples, prm->seed, d_q);
-    };
-    const float4* d_det_in = d_ent;
-    if (compensate) {
-        auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, nblk * sizeof(float4)));
-        if (!d_comp) return OFPS_HIP_ENOMEM;
-        float4* d_quat_dev = reinterpret_cast<float4*>(d_out + 16);
-        rc = estimate(d_quat_dev);
-        if (rc != OFPS_HIP_OK) return rc;
-        rc = ofps::compensate_device(ctx, d_ent, nblk, 1, d_kept, prm->aspect, prm->fov_y_deg, d_quat_dev, d_comp, direct ? d_quat : nullptr);
-        if (rc != OFPS_HIP_OK) return rc;
-        d_det_in = d_comp;
-    }
-    // the estimator is enqueued first: it is the long pole (0.1 ms of dependent steps against the detector's seven small
-    // launches), and whatever is enqueued second starts a host-enqueue time later
-    if (prm->run_estimator && !compensate) {
-        rc = estimate(d_quat);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (prm->run_detector) {
-        if (fork) ctx->stream = ctx->pipe.aux_stream;           // the stage entry points enqueue on ctx->stream
-        rc = ofps::detect_device(ctx, d_det_in, nblk, 1, prm->min_size, prm->subdivide, prm->target_motion, d_res, d_field, &dim, d_kept);
-        if (fork) {
-            ctx->stream = s;
-            if (rc == OFPS_HIP_OK) OFPS_HIP_TRY(ctx, hipEventRecord(ctx->pipe.join, ctx->pipe.aux_stream));
-        }
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (fork) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pipe.join, 0));
-    if ((prm->run_detector || prm->run_estimator) && !direct) {
-        rc = ofps::read_back_device(ctx, t.pinned, d_out, kPipeOutPlain, s);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (filtered) {                                              // the kept count travels in the ticket's page-locked block
-        rc = ofps::read_back_device(ctx, static_cast<char*>(t.pinned) + offsetof(PipeOut, kept), d_kept, sizeof(uint32_t), s);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (out_entries && nblk) {
-        rc = ofps::read_back_device(ctx, out_entries, d_ent, nblk * sizeof(float4), s);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (out_field && prm->run_detector) {
-        rc = ofps::read_back_device(ctx, out_field, d_field, (size_t)dim * dim * sizeof(float2), s);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
-    *ticket = ctx->pipe.ring.commit();
-    return OFPS_HIP_OK;
+    return rc == OFPS_HIP_OK ? p.commit(ticket) : rc;
 }
 
 int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* out) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, out, "frame_wait: null pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto* t = ctx->pipe.ring.find(ticket);
-    OFPS_REQUIRE(ctx, t, "frame_wait: ticket %d is not in flight", ticket);
-    OFPS_REQUIRE(ctx, t->pending, "frame_wait: ticket %d was already collected", ticket);
+    auto* t = ctx->pipe.ring.claim(ctx, ticket, "frame_wait", "was already");
+    if (!t) return OFPS_HIP_EINVAL;
     // a per-frame result is tens of microseconds away: poll first (hipEventSynchronize may put the thread to sleep, and a
     // wake-up costs more than the whole frame -- 0.23 vs 0.06 ms per frame measured inside a process that initialised
     // torch's runtime), then block
@@ -343,11 +277,11 @@ int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* ou
         const auto* host = static_cast<const PipeOut*>(t->pinned);
         if (t->gated) out->n_vectors = host->kept[0] < t->n_vectors ? host->kept[0] : t->n_vectors;
         if (t->run_detector) {
-            out->has_motion = host->result[0];
-            out->area = (size_t)host->result[1];
-            out->dim = host->result[2];
+            out->has_motion = host->r.result[0];
+            out->area = (size_t)host->r.result[1];
+            out->dim = host->r.result[2];
         }
-        if (t->run_estimator) memcpy(out->quat, host->quat, sizeof(out->quat));
+        if (t->run_estimator) memcpy(out->quat, host->r.quat, sizeof(out->quat));
     }
     return OFPS_HIP_OK;
 }
@@ -393,7 +327,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const int tix = (int)(tno % kTickets);
     // capacity: both buffers and the per-ticket outputs are sized for the largest batch seen (grow-only; growing waits
     // for work in flight)
-    constexpr size_t kOutBytes = 32;                             // {result[4], quat[4]} per frame
+    constexpr size_t kOutBytes = sizeof(TailRecord);             // per frame
     const size_t cap_frames = (size_t)n + 1;
     auto& fs = ctx->scratch[ofps::S_BATCH_FRAMES];
     size_t per_buf = fs.cap / kTickets / (pitch ? pitch : 1);
@@ -464,31 +398,18 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         rc = ofps::sad_pairs_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
                                     prm->block, prm->range, ent0, nullptr);
         if (rc != OFPS_HIP_OK) return rc;
-        int* d_res = reinterpret_cast<int*>(d_out);                                 // [n][4]
-        float4* d_quat = reinterpret_cast<float4*>(d_out + (size_t)n * 16);          // [n]
-        if (prm->run_estimator) {
-            rc = ofps::almeida_device(ctx, ent0, nblk, pairs, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters, prm->inlier_deg,
-                                      prm->num_samples, prm->seed + (uint64_t)first, d_quat + first);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
+        auto* d_res = reinterpret_cast<int(*)[4]>(d_out);                           // [n][4]
+        float4* d_quat = reinterpret_cast<float4*>(d_out + (size_t)n * kBatchResult); // [n]
+        float2* d_field = nullptr;
         if (prm->run_detector) {
-            int dim = 0;
-            auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_BATCH_FIELD, (size_t)pairs * 160 * 160 * sizeof(float2)));   // its own slot: the densifier works in S_WORK*
+            d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_BATCH_FIELD, (size_t)pairs * kMaxFieldBytes));   // its own slot: the densifier works in S_WORK*
             if (!d_field) return OFPS_HIP_ENOMEM;
-            // detect-compensation mode 1: ONE compensation launch over the batch, item j with the quaternion the estimator's launch above left
-            // for it in device memory, into a slot of its own; then the batched detector chain as it is.  The multi-device dispatcher's
-            // worker contexts (halo_mode 1) keep the raw detector.
-            const float4* det_in = ent0;
-            if (ctx->opt.detect_compensate == 1 && prm->run_estimator && !halo_mode) {
-                auto* d_comp = static_cast<float4*>(ofps::scratch(ctx, ofps::S_COMP, (size_t)pairs * nblk * sizeof(float4)));
-                if (!d_comp) return OFPS_HIP_ENOMEM;
-                rc = ofps::compensate_device(ctx, ent0, nblk, pairs, nullptr, prm->aspect, prm->fov_y_deg, d_quat + first, d_comp, nullptr);
-                if (rc != OFPS_HIP_OK) return rc;
-                det_in = d_comp;
-            }
-            rc = ofps::detect_device(ctx, det_in, nblk, pairs, prm->min_size, prm->subdivide, prm->target_motion, d_res + 4 * first, d_field, &dim);
-            if (rc != OFPS_HIP_OK) return rc;
         }
+        // one estimator launch, [one compensation launch,] one detector chain over the batch, item j seeded seed + j.  The multi-device
+        // dispatcher's worker contexts (halo_mode 1) keep the raw detector whatever their detect-compensation mode
+        rc = frame_tail_device(ctx, ent0, nblk, pairs, nullptr, 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode, d_res[first],
+                               d_quat + first, d_field, nullptr, nullptr);
+        if (rc != OFPS_HIP_OK) return rc;
         if (prm->run_detector || prm->run_estimator) {
             rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * kOutBytes, s);
             if (rc != OFPS_HIP_OK) return rc;
@@ -516,13 +437,12 @@ int ofps_hip_frames_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* o
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, out, "frames_wait: null pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto* t = ctx->batch.ring.find(ticket);
-    OFPS_REQUIRE(ctx, t, "frames_wait: ticket %d is not in flight", ticket);
-    OFPS_REQUIRE(ctx, t->pending, "frames_wait: ticket %d was already collected", ticket);
+    auto* t = ctx->batch.ring.claim(ctx, ticket, "frames_wait", "was already");
+    if (!t) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
-    const auto* res = static_cast<const int*>(t->pinned);
-    const auto* quat = reinterpret_cast<const float*>(static_cast<const char*>(t->pinned) + (size_t)t->n * 16);
+    const auto* res = static_cast<const int(*)[4]>(t->pinned);
+    const auto* quat = reinterpret_cast<const float(*)[4]>(static_cast<const char*>(t->pinned) + (size_t)t->n * kBatchResult);
     for (int j = 0; j < t->n; ++j) {
         ofps_hip_frame_result& o = out[j];
         memset(&o, 0, sizeof(o));
@@ -531,8 +451,8 @@ int ofps_hip_frames_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* o
         o.have_vectors = has ? 1 : 0;
         o.n_vectors = has ? t->n_vectors : 0;
         if (!has) continue;
-        if (t->run_detector) { o.has_motion = res[4 * j]; o.area = (size_t)res[4 * j + 1]; o.dim = res[4 * j + 2]; }
-        if (t->run_estimator) memcpy(o.quat, quat + 4 * j, sizeof(o.quat));
+        if (t->run_detector) { o.has_motion = res[j][0]; o.area = (size_t)res[j][1]; o.dim = res[j][2]; }
+        if (t->run_estimator) memcpy(o.quat, quat[j], sizeof(o.quat));
     }
     return OFPS_HIP_OK;
 }

@@ -1198,36 +1198,27 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (!d_frames || !d_ent || !d_best) return OFPS_HIP_ENOMEM;
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames, dstride, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames + pitch, dstride, cur, stride, W, H, ctx->stream));
+    // contrast gate and / or consistency check (sad_gate.hip: SadFilter): the kept records first, their count from the device with them
+    uint32_t kept = UINT32_MAX;
+    int rc;
     if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0) {
-        // contrast gate (sad_gate.hip) and / or consistency check (sad_consistency.hip): the kept records first, their count from the device with them
         auto* d_kept = static_cast<uint32_t*>(ofps::scratch(ctx, ofps::S_RESULT, sizeof(uint32_t)));
         if (!d_kept) return OFPS_HIP_ENOMEM;
-        int rc = ctx->opt.sad_consistency > 0
-                     ? ofps::sad_flow_checked_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate,
-                                                     ctx->opt.sad_consistency, reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept)
-                     : ofps::sad_flow_gated_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate,
-                                                   reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept);
+        rc = ofps::sad_flow_filtered_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
+                                            reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept);
         if (rc != OFPS_HIP_OK) return rc;
-        uint32_t kept = 0;
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
-        if (nblk) {
-            OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_entries, d_ent, nblk * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            if (out_best)
-                OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_best, d_best, nblk * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (n_out) *n_out = kept < nblk ? kept : nblk;
-        return OFPS_HIP_OK;
+    } else {
+        rc = ofps_hip_sad_flow_dev(ctx, d_frames, 2, W, H, dstride, pitch, 0, block, range, d_ent, d_best);
+        if (rc != OFPS_HIP_OK) return rc;
     }
-    int rc = ofps_hip_sad_flow_dev(ctx, d_frames, 2, W, H, dstride, pitch, 0, block, range, d_ent, d_best);
-    if (rc != OFPS_HIP_OK) return rc;
     if (nblk) {
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_entries, d_ent, nblk * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         if (out_best)
             OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_best, d_best, nblk * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_out) *n_out = nblk;
+    if (n_out) *n_out = kept < nblk ? kept : nblk;
     return OFPS_HIP_OK;
 }
 

@@ -68,55 +68,6 @@ int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const
     return OFPS_HIP_OK;
 }
 
-// Forward search (records into d_raw; its integer winners into the check's own slot, whatever the motion scale), then the backward search,
-// integer only, right behind it -- both on ctx->stream.  -> *d_fwd, *d_bwd: the integer winners; *d_triples (want_triples): the triples
-// that belong to the records -- the integer winners themselves at scale 1, the refined ones (S_GATE_BEST) at scale 4
-int sad_consistency_searches_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                                    float4* d_raw, bool want_triples, const int** d_fwd, const int** d_bwd, const int** d_triples) {
-    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
-    const bool qpel = ctx->opt.sad_motion_scale == 4;
-    auto* fwd = static_cast<int*>(scratch(ctx, S_CONS_FWD, nblk * 3 * sizeof(int)));
-    auto* bwd = static_cast<int*>(scratch(ctx, S_CONS_BWD, nblk * 3 * sizeof(int)));
-    auto* bwd_ent = static_cast<float4*>(scratch(ctx, S_CONS_BWD_ENT, nblk * sizeof(float4)));     // the search kernels always write records
-    auto* refined = qpel && want_triples ? static_cast<int*>(scratch(ctx, S_GATE_BEST, nblk * 3 * sizeof(int))) : nullptr;
-    if (!fwd || !bwd || !bwd_ent || (qpel && want_triples && !refined)) return OFPS_HIP_ENOMEM;
-    int rc = qpel ? sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, refined, /*integer_only=*/false, fwd)
-                  : sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, fwd);
-    if (rc != OFPS_HIP_OK) return rc;
-    rc = sad_pairs_device(ctx, d_cur, 0, d_prev, 0, 1, W, H, stride, block, range, bwd_ent, bwd, /*integer_only=*/true);
-    *d_fwd = fwd; *d_bwd = bwd;
-    if (d_triples) *d_triples = want_triples ? (qpel ? refined : fwd) : nullptr;
-    return rc;
-}
-
-// One pair, everything on ctx->stream: both searches, [the contrast flags of `cur`,] the check's flags, one compaction, one count.
-int sad_flow_checked_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                            int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count) {
-    int rc = sad_consistency_check(ctx, block, limit, "sad_flow");
-    if (rc != OFPS_HIP_OK) return rc;
-    OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
-    if (min_pixels > 0) {
-        rc = sad_gate_check(ctx, block, min_pixels, "sad_flow");
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
-    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
-    auto* d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, nblk * sizeof(float4)));
-    auto* d_flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, gate_flags_bytes(nblk)));
-    if (!d_raw || !d_flags) return OFPS_HIP_ENOMEM;
-    const int *d_fwd = nullptr, *d_bwd = nullptr, *d_raw_best = nullptr;
-    rc = sad_consistency_searches_device(ctx, d_prev, d_cur, W, H, stride, block, range, d_raw, d_out_best != nullptr, &d_fwd, &d_bwd, &d_raw_best);
-    if (rc != OFPS_HIP_OK) return rc;
-    uint8_t* d_keep = gate_keep(d_flags, nblk);
-    if (min_pixels > 0) {
-        rc = sad_gate_flags_device(ctx, d_cur, W, H, stride, block, min_pixels, gate_counts(d_flags), d_keep, ctx->stream);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    rc = sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, min_pixels > 0 ? d_keep : nullptr, nullptr, d_keep, ctx->stream);
-    if (rc != OFPS_HIP_OK) return rc;
-    return sad_gate_compact_device(ctx, d_raw, d_raw_best, d_keep, nblk, d_out, d_out_best, d_count);
-}
-
 }  // namespace ofps
 
 extern "C" {
@@ -173,9 +124,12 @@ int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const v
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "sad_flow_checked_dev: null device pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ofps::sad_flow_checked_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                         min_pixels, limit, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                         static_cast<uint32_t*>(d_out_count));
+    const int rc = ofps::sad_consistency_check(ctx, block, limit, "sad_flow");           // (the filter itself takes 0 for "no check")
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
+    return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
+                                          min_pixels, limit, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          static_cast<uint32_t*>(d_out_count));
 }
 
 }  // extern "C"

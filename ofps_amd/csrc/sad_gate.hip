@@ -10,6 +10,9 @@
 // result does not depend on the order).
 // block_keep_kernel: count >= min_pixels -> one byte per block, the flag the ordered compactions of mask.hip take.
 // compact_best_kernel: the (dx, dy, SAD) triples compacted by the same flags in the same order.
+//
+// Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate and / or the consistency check
+// (sad_consistency.hip) in front of one compaction and one device-side count -- for the one-pair entry points and the fused per-frame path.
 #include "common.hpp"
 #include "mask_tile.hpp"
 
@@ -100,56 +103,89 @@ int block_contrast_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, int W, int H
     return OFPS_HIP_OK;
 }
 
-int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const char* who) {
+static int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const char* who) {          // min_pixels in [1, block * block]
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "%s: block=%d outside [1,64]", who, block);
     OFPS_REQUIRE(ctx, min_pixels >= 1 && min_pixels <= block * block, "%s: contrast gate %d outside [1, %d] for block %d", who, min_pixels,
                  block * block, block);
     return OFPS_HIP_OK;
 }
 
-int sad_gate_flags_device(ofps_hip_ctx* ctx, const uint8_t* d_cur, int W, int H, int stride, int block, int min_pixels, uint32_t* d_counts,
-                          uint8_t* d_keep, hipStream_t st) {
-    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
-    if (!nblk) return OFPS_HIP_OK;
-    const int rc = block_contrast_device(ctx, d_cur, W, H, stride, block, d_counts, st);
+// ---- SadFilter (common.hpp): the steps of one pair's filtered search
+int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
+    int rc = limit > 0 ? sad_consistency_check(ctx, block, limit, who) : OFPS_HIP_OK;
+    if (rc == OFPS_HIP_OK && gate > 0) rc = sad_gate_check(ctx, block, gate, who);
     if (rc != OFPS_HIP_OK) return rc;
-    hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_counts, (uint32_t)nblk, (uint32_t)min_pixels, d_keep);
+    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "%s: bad geometry W=%d H=%d stride=%d", who, W, H, stride);
+    nblk = ofps_hip_sad_block_count(W, H, block);
+    return OFPS_HIP_OK;
+}
+
+int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
+    if (!on()) return OFPS_HIP_OK;
+    const size_t fbytes = gate_flags_bytes(nblk), tri = nblk * 3 * sizeof(int);
+    d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, nblk * sizeof(float4)));
+    auto* flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, tickets * fbytes));
+    if (!d_raw || !flags) return OFPS_HIP_ENOMEM;
+    d_flags = flags + tix * fbytes;
+    if (limit > 0) {
+        d_fwd = static_cast<int*>(scratch(ctx, S_CONS_FWD, tri));
+        d_bwd = static_cast<int*>(scratch(ctx, S_CONS_BWD, tri));
+        d_bwd_ent = static_cast<float4*>(scratch(ctx, S_CONS_BWD_ENT, nblk * sizeof(float4)));     // the search kernels always write records
+        if (!d_fwd || !d_bwd || !d_bwd_ent) return OFPS_HIP_ENOMEM;
+    }
+    // the records' triples: the forward search's integer winners themselves when the check keeps them and nothing refines them
+    if (want_triples) d_triples = limit > 0 && ctx->opt.sad_motion_scale != 4 ? d_fwd : static_cast<int*>(scratch(ctx, S_GATE_BEST, tri));
+    return want_triples && !d_triples ? OFPS_HIP_ENOMEM : OFPS_HIP_OK;
+}
+
+int SadFilter::search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out) {
+    if (limit == 0) return sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
+    // check on (the two hazards: sad_consistency.hip): the forward search leaves its integer winners in d_fwd whatever the motion scale -- at
+    // scale 4 as d_int_best, the refinement then writes d_triples or nothing -- and the backward search, integer only, runs right behind it
+    const bool qpel = ctx->opt.sad_motion_scale == 4;
+    const int rc = sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, qpel ? d_triples : d_fwd, /*integer_only=*/false,
+                                    qpel ? d_fwd : nullptr);
+    if (rc != OFPS_HIP_OK) return rc;
+    return sad_pairs_device(ctx, d_cur, 0, d_prev, 0, 1, W, H, stride, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
+}
+
+int SadFilter::contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st) {
+    if (gate <= 0 || !nblk) return OFPS_HIP_OK;
+    const int rc = block_contrast_device(ctx, d_cur, W, H, stride, block, gate_counts(d_flags), st);
+    if (rc != OFPS_HIP_OK) return rc;
+    hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, gate_counts(d_flags), (uint32_t)nblk, (uint32_t)gate, keep());
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
 
-int sad_gate_compact_device(ofps_hip_ctx* ctx, const float4* d_raw, const int* d_raw_best, const uint8_t* d_keep, size_t nblk, float4* d_out,
-                            int* d_out_best, uint32_t* d_count) {
+int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count) {
+    if (!on()) return OFPS_HIP_OK;
+    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream)
+                       : OFPS_HIP_OK;
+    if (rc != OFPS_HIP_OK) return rc;
     if (nblk == 0) {
         OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
         return OFPS_HIP_OK;
     }
-    const int rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_keep, nblk, d_out, d_count)
-                                            : compact_entries_device(ctx, d_raw, d_keep, nblk, d_out, d_count);
+    rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, keep(), nblk, d_out, d_count)
+                                  : compact_entries_device(ctx, d_raw, keep(), nblk, d_out, d_count);
     if (rc != OFPS_HIP_OK) return rc;
     if (d_out_best) {
-        hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_raw_best, d_keep, (uint32_t)nblk, d_out_best);
+        hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_triples, keep(), (uint32_t)nblk, d_out_best);
         OFPS_HIP_TRY(ctx, hipGetLastError());
     }
     return OFPS_HIP_OK;
 }
 
-// One pair, everything on ctx->stream: search into the gate's own slots, flags of `cur`, compaction into the caller's buffers.
-int sad_flow_gated_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                          int min_pixels, float4* d_out, int* d_out_best, uint32_t* d_count) {
-    int rc = sad_gate_check(ctx, block, min_pixels, "sad_flow");
-    if (rc != OFPS_HIP_OK) return rc;
-    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
-    const size_t nblk = ofps_hip_sad_block_count(W, H, block);
-    auto* d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, nblk * sizeof(float4)));
-    auto* d_raw_best = d_out_best ? static_cast<int*>(scratch(ctx, S_GATE_BEST, nblk * 3 * sizeof(int))) : nullptr;
-    auto* d_flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, gate_flags_bytes(nblk)));
-    if (!d_raw || !d_flags || (d_out_best && !d_raw_best)) return OFPS_HIP_ENOMEM;
-    rc = sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, d_raw_best);
-    if (rc != OFPS_HIP_OK) return rc;
-    rc = sad_gate_flags_device(ctx, d_cur, W, H, stride, block, min_pixels, gate_counts(d_flags), gate_keep(d_flags, nblk), ctx->stream);
-    if (rc != OFPS_HIP_OK) return rc;
-    return sad_gate_compact_device(ctx, d_raw, d_raw_best, gate_keep(d_flags, nblk), nblk, d_out, d_out_best, d_count);
+// One pair, everything on ctx->stream: search[es], [contrast flags of `cur`,] [the check's flags,] one compaction, one count.
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
+                             int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count) {
+    SadFilter f{W, H, stride, block, range, min_pixels, limit, d_out_best != nullptr};
+    int rc = f.plan(ctx, "sad_flow");
+    if (rc == OFPS_HIP_OK) rc = f.reserve(ctx);
+    if (rc == OFPS_HIP_OK) rc = f.search(ctx, d_prev, d_cur, d_out);
+    if (rc == OFPS_HIP_OK) rc = f.contrast_flags(ctx, d_cur, ctx->stream);
+    return rc == OFPS_HIP_OK ? f.finish(ctx, d_out, d_out_best, d_count) : rc;
 }
 
 }  // namespace ofps
@@ -196,9 +232,11 @@ int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "sad_flow_gated_dev: null device pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ofps::sad_flow_gated_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                       min_pixels, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                       static_cast<uint32_t*>(d_out_count));
+    const int rc = ofps::sad_gate_check(ctx, block, min_pixels, "sad_flow");             // (the filter itself takes 0 for "no gate")
+    if (rc != OFPS_HIP_OK) return rc;
+    return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
+                                          min_pixels, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          static_cast<uint32_t*>(d_out_count));
 }
 
 }  // extern "C"

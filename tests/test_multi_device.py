@@ -264,3 +264,36 @@ def test_multi_fetch_refuses_results_of_another_batch_or_block_size():
         np.testing.assert_array_equal(md.fetch(16).view(np.uint32), a[:3].view(np.uint32))
     finally:
         md.close()
+
+
+@pytest.mark.gpu
+def test_multi_workers_keep_the_raw_detector_under_detect_compensation(monkeypatch):
+    """A worker context reads OFPS_HIP_DETECT_COMPENSATE=1 at its own init like any context, but its pushes are the halo form of the batched
+    path, whose tail never compensates: every frame's motion is ofps_hip_detect on that frame's returned records, not on the records
+    compensated with its quaternion -- which answer differently for at least one frame of this stream, or the test could not tell."""
+    import sad_gate_cases as gc
+    from ofps_amd.runtime import HipContext
+    f = gc.frames()
+    prm = dict(block=gc.BLOCK, search_range=gc.RANGE, aspect=gc.FRAME_CAM[0], fov_y_deg=gc.FRAME_CAM[1], seed=gc.SEED, **gc.FRAME_DETECTOR)
+    ctx = HipContext(0)                                                  # the stage calls; made before the environment changes
+    monkeypatch.setenv("OFPS_HIP_DETECT_COMPENSATE", "1")                # the workers read the environment at their own init
+    md = MultiDevice([0, 0])
+    try:
+        ent = np.zeros((2, 2, gc.NBLK, 4), np.float32)
+        got = []
+        for b in range(2):                                               # one batch of two frames per worker: the second one's first pair needs its halo
+            got += md.frames_wait(md.push_frames_async(np.ascontiguousarray(f[2 * b:2 * b + 2]), out_entries=ent[b], **prm))
+        assert [g["have_vectors"] for g in got] == [False, True, True, True]
+        dim = ctx.block_dim(gc.FRAME_DETECTOR["min_size"], gc.FRAME_DETECTOR["subdivide"])
+        differs = 0
+        for k in range(1, gc.N_FRAMES):
+            rec = ent.reshape(-1, gc.NBLK, 4)[k]
+            raw = ctx.detect(rec, **gc.FRAME_DETECTOR)
+            comp = ctx.detect(ctx.compensate(rec, *gc.FRAME_CAM, got[k]["quat"]), **gc.FRAME_DETECTOR)
+            print(f"frame {k}: motion {got[k]['motion']}, detect raw {gc.area_of(raw)}, compensated {gc.area_of(comp)}, quat {got[k]['quat']}")
+            assert got[k]["motion"] == (None if raw is None else (raw[0], dim)), k
+            differs += gc.area_of(raw) != gc.area_of(comp)
+        assert differs >= 1, "the stream does not tell the raw detector from the compensated one"
+    finally:
+        md.close()
+        ctx.close()
