@@ -89,6 +89,7 @@ int ofps_hip_timer_stop(ofps_hip_ctx* ctx, float* elapsed_ms);   /* synchronises
  * Blocks on a block x block lattice from (0,0), full blocks only; candidates (dx,dy) in
  * [-range,range]^2 whose block lies inside the frame; winner = min of
  * (SAD, dx*dx+dy*dy, dy+range, dx+range); entry = (pos = (centre+d)/(W,H), motion = -d/(W,H)).
+ * Motion beyond `range`: the search levels, N1h below.
  * Supported: block in {8,16} with range in {8,12,16,20,24,28,32} and 16-byte aligned rows run on the packed-SAD strip
  * kernel (the same geometries with rows only 4-byte aligned: the per-block packed kernel); any other block <= 64,
  * range <= 64 runs on the generic kernel (correctness path, ~30x slower).  stride % 4 == 0. */
@@ -220,6 +221,51 @@ int ofps_hip_get_sad_consistency(ofps_hip_ctx* ctx);
 int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
                                   int min_pixels /* 0 = no contrast gate */, int limit /* >= 1 */, void* d_out_entries,
                                   void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
+
+/* ---- N1h: hip_sad's search levels -- coarse-to-fine search for motion beyond the search range (csrc/sad_hier.hip) ----
+ * The plain search cannot return a vector that was never a candidate: range 16 at 1080p ends at about one degree of camera rotation per
+ * frame.  With levels = L in {2, 3} the search runs on the frames halved L - 1 times and every finer level repairs the doubled vectors in a
+ * small window, as the hierarchical searches of the encoders do whose vectors av-decoder consumes.  Build-defined, like N1, N1q, N1g and
+ * N1c.  For a frame pair (prev, cur), lattice `block` = B, `range` = R:
+ *   pyramid: level 0 is the frame; level l+1 has W_{l+1} = W_l >> 1, H_{l+1} = H_l >> 1 and pixel (x, y) = (a + b + c + d + 2) >> 2 of the
+ *     2 x 2 quad at (2x, 2y) of level l (a last odd column or row is unused): what ofps_hip_sad_down2 returns;
+ *   top: T = the N1 winners of the plain search (block B, range R) on the level L-1 pair: exactly what ofps_hip_sad_flow returns for those two
+ *     images at levels 1 (the kernel selection and the PRUNED mode apply to it as they do to any plain search);
+ *   reach: R_{L-1} = R, R_l = 2 * R_{l+1} + 3;
+ *   refinement, for l = L-2 down to 0, on the level-l lattice (nbx_l = W_l / B, nby_l = H_l / B, full blocks from (0, 0)); for the block
+ *     (bx, by) at (x0, y0) = (bx*B, by*B): what ofps_hip_sad_refine returns:
+ *       parent = (min(bx >> 1, nbx_{l+1} - 1), min(by >> 1, nby_{l+1} - 1)) of the level l+1 lattice;
+ *       predictor p = 2 * the parent's winner, clamped so that the block lies inside the frame: px = clamp(px, -x0, W_l - B - x0), py alike
+ *         (zero is always inside: the clamp never enlarges |p|);
+ *       candidates d = p + e, e in [-3, 3]^2, valid iff 0 <= x0 + dx <= W_l - B and the same in y (e = 0 always is);
+ *       cost = sum |cur_l - prev_l| over the block, prev_l displaced by d;
+ *       winner = min of (SAD, dx*dx + dy*dy, dy + R_l, dx + R_l), lexicographic, d the total displacement;
+ *   output: the level-0 winners (dx, dy, SAD) and their records in N1's convention, one per lattice block in raster order.
+ * levels 1 = off, the default: every entry point then uses the launches, streams and bytes of a build without this section.  levels outside
+ * {1, 2, 3} is OFPS_HIP_EINVAL at the setter.  A call is OFPS_HIP_EINVAL when the top level has no full block (W >> (L-1) < B or
+ * H >> (L-1) < B) or when R_0 > 127 (the 10-bit fields of the quarter-pel key: 8 * R_0 + 6 <= 1023): levels 2 takes range <= 62, levels 3
+ * range <= 29; the top search keeps N1's limits on block and range.  The option OFPS_HIP_SAD_LEVELS (environment / ofps_hip_set_option) sets
+ * the same field.  ofps_hip_sad_reach(range, levels) = R_0, or a negative value when (range, levels) is invalid.
+ * Every search of the context follows it: ofps_hip_sad_flow, ofps_hip_sad_flow_dev (both ref modes), ofps_hip_sad_flow_gated_dev /
+ * _checked_dev, ofps_hip_push_frame[_async], ofps_hip_push_frames_async and the ofps_hip_multi_* workers (through the environment option).
+ * Composition: quarter-pel (N1q) refines the level-0 winners, with R_0 where its key has `range`; the consistency check (N1c) runs both
+ * directions over the same levels, its limits stay [1, 129] and "a limit above 2*range + 1 keeps every block" holds with R_0 for `range`; the
+ * contrast gate (N1g) is untouched.  The refinement radius 3 is a constant of the build.
+ * ofps_hip_sad_down2[_dev]: one frame, W, H >= 2, stride >= W -> (W >> 1) x (H >> 1) bytes, dst_stride >= W >> 1.
+ * ofps_hip_sad_refine[_dev]: one refinement step of one pair: parent_best = the nbx_parent x nby_parent triples (dx, dy, sad) of the coarser
+ *   lattice (only dx, dy are read), reach = R_l in [0, 127] for the key; out_best: nblk triples; out_entries: nblk records or NULL.  The
+ *   triples are the caller's responsibility: a predictor is clamped to the frame whatever they hold (no access out of bounds), the winner is
+ *   the definition's while every |d| <= 508.  The _dev forms enqueue only; their frames' rows must be 4-byte aligned (stride % 4 == 0). */
+int ofps_hip_set_sad_levels(ofps_hip_ctx* ctx, int levels);   /* 1 = off (default) */
+int ofps_hip_get_sad_levels(ofps_hip_ctx* ctx);
+int ofps_hip_sad_reach(int range, int levels);
+int ofps_hip_sad_down2(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int stride, uint8_t* dst /* (H >> 1) rows of dst_stride bytes */, int dst_stride);
+int ofps_hip_sad_down2_dev(ofps_hip_ctx* ctx, const void* d_src, int W, int H, int stride, void* d_dst, int dst_stride);
+int ofps_hip_sad_refine(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
+                        const int32_t* parent_best /* 3 * nbx_parent * nby_parent */, int nbx_parent, int nby_parent, int reach,
+                        int32_t* out_best /* 3 * nblk */, float* out_entries /* 4 * nblk or NULL */);
+int ofps_hip_sad_refine_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
+                            const void* d_parent_best, int nbx_parent, int nby_parent, int reach, void* d_out_best, void* d_out_entries /* or NULL */);
 
 /* ---- N2: dense per-pixel flow, pyramidal Lucas-Kanade ("hip_lk" Decoder) ----
  * The reference's only per-pixel flow is OpenCV's Farneback inside cv-decoder (cv-decoder/src/lib.rs:188-199); this

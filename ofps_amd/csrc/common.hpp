@@ -204,6 +204,7 @@ struct ofps_hip_ctx {
         int detect_compensate = 0;       // OFPS_HIP_DETECT_COMPENSATE / ofps_hip_set_detect_compensation: 0 the fused entry points' detector reads the raw vectors, 1 the vectors compensated with the frame's own quaternion (compensate.hip)
         int sad_gate = 0;                // OFPS_HIP_SAD_GATE / ofps_hip_set_sad_gate: 0 one record per lattice block, N >= 1 only blocks with at least N contrast-mask pixels of the current frame (sad_gate.hip)
         int sad_consistency = 0;         // OFPS_HIP_SAD_CONSISTENCY / ofps_hip_set_sad_consistency: 0 off, N in [1, 129] only blocks whose forward-backward residual is below N (sad_consistency.hip)
+        int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -228,7 +229,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 48;
+    static constexpr int kNumScratch = 52;
     Scratch scratch[kNumScratch];
 };
 
@@ -260,9 +261,12 @@ enum ScratchSlot {
                             // record copy and the estimator read are never overwritten.  Written and read on the compute stream only
     S_CONS_FWD,             // hip_sad's consistency check (sad_consistency.hip): the forward search's integer winners, kept through a quarter-pel refinement
     S_CONS_BWD,             // ... the backward search's integer winners
-    S_CONS_BWD_ENT          // ... and its records, which nobody reads (the search kernels always write them).  All three: compute stream only
+    S_CONS_BWD_ENT,         // ... and its records, which nobody reads (the search kernels always write them).  All three: compute stream only
+    S_HIER_PYR,             // hip_sad's search levels (sad_hier.hip): the halved frames of one search's two frame sets, every level above 0
+    S_HIER_BEST,            // ... the winners of every level above 0
+    S_HIER_ENT              // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
 };
-static_assert(S_CONS_BWD_ENT < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_HIER_ENT < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -287,6 +291,17 @@ void* scratch(ofps_hip_ctx* ctx, int slot, size_t bytes);
 int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
                      size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
                      void* d_out_best, bool integer_only = false, void* d_int_best = nullptr);
+// the plain integer search alone (N1): what sad_pairs_device runs at one search level, and the top search of sad_hier_pairs_device
+int sad_search_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
+                      int W, int H, int stride, int block, int range, void* d_out_entries, void* d_out_best);
+// sad_hier.hip (include/ofps_hip.h N1h): the integer winners of a search over `levels` > 1 levels; never refines to quarter-pel and never
+// looks at the context's levels, so it cannot come back to itself through the top search.  d_out_best may be null
+constexpr int kSadHierRefine = 3;                           // the refinement's radius: 49 candidates in a 64-lane wave
+constexpr int kSadHierMaxReach = 127;                       // 8 * reach + 6 <= 1023: the quarter-pel key's 10-bit fields
+int sad_hier_reach(int range, int levels);                  // R_0, or -1
+int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
+int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
+                          int W, int H, int stride, int block, int range, int levels, void* d_out_entries, void* d_out_best);
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);

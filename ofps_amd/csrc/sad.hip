@@ -1083,18 +1083,21 @@ size_t ofps_hip_sad_block_count(int W, int H, int block) {
 
 }  // extern "C" (reopened below)
 
-namespace ofps {
-// Shared by the batched entry point and the per-frame pipeline (pipeline.hip): `pairs` searches,
-// pair k between prev_base + k*prev_pitch and cur_base + k*cur_pitch.
-int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
-                     size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
-                     void* d_out_best, bool integer_only, void* d_int_best) {
+namespace {
+// what every search asks of its frames and parameters, in one place: sad_pairs_device and sad_search_device say the same words
+int sad_check_args(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int W, int H,
+                   int stride, int block, int range) {
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
     OFPS_REQUIRE(ctx, stride % 4 == 0 && ((uintptr_t)prev_base % 4) == 0 && ((uintptr_t)cur_base % 4) == 0 &&
                           prev_pitch % 4 == 0 && cur_pitch % 4 == 0,
                  "sad_flow: rows must be 4-byte aligned (stride=%d)", stride);
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64 && range >= 0 && range <= 64,
                  "sad_flow: block=%d range=%d outside [1,64]/[0,64]", block, range);
+    return OFPS_HIP_OK;
+}
+
+SadParams sad_params(const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int W, int H, int stride, int block,
+                     void* d_out_entries, void* d_out_best) {
     SadParams p{};
     p.prev_base = prev_base; p.cur_base = cur_base;
     p.prev_pitch = prev_pitch; p.cur_pitch = cur_pitch;
@@ -1103,17 +1106,14 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     p.nx = 1.0f / (float)W; p.ny = 1.0f / (float)H;
     p.out_entries = static_cast<float4*>(d_out_entries);
     p.out_best = static_cast<int*>(d_out_best);
-    if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
-    OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
-    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // motion scale 4: the refinement (sad_qpel.hip) starts from the integer winners, so they are kept even when the caller wants none
-    // (consistency check, sad_consistency.hip: its backward search is integer_only; its forward search keeps the integer winners in d_int_best)
-    const bool qpel = ctx->opt.sad_motion_scale == 4 && !integer_only;
-    if (qpel && d_int_best) p.out_best = static_cast<int*>(d_int_best);
-    else if (qpel && !p.out_best) {
-        p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
-        if (!p.out_best) return OFPS_HIP_ENOMEM;
-    }
+    return p;
+}
+
+// the launches of one plain search: kernel selection by geometry, alignment and the context's mode
+int sad_launch(ofps_hip_ctx* ctx, const SadParams& p, int pairs, int block, int range) {
+    const uint8_t* prev_base = p.prev_base; const uint8_t* cur_base = p.cur_base;
+    const size_t prev_pitch = p.prev_pitch, cur_pitch = p.cur_pitch;
+    const int stride = p.stride;
     hipStream_t s = ctx->stream;
     const int key = block * 1000 + range;
     const bool force_block = ctx->opt.sad_force_block != 0;     // OFPS_HIP_SAD_KERNEL=block (A/B profiling)
@@ -1160,9 +1160,53 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
         }
     }
     OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+}  // namespace
+
+namespace ofps {
+int sad_search_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
+                      int W, int H, int stride, int block, int range, void* d_out_entries, void* d_out_best) {
+    const int rc = sad_check_args(ctx, prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, range);
+    if (rc != OFPS_HIP_OK) return rc;
+    const SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
+    if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return sad_launch(ctx, p, pairs, block, range);
+}
+
+// Shared by the batched entry point and the per-frame pipeline (pipeline.hip): `pairs` searches,
+// pair k between prev_base + k*prev_pitch and cur_base + k*cur_pitch.
+int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
+                     size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
+                     void* d_out_best, bool integer_only, void* d_int_best) {
+    int rc = sad_check_args(ctx, prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, range);
+    if (rc != OFPS_HIP_OK) return rc;
+    // search levels (sad_hier.hip): the integer search below becomes top search + refinements; everything around it stays
+    const int levels = ctx->opt.sad_levels;
+    if (levels > 1 && (rc = ofps::sad_hier_check(ctx, W, H, block, range, levels)) != OFPS_HIP_OK) return rc;
+    SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
+    if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // motion scale 4: the refinement (sad_qpel.hip) starts from the integer winners, so they are kept even when the caller wants none
+    // (consistency check, sad_consistency.hip: its backward search is integer_only; its forward search keeps the integer winners in d_int_best)
+    const bool qpel = ctx->opt.sad_motion_scale == 4 && !integer_only;
+    if (qpel && d_int_best) p.out_best = static_cast<int*>(d_int_best);
+    else if (qpel && !p.out_best) {
+        p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
+        if (!p.out_best) return OFPS_HIP_ENOMEM;
+    }
+    // with levels > 1 the level-0 winners land where the plain search's would (d_int_best included), and the quarter-pel key takes the reach
+    if (levels > 1)
+        rc = ofps::sad_hier_pairs_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block, range, levels,
+                                         d_out_entries, p.out_best);
+    else rc = sad_launch(ctx, p, pairs, block, range);
+    if (rc != OFPS_HIP_OK) return rc;
     if (qpel)
-        return ofps::sad_qpel_refine_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block, range, d_out_entries,
-                                            p.out_best, d_out_best);
+        return ofps::sad_qpel_refine_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block,
+                                            levels > 1 ? ofps::sad_hier_reach(range, levels) : range, d_out_entries, p.out_best, d_out_best);
     return OFPS_HIP_OK;
 }
 }  // namespace ofps

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(64 * WAVES) void sad_qpel_kernel(const QpelParams p
             }
     }
 
-    // ---- 4. key = (SAD, Dx^2 + Dy^2, Dy + 4R + 3, Dx + 4R + 3): 24 + 20 + 10 + 10 bits (B, R <= 64)
+    // ---- 4. key = (SAD, Dx^2 + Dy^2, Dy + 4R + 3, Dx + 4R + 3): 24 + 20 + 10 + 10 bits (B <= 64, R <= 127)
     const int Dx = 4 * dx + fx, Dy = 4 * dy + fy;
     const bool valid = lane < 49 && 4 * x0 + Dx >= 0 && 4 * (x0 + B - 1) + Dx <= 4 * (p.W - 1) && 4 * y0 + Dy >= 0 &&
                        4 * (y0 + B - 1) + Dy <= 4 * (p.H - 1);
@@ -241,8 +241,8 @@ namespace ofps {
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best) {
-    OFPS_REQUIRE(ctx, block >= 1 && block <= 64 && range >= 0 && range <= 64, "sad_qpel: block=%d range=%d outside [1,64]/[0,64]", block,
-                 range);
+    OFPS_REQUIRE(ctx, block >= 1 && block <= 64 && range >= 0 && range <= kSadHierMaxReach, "sad_qpel: block=%d range=%d outside [1,64]/[0,127]",
+                 block, range);                 // range above 64: the reach of a search over levels (sad_hier.hip); the key's fields hold 8 * 127 + 6
     OFPS_REQUIRE(ctx, d_entries && d_in_best, "sad_qpel: null device pointer");
     QpelParams p{};
     p.prev_base = prev_base; p.cur_base = cur_base;

@@ -77,7 +77,10 @@ class HipSadDecoder(Properties):
               ("Contrast gate", "usize", "contrast_gate", 0, 256),
               # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
               # include/ofps_hip.h N1c).  Costs a second search per frame
-              ("Consistency check", "usize", "consistency", 0, 129))
+              ("Consistency check", "usize", "consistency", 0, 129),
+              # build-defined: 1 = the plain search; 2 | 3 = coarse-to-fine over that many levels, for motion beyond the search range
+              # (reach 2 * range + 3, 4 * range + 9, at most 127; include/ofps_hip.h N1h)
+              ("Search levels", "usize", "levels", 1, 3))
 
     def __init__(self, frames: Iterable[np.ndarray], framerate: Optional[float] = None, device: int = 0):
         self.ctx = HipContext(device)
@@ -87,6 +90,7 @@ class HipSadDecoder(Properties):
         self.quarter_pel = False
         self.contrast_gate = 0
         self.consistency = 0
+        self.levels = 1
         self._prev: Optional[np.ndarray] = None
         self._cur: Optional[np.ndarray] = None
         self._fps = framerate
@@ -126,6 +130,7 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_motion_scale(4 if self.quarter_pel else 1)
         self.ctx.set_sad_gate(self.contrast_gate)
         self.ctx.set_sad_consistency(self.consistency)
+        self.ctx.set_sad_levels(self.levels)
         r = self.ctx.push_frame(self._cur, self.block, self.range, detector=False, estimator=False, want_entries=True)
         if not r["have_vectors"]:                          # first frame of the stream / geometry change
             return False

@@ -184,6 +184,60 @@ class HipContext:
                                                             min_pixels, limit, C.c_void_p(d_out_entries), C.c_void_p(d_out_best or 0),
                                                             C.c_void_p(d_out_count)))
 
+    def set_sad_levels(self, levels: int):
+        """hip_sad's search levels (include/ofps_hip.h N1h): 1 = the plain search (default); 2 | 3 = the search runs on the frames halved
+        levels - 1 times and every finer level repairs the doubled vectors in a +-3 window: reach 2 * range + 3, 4 * range + 9."""
+        self._check(self._lib.ofps_hip_set_sad_levels(self._h, levels))
+
+    def get_sad_levels(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_levels(self._h))
+
+    def sad_reach(self, search_range: int, levels: int) -> int:
+        """The largest |dx|, |dy| a search of `search_range` over `levels` levels can return (R_0); ValueError when the pair is invalid."""
+        r = int(self._lib.ofps_hip_sad_reach(search_range, levels))
+        if r < 0:
+            raise ValueError(f"range {search_range} with levels {levels} is no valid search")
+        return r
+
+    def sad_down2(self, img: np.ndarray, stride: int | None = None) -> np.ndarray:
+        """One pyramid step: [H, W] u8 -> [H >> 1, W >> 1], (a + b + c + d + 2) >> 2 of every 2 x 2 quad.  stride: None, or the row pitch in
+        bytes of `img` (a view of a wider buffer)."""
+        if stride is None:
+            g = np.ascontiguousarray(img, np.uint8)
+            stride = g.shape[1]
+        else:
+            g = img
+            assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
+        H, W = g.shape
+        out = np.zeros((H >> 1, W >> 1), np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.ofps_hip_sad_down2(self._h, C.cast(C.c_void_p(g.ctypes.data), u8), W, H, stride,
+                                                 C.cast(C.c_void_p((out if out.size else np.zeros(1, np.uint8)).ctypes.data), u8), max(W >> 1, 1)))
+        return out
+
+    def sad_down2_dev(self, d_src: int, W: int, H: int, stride: int, d_dst: int, dst_stride: int):
+        self._check(self._lib.ofps_hip_sad_down2_dev(self._h, C.c_void_p(d_src), W, H, stride, C.c_void_p(d_dst), dst_stride))
+
+    def sad_refine(self, prev: np.ndarray, cur: np.ndarray, block: int, parent_best: np.ndarray, reach: int, want_entries=False):
+        """One refinement step of the search levels: parent_best [nby_parent, nbx_parent, 3] = the coarser lattice's (dx, dy, sad) ->
+        triples [nblk, 3] (and records [nblk, 4])."""
+        prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
+        par = np.ascontiguousarray(parent_best, np.int32)
+        assert prev.shape == cur.shape and prev.ndim == 2 and par.ndim == 3 and par.shape[2] == 3
+        H, W = prev.shape
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        best = np.zeros((max(nb, 1), 3), np.int32)
+        ent = np.zeros((max(nb, 1), 4), np.float32)
+        u8 = C.POINTER(C.c_uint8); i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_sad_refine(self._h, prev.ctypes.data_as(u8), cur.ctypes.data_as(u8), W, H, W, block, par.ctypes.data_as(i32),
+                                                  par.shape[1], par.shape[0], reach, best.ctypes.data_as(i32), _fp(ent) if want_entries else None))
+        return (best[:nb], ent[:nb]) if want_entries else best[:nb]
+
+    def sad_refine_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, d_parent_best: int, nbx_parent: int,
+                       nby_parent: int, reach: int, d_out_best: int, d_out_entries: int | None = None):
+        self._check(self._lib.ofps_hip_sad_refine_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, C.c_void_p(d_parent_best),
+                                                      nbx_parent, nby_parent, reach, C.c_void_p(d_out_best), C.c_void_p(d_out_entries or 0)))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))

@@ -13,6 +13,9 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               cv-decoder's own arguments: levels 5, winsize 13, 3 iterations, poly_n 7, poly_sigma 1.5; same mask and records)
               with --quarter-pel also hip_sad_q: hip_sad with its "Quarter pel" property on (motion scale 4, include/ofps_hip.h N1q)
               with --sad-consistency N also hip_sad_c: hip_sad with its "Consistency check" property at N (include/ofps_hip.h N1c)
+              with --sad-levels N also hip_sad_h: hip_sad with its "Search levels" property at N (include/ofps_hip.h N1h; reach 2 * 16 + 3 =
+              35 px at N = 2, 73 px at N = 3); --fast-clips adds 1080p pans of 1.5 and 3 degrees per frame (24 and 49 px at the centre:
+              beyond the plain search's +-16); --sad-only leaves the dense decoders' columns out
   estimators  hip_almeida LSQ  |  hip_almeida RANSAC (the reference's default: 200 hypotheses x 1000 samples, 0.05 degree inliers)
 Per clip and combination: mean and max of angle_to(planted q_k, estimated r_k) over the frames, that mean relative to the clip's mean
 rotation per frame (the reference's own test bound is 10 %: almeida-estimator/src/lib.rs:347-348), and the pose drift after the
@@ -39,7 +42,7 @@ def triangle(rate, n, period):
     return np.where(((k + period) // (2 * period)) % 2 == 0, rate, -rate).astype(np.float64)
 
 
-def clip_table(quick=False):
+def clip_table(quick=False, fast_clips=False):
     """name -> (W, H, fov_y_deg, per-frame eulers [n, 3] (roll = tilt, pitch = image roll, yaw = pan), distractor)"""
     n = 24 if quick else 60
     W, H = 1920, 1080
@@ -57,6 +60,9 @@ def clip_table(quick=False):
     t["mixed_sine_dyn"] = (W, H, 60.0, mixed, dict(size=(W // 5, H // 4), start=(W // 10, H // 3), velocity=(W / 1920 * 7.0, -H / 1080 * 2.0)))
     if not quick:
         t["1deg_mixed_360p"] = (640, 360, 60.0, np.stack([triangle(0.6, n, 8), triangle(0.3, n, 10), triangle(0.7, n, 6)], 1), None)
+    if fast_clips:      # beyond the plain search's reach at 1080p (16.32 px per degree at the centre); the accumulated pan stays within +-9 degrees
+        t["fast_pan_1.5"] = (W, H, 60.0, np.stack([z, z, triangle(1.5, n, 4)], 1), None)
+        t["fast_pan_3.0"] = (W, H, 60.0, np.stack([z, z, triangle(3.0, n, 3)], 1), None)
     return t
 
 
@@ -124,7 +130,8 @@ def flat_third(frames, seed=5):
     return out
 
 
-def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0):
+def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
+        fast_clips=False, sad_only=False):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -143,9 +150,17 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         if quarter_pel:
             props_qc = {"Quarter pel": True, "Consistency check": sad_consistency}
             combos[2:2] = [("hip_sad_qc", HipSadDecoder, False, props_qc), ("hip_sad_qc", HipSadDecoder, True, props_qc)]
+    if sad_levels:      # hip_sad with its "Search levels" property at N (include/ofps_hip.h N1h); with --quarter-pel also on top of "Quarter pel"
+        props_h = {"Search levels": sad_levels}
+        combos[2:2] = [("hip_sad_h", HipSadDecoder, False, props_h), ("hip_sad_h", HipSadDecoder, True, props_h)]
+        if quarter_pel:
+            props_qh = {"Quarter pel": True, "Search levels": sad_levels}
+            combos[2:2] = [("hip_sad_qh", HipSadDecoder, False, props_qh), ("hip_sad_qh", HipSadDecoder, True, props_qh)]
+    if sad_only:
+        combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
     clips = []
-    for name, geom in clip_table(quick).items():
+    for name, geom in clip_table(quick, fast_clips).items():
         if only and name not in only:
             continue
         clip_seed = 21 + sum(1 for c in clips if not c[3])         # the n-th clip that runs renders with seed 21 + n
@@ -174,15 +189,16 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
             qo = np.array([oracle.solve_ypr_given(oracle.sad_flow(frames[k], frames[k + 1], 16, 16, threads=min(16, oracle.num_threads()))[0], ocam)
                            for k in range(len(truth))])
             row["cpu_oracle:sad+lsq"] = dict(stats(qo, truth), max_abs_dq_vs_hip=float(np.abs(qo - per_pair["hip_sad+lsq"]).max()))
-            m = min(oracle_lk_pairs, len(truth))
+            m = min(oracle_lk_pairs, len(truth)) if "hip_lk+lsq" in per_pair else 0
             ql = []
             for k in range(m):
                 flow = oracle.lk_flow(frames[k], frames[k + 1], 3, 4, 3)
                 ent = oracle.densify_to_entries(oracle.masked_flow_to_entries(flow, oracle.contrast_mask(frames[k + 1])), 150, 84)
                 ql.append(oracle.solve_ypr_given(ent, ocam))
             ql = np.array(ql)
-            row["cpu_oracle:lk+lsq"] = {"pairs": m, "mean_err_deg": float(np.mean([synth.quat_angle_deg(a, b) for a, b in zip(ql, truth[:m])])),
-                                        "max_abs_dq_vs_hip": float(np.abs(ql - per_pair["hip_lk+lsq"][:m]).max())}
+            if m:
+                row["cpu_oracle:lk+lsq"] = {"pairs": m, "mean_err_deg": float(np.mean([synth.quat_angle_deg(a, b) for a, b in zip(ql, truth[:m])])),
+                                            "max_abs_dq_vs_hip": float(np.abs(ql - per_pair["hip_lk+lsq"][:m]).max())}
         res[name] = row
         log(f"[accuracy] {name}: " + "  ".join(f"{k} {v['mean_err_deg']:.4f}" for k, v in row.items() if isinstance(v, dict) and "mean_err_deg" in v))
     return res
@@ -195,9 +211,11 @@ def table(res):
         cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
     if any("hip_sad_g+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
-    for tag in ("hip_sad_c", "hip_sad_qc"):
+    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh"):
         if any(tag + "+lsq" in r for r in res.values()):
             cols[2:2] = [tag + "+lsq", tag + "+ransac"]
+    if not any("hip_lk+lsq" in r for r in res.values()):       # --sad-only: no dense decoder ran
+        cols = [c for c in cols if c.startswith(("hip_sad", "cpu_oracle"))]
     lines = []
     lines.append("mean rotation error per frame, degrees (docs/statistics/err_av.csv's unit); clip rows, decoder+estimator columns")
     lines.append("clip,geometry,mean_rot_deg_per_frame,px_per_deg," + ",".join(cols))
@@ -225,7 +243,7 @@ def table(res):
     for name, r in res.items():
         a, b = r.get("cpu_oracle:sad+lsq", {}), r.get("cpu_oracle:lk+lsq", {})
         lines.append(f"{name},{a.get('max_abs_dq_vs_hip', float('nan')):.2e},{b.get('max_abs_dq_vs_hip', float('nan')):.2e},{b.get('pairs', 0)},"
-                     f"{r['hip_sad+lsq']['ms_per_frame']},{r['hip_lk+lsq']['ms_per_frame']},{r['hip_sad+ransac']['ms_per_frame']}")
+                     f"{r['hip_sad+lsq']['ms_per_frame']},{r.get('hip_lk+lsq', {}).get('ms_per_frame', '')},{r['hip_sad+ransac']['ms_per_frame']}")
     return "\n".join(lines) + "\n"
 
 
@@ -242,9 +260,14 @@ def main():
                     help="add the hip_sad_g columns (hip_sad with \"Contrast gate\" = N) and a variant of every clip with a flat noisy right third")
     ap.add_argument("--sad-consistency", type=int, default=0, metavar="N",
                     help="add the hip_sad_c columns (hip_sad with \"Consistency check\" = N; with --quarter-pel also hip_sad_qc: on top of \"Quarter pel\")")
+    ap.add_argument("--sad-levels", type=int, default=0, metavar="N",
+                    help="add the hip_sad_h columns (hip_sad with \"Search levels\" = N; with --quarter-pel also hip_sad_qh: on top of \"Quarter pel\")")
+    ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
+    ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
-              sad_gate=args.sad_gate, sad_consistency=args.sad_consistency)
+              sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
+              sad_only=args.sad_only)
     txt = table(res)
     print(txt)
     if args.out:
