@@ -267,6 +267,36 @@ int ofps_hip_sad_refine(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* c
 int ofps_hip_sad_refine_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
                             const void* d_parent_best, int nbx_parent, int nby_parent, int reach, void* d_out_best, void* d_out_entries /* or NULL */);
 
+/* ---- N1p: neighbour and zero predictors for the search levels (csrc/sad_hier.hip) ----
+ * Under N1h a refined block has one predictor, its parent's doubled winner: where that parent straddles a motion boundary, sits on low
+ * texture in the box-filtered image, or had its match clipped by the frame edge, the +-3 window around it cannot return to the true
+ * vector.  With sad_predictors = OFPS_HIP_SAD_PRED_NEIGHBOURS a block tries several predictors, as hierarchical encoder searches do, and
+ * only the refinement paragraph of N1h changes.  Build-defined, all-integer, off by default.  For the block (bx, by) at (x0, y0) of level l:
+ *   parent (qx, qy) = (min(bx >> 1, nbx_{l+1} - 1), min(by >> 1, nby_{l+1} - 1)), as in N1h;
+ *   predictor list, in this order: 2 * the winner of parent (qx, qy); 2 * the winners of (qx - 1, qy), (qx + 1, qy), (qx, qy - 1),
+ *     (qx, qy + 1), for those that exist in the parent lattice; (0, 0);
+ *   each predictor is clamped on its own, after the doubling, with N1h's clamp: px = clamp(px, -x0, W_l - B - x0), py alike;
+ *   candidates: the multiset of d = p + e over all predictors p and e in [-3, 3]^2, valid iff the displaced block lies inside the frame;
+ *   cost and winner as in N1h: min of (SAD, dx*dx + dy*dy, dy + R_l, dx + R_l).  The key is a total order on d, so duplicate candidates and
+ *     duplicate predictors cannot change the winner (the kernel drops duplicate predictors).
+ * The pyramid, the top search, the reach R_l = 2 * R_{l+1} + 3 (every candidate still has |d| <= R_l: the neighbours' winners obey the
+ * parent's bound and zero is inside), the EINVAL conditions and the output convention are N1h's.  OFPS_HIP_SAD_PRED_PARENT (0, the default)
+ * is N1h as it stands: the launches and bytes of a build without this section.  Any other mode is OFPS_HIP_EINVAL at the setter, at the
+ * option OFPS_HIP_SAD_PREDICTORS (environment / ofps_hip_set_option; the ofps_hip_multi_* workers follow it) and at
+ * ofps_hip_sad_refine_pred[_dev].  At levels 1 the field is stored and has no effect.  Every search that follows `levels` follows it, and
+ * the consistency check (N1c) runs both directions in the same mode.
+ * ofps_hip_sad_refine_pred[_dev]: ofps_hip_sad_refine[_dev] with the predictor mode as an argument (mode 0 is that call). */
+#define OFPS_HIP_SAD_PRED_PARENT 0
+#define OFPS_HIP_SAD_PRED_NEIGHBOURS 1
+int ofps_hip_set_sad_predictors(ofps_hip_ctx* ctx, int mode);   /* 0 = parent only (default) */
+int ofps_hip_get_sad_predictors(ofps_hip_ctx* ctx);
+int ofps_hip_sad_refine_pred(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
+                             const int32_t* parent_best /* 3 * nbx_parent * nby_parent */, int nbx_parent, int nby_parent, int reach,
+                             int predictors, int32_t* out_best /* 3 * nblk */, float* out_entries /* 4 * nblk or NULL */);
+int ofps_hip_sad_refine_pred_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
+                                 const void* d_parent_best, int nbx_parent, int nby_parent, int reach, int predictors, void* d_out_best,
+                                 void* d_out_entries /* or NULL */);
+
 /* ---- N2: dense per-pixel flow, pyramidal Lucas-Kanade ("hip_lk" Decoder) ----
  * The reference's only per-pixel flow is OpenCV's Farneback inside cv-decoder (cv-decoder/src/lib.rs:188-199); this
  * is a build-defined algorithm (oracle/ofps_oracle.c:orc_lk_flow) with cv-decoder's conventions: prev(x,y) ~

@@ -205,6 +205,7 @@ struct ofps_hip_ctx {
         int sad_gate = 0;                // OFPS_HIP_SAD_GATE / ofps_hip_set_sad_gate: 0 one record per lattice block, N >= 1 only blocks with at least N contrast-mask pixels of the current frame (sad_gate.hip)
         int sad_consistency = 0;         // OFPS_HIP_SAD_CONSISTENCY / ofps_hip_set_sad_consistency: 0 off, N in [1, 129] only blocks whose forward-backward residual is below N (sad_consistency.hip)
         int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
+        int sad_predictors = 0;          // OFPS_HIP_SAD_PREDICTORS / ofps_hip_set_sad_predictors: 0 a refined block's one predictor is its parent's winner, 1 the parent's, its four lattice neighbours' and zero (sad_hier.hip, N1p); no effect at levels 1
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -295,13 +296,14 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
 int sad_search_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
                       int W, int H, int stride, int block, int range, void* d_out_entries, void* d_out_best);
 // sad_hier.hip (include/ofps_hip.h N1h): the integer winners of a search over `levels` > 1 levels; never refines to quarter-pel and never
-// looks at the context's levels, so it cannot come back to itself through the top search.  d_out_best may be null
+// looks at the context's levels or predictor mode, so it cannot come back to itself through the top search.  d_out_best may be null
 constexpr int kSadHierRefine = 3;                           // the refinement's radius: 49 candidates in a 64-lane wave
+constexpr int kSadHierPredictors = 6;                       // N1p: parent, four lattice neighbours, zero
 constexpr int kSadHierMaxReach = 127;                       // 8 * reach + 6 <= 1023: the quarter-pel key's 10-bit fields
 int sad_hier_reach(int range, int levels);                  // R_0, or -1
 int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
 int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                          int W, int H, int stride, int block, int range, int levels, void* d_out_entries, void* d_out_best);
+                          int W, int H, int stride, int block, int range, int levels, int predictors, void* d_out_entries, void* d_out_best);
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);

@@ -1184,7 +1184,7 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     int rc = sad_check_args(ctx, prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, range);
     if (rc != OFPS_HIP_OK) return rc;
     // search levels (sad_hier.hip): the integer search below becomes top search + refinements; everything around it stays
-    const int levels = ctx->opt.sad_levels;
+    const int levels = ctx->opt.sad_levels, predictors = ctx->opt.sad_predictors;     // read once: every level of this search runs in one mode
     if (levels > 1 && (rc = ofps::sad_hier_check(ctx, W, H, block, range, levels)) != OFPS_HIP_OK) return rc;
     SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
     if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
@@ -1201,7 +1201,7 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     // with levels > 1 the level-0 winners land where the plain search's would (d_int_best included), and the quarter-pel key takes the reach
     if (levels > 1)
         rc = ofps::sad_hier_pairs_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block, range, levels,
-                                         d_out_entries, p.out_best);
+                                         predictors, d_out_entries, p.out_best);
     else rc = sad_launch(ctx, p, pairs, block, range);
     if (rc != OFPS_HIP_OK) return rc;
     if (qpel)

@@ -198,10 +198,189 @@ __global__ __launch_bounds__(64 * WAVES) void sad_hier_refine_kernel(const Refin
     }
 }
 
+// N1p: the refinement with neighbour and zero predictors.  The phases of sad_hier_refine_kernel, with up to kSadHierPredictors windows:
+//   0. the triples of the parent, its four lattice neighbours (those that exist) and zero -> doubled, each clamped like the one predictor
+//      above; a predictor equal to an earlier one is dropped (all wave-uniform, so is every branch on it).  Packed path: the windows of all
+//      distinct predictors go to LDS slots of their own -- every load is issued before the first value is stored -- and the current block is
+//      staged once.  Generic path (a window reaches 9 KB): one slot, predictor after predictor;
+//   1. lane = candidate of each distinct predictor in turn; the lane keeps the minimum of its keys;
+//   2. one butterfly over the wave.  The key is a total order on d, so dropping duplicates cannot change the winner.
+// The two properties of the kernel above hold per window: positions outside the frame belong to invalid candidates only and their loads are
+// clamped to the frame; the two pad bytes per row are written before the packed reads touch them.
+constexpr int kPred = ofps::kSadHierPredictors;
+__host__ __device__ constexpr int hp_wave_bytes(int B, bool packed) {
+    return packed ? (kPred * h_off_cur(B) + ((B * B + 3) & ~3) + 15) & ~15 : h_wave_bytes(B);
+}
+
+template <int BT, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void sad_hier_refine_pred_kernel(const RefineParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t h_lds[];
+    constexpr int E = ofps::kSadHierRefine, N = 2 * E + 1;
+    static_assert(N * N <= 64 && E == 3 && kPred == 6, "lane = candidate; parent + four neighbours + zero");
+    const int B = BT ? BT : p.B;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const long long k = (long long)blockIdx.x * WAVES + wave;
+    if (k >= p.total) return;
+    const int per_pair = p.nbx * p.nby;
+    const int pair = (int)(k / per_pair);
+    const int rem = (int)(k - (long long)pair * per_pair);
+    const int by = rem / p.nbx, bx = rem - by * p.nbx;
+    const int x0 = bx * B, y0 = by * B;
+    const uint8_t* __restrict__ prev = p.f.prev_base + (size_t)pair * p.f.prev_pitch;
+    const uint8_t* __restrict__ cur = p.f.cur_base + (size_t)pair * p.f.cur_pitch;
+    const int W = p.f.W, H = p.f.H, stride = p.f.stride;
+
+    // ---- 0. predictors.  A neighbour outside the parent lattice reads the parent's own triple and is dropped
+    const int pbx = min(bx >> 1, p.pnbx - 1), pby = min(by >> 1, p.pnby - 1);
+    const int* __restrict__ pb = p.parent_best + (size_t)pair * p.pnby * p.pnbx * 3;
+    const int ox[kPred - 1] = {0, -1, 1, 0, 0}, oy[kPred - 1] = {0, 0, 0, -1, 1};
+    int rx[kPred - 1], ry[kPred - 1];
+    bool use[kPred];
+#pragma unroll
+    for (int w = 0; w < kPred - 1; ++w) {
+        const int nx = pbx + ox[w], ny = pby + oy[w];
+        use[w] = nx >= 0 && nx < p.pnbx && ny >= 0 && ny < p.pnby;
+        const size_t pk = use[w] ? (size_t)ny * p.pnbx + nx : (size_t)pby * p.pnbx + pbx;
+        rx[w] = pb[3 * pk + 0];
+        ry[w] = pb[3 * pk + 1];
+    }
+    int px[kPred], py[kPred];
+#pragma unroll
+    for (int w = 0; w < kPred; ++w) {
+        // (the doubling cannot overflow for any triple whose clamp below matters: saturate first)
+        const int qx = w < kPred - 1 ? clampi(__builtin_amdgcn_readfirstlane(rx[w]), -(1 << 20), 1 << 20) : 0;
+        const int qy = w < kPred - 1 ? clampi(__builtin_amdgcn_readfirstlane(ry[w]), -(1 << 20), 1 << 20) : 0;
+        px[w] = clampi(2 * qx, -x0, W - B - x0);
+        py[w] = clampi(2 * qy, -y0, H - B - y0);
+        if (w == kPred - 1) use[w] = true;
+#pragma unroll
+        for (int j = 0; j < w; ++j) use[w] = use[w] && !(use[j] && px[j] == px[w] && py[j] == py[w]);
+    }
+
+    const int IW = B + 2 * E, WS = h_ws(B);
+    uint8_t* base = h_lds + (size_t)wave * hp_wave_bytes(B, BT != 0);
+    uint8_t* cl = base + (BT ? kPred : 1) * h_off_cur(B);
+    if constexpr (BT != 0) {
+        constexpr int BW = BT / 4, IWT = BT + 2 * E, PER = (IWT * IWT + 63) / 64;
+        uint8_t v[kPred][PER];
+#pragma unroll
+        for (int w = 0; w < kPred; ++w)
+            if (use[w]) {
+#pragma unroll
+                for (int j = 0; j < PER; ++j) {
+                    const int i = min(lane + 64 * j, IWT * IWT - 1);
+                    const int wy = i / IWT, wx = i - wy * IWT;
+                    const int gx = clampi(x0 + px[w] - E + wx, 0, W - 1), gy = clampi(y0 + py[w] - E + wy, 0, H - 1);
+                    v[w][j] = prev[(size_t)gy * stride + gx];
+                }
+            }
+        for (int i = lane; i < BT * BW; i += 64) {
+            const int y = i / BW, q = i - y * BW;
+            reinterpret_cast<uint32_t*>(cl)[i] = *reinterpret_cast<const uint32_t*>(cur + (size_t)(y0 + y) * stride + x0 + 4 * q);
+        }
+#pragma unroll
+        for (int w = 0; w < kPred; ++w)
+            if (use[w]) {
+                uint8_t* win = base + w * h_off_cur(BT);
+#pragma unroll
+                for (int j = 0; j < PER; ++j) {
+                    const int i = min(lane + 64 * j, IWT * IWT - 1);     // (the last step's spare lanes write the last byte again)
+                    const int wy = i / IWT, wx = i - wy * IWT;
+                    win[wy * WS + wx] = v[w][j];
+                }
+                // the packed reads run two bytes past the window's B + 6 columns: written before they are read, as above
+                for (int i = lane; i < IWT; i += 64) { win[i * WS + IWT] = 0; win[i * WS + IWT + 1] = 0; }
+            }
+        wave_sync();
+    } else {
+        for (int i = lane; i < B * B; i += 64) {
+            const int y = i / B, x = i - y * B;
+            cl[i] = cur[(size_t)(y0 + y) * stride + x0 + x];
+        }
+    }
+
+    // ---- 1. lane = candidate, predictor after predictor
+    const int cand = lane < N * N ? lane : N * N - 1;
+    const int ey = cand / N - E, ex = cand - (cand / N) * N - E;
+    unsigned long long best = ~0ull;
+#pragma unroll
+    for (int w = 0; w < kPred; ++w) {
+        if (!use[w]) continue;
+        uint32_t sad = 0;
+        if constexpr (BT != 0) {
+            constexpr int BW = BT / 4, WSD = h_ws(BT) / 4;
+            const uint32_t* wp = reinterpret_cast<const uint32_t*>(base + w * h_off_cur(BT)) + (ey + E) * WSD + ((ex + E) >> 2);
+            const uint32_t* cp = reinterpret_cast<const uint32_t*>(cl);
+            const uint32_t ph = (uint32_t)(ex + E) & 3u;
+#pragma unroll
+            for (int y = 0; y < BT; ++y) {
+                uint32_t a[BW + 1];
+#pragma unroll
+                for (int g = 0; g <= BW; ++g) a[g] = wp[y * WSD + g];
+#pragma unroll
+                for (int g = 0; g < BW; ++g) sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(a[g + 1], a[g], ph), cp[y * BW + g], sad);
+            }
+        } else {
+            wave_sync();                                     // the window before this one has been read by every lane
+            for (int i = lane; i < IW * IW; i += 64) {
+                const int wy = i / IW, wx = i - wy * IW;
+                const int gx = clampi(x0 + px[w] - E + wx, 0, W - 1), gy = clampi(y0 + py[w] - E + wy, 0, H - 1);
+                base[wy * WS + wx] = prev[(size_t)gy * stride + gx];
+            }
+            wave_sync();
+            const uint8_t* wp = base + (ey + E) * WS + (ex + E);
+            for (int y = 0; y < B; ++y)
+                for (int x = 0; x < B; ++x) {
+                    const int d = (int)cl[y * B + x] - (int)wp[y * WS + x];
+                    sad += (uint32_t)(d < 0 ? -d : d);
+                }
+        }
+        // the key of sad_hier_refine_kernel
+        const int dx = px[w] + ex, dy = py[w] + ey;
+        const bool valid = lane < N * N && x0 + dx >= 0 && x0 + dx <= W - B && y0 + dy >= 0 && y0 + dy <= H - B;
+        if (valid) {
+            const unsigned long long key = ((unsigned long long)sad << 40) | ((unsigned long long)((uint32_t)(dx * dx + dy * dy) & 0xFFFFFu) << 20) |
+                                           ((unsigned long long)((uint32_t)(dy + 512) & 1023u) << 10) | (unsigned long long)((uint32_t)(dx + 512) & 1023u);
+            best = key < best ? key : best;
+        }
+    }
+
+    // ---- 2. the minimum over the wave
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = shfl_xor_u64(best, m);
+        best = o < best ? o : best;
+    }
+    if (lane == 0) {
+        const int bsad = (int)(best >> 40);
+        const int bdy = (int)((best >> 10) & 1023) - 512, bdx = (int)(best & 1023) - 512;
+        if (p.out_best) {
+            p.out_best[3 * k + 0] = bdx;
+            p.out_best[3 * k + 1] = bdy;
+            p.out_best[3 * k + 2] = bsad;
+        }
+        if (p.out_entries) {
+            float4 e;
+            e.x = (float)(x0 + B / 2 + bdx) * p.nx;
+            e.y = (float)(y0 + B / 2 + bdy) * p.ny;
+            e.z = ((float)bdx / 1.0f) * (-p.nx);
+            e.w = ((float)bdy / 1.0f) * (-p.ny);
+            p.out_entries[k] = e;
+        }
+    }
+}
+
 template <int BT, int WAVES>
 void launch_refine(const RefineParams& p, hipStream_t s) {
     const unsigned nwg = (unsigned)((p.total + WAVES - 1) / WAVES);
     hipLaunchKernelGGL((sad_hier_refine_kernel<BT, WAVES>), dim3(nwg), dim3(64 * WAVES), (size_t)WAVES * h_wave_bytes(p.B), s, p);
+}
+
+template <int BT, int WAVES>
+void launch_refine_pred(const RefineParams& p, hipStream_t s) {
+    const unsigned nwg = (unsigned)((p.total + WAVES - 1) / WAVES);
+    hipLaunchKernelGGL((sad_hier_refine_pred_kernel<BT, WAVES>), dim3(nwg), dim3(64 * WAVES), (size_t)WAVES * hp_wave_bytes(p.B, BT != 0), s, p);
 }
 
 // `frames` frames of W x H at src + k*src_pitch -> (W >> 1) x (H >> 1) at dst + k*dst_pitch
@@ -221,8 +400,9 @@ int down2_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W,
 }
 
 // (the level's reach R_l biases the last two fields of the definition's key and so never changes its order: the kernel does not need it)
-int refine_device(ofps_hip_ctx* ctx, const HierLevel& f, int pairs, int block, const int* d_parent, int pnbx, int pnby, int* d_out_best,
-                  float4* d_out_entries) {
+// predictors: OFPS_HIP_SAD_PRED_PARENT the kernel above alone, OFPS_HIP_SAD_PRED_NEIGHBOURS sad_hier_refine_pred_kernel (N1p)
+int refine_device(ofps_hip_ctx* ctx, const HierLevel& f, int pairs, int block, const int* d_parent, int pnbx, int pnby, int predictors,
+                  int* d_out_best, float4* d_out_entries) {
     RefineParams p{};
     p.f = f;
     p.nbx = f.W / block; p.nby = f.H / block; p.B = block;
@@ -233,7 +413,11 @@ int refine_device(ofps_hip_ctx* ctx, const HierLevel& f, int pairs, int block, c
     if (p.total <= 0) return OFPS_HIP_OK;
     OFPS_REQUIRE(ctx, p.total < (1ll << 31), "sad_refine: grid too large");
     // the packed forms read the current block by dwords: rows 4-byte aligned (every caller requires it)
-    if (block == 16) launch_refine<16, 4>(p, ctx->stream);
+    if (predictors == OFPS_HIP_SAD_PRED_NEIGHBOURS) {
+        if (block == 16) launch_refine_pred<16, 4>(p, ctx->stream);
+        else if (block == 8) launch_refine_pred<8, 4>(p, ctx->stream);
+        else launch_refine_pred<0, 1>(p, ctx->stream);
+    } else if (block == 16) launch_refine<16, 4>(p, ctx->stream);
     else if (block == 8) launch_refine<8, 4>(p, ctx->stream);
     else launch_refine<0, 1>(p, ctx->stream);
     OFPS_HIP_TRY(ctx, hipGetLastError());
@@ -241,7 +425,9 @@ int refine_device(ofps_hip_ctx* ctx, const HierLevel& f, int pairs, int block, c
 }
 
 int refine_check(ofps_hip_ctx* ctx, const void* prev, const void* cur, const void* parent, const void* out_best, int W, int H, int stride, int block,
-                 int pnbx, int pnby, int reach) {
+                 int pnbx, int pnby, int reach, int predictors) {
+    OFPS_REQUIRE(ctx, predictors == OFPS_HIP_SAD_PRED_PARENT || predictors == OFPS_HIP_SAD_PRED_NEIGHBOURS, "sad_refine: predictors=%d is not 0|1",
+                 predictors);
     OFPS_REQUIRE(ctx, prev && cur && parent && out_best, "sad_refine: null pointer");
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_refine: bad geometry W=%d H=%d stride=%d", W, H, stride);
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "sad_refine: block=%d outside [1,64]", block);
@@ -275,7 +461,7 @@ int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int le
 // above 0 live in S_HIER_*: written and read on ctx->stream only, by this search alone -- the next search (the consistency check's backward
 // one, the next ticket's) is ordered behind it by that stream.
 int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                          int W, int H, int stride, int block, int range, int levels, void* d_out_entries, void* d_out_best) {
+                          int W, int H, int stride, int block, int range, int levels, int predictors, void* d_out_entries, void* d_out_best) {
     int rc = sad_hier_check(ctx, W, H, block, range, levels);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, levels > 1 && pairs >= 1 && d_out_entries, "sad_flow: levels=%d pairs=%d is no search over levels", levels, pairs);
@@ -317,7 +503,7 @@ int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t pr
     if (rc != OFPS_HIP_OK) return rc;
     for (int l = top - 1; l >= 0; --l) {
         int* out = l == 0 ? static_cast<int*>(d_out_best) : reinterpret_cast<int*>(bestbuf + best_off[l]);
-        rc = refine_device(ctx, lv[l], pairs, block, parent, lv[l + 1].W / block, lv[l + 1].H / block, out,
+        rc = refine_device(ctx, lv[l], pairs, block, parent, lv[l + 1].W / block, lv[l + 1].H / block, predictors, out,
                            l == 0 ? static_cast<float4*>(d_out_entries) : nullptr);
         if (rc != OFPS_HIP_OK) return rc;
         parent = out;
@@ -337,6 +523,15 @@ int ofps_hip_set_sad_levels(ofps_hip_ctx* ctx, int levels) {
 }
 
 int ofps_hip_get_sad_levels(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.sad_levels : OFPS_HIP_EINVAL; }
+
+int ofps_hip_set_sad_predictors(ofps_hip_ctx* ctx, int mode) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, mode == OFPS_HIP_SAD_PRED_PARENT || mode == OFPS_HIP_SAD_PRED_NEIGHBOURS, "set_sad_predictors: %d is not 0 or 1", mode);
+    ctx->opt.sad_predictors = mode;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_sad_predictors(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.sad_predictors : OFPS_HIP_EINVAL; }
 
 int ofps_hip_sad_reach(int range, int levels) {
     const int r = ofps::sad_hier_reach(range, levels);
@@ -370,23 +565,31 @@ int ofps_hip_sad_down2(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int 
     return OFPS_HIP_OK;
 }
 
-int ofps_hip_sad_refine_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
-                            const void* d_parent_best, int nbx_parent, int nby_parent, int reach, void* d_out_best, void* d_out_entries) {
+int ofps_hip_sad_refine_pred_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
+                                 const void* d_parent_best, int nbx_parent, int nby_parent, int reach, int predictors, void* d_out_best,
+                                 void* d_out_entries) {
     if (!ctx) return OFPS_HIP_EINVAL;
-    const int rc = refine_check(ctx, d_prev, d_cur, d_parent_best, d_out_best, W, H, stride, block, nbx_parent, nby_parent, reach);
+    const int rc = refine_check(ctx, d_prev, d_cur, d_parent_best, d_out_best, W, H, stride, block, nbx_parent, nby_parent, reach, predictors);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, stride % 4 == 0 && ((uintptr_t)d_prev % 4) == 0 && ((uintptr_t)d_cur % 4) == 0,
                  "sad_refine: rows must be 4-byte aligned (stride=%d)", stride);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const HierLevel f{static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride};
-    return refine_device(ctx, f, 1, block, static_cast<const int*>(d_parent_best), nbx_parent, nby_parent, static_cast<int*>(d_out_best),
+    return refine_device(ctx, f, 1, block, static_cast<const int*>(d_parent_best), nbx_parent, nby_parent, predictors, static_cast<int*>(d_out_best),
                          static_cast<float4*>(d_out_entries));
 }
 
-int ofps_hip_sad_refine(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
-                        const int32_t* parent_best, int nbx_parent, int nby_parent, int reach, int32_t* out_best, float* out_entries) {
+int ofps_hip_sad_refine_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block,
+                            const void* d_parent_best, int nbx_parent, int nby_parent, int reach, void* d_out_best, void* d_out_entries) {
+    return ofps_hip_sad_refine_pred_dev(ctx, d_prev, d_cur, W, H, stride, block, d_parent_best, nbx_parent, nby_parent, reach,
+                                        OFPS_HIP_SAD_PRED_PARENT, d_out_best, d_out_entries);
+}
+
+int ofps_hip_sad_refine_pred(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
+                             const int32_t* parent_best, int nbx_parent, int nby_parent, int reach, int predictors, int32_t* out_best,
+                             float* out_entries) {
     if (!ctx) return OFPS_HIP_EINVAL;
-    int rc = refine_check(ctx, prev, cur, parent_best, out_best, W, H, stride, block, nbx_parent, nby_parent, reach);
+    int rc = refine_check(ctx, prev, cur, parent_best, out_best, W, H, stride, block, nbx_parent, nby_parent, reach, predictors);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // repack to a 64-byte-multiple device stride so any host stride is accepted (as ofps_hip_sad_flow does)
@@ -401,13 +604,19 @@ int ofps_hip_sad_refine(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* c
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames, dstride, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames + pitch, dstride, cur, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_par, parent_best, npar * 3 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    rc = ofps_hip_sad_refine_dev(ctx, d_frames, d_frames + pitch, W, H, dstride, block, d_par, nbx_parent, nby_parent, reach, d_best,
-                                 out_entries ? d_ent : nullptr);
+    rc = ofps_hip_sad_refine_pred_dev(ctx, d_frames, d_frames + pitch, W, H, dstride, block, d_par, nbx_parent, nby_parent, reach, predictors, d_best,
+                                      out_entries ? d_ent : nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_best, d_best, nblk * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (out_entries) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_entries, d_ent, nblk * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return OFPS_HIP_OK;
+}
+
+int ofps_hip_sad_refine(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
+                        const int32_t* parent_best, int nbx_parent, int nby_parent, int reach, int32_t* out_best, float* out_entries) {
+    return ofps_hip_sad_refine_pred(ctx, prev, cur, W, H, stride, block, parent_best, nbx_parent, nby_parent, reach, OFPS_HIP_SAD_PRED_PARENT,
+                                    out_best, out_entries);
 }
 
 }  // extern "C"

@@ -238,6 +238,37 @@ class HipContext:
         self._check(self._lib.ofps_hip_sad_refine_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, C.c_void_p(d_parent_best),
                                                       nbx_parent, nby_parent, reach, C.c_void_p(d_out_best), C.c_void_p(d_out_entries or 0)))
 
+    SAD_PRED_PARENT, SAD_PRED_NEIGHBOURS = 0, 1
+
+    def set_sad_predictors(self, mode: int):
+        """The predictors of a refined block of the search levels (include/ofps_hip.h N1p): 0 = its parent's winner alone (default);
+        1 = the parent's, its four lattice neighbours' and zero, each repaired in its own +-3 window.  No effect at levels 1."""
+        self._check(self._lib.ofps_hip_set_sad_predictors(self._h, mode))
+
+    def get_sad_predictors(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_predictors(self._h))
+
+    def sad_refine_pred(self, prev: np.ndarray, cur: np.ndarray, block: int, parent_best: np.ndarray, reach: int, predictors: int, want_entries=False):
+        """sad_refine with the predictor mode as an argument (0 is sad_refine)."""
+        prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
+        par = np.ascontiguousarray(parent_best, np.int32)
+        assert prev.shape == cur.shape and prev.ndim == 2 and par.ndim == 3 and par.shape[2] == 3
+        H, W = prev.shape
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        best = np.zeros((max(nb, 1), 3), np.int32)
+        ent = np.zeros((max(nb, 1), 4), np.float32)
+        u8 = C.POINTER(C.c_uint8); i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_sad_refine_pred(self._h, prev.ctypes.data_as(u8), cur.ctypes.data_as(u8), W, H, W, block,
+                                                       par.ctypes.data_as(i32), par.shape[1], par.shape[0], reach, predictors,
+                                                       best.ctypes.data_as(i32), _fp(ent) if want_entries else None))
+        return (best[:nb], ent[:nb]) if want_entries else best[:nb]
+
+    def sad_refine_pred_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, d_parent_best: int, nbx_parent: int,
+                            nby_parent: int, reach: int, predictors: int, d_out_best: int, d_out_entries: int | None = None):
+        self._check(self._lib.ofps_hip_sad_refine_pred_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block,
+                                                           C.c_void_p(d_parent_best), nbx_parent, nby_parent, reach, predictors,
+                                                           C.c_void_p(d_out_best), C.c_void_p(d_out_entries or 0)))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))

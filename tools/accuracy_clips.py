@@ -16,6 +16,7 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               with --sad-levels N also hip_sad_h: hip_sad with its "Search levels" property at N (include/ofps_hip.h N1h; reach 2 * 16 + 3 =
               35 px at N = 2, 73 px at N = 3); --fast-clips adds 1080p pans of 1.5 and 3 degrees per frame (24 and 49 px at the centre:
               beyond the plain search's +-16); --sad-only leaves the dense decoders' columns out
+              with --sad-levels N --sad-predictors 1 also hip_sad_hp: the same with "Neighbour predictors" on (include/ofps_hip.h N1p)
   estimators  hip_almeida LSQ  |  hip_almeida RANSAC (the reference's default: 200 hypotheses x 1000 samples, 0.05 degree inliers)
 Per clip and combination: mean and max of angle_to(planted q_k, estimated r_k) over the frames, that mean relative to the clip's mean
 rotation per frame (the reference's own test bound is 10 %: almeida-estimator/src/lib.rs:347-348), and the pose drift after the
@@ -131,7 +132,7 @@ def flat_third(frames, seed=5):
 
 
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
-        fast_clips=False, sad_only=False):
+        fast_clips=False, sad_only=False, sad_predictors=0):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -156,6 +157,15 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         if quarter_pel:
             props_qh = {"Quarter pel": True, "Search levels": sad_levels}
             combos[2:2] = [("hip_sad_qh", HipSadDecoder, False, props_qh), ("hip_sad_qh", HipSadDecoder, True, props_qh)]
+        if sad_predictors:      # ... and beside them the same columns with "Neighbour predictors" on (include/ofps_hip.h N1p)
+            props_hp = {"Search levels": sad_levels, "Neighbour predictors": True}
+            combos[2:2] = [("hip_sad_hp", HipSadDecoder, False, props_hp), ("hip_sad_hp", HipSadDecoder, True, props_hp)]
+            if sad_consistency:
+                props_hpc = dict(props_hp, **{"Consistency check": sad_consistency})
+                combos[2:2] = [("hip_sad_hpc", HipSadDecoder, False, props_hpc), ("hip_sad_hpc", HipSadDecoder, True, props_hpc)]
+            if quarter_pel:
+                props_qhp = dict(props_hp, **{"Quarter pel": True})
+                combos[2:2] = [("hip_sad_qhp", HipSadDecoder, False, props_qhp), ("hip_sad_qhp", HipSadDecoder, True, props_qhp)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
@@ -211,7 +221,7 @@ def table(res):
         cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
     if any("hip_sad_g+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
-    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh"):
+    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp"):
         if any(tag + "+lsq" in r for r in res.values()):
             cols[2:2] = [tag + "+lsq", tag + "+ransac"]
     if not any("hip_lk+lsq" in r for r in res.values()):       # --sad-only: no dense decoder ran
@@ -262,12 +272,15 @@ def main():
                     help="add the hip_sad_c columns (hip_sad with \"Consistency check\" = N; with --quarter-pel also hip_sad_qc: on top of \"Quarter pel\")")
     ap.add_argument("--sad-levels", type=int, default=0, metavar="N",
                     help="add the hip_sad_h columns (hip_sad with \"Search levels\" = N; with --quarter-pel also hip_sad_qh: on top of \"Quarter pel\")")
+    ap.add_argument("--sad-predictors", type=int, default=0, choices=[0, 1],
+                    help="with --sad-levels N: 1 adds the hip_sad_hp columns beside hip_sad_h (\"Search levels\" = N with \"Neighbour predictors\" on; with "
+                         "--sad-consistency also hip_sad_hpc, with --quarter-pel also hip_sad_qhp); 0 = hip_sad_h alone")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
     ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
-              sad_only=args.sad_only)
+              sad_only=args.sad_only, sad_predictors=args.sad_predictors)
     txt = table(res)
     print(txt)
     if args.out:
