@@ -297,6 +297,34 @@ int ofps_hip_sad_refine_pred_dev(ofps_hip_ctx* ctx, const void* d_prev, const vo
                                  const void* d_parent_best, int nbx_parent, int nby_parent, int reach, int predictors, void* d_out_best,
                                  void* d_out_entries /* or NULL */);
 
+/* ---- N1m: hip_sad's mean removal -- a search that does not see a brightness change between the two frames (csrc/sad_prefilter.hip) ----
+ * N1 compares raw luma: an exposure step, a flickering lamp or a passing cloud moves every block's SAD minimum away from the true vector, and
+ * no later filter repairs it.  With sad_prefilter = r in [1, 16] every search of the context runs on the filtered pair F(prev), F(cur), the
+ * prefilter of every stereo and block matcher.  Build-defined, like N1q / N1g / N1c / N1h; all-integer, so bit-exact on every device.  For a
+ * frame v of W x H:
+ *   window k = 2r + 1, n = k * k;
+ *   S(x, y) = sum of v(clamp(x + i, 0, W - 1), clamp(y + j, 0, H - 1)) over i, j in [-r, r]: a replicated border; a frame smaller than the
+ *     window is valid;
+ *   m = (S + (n >> 1)) / n, integer division;
+ *   F(x, y) = clamp(v(x, y) - m + 128, 0, 255): what ofps_hip_sad_prefilter returns.
+ * Every search means: the plain and the PRUNED search; the search levels (N1h: the pyramid is built from F, not from the raw frames) and
+ * their neighbour predictors (N1p); the quarter-pel refinement (N1q), which interpolates F; both directions of the consistency check (N1c).
+ * The SAD field of the out_best triples is then the SAD of the FILTERED blocks (quarter-pel: of the interpolated filtered block).  The
+ * contrast gate (N1g) keeps counting mask pixels of the UNFILTERED current frame.  Positions, the record convention, the reach and every
+ * existing OFPS_HIP_EINVAL condition are unchanged.  It follows: ofps_hip_sad_flow, ofps_hip_sad_flow_dev (both ref modes; consecutive pairs
+ * of one sequence are filtered once over n_frames frames, a shared key frame once), ofps_hip_sad_flow_gated_dev / _checked_dev,
+ * ofps_hip_push_frame[_async], ofps_hip_push_frames_async and the ofps_hip_multi_* workers (through the environment option).  No filtered
+ * frame is kept across searches: the two searches of the consistency check each filter their own pair.
+ * 0 = off, the default: every entry point then uses the launches, streams, scratch and bytes of a build without this section.  A radius
+ * outside [0, 16] is OFPS_HIP_EINVAL at the setter and at the option OFPS_HIP_SAD_PREFILTER (environment / ofps_hip_set_option), with the
+ * value in the message.  The dense decoders (hip_lk, hip_flow) are not touched.
+ * ofps_hip_sad_prefilter[_dev]: the filter alone on one frame, radius in [1, 16], W, H >= 1, stride >= W, dst_stride >= W; bytes of a dst row
+ *   behind W are not written.  The _dev form enqueues only and takes any alignment (4-byte aligned rows are the fast path). */
+int ofps_hip_set_sad_prefilter(ofps_hip_ctx* ctx, int radius);   /* 0 = off (default) */
+int ofps_hip_get_sad_prefilter(ofps_hip_ctx* ctx);
+int ofps_hip_sad_prefilter(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int stride, int radius, uint8_t* dst /* H rows of dst_stride bytes */, int dst_stride);
+int ofps_hip_sad_prefilter_dev(ofps_hip_ctx* ctx, const void* d_src, int W, int H, int stride, int radius, void* d_dst, int dst_stride);
+
 /* ---- N2: dense per-pixel flow, pyramidal Lucas-Kanade ("hip_lk" Decoder) ----
  * The reference's only per-pixel flow is OpenCV's Farneback inside cv-decoder (cv-decoder/src/lib.rs:188-199); this
  * is a build-defined algorithm (oracle/ofps_oracle.c:orc_lk_flow) with cv-decoder's conventions: prev(x,y) ~

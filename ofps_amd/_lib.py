@@ -66,6 +66,10 @@ PROTOTYPES = {
     "ofps_hip_get_sad_predictors": (C.c_int, [_ctx]),
     "ofps_hip_sad_refine_pred": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "ofps_hip_sad_refine_pred_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ofps_hip_set_sad_prefilter": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_prefilter": (C.c_int, [_ctx]),
+    "ofps_hip_sad_prefilter": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "ofps_hip_sad_prefilter_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
     "ofps_hip_lk_flow": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     "ofps_hip_farneback_flow": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _f32p, _f32p]),
     "ofps_hip_farneback_flow_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp]),

@@ -206,6 +206,7 @@ struct ofps_hip_ctx {
         int sad_consistency = 0;         // OFPS_HIP_SAD_CONSISTENCY / ofps_hip_set_sad_consistency: 0 off, N in [1, 129] only blocks whose forward-backward residual is below N (sad_consistency.hip)
         int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
         int sad_predictors = 0;          // OFPS_HIP_SAD_PREDICTORS / ofps_hip_set_sad_predictors: 0 a refined block's one predictor is its parent's winner, 1 the parent's, its four lattice neighbours' and zero (sad_hier.hip, N1p); no effect at levels 1
+        int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -230,7 +231,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 52;
+    static constexpr int kNumScratch = 53;
     Scratch scratch[kNumScratch];
 };
 
@@ -265,9 +266,10 @@ enum ScratchSlot {
     S_CONS_BWD_ENT,         // ... and its records, which nobody reads (the search kernels always write them).  All three: compute stream only
     S_HIER_PYR,             // hip_sad's search levels (sad_hier.hip): the halved frames of one search's two frame sets, every level above 0
     S_HIER_BEST,            // ... the winners of every level above 0
-    S_HIER_ENT              // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
+    S_HIER_ENT,             // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
+    S_SAD_PREF              // hip_sad's mean removal (sad_prefilter.hip): the filtered frames of one search's two frame sets.  Compute stream only, written anew by every search
 };
-static_assert(S_HIER_ENT < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_SAD_PREF < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -304,6 +306,13 @@ int sad_hier_reach(int range, int levels);                  // R_0, or -1
 int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
 int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
                           int W, int H, int stride, int block, int range, int levels, int predictors, void* d_out_entries, void* d_out_best);
+// sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
+constexpr int kSadPrefilterMax = 16;
+int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
+                         int dst_stride, long long frames, int radius);
+// a search's two frame sets -> S_SAD_PREF; bases, pitches and stride are replaced by the filtered frames'
+int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const uint8_t** prev_base, size_t* prev_pitch, const uint8_t** cur_base,
+                               size_t* cur_pitch, int pairs, int W, int H, int* stride);
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);

@@ -1185,6 +1185,7 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     if (rc != OFPS_HIP_OK) return rc;
     // search levels (sad_hier.hip): the integer search below becomes top search + refinements; everything around it stays
     const int levels = ctx->opt.sad_levels, predictors = ctx->opt.sad_predictors;     // read once: every level of this search runs in one mode
+    const int prefilter = ctx->opt.sad_prefilter;                                     // ... and on one kind of frames
     if (levels > 1 && (rc = ofps::sad_hier_check(ctx, W, H, block, range, levels)) != OFPS_HIP_OK) return rc;
     SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
     if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
@@ -1197,6 +1198,12 @@ int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pi
     else if (qpel && !p.out_best) {
         p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
         if (!p.out_best) return OFPS_HIP_ENOMEM;
+    }
+    // mean removal (sad_prefilter.hip): everything below -- levels, plain launch, quarter-pel -- reads the filtered frames in S_SAD_PREF
+    if (prefilter > 0) {
+        rc = ofps::sad_prefilter_pairs_device(ctx, prefilter, &prev_base, &prev_pitch, &cur_base, &cur_pitch, pairs, W, H, &stride);
+        if (rc != OFPS_HIP_OK) return rc;
+        p.prev_base = prev_base; p.cur_base = cur_base; p.prev_pitch = prev_pitch; p.cur_pitch = cur_pitch; p.stride = stride;
     }
     // with levels > 1 the level-0 winners land where the plain search's would (d_int_best included), and the quarter-pel key takes the reach
     if (levels > 1)

@@ -77,6 +77,9 @@ class HipSadDecoder(Properties):
               ("Contrast gate", "usize", "contrast_gate", 0, 256),
               # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
               # include/ofps_hip.h N1c).  Costs a second search per frame
+              # build-defined: 0 = the search compares the frames as they are; r = both frames minus their box mean of radius r, for streams
+              # whose brightness changes between frames (include/ofps_hip.h N1m)
+              ("Mean removal", "usize", "prefilter", 0, 16),
               # build-defined: with "Search levels" above 1, a refined block tries its parent's vector, the parent's four lattice neighbours'
               # and zero instead of the parent's alone (include/ofps_hip.h N1p); no effect at "Search levels" 1
               ("Neighbour predictors", "bool", "neighbour_predictors", None, None),
@@ -95,6 +98,7 @@ class HipSadDecoder(Properties):
         self.consistency = 0
         self.levels = 1
         self.neighbour_predictors = False
+        self.prefilter = 0
         self._prev: Optional[np.ndarray] = None
         self._cur: Optional[np.ndarray] = None
         self._fps = framerate
@@ -136,6 +140,7 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_consistency(self.consistency)
         self.ctx.set_sad_levels(self.levels)
         self.ctx.set_sad_predictors(1 if self.neighbour_predictors else 0)
+        self.ctx.set_sad_prefilter(self.prefilter)
         r = self.ctx.push_frame(self._cur, self.block, self.range, detector=False, estimator=False, want_entries=True)
         if not r["have_vectors"]:                          # first frame of the stream / geometry change
             return False

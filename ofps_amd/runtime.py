@@ -269,6 +269,32 @@ class HipContext:
                                                            C.c_void_p(d_parent_best), nbx_parent, nby_parent, reach, predictors,
                                                            C.c_void_p(d_out_best), C.c_void_p(d_out_entries or 0)))
 
+    def set_sad_prefilter(self, radius: int):
+        """hip_sad's mean removal (include/ofps_hip.h N1m): 0 = off (default); r in [1, 16] = every search of the context runs on
+        clamp(v - box mean of radius r + 128) of both frames, so a brightness change between them no longer moves the SAD minimum."""
+        self._check(self._lib.ofps_hip_set_sad_prefilter(self._h, radius))
+
+    def get_sad_prefilter(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_prefilter(self._h))
+
+    def sad_prefilter(self, img: np.ndarray, radius: int, stride: int | None = None) -> np.ndarray:
+        """The filter alone: [H, W] u8 -> [H, W] u8.  stride: None, or the row pitch in bytes of `img` (a view of a wider buffer)."""
+        if stride is None:
+            g = np.ascontiguousarray(img, np.uint8)
+            stride = g.shape[1]
+        else:
+            g = img
+            assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
+        H, W = g.shape
+        out = np.zeros((H, W), np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.ofps_hip_sad_prefilter(self._h, C.cast(C.c_void_p(g.ctypes.data), u8), W, H, stride, radius,
+                                                     C.cast(C.c_void_p(out.ctypes.data), u8), W))
+        return out
+
+    def sad_prefilter_dev(self, d_src: int, W: int, H: int, stride: int, radius: int, d_dst: int, dst_stride: int):
+        self._check(self._lib.ofps_hip_sad_prefilter_dev(self._h, C.c_void_p(d_src), W, H, stride, radius, C.c_void_p(d_dst), dst_stride))
+
     def sad_pruned_overflow_strips(self) -> int:
         n = C.c_uint32(0)
         self._check(self._lib.ofps_hip_sad_pruned_overflow_strips(self._h, C.byref(n)))

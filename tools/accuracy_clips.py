@@ -17,6 +17,11 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               35 px at N = 2, 73 px at N = 3); --fast-clips adds 1080p pans of 1.5 and 3 degrees per frame (24 and 49 px at the centre:
               beyond the plain search's +-16); --sad-only leaves the dense decoders' columns out
               with --sad-levels N --sad-predictors 1 also hip_sad_hp: the same with "Neighbour predictors" on (include/ofps_hip.h N1p)
+              with --sad-prefilter R [R ...] also hip_sad_m<R>: hip_sad with its "Mean removal" property at R (include/ofps_hip.h N1m)
+  lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
+              toggles by 20 grey levels every 4 frames (a quarter of the pairs straddle a step); flicker = +12 on odd frames, -12 on even
+              ones (every pair differs by 24); ramp = odd frames gain 30 x/(W-1) - 10 y/(H-1) - 8 (a gradient that comes and goes); all
+              rounded to nearest and clamped to 0..255
   estimators  hip_almeida LSQ  |  hip_almeida RANSAC (the reference's default: 200 hypotheses x 1000 samples, 0.05 degree inliers)
 Per clip and combination: mean and max of angle_to(planted q_k, estimated r_k) over the frames, that mean relative to the clip's mean
 rotation per frame (the reference's own test bound is 10 %: almeida-estimator/src/lib.rs:347-348), and the pose drift after the
@@ -131,8 +136,27 @@ def flat_third(frames, seed=5):
     return out
 
 
+def relight_clip(frames, lighting):
+    """the clip under --lighting's change of brightness -> uint8 [n, H, W]"""
+    if lighting == "none":
+        return frames
+    f = np.asarray(frames, np.uint8).astype(np.float32)
+    n, H, W = f.shape
+    k = np.arange(n)
+    if lighting == "step":
+        f += (20.0 * ((k // 4) % 2)).astype(np.float32)[:, None, None]
+    elif lighting == "flicker":
+        f += np.where(k % 2 == 1, 12.0, -12.0).astype(np.float32)[:, None, None]
+    elif lighting == "ramp":
+        ramp = 30.0 * np.arange(W, dtype=np.float32)[None, :] / (W - 1) - 10.0 * np.arange(H, dtype=np.float32)[:, None] / (H - 1) - 8.0
+        f[1::2] += ramp[None]
+    else:
+        raise ValueError(lighting)
+    return np.clip(np.floor(f + 0.5), 0, 255).astype(np.uint8)
+
+
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
-        fast_clips=False, sad_only=False, sad_predictors=0):
+        fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=()):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -166,6 +190,11 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
             if quarter_pel:
                 props_qhp = dict(props_hp, **{"Quarter pel": True})
                 combos[2:2] = [("hip_sad_qhp", HipSadDecoder, False, props_qhp), ("hip_sad_qhp", HipSadDecoder, True, props_qhp)]
+    for radius in sad_prefilter:    # hip_sad with its "Mean removal" property at R (include/ofps_hip.h N1m); with --sad-levels N also on top of "Search levels"
+        combos[2:2] = [(f"hip_sad_m{radius}", HipSadDecoder, False, {"Mean removal": radius}), (f"hip_sad_m{radius}", HipSadDecoder, True, {"Mean removal": radius})]
+        if sad_levels:
+            props_hm = {"Search levels": sad_levels, "Mean removal": radius}
+            combos[2:2] = [(f"hip_sad_hm{radius}", HipSadDecoder, False, props_hm), (f"hip_sad_hm{radius}", HipSadDecoder, True, props_hm)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
@@ -173,15 +202,21 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
     for name, geom in clip_table(quick, fast_clips).items():
         if only and name not in only:
             continue
-        clip_seed = 21 + sum(1 for c in clips if not c[3])         # the n-th clip that runs renders with seed 21 + n
-        clips.append((name, geom, clip_seed, False))
-        if sad_gate:
-            clips.append((name + "_flat_third", geom, clip_seed, True))
-    for name, (W, H, fov, eul, dis), clip_seed, flat in clips:
+        clip_seed = 21 + len({c[2] for c in clips})                # the n-th clip that runs renders with seed 21 + n
+        for light in lighting:                                      # the clip once per --lighting, rendered once
+            tag = "" if light == "none" else "@" + light
+            clips.append((name + tag, geom, clip_seed, False, light))
+            if sad_gate:
+                clips.append((name + "_flat_third" + tag, geom, clip_seed, True, light))
+    rendered = (None, None)
+    for name, (W, H, fov, eul, dis), clip_seed, flat, light in clips:
         t0 = time.perf_counter()
-        frames, truth = synth.rotation_clip(eul, W, H, fov, seed=clip_seed, distractor=dis)
+        if rendered[0] != (name.split("@")[0].replace("_flat_third", ""), clip_seed):
+            rendered = ((name.split("@")[0].replace("_flat_third", ""), clip_seed), synth.rotation_clip(eul, W, H, fov, seed=clip_seed, distractor=dis))
+        frames, truth = rendered[1]
         if flat:
             frames = flat_third(frames)
+        frames = relight_clip(frames, light)
         t_render = time.perf_counter() - t0
         cam = StandardCamera(W / H, fov)
         row = {"geometry": f"{W}x{H}", "fov_y_deg": fov, "frames": len(frames), "px_per_deg_at_centre": round(H / 2 / np.tan(np.radians(fov) / 2) * np.radians(1.0), 2),
@@ -221,7 +256,9 @@ def table(res):
         cols[2:2] = ["hip_sad_q+lsq", "hip_sad_q+ransac"]
     if any("hip_sad_g+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
-    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp"):
+    radii = sorted({int(k.split("+")[0].rsplit("m", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_m", "hip_sad_hm"))})
+    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp") + tuple(
+            f"hip_sad_{t}{radius}" for radius in reversed(radii) for t in ("hm", "m")):
         if any(tag + "+lsq" in r for r in res.values()):
             cols[2:2] = [tag + "+lsq", tag + "+ransac"]
     if not any("hip_lk+lsq" in r for r in res.values()):       # --sad-only: no dense decoder ran
@@ -275,12 +312,17 @@ def main():
     ap.add_argument("--sad-predictors", type=int, default=0, choices=[0, 1],
                     help="with --sad-levels N: 1 adds the hip_sad_hp columns beside hip_sad_h (\"Search levels\" = N with \"Neighbour predictors\" on; with "
                          "--sad-consistency also hip_sad_hpc, with --quarter-pel also hip_sad_qhp); 0 = hip_sad_h alone")
+    ap.add_argument("--lighting", nargs="+", default=["none"], choices=["none", "step", "flicker", "ramp"],
+                    help="run every clip once per lighting (rendered once): none, step (+20 every other 4 frames), flicker (+-12 alternating), "
+                         "ramp (a gradient on odd frames)")
+    ap.add_argument("--sad-prefilter", nargs="*", type=int, default=[], metavar="R",
+                    help="add the hip_sad_m<R> columns (hip_sad with \"Mean removal\" = R; with --sad-levels N also hip_sad_hm<R>: on top of \"Search levels\")")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
     ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
-              sad_only=args.sad_only, sad_predictors=args.sad_predictors)
+              sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter))
     txt = table(res)
     print(txt)
     if args.out:
