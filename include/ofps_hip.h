@@ -222,6 +222,55 @@ int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const v
                                   int min_pixels /* 0 = no contrast gate */, int limit /* >= 1 */, void* d_out_entries,
                                   void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
 
+/* ---- N1v: hip_sad's median test -- a winner that disagrees with its neighbours yields no record (csrc/sad_median.hip) ----
+ * The median test of vector-field post-processing (the outlier test of PIV and of every encoder's vector smoothing): a vector is compared
+ * with the median of its neighbours' and dropped when it lies far from it.  It drops what gate (N1g) and check (N1c) keep: a clean, textured,
+ * round-trip-consistent match at the wrong place -- repeated texture on which both directions lock onto the same alias, a block clipped by
+ * the frame edge, the ring of blocks the mask's dilation carries across a texture edge.  Build-defined, like N1g and N1c; all-integer, so
+ * bit-exact on every device.  For a frame pair, lattice `block` = B, nbx = W / B, nby = H / B:
+ *   F[k] = (dx, dy): the INTEGER forward winner of block k, as N1c uses it: at motion scale 4 the winner in front of the quarter-pel
+ *     refinement, with search levels (N1h) the level-0 winner;
+ *   keep_in[k]: what the other criteria say: contrast gate AND consistency check, whichever are on; neither on: all ones;
+ *   N(k) for k = (bx, by): the blocks (bx + i, by + j), i, j in {-1, 0, 1}, not both 0, that lie inside the lattice and have keep_in = 1;
+ *     n = |N(k)|;
+ *   per component c in {x, y}: the neighbours' d_c sorted ascending into s[0..n-1]; the doubled median M_c = s[(n-1) >> 1] + s[n >> 1]: twice
+ *     the middle value for odd n, the sum of the two middle values for even n -- component-wise and in half-pixels, nothing is ever rounded;
+ *   r2(k) = max(|2*dx - M_x|, |2*dy - M_y|) for n >= 1, r2(k) = 0 for n = 0: an integer in half-pixels;
+ *   a block is KEPT iff keep_in[k] and r2(k) < 2*limit, limit in [1, 255]: at limit 1 the vector lies less than one pixel from the
+ *     neighbours' median.  A block with no kept neighbour is kept: nothing contradicts it.
+ *   One pass: every verdict reads the INCOMING flags of its neighbours, never another block's verdict of this test; nothing is iterated.
+ *   Kept records and out_best triples keep raster order and are the unfiltered call's records and triples bit for bit, quarter-pel or not.
+ * Limit 0 = off, the default: every entry point then uses the launches, streams, scratch and bytes of a build without the test.  Negative
+ * values and values above 255 are OFPS_HIP_EINVAL at the setter.  The option OFPS_HIP_SAD_MEDIAN (environment / ofps_hip_set_option) sets
+ * the same field.
+ * ofps_hip_sad_median[_dev]: the test alone on caller-held (dx, dy, sad) triples in integer units (only dx and dy are read), limit in
+ *   [1, 255]; keep_in: one byte per block (non-zero = kept) or NULL = all ones; either output may be NULL; out_residual2 = r2, saturated at
+ *   2^32 - 1.  Any |d| gives a defined flag and never an access out of bounds.  The _dev form enqueues only; its d_out_keep may not be
+ *   d_keep_in (OFPS_HIP_EINVAL): a verdict reads its neighbours' incoming flags.
+ * With the context's limit > 0:
+ *   ofps_hip_sad_flow: *n_out = the kept count, the kept records first (capacity nblk, as for the gate); gate and check are applied as well
+ *     when they are on.
+ *   ofps_hip_push_frame[_async] / ofps_hip_frame_wait: the gate's path with a third producer of keep flags -- on the compute stream, behind
+ *     the check's flags (if any): the median flags, read from those and written to an array of their own, then ONE compaction and the count
+ *     in device memory; no host synchronisation is added.  n_vectors = the kept count; have_vectors stays 1 for every frame that ran a
+ *     search; fewer than 3 kept -> identity, none -> no motion, as N1g documents them.  A ticket follows the limit the context has when it
+ *     is pushed.
+ * ofps_hip_sad_flow_median_dev: one pair of device frames with explicit values -- min_pixels (0 = no contrast gate, else [1, B*B]), limit
+ *   (0 = no consistency check, else [1, 129]), median_limit in [1, 255]; the context's three fields are not looked at; capacities and count as
+ *   ofps_hip_sad_flow_checked_dev; enqueues only.
+ * Out of scope, as for N1g / N1c: ofps_hip_sad_flow_dev, ofps_hip_push_frames_async and the ofps_hip_multi_* workers ignore the limit and
+ * always produce nblk records per pair; replacing an outlier by the median (it would need a re-scored SAD and a moved record position); a
+ * normalised (fluctuation-scaled) threshold; the dense decoders. */
+int ofps_hip_sad_median(ofps_hip_ctx* ctx, const int32_t* best, const uint8_t* keep_in /* nblk or NULL = all ones */, int W, int H, int block,
+                        int limit, uint32_t* out_residual2 /* nblk or NULL */, uint8_t* out_keep /* nblk or NULL */);
+int ofps_hip_sad_median_dev(ofps_hip_ctx* ctx, const void* d_best, const void* d_keep_in /* or NULL */, int W, int H, int block, int limit,
+                            void* d_out_residual2 /* or NULL */, void* d_out_keep /* or NULL */);
+int ofps_hip_set_sad_median(ofps_hip_ctx* ctx, int limit);   /* 0 = off (default) */
+int ofps_hip_get_sad_median(ofps_hip_ctx* ctx);
+int ofps_hip_sad_flow_median_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
+                                 int min_pixels /* 0 = no contrast gate */, int limit /* 0 = no consistency check */, int median_limit /* >= 1 */,
+                                 void* d_out_entries, void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
+
 /* ---- N1h: hip_sad's search levels -- coarse-to-fine search for motion beyond the search range (csrc/sad_hier.hip) ----
  * The plain search cannot return a vector that was never a candidate: range 16 at 1080p ends at about one degree of camera rotation per
  * frame.  With levels = L in {2, 3} the search runs on the frames halved L - 1 times and every finer level repairs the doubled vectors in a

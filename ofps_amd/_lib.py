@@ -55,6 +55,11 @@ PROTOTYPES = {
     "ofps_hip_set_sad_consistency": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_consistency": (C.c_int, [_ctx]),
     "ofps_hip_sad_flow_checked_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_sad_median": (C.c_int, [_ctx, _i32p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u32p, _u8p]),
+    "ofps_hip_sad_median_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ofps_hip_set_sad_median": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_median": (C.c_int, [_ctx]),
+    "ofps_hip_sad_flow_median_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "ofps_hip_set_sad_levels": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_levels": (C.c_int, [_ctx]),
     "ofps_hip_sad_reach": (C.c_int, [C.c_int, C.c_int]),

@@ -206,6 +206,7 @@ struct ofps_hip_ctx {
         int sad_consistency = 0;         // OFPS_HIP_SAD_CONSISTENCY / ofps_hip_set_sad_consistency: 0 off, N in [1, 129] only blocks whose forward-backward residual is below N (sad_consistency.hip)
         int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
         int sad_predictors = 0;          // OFPS_HIP_SAD_PREDICTORS / ofps_hip_set_sad_predictors: 0 a refined block's one predictor is its parent's winner, 1 the parent's, its four lattice neighbours' and zero (sad_hier.hip, N1p); no effect at levels 1
+        int sad_median = 0;              // OFPS_HIP_SAD_MEDIAN / ofps_hip_set_sad_median: 0 off, N in [1, 255] only blocks whose integer winner lies less than N pixels from the median of their kept lattice neighbours' (sad_median.hip, N1v)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
@@ -231,7 +232,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 53;
+    static constexpr int kNumScratch = 54;
     Scratch scratch[kNumScratch];
 };
 
@@ -267,9 +268,10 @@ enum ScratchSlot {
     S_HIER_PYR,             // hip_sad's search levels (sad_hier.hip): the halved frames of one search's two frame sets, every level above 0
     S_HIER_BEST,            // ... the winners of every level above 0
     S_HIER_ENT,             // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
-    S_SAD_PREF              // hip_sad's mean removal (sad_prefilter.hip): the filtered frames of one search's two frame sets.  Compute stream only, written anew by every search
+    S_SAD_PREF,             // hip_sad's mean removal (sad_prefilter.hip): the filtered frames of one search's two frame sets.  Compute stream only, written anew by every search
+    S_MED_KEEP              // hip_sad's median test (sad_median.hip): the outgoing keep flags, u8 per block, one per ticket in flight in the fused path (the incoming ones stay in S_GATE_FLAGS)
 };
-static_assert(S_SAD_PREF < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_MED_KEEP < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -371,33 +373,44 @@ int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* w
 int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
                                  const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st);
 
+// sad_median.hip: hip_sad's median test (include/ofps_hip.h N1v)
+constexpr int kSadMedianMax = 255;
+int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);             // limit in [1, 255]
+// doubled residual and / or keep byte per block from the integer winners, on stream st; d_keep_in (optional: absent = all ones) is ANDed in
+// and may NOT be d_out_keep: a verdict reads its neighbours' incoming flags
+int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t* d_keep_in, int W, int H, int block, int limit,
+                            uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st);
+
 // sad_gate.hip: one pair's filtered search -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device -- in the
 // steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  The one-pair entry points run them all on ctx->stream
-// (sad_flow_filtered_device); the fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  With gate == 0 and
-// limit == 0 search() is the plain search into d_out and no other step reserves or enqueues anything.
+// (sad_flow_filtered_device); the fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  With gate == 0,
+// limit == 0 and median == 0 search() is the plain search into d_out and no other step reserves or enqueues anything.
 struct SadFilter {
     int W, H, stride, block, range;
-    int gate, limit;                     // the contrast gate's min_pixels, the consistency check's limit; 0 = off
+    int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
     size_t nblk = 0;
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
     char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
-    int *d_fwd = nullptr, *d_bwd = nullptr;      // S_CONS_FWD, S_CONS_BWD: the two directions' integer winners (limit > 0)
+    int *d_fwd = nullptr, *d_bwd = nullptr;      // S_CONS_FWD (limit > 0 or median > 0), S_CONS_BWD (limit > 0): the two directions' integer winners
     float4* d_bwd_ent = nullptr;         // S_CONS_BWD_ENT
-    int* d_triples = nullptr;            // the triples that belong to d_raw: S_GATE_BEST, or d_fwd itself (limit > 0 at motion scale 1)
-    bool on() const { return gate > 0 || limit > 0; }
+    int* d_triples = nullptr;            // the triples that belong to d_raw: S_GATE_BEST, or d_fwd itself (integer winners kept, motion scale 1)
+    uint8_t* d_med_keep = nullptr;       // S_MED_KEEP, this ticket's block: the median test's outgoing flags (median > 0)
+    bool on() const { return gate > 0 || limit > 0 || median > 0; }
+    bool winners() const { return limit > 0 || median > 0; }       // both read the forward search's INTEGER winners, whatever the motion scale
     uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk) : nullptr; }
-    uint8_t* keep() const { return gate_keep(d_flags, nblk); }
+    uint8_t* keep() const { return gate_keep(d_flags, nblk); }      // the incoming flags: contrast gate AND consistency check
     int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
     // the scratch slots; S_GATE_FLAGS holds `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
     int reserve(ofps_hip_ctx* ctx, int tix = 0, int tickets = 1);
     int search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out);      // on ctx->stream; d_out: the unfiltered search's records
     int contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st);                    // gate > 0: counts and keep flags of `cur`, which they depend on alone
-    // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] kept records [and triples] in raster order -> count
+    // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] [median flags read from those, into
+    // d_med_keep ->] kept records [and triples] in raster order -> count
     int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
 };
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                             int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count);
+                             int min_pixels, int limit, int median, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.

@@ -19,7 +19,7 @@ using ofps::PipeStream;
 using ofps::TailRecord;
 struct PipeOut {                 // a ticket's result block: page-locked, and in device scratch at the head of its kPipeOutBytes
     TailRecord r;
-    uint32_t kept[4];            // contrast gate or consistency check on: the kept record count (sad_gate.hip); not read back, not looked at, with both off
+    uint32_t kept[4];            // contrast gate, consistency check or median test on: the kept record count (sad_gate.hip); not read back, not looked at, with all off
 };
 constexpr size_t kPipeOutPlain = offsetof(PipeOut, kept);       // what a ticket without the gate reads back
 constexpr size_t kPipeField = 4096;                             // the detector's field in the device copy, behind the block
@@ -98,7 +98,7 @@ int pipe_upload(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride
 struct Push {
     ofps_hip_ctx* ctx;
     const ofps_hip_frame_params* prm;
-    ofps::SadFilter f;                   // contrast gate and consistency check as the context has them at this push; both 0: the plain search
+    ofps::SadFilter f;                   // contrast gate, consistency check and median test as the context has them at this push; all 0: the plain search
     PipeStream::Ticket* t = nullptr;
     int tix = 0;
     long frame_no = 0;                   // the frame this push uploads
@@ -236,7 +236,7 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    Push p{ctx, prm, {W, H, (W + 63) & ~63, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency, /*want_triples=*/false}};
+    Push p{ctx, prm, {W, H, (W + 63) & ~63, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency, ctx->opt.sad_median, /*want_triples=*/false}};
     rc = p.claim();                                     // refused before anything is uploaded
     if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
     if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)

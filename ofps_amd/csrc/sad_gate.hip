@@ -11,8 +11,8 @@
 // block_keep_kernel: count >= min_pixels -> one byte per block, the flag the ordered compactions of mask.hip take.
 // compact_best_kernel: the (dx, dy, SAD) triples compacted by the same flags in the same order.
 //
-// Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate and / or the consistency check
-// (sad_consistency.hip) in front of one compaction and one device-side count -- for the one-pair entry points and the fused per-frame path.
+// Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate, the consistency check (sad_consistency.hip)
+// and / or the median test (sad_median.hip) in front of one compaction and one device-side count -- for the one-pair entry points and the fused per-frame path.
 #include "common.hpp"
 #include "mask_tile.hpp"
 
@@ -114,6 +114,7 @@ static int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const ch
 int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     int rc = limit > 0 ? sad_consistency_check(ctx, block, limit, who) : OFPS_HIP_OK;
     if (rc == OFPS_HIP_OK && gate > 0) rc = sad_gate_check(ctx, block, gate, who);
+    if (rc == OFPS_HIP_OK && median > 0) rc = sad_median_check(ctx, block, median, who);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "%s: bad geometry W=%d H=%d stride=%d", who, W, H, stride);
     nblk = ofps_hip_sad_block_count(W, H, block);
@@ -127,25 +128,34 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
     auto* flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, tickets * fbytes));
     if (!d_raw || !flags) return OFPS_HIP_ENOMEM;
     d_flags = flags + tix * fbytes;
-    if (limit > 0) {
+    if (winners()) {
         d_fwd = static_cast<int*>(scratch(ctx, S_CONS_FWD, tri));
+        if (!d_fwd) return OFPS_HIP_ENOMEM;
+    }
+    if (limit > 0) {
         d_bwd = static_cast<int*>(scratch(ctx, S_CONS_BWD, tri));
         d_bwd_ent = static_cast<float4*>(scratch(ctx, S_CONS_BWD_ENT, nblk * sizeof(float4)));     // the search kernels always write records
-        if (!d_fwd || !d_bwd || !d_bwd_ent) return OFPS_HIP_ENOMEM;
+        if (!d_bwd || !d_bwd_ent) return OFPS_HIP_ENOMEM;
     }
-    // the records' triples: the forward search's integer winners themselves when the check keeps them and nothing refines them
-    if (want_triples) d_triples = limit > 0 && ctx->opt.sad_motion_scale != 4 ? d_fwd : static_cast<int*>(scratch(ctx, S_GATE_BEST, tri));
+    if (median > 0) {
+        const size_t mbytes = (nblk + 15) & ~size_t(15);
+        auto* mk = static_cast<uint8_t*>(scratch(ctx, S_MED_KEEP, tickets * mbytes));
+        if (!mk) return OFPS_HIP_ENOMEM;
+        d_med_keep = mk + tix * mbytes;
+    }
+    // the records' triples: the forward search's integer winners themselves when they are kept and nothing refines them
+    if (want_triples) d_triples = winners() && ctx->opt.sad_motion_scale != 4 ? d_fwd : static_cast<int*>(scratch(ctx, S_GATE_BEST, tri));
     return want_triples && !d_triples ? OFPS_HIP_ENOMEM : OFPS_HIP_OK;
 }
 
 int SadFilter::search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out) {
-    if (limit == 0) return sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
-    // check on (the two hazards: sad_consistency.hip): the forward search leaves its integer winners in d_fwd whatever the motion scale -- at
+    if (!winners()) return sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
+    // check or median test on (the two hazards: sad_consistency.hip): the forward search leaves its integer winners in d_fwd whatever the motion scale -- at
     // scale 4 as d_int_best, the refinement then writes d_triples or nothing -- and the backward search, integer only, runs right behind it
     const bool qpel = ctx->opt.sad_motion_scale == 4;
     const int rc = sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, qpel ? d_triples : d_fwd, /*integer_only=*/false,
                                     qpel ? d_fwd : nullptr);
-    if (rc != OFPS_HIP_OK) return rc;
+    if (rc != OFPS_HIP_OK || limit == 0) return rc;
     return sad_pairs_device(ctx, d_cur, 0, d_prev, 0, 1, W, H, stride, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
 }
 
@@ -163,24 +173,28 @@ int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_
     int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream)
                        : OFPS_HIP_OK;
     if (rc != OFPS_HIP_OK) return rc;
+    // one pass: the median test reads the other criteria's flags (none on: all ones) and writes its own array
+    if (median > 0) rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, W, H, block, median, nullptr, d_med_keep, ctx->stream);
+    if (rc != OFPS_HIP_OK) return rc;
     if (nblk == 0) {
         OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
         return OFPS_HIP_OK;
     }
-    rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, keep(), nblk, d_out, d_count)
-                                  : compact_entries_device(ctx, d_raw, keep(), nblk, d_out, d_count);
+    const uint8_t* flags = median > 0 ? d_med_keep : keep();
+    rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, flags, nblk, d_out, d_count)
+                                  : compact_entries_device(ctx, d_raw, flags, nblk, d_out, d_count);
     if (rc != OFPS_HIP_OK) return rc;
     if (d_out_best) {
-        hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_triples, keep(), (uint32_t)nblk, d_out_best);
+        hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_triples, flags, (uint32_t)nblk, d_out_best);
         OFPS_HIP_TRY(ctx, hipGetLastError());
     }
     return OFPS_HIP_OK;
 }
 
-// One pair, everything on ctx->stream: search[es], [contrast flags of `cur`,] [the check's flags,] one compaction, one count.
+// One pair, everything on ctx->stream: search[es], [contrast flags of `cur`,] [the check's flags,] [the median test's flags,] one compaction, one count.
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                             int min_pixels, int limit, float4* d_out, int* d_out_best, uint32_t* d_count) {
-    SadFilter f{W, H, stride, block, range, min_pixels, limit, d_out_best != nullptr};
+                             int min_pixels, int limit, int median, float4* d_out, int* d_out_best, uint32_t* d_count) {
+    SadFilter f{W, H, stride, block, range, min_pixels, limit, median, d_out_best != nullptr};
     int rc = f.plan(ctx, "sad_flow");
     if (rc == OFPS_HIP_OK) rc = f.reserve(ctx);
     if (rc == OFPS_HIP_OK) rc = f.search(ctx, d_prev, d_cur, d_out);
@@ -235,7 +249,7 @@ int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
     const int rc = ofps::sad_gate_check(ctx, block, min_pixels, "sad_flow");             // (the filter itself takes 0 for "no gate")
     if (rc != OFPS_HIP_OK) return rc;
     return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                          min_pixels, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          min_pixels, 0, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
                                           static_cast<uint32_t*>(d_out_count));
 }
 

@@ -75,6 +75,9 @@ class HipSadDecoder(Properties):
               # current frame (include/ofps_hip.h N1g).  The upper bound is the largest block's area; a value above Block size^2 is refused
               # by the call
               ("Contrast gate", "usize", "contrast_gate", 0, 256),
+              # build-defined: 0 = off; N = only blocks whose integer vector lies less than N pixels from the median of their kept lattice
+              # neighbours' (include/ofps_hip.h N1v)
+              ("Median test", "usize", "median_test", 0, 255),
               # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
               # include/ofps_hip.h N1c).  Costs a second search per frame
               # build-defined: 0 = the search compares the frames as they are; r = both frames minus their box mean of radius r, for streams
@@ -96,6 +99,7 @@ class HipSadDecoder(Properties):
         self.quarter_pel = False
         self.contrast_gate = 0
         self.consistency = 0
+        self.median_test = 0
         self.levels = 1
         self.neighbour_predictors = False
         self.prefilter = 0
@@ -138,6 +142,7 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_motion_scale(4 if self.quarter_pel else 1)
         self.ctx.set_sad_gate(self.contrast_gate)
         self.ctx.set_sad_consistency(self.consistency)
+        self.ctx.set_sad_median(self.median_test)
         self.ctx.set_sad_levels(self.levels)
         self.ctx.set_sad_predictors(1 if self.neighbour_predictors else 0)
         self.ctx.set_sad_prefilter(self.prefilter)

@@ -184,6 +184,45 @@ class HipContext:
                                                             min_pixels, limit, C.c_void_p(d_out_entries), C.c_void_p(d_out_best or 0),
                                                             C.c_void_p(d_out_count)))
 
+    def set_sad_median(self, limit: int):
+        """hip_sad's median test (include/ofps_hip.h N1v): 0 = off (default); N in [1, 255] = only the blocks whose integer winner lies
+        less than N pixels (Chebyshev, in half-pixel steps) from the component-wise median of their kept lattice neighbours' winners yield
+        a record (sad_flow, push_frame[_async])."""
+        self._check(self._lib.ofps_hip_set_sad_median(self._h, limit))
+
+    def get_sad_median(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_median(self._h))
+
+    def sad_median(self, best: np.ndarray, keep_in: np.ndarray | None, W: int, H: int, block: int, limit: int, want_residual=True,
+                   want_keep=True):
+        """The test alone on a [nblk, 3] array of (dx, dy, sad) integer winners and the other criteria's keep bytes (None = all ones)
+        -> (doubled residual uint32 [nblk] or None, keep uint8 [nblk] or None)."""
+        b = np.ascontiguousarray(best, np.int32)
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        assert b.shape == (nb, 3)
+        k = None if keep_in is None else np.ascontiguousarray(keep_in, np.uint8)
+        assert k is None or k.shape == (nb,)
+        res = np.zeros(max(nb, 1), np.uint32) if want_residual else None
+        keep = np.zeros(max(nb, 1), np.uint8) if want_keep else None
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.ofps_hip_sad_median(self._h, b.ctypes.data_as(C.POINTER(C.c_int32)), None if k is None else k.ctypes.data_as(u8),
+                                                  W, H, block, limit, res.ctypes.data_as(C.POINTER(C.c_uint32)) if want_residual else None,
+                                                  keep.ctypes.data_as(u8) if want_keep else None))
+        return (res[:nb] if want_residual else None), (keep[:nb] if want_keep else None)
+
+    def sad_median_dev(self, d_best: int, d_keep_in: int | None, W: int, H: int, block: int, limit: int, d_out_residual2: int | None,
+                       d_out_keep: int | None):
+        self._check(self._lib.ofps_hip_sad_median_dev(self._h, C.c_void_p(d_best), C.c_void_p(d_keep_in or 0), W, H, block, limit,
+                                                      C.c_void_p(d_out_residual2 or 0), C.c_void_p(d_out_keep or 0)))
+
+    def sad_flow_median_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, search_range: int, min_pixels: int,
+                            limit: int, median_limit: int, d_out_entries: int, d_out_best: int | None, d_out_count: int):
+        """One pair of device frames through the median test (the contrast gate when min_pixels > 0, the consistency check when limit > 0):
+        the kept records first (capacity nblk), their count in *d_out_count (u32).  Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_median_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, search_range,
+                                                           min_pixels, limit, median_limit, C.c_void_p(d_out_entries),
+                                                           C.c_void_p(d_out_best or 0), C.c_void_p(d_out_count)))
+
     def set_sad_levels(self, levels: int):
         """hip_sad's search levels (include/ofps_hip.h N1h): 1 = the plain search (default); 2 | 3 = the search runs on the frames halved
         levels - 1 times and every finer level repairs the doubled vectors in a +-3 window: reach 2 * range + 3, 4 * range + 9."""

@@ -18,6 +18,8 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               beyond the plain search's +-16); --sad-only leaves the dense decoders' columns out
               with --sad-levels N --sad-predictors 1 also hip_sad_hp: the same with "Neighbour predictors" on (include/ofps_hip.h N1p)
               with --sad-prefilter R [R ...] also hip_sad_m<R>: hip_sad with its "Mean removal" property at R (include/ofps_hip.h N1m)
+              with --sad-median N [N ...] also hip_sad_v<N>: hip_sad with its "Median test" property at N (include/ofps_hip.h N1v); with
+              --sad-consistency C also hip_sad_cv<N>: on top of "Consistency check" = C
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
               toggles by 20 grey levels every 4 frames (a quarter of the pairs straddle a step); flicker = +12 on odd frames, -12 on even
               ones (every pair differs by 24); ramp = odd frames gain 30 x/(W-1) - 10 y/(H-1) - 8 (a gradient that comes and goes); all
@@ -156,7 +158,7 @@ def relight_clip(frames, lighting):
 
 
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
-        fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=()):
+        fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=()):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -195,6 +197,11 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         if sad_levels:
             props_hm = {"Search levels": sad_levels, "Mean removal": radius}
             combos[2:2] = [(f"hip_sad_hm{radius}", HipSadDecoder, False, props_hm), (f"hip_sad_hm{radius}", HipSadDecoder, True, props_hm)]
+    for limit in sad_median:        # hip_sad with its "Median test" property at N (include/ofps_hip.h N1v); with --sad-consistency C also on top of "Consistency check"
+        combos[2:2] = [(f"hip_sad_v{limit}", HipSadDecoder, False, {"Median test": limit}), (f"hip_sad_v{limit}", HipSadDecoder, True, {"Median test": limit})]
+        if sad_consistency:
+            props_cv = {"Consistency check": sad_consistency, "Median test": limit}
+            combos[2:2] = [(f"hip_sad_cv{limit}", HipSadDecoder, False, props_cv), (f"hip_sad_cv{limit}", HipSadDecoder, True, props_cv)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
@@ -257,7 +264,9 @@ def table(res):
     if any("hip_sad_g+lsq" in r for r in res.values()):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
     radii = sorted({int(k.split("+")[0].rsplit("m", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_m", "hip_sad_hm"))})
-    for tag in ("hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp") + tuple(
+    limits = sorted({int(k.split("+")[0].rsplit("v", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_v", "hip_sad_cv"))})
+    for tag in tuple(f"hip_sad_{t}{limit}" for limit in reversed(limits) for t in ("cv", "v")) + (
+            "hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp") + tuple(
             f"hip_sad_{t}{radius}" for radius in reversed(radii) for t in ("hm", "m")):
         if any(tag + "+lsq" in r for r in res.values()):
             cols[2:2] = [tag + "+lsq", tag + "+ransac"]
@@ -317,12 +326,15 @@ def main():
                          "ramp (a gradient on odd frames)")
     ap.add_argument("--sad-prefilter", nargs="*", type=int, default=[], metavar="R",
                     help="add the hip_sad_m<R> columns (hip_sad with \"Mean removal\" = R; with --sad-levels N also hip_sad_hm<R>: on top of \"Search levels\")")
+    ap.add_argument("--sad-median", nargs="*", type=int, default=[], metavar="N",
+                    help="add the hip_sad_v<N> columns (hip_sad with \"Median test\" = N; with --sad-consistency C also hip_sad_cv<N>: on top of \"Consistency check\")")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
     ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
-              sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter))
+              sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
+              sad_median=tuple(args.sad_median))
     txt = table(res)
     print(txt)
     if args.out:
