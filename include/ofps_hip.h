@@ -425,7 +425,9 @@ int ofps_hip_contrast_mask_dev(ofps_hip_ctx* ctx, const void* d_gray, int W, int
                                         configs[2] that feed ofps_hip_densify_raster_dev / ofps_hip_almeida_dev directly
                                         (API version 1 called this bit OFPS_HIP_LK_PER_PIXEL and mislabelled it "Process Fullres = false") */
 #define OFPS_HIP_FLOW_FARNEBACK   4u /* the flow is Farneback's (ofps_hip_farneback_flow: levels = pyramid levels, winsize = 2 * radius + 1,
-                                        iters = iterations, poly_n 7, poly_sigma 1.5) instead of the iterative Lucas-Kanade: "hip_flow" */
+                                        iters = iterations, poly_n 7, poly_sigma 1.5) instead of the iterative Lucas-Kanade: "hip_flow".
+                                        With this flag levels and radius may be 0 (no layer above the frame; a 1 x 1 window), as they may
+                                        in ofps_hip_farneback_flow; winsize <= 15 means radius <= 7 */
 #define OFPS_HIP_FLOW_USE_PREVIOUS 8u /* with OFPS_HIP_FLOW_FARNEBACK, stream forms: the flow of the stream's previous pair is this pair's initial
                                         flow -- OPTFLOW_USE_INITIAL_FLOW exactly as cv-decoder sets it from its second pair on
                                         (cv-decoder/src/lib.rs:161-165: `self.flow` persists between process_frame calls).  A stream's first

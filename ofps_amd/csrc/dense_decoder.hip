@@ -54,7 +54,9 @@ int dense_grid_of(ofps_hip_ctx* ctx, int W, int H, int stride, int max_w, int ma
     g->raw_row = ((size_t)W * g->cn + 3) & ~(size_t)3;
     // The flow's own parameter limits, checked where a stream's FIRST frame is pushed (it runs no flow) and before any upload: a stream must not
     // accept a frame and then fail every later one.  Farneback: winsize = 2 radius + 1 <= 15, and the layers of the fw x fh frames.
-    OFPS_REQUIRE(ctx, levels >= 1 && levels <= 8 && radius >= 1 && radius <= 15 && iters >= 1 && iters <= 64,
+    // (Farneback's levels count the layers ABOVE the frame and its window is 2 radius + 1: 0 is a value of both -- the frame alone, the pixel alone)
+    const int lowest = g->farneback ? 0 : 1;
+    OFPS_REQUIRE(ctx, levels >= lowest && levels <= 8 && radius >= lowest && radius <= 15 && iters >= 1 && iters <= 64,
                  "%s: levels=%d radius=%d iters=%d out of range", who, levels, radius, iters);
     return g->farneback ? ofps::farneback_check_params(ctx, g->fw, g->fh, levels, 2 * radius + 1, 7) : OFPS_HIP_OK;
 }

@@ -60,6 +60,8 @@ def layer_image(img, k, w, h):
 
 
 def poly_kernels(n, sigma):
+    if sigma < 1.19e-7:                                              # FarnebackPrepareGaussian: sigma < FLT_EPSILON -> 0.3 n
+        sigma = 0.3 * n
     x = np.arange(-n, n + 1)
     g = np.exp(-x * x / (2 * sigma * sigma)).astype(np.float32).astype(np.float64)
     g = (g / g.sum()).astype(np.float32).astype(np.float64)
@@ -121,14 +123,29 @@ def update_flow(M, winsize):
     return np.stack([(g11 * h2 - g12 * h1) * idet, (g22 * h1 - g12 * h2) * idet], -1)
 
 
-def farneback(prev, cur, levels=5, winsize=13, iters=3, poly_n=7, poly_sigma=1.5):
+def initial_flow(init, w, h, scale):
+    """OPTFLOW_USE_INITIAL_FLOW: resize(flow0, coarsest layer, INTER_AREA) * scale.  Restated only where the layer divides the frame
+    exactly in both directions: there INTER_AREA is the plain mean of every (H / h) x (W / w) block and no convention is open."""
+    init = np.asarray(init, np.float64)
+    H, W = init.shape[:2]
+    if W % w or H % h:
+        raise NotImplementedError(f"initial flow {W}x{H} -> {w}x{h}: INTER_AREA is restated for integer ratios only")
+    return init.reshape(h, H // h, w, W // w, 2).mean(axis=(1, 3)) * scale
+
+
+def farneback(prev, cur, levels=5, winsize=13, iters=3, poly_n=7, poly_sigma=1.5, init=None):
     H, W = prev.shape
     L = layers(W, H, levels)
     flow = None
     for k in range(L, -1, -1):
         scale = 0.5 ** k
         w, h = round_half_even(W * scale), round_half_even(H * scale)
-        flow = np.zeros((h, w, 2)) if flow is None else resize_linear(flow, w, h) * 2.0
+        if flow is not None:
+            flow = resize_linear(flow, w, h) * 2.0
+        elif init is not None:
+            flow = initial_flow(init, w, h, scale)
+        else:
+            flow = np.zeros((h, w, 2))
         R0 = poly_exp(layer_image(prev, k, w, h), poly_n, poly_sigma)
         R1 = poly_exp(layer_image(cur, k, w, h), poly_n, poly_sigma)
         M = matrices(R0, R1, flow)
