@@ -165,8 +165,9 @@ int ofps_hip_sad_flow_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames,
  *     context has when it is pushed.
  * ofps_hip_sad_flow_gated_dev: one pair of device frames with an explicit min_pixels in [1, B*B] (the context's gate is not looked at);
  *   d_out_entries / d_out_best have capacity nblk, d_out_count is one uint32 in device memory; enqueues only.
- * Out of scope: the batched forms -- ofps_hip_sad_flow_dev, ofps_hip_push_frames_async, the ofps_hip_multi_* workers -- ignore the gate and
- * always produce nblk records per pair (the device-count forms of the tail are one-item forms); a second criterion on the SAD surface
+ * The batched forms: ofps_hip_sad_flow_dev and ofps_hip_multi_sad_flow / _run_resident / _fetch ignore the gate and always produce nblk
+ * records per pair; ofps_hip_push_frames_async and the ofps_hip_multi_* workers' pushes do so unless the batch filter switch is on (N1b
+ * below, which also holds the filtered sibling of ofps_hip_sad_flow_dev).  Out of scope: a second criterion on the SAD surface
  * (best against second best) is not part of this (the forward-backward check, N1c below, is the second criterion this build has). */
 int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_counts /* nblk */);
 int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts);
@@ -210,8 +211,9 @@ int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
  * ofps_hip_sad_flow_checked_dev: one pair of device frames with an explicit min_pixels (0 = no contrast gate, else [1, B*B]) and limit in
  *   [1, 129] (the context's values are not looked at); capacities and count as ofps_hip_sad_flow_gated_dev; enqueues only.
  * In PRUNED mode ofps_hip_sad_pruned_overflow_strips then reports the backward search, the last one of the call.
- * Out of scope, as for N1g: ofps_hip_sad_flow_dev, ofps_hip_push_frames_async and the ofps_hip_multi_* workers ignore the limit and always
- * produce nblk records per pair. */
+ * The batched forms, as for N1g: ofps_hip_sad_flow_dev and ofps_hip_multi_sad_flow / _run_resident / _fetch ignore the limit and always
+ * produce nblk records per pair; ofps_hip_push_frames_async and the ofps_hip_multi_* workers' pushes follow it with the batch filter
+ * switch on (N1b below). */
 int ofps_hip_sad_consistency(ofps_hip_ctx* ctx, const int32_t* fwd_best, const int32_t* bwd_best, int W, int H, int block, int limit,
                              uint32_t* out_residual /* nblk or NULL */, uint8_t* out_keep /* nblk or NULL */);
 int ofps_hip_sad_consistency_dev(ofps_hip_ctx* ctx, const void* d_fwd_best, const void* d_bwd_best, int W, int H, int block, int limit,
@@ -258,8 +260,9 @@ int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const v
  * ofps_hip_sad_flow_median_dev: one pair of device frames with explicit values -- min_pixels (0 = no contrast gate, else [1, B*B]), limit
  *   (0 = no consistency check, else [1, 129]), median_limit in [1, 255]; the context's three fields are not looked at; capacities and count as
  *   ofps_hip_sad_flow_checked_dev; enqueues only.
- * Out of scope, as for N1g / N1c: ofps_hip_sad_flow_dev, ofps_hip_push_frames_async and the ofps_hip_multi_* workers ignore the limit and
- * always produce nblk records per pair; replacing an outlier by the median (it would need a re-scored SAD and a moved record position); a
+ * The batched forms, as for N1g / N1c: ofps_hip_sad_flow_dev and ofps_hip_multi_sad_flow / _run_resident / _fetch ignore the limit and
+ * always produce nblk records per pair; ofps_hip_push_frames_async and the ofps_hip_multi_* workers' pushes follow it with the batch
+ * filter switch on (N1b below).  Out of scope: replacing an outlier by the median (it would need a re-scored SAD and a moved record position); a
  * normalised (fluctuation-scaled) threshold; the dense decoders. */
 int ofps_hip_sad_median(ofps_hip_ctx* ctx, const int32_t* best, const uint8_t* keep_in /* nblk or NULL = all ones */, int W, int H, int block,
                         int limit, uint32_t* out_residual2 /* nblk or NULL */, uint8_t* out_keep /* nblk or NULL */);
@@ -270,6 +273,38 @@ int ofps_hip_get_sad_median(ofps_hip_ctx* ctx);
 int ofps_hip_sad_flow_median_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
                                  int min_pixels /* 0 = no contrast gate */, int limit /* 0 = no consistency check */, int median_limit /* >= 1 */,
                                  void* d_out_entries, void* d_out_best /* or NULL */, void* d_out_count /* one uint32 */);
+
+/* ---- N1b: gate, check and median test in the batched forms (csrc/sad_gate.hip, csrc/pipeline.hip) ----
+ * The three criteria above over a whole batch of pairs, with a number of launches that does not depend on the number of pairs: contrast
+ * counts + keep flags, consistency flags, median flags and the compaction are one launch each over the batch (the item in a grid
+ * dimension), the compaction segmented -- one workgroup scans one item, one path for every nblk -- with one count per item; neighbour and
+ * partner indices never cross an item boundary.
+ * ofps_hip_sad_flow_filtered_dev: frames and pairs as ofps_hip_sad_flow_dev, in both ref_modes (ref_mode 1: the current frame of pair k is
+ *   frame k + 1 -- the gate reads it, the backward search goes from it to the key frame).  min_pixels (0 = no contrast gate, else [1, B*B]),
+ *   limit (0 = no consistency check, else [1, 129]) and median (0 = no median test, else [1, 255]) are explicit, the context's three fields
+ *   are not looked at; all three 0 is OFPS_HIP_EINVAL.  Everything else of the context applies as to any search: motion scale 4, search
+ *   levels and predictors, mean removal (the gate reads the raw frames), PRUNED.  Item k's slot -- d_out_entries + k*nblk records,
+ *   d_out_best + k*nblk triples -- and d_out_counts[k] are bit for bit what ofps_hip_sad_flow_median_dev (_checked_dev / _gated_dev where
+ *   the later criteria are 0) returns for that pair with the same three values: the kept records and triples first, in raster order; the
+ *   rest of the slot is unspecified, nothing is written outside it.  Enqueues only: no host synchronisation, no read-back.
+ * ofps_hip_set_sad_batch_filter: 0 (default) = ofps_hip_push_frames_async and the ofps_hip_multi_* workers' pushes ignore the context's
+ *   gate, limit and median limit, as they always have, and enqueue what a build without this section enqueues; 1 = a ticket pushed while at
+ *   least one of the three is on runs the filtered batched search and the tail's device-count forms with one count per item:
+ *   ofps_hip_frames_wait fills out[j].n_vectors with item j's kept count (it travels in the ticket's page-locked block in the one read-back;
+ *   nothing is synchronised between push and wait), have_vectors stays 1 for every frame that ran a search, also with 0 kept, out_entries
+ *   holds the kept records first in slot j.  Records and counts of item j equal a single ofps_hip_push_frame of that frame with the same
+ *   settings bit for bit, the detector's result likewise, the quaternion to 2e-6; fewer than 3 kept -> identity with either solver, none
+ *   kept -> no motion.  A ticket follows the settings the context has when it is pushed.  Detect-compensation mode 1 works where it does
+ *   without the switch (not in the multi-device workers).  Any value but 0 / 1 is OFPS_HIP_EINVAL.  The option OFPS_HIP_SAD_BATCH_FILTER
+ *   (environment / ofps_hip_set_option) sets the same field; the multi-device workers read it from the environment at their init, as they
+ *   read OFPS_HIP_SAD_GATE, so ofps_hip_multi_push_frames_async follows it, n_vectors and records in frame order as ever.
+ * Still ignoring all three: ofps_hip_sad_flow_dev (its filtered sibling is the call above), ofps_hip_multi_sad_flow / _run_resident / _fetch. */
+int ofps_hip_sad_flow_filtered_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch,
+                                   int ref_mode, int block, int range, int min_pixels, int limit, int median,
+                                   void* d_out_entries /* pairs * nblk * 4 f32 */, void* d_out_best /* pairs * nblk * 3 i32, or NULL */,
+                                   void* d_out_counts /* pairs uint32 */);
+int ofps_hip_set_sad_batch_filter(ofps_hip_ctx* ctx, int on);   /* 0 = the batched forms ignore gate, check and median test (default) */
+int ofps_hip_get_sad_batch_filter(ofps_hip_ctx* ctx);
 
 /* ---- N1h: hip_sad's search levels -- coarse-to-fine search for motion beyond the search range (csrc/sad_hier.hip) ----
  * The plain search cannot return a vector that was never a candidate: range 16 at 1080p ends at about one degree of camera rotation per

@@ -60,6 +60,10 @@ PROTOTYPES = {
     "ofps_hip_set_sad_median": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_median": (C.c_int, [_ctx]),
     "ofps_hip_sad_flow_median_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_sad_flow_filtered_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_set_sad_batch_filter": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_batch_filter": (C.c_int, [_ctx]),
     "ofps_hip_set_sad_levels": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_levels": (C.c_int, [_ctx]),
     "ofps_hip_sad_reach": (C.c_int, [C.c_int, C.c_int]),

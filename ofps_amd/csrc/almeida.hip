@@ -613,9 +613,9 @@ __global__ __launch_bounds__(1024) void almeida_lsq_step_kernel(const float4* __
     const size_t item = blockIdx.y;
     const int nblk = gridDim.x;
     // n_dev (optional): the record count lives on the device -- the launch partitions the n records it was sized for, the workgroup reads
-    // the count once and works on the first min(*n_dev, n) of them
+    // its item's count once and works on the first min(n_dev[item], n) of them
     const float4* __restrict__ ent = entries + item * n;
-    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
+    if (n_dev) { const size_t nd = (size_t)n_dev[item]; n = nd < n ? nd : n; }
     const float eps = almeida_eps();
     const Mat3 mroll = mat3_from_euler(0.0f, eps, 0.0f);
     const Mat3 mpitch = mat3_from_euler(eps, 0.0f, 0.0f);
@@ -1367,13 +1367,14 @@ __device__ __forceinline__ Quat almeida_update_quad_lu(const Quat& rotation, con
 
 constexpr int kHypPerWave = 16;
 
-// n_dev (optional, all three RANSAC kernels): the record count lives on the device -- n is then the capacity the launches were sized
-// for, and n = min(*n_dev, n), ns = min(ns, n) are formed here, so the sampler draws what a host-n call with that n draws
+// n_dev (optional, all three RANSAC kernels): the record counts live on the device, one per item -- n is then the capacity the launches
+// were sized for and the stride of every item, and n = min(n_dev[item], n), ns = min(ns, n) are formed here, so the sampler draws what a
+// host-n call with that n draws
 __global__ __launch_bounds__(64) void ransac_hyp_kernel(const float4* __restrict__ entries, uint32_t n, uint32_t iters,
                                                         uint64_t seed, Camera cam, Mat3* __restrict__ hyp, const uint32_t* __restrict__ n_dev) {
     const size_t item = blockIdx.y;
     const float4* __restrict__ ent = entries + item * n;
-    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; if (n == 0) return; }      // (no record to draw: the count kernel finds no inlier)
+    if (n_dev) { const uint32_t nd = n_dev[item]; n = nd < n ? nd : n; if (n == 0) return; }      // (no record to draw: the count kernel finds no inlier)
     const int q = threadIdx.x & 3;
     const uint32_t it_raw = blockIdx.x * kHypPerWave + (threadIdx.x >> 2);
     const bool live = it_raw < iters;
@@ -1433,7 +1434,7 @@ __global__ __launch_bounds__(kCountThreads) void ransac_count_kernel(const float
     __shared__ uint32_t total;
     const size_t item = blockIdx.y;
     const float4* __restrict__ ent = entries + item * n;
-    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
+    if (n_dev) { const uint32_t nd = n_dev[item]; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
     const uint32_t it = blockIdx.x;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
@@ -1464,7 +1465,7 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float4* __res
     const size_t item = blockIdx.x;
     const float4* __restrict__ ent = entries + item * n;
     const size_t sel_stride = ns;                  // sel[item][0 .. ns): the capacity, whatever the count turns out to be
-    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
+    if (n_dev) { const uint32_t nd = n_dev[item]; n = nd < n ? nd : n; ns = ns < n ? ns : n; }
     if (threadIdx.x == 0) { best = 0; base = 0; }
     __syncthreads();
     unsigned long long k = 0;
@@ -1722,8 +1723,9 @@ static int lsq_stepped(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max,
     return OFPS_HIP_OK;
 }
 
-// multi: a device-side count (d_n) may take the cluster and the launch-per-step solver too -- one problem, every choice below made from
-// n_max alone.  Without it a device-side count keeps to the one-workgroup solver, as the RANSAC refit of a host-n call always has.
+// multi: a device-side count (d_n) may take the cluster solver (one problem) and the launch-per-step solver (any batch: one count per
+// item) too, every choice below made from n_max alone.  Without it a device-side count keeps to the one-workgroup solver, as the RANSAC
+// refit of a host-n call always has.
 static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride, size_t n_max, const uint32_t* d_n,
                       uint32_t min_n, int batch, const Camera& cam, float4* d_quat, bool multi = false) {
     const bool any_path = d_n == nullptr || (multi && batch == 1);
@@ -1753,17 +1755,16 @@ static int lsq_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t stride,
         OFPS_HIP_TRY(ctx, hipGetLastError());
         return OFPS_HIP_OK;
     }
-    OFPS_REQUIRE(ctx, any_path && stride == n_max, "almeida: per-item device-side counts need n <= 8192");
+    OFPS_REQUIRE(ctx, (any_path || multi) && stride == n_max, "almeida: this refit's device-side counts need n <= 8192");
     return lsq_stepped(ctx, d_entries, n_max, batch, cam, d_quat, d_n, min_n);
 }
 
-// d_n == nullptr: n records per item, known to the host.  d_n != nullptr (batch == 1): the estimate over the first min(*d_n, n) of n
-// records, the count read on the device -- no launch, grid or path depends on it, nothing is read back.
+// d_n == nullptr: n records per item, known to the host.  d_n != nullptr: item j's estimate over the first min(d_n[j], n) of its n
+// records, the counts read on the device -- no launch, grid or path depends on them, nothing is read back.
 static int almeida_impl(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, const uint32_t* d_n, int batch, float aspect, float fov_y_deg,
                         int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed,
                         float4* d_quat, uint32_t lsq_min_n = 0) {
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "almeida: batch %d out of range", batch);
-    OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "almeida: a device-side count is for one problem (batch %d)", batch);
     OFPS_REQUIRE(ctx, n < (1ull << 31), "almeida: too many entries");
     OFPS_REQUIRE(ctx, aspect > 0.0f && fov_y_deg > 0.0f && fov_y_deg < 180.0f, "almeida: bad camera (aspect=%g fov_y=%g)",
                  (double)aspect, (double)fov_y_deg);
@@ -1798,7 +1799,7 @@ static int almeida_impl(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, co
     const size_t cap = ns ? ns : 1;
     if (cap <= 8192) return lsq_device(ctx, sel, cap, cap, sel_n, 3, batch, cam, d_quat);
     // (the device-count form never reads anything back: its refit takes the cluster / launch-per-step solver with the inlier count on the device)
-    if (d_n) return lsq_device(ctx, sel, cap, cap, sel_n, 3, 1, cam, d_quat, /*multi=*/true);
+    if (d_n) return lsq_device(ctx, sel, cap, cap, sel_n, 3, batch, cam, d_quat, /*multi=*/true);
     // "Ransac samples" can reach 16000 (lib.rs:92-95): refit sets above 8192 need their size on the
     // host to pick the multi-launch path -- one small read-back per item.
     for (int b = 0; b < batch; ++b) {
@@ -1820,9 +1821,9 @@ int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
 
 int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
                      int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat,
-                     uint32_t lsq_min_n) {
+                     uint32_t lsq_min_n, int batch) {
     OFPS_REQUIRE(ctx, d_n, "almeida: null device count");
-    return almeida_impl(ctx, d_entries, n_max, d_n, 1, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat, lsq_min_n);
+    return almeida_impl(ctx, d_entries, n_max, d_n, batch, aspect, fov_y_deg, use_ransac, num_iters, inlier_deg, num_samples, seed, d_quat, lsq_min_n);
 }
 
 }  // namespace ofps

@@ -133,8 +133,9 @@ struct BatchStream {
         bool pending = false;
         hipEvent_t done = nullptr, uploaded = nullptr, prev_copied = nullptr;
         bool prev_copied_valid = false;
-        void* pinned = nullptr; size_t pinned_cap = 0;       // n x {result[4], quat[4]}
+        void* pinned = nullptr; size_t pinned_cap = 0;       // [n results][n quaternions][n kept counts, filtered tickets only]
         int n = 0, first_has_prev = 0, run_detector = 0, run_estimator = 0;
+        int filtered = 0;                // pushed with the batch filter switch and a criterion on: n kept counts follow the quaternions in the page-locked block
         size_t n_vectors = 0;
     };
     TicketRing<Ticket, kTickets> ring;
@@ -207,6 +208,7 @@ struct ofps_hip_ctx {
         int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
         int sad_predictors = 0;          // OFPS_HIP_SAD_PREDICTORS / ofps_hip_set_sad_predictors: 0 a refined block's one predictor is its parent's winner, 1 the parent's, its four lattice neighbours' and zero (sad_hier.hip, N1p); no effect at levels 1
         int sad_median = 0;              // OFPS_HIP_SAD_MEDIAN / ofps_hip_set_sad_median: 0 off, N in [1, 255] only blocks whose integer winner lies less than N pixels from the median of their kept lattice neighbours' (sad_median.hip, N1v)
+        int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
@@ -318,8 +320,8 @@ int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const uint8_t** pr
 int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
                            int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);
-// d_n (densify_device, densify_device_raw, detect_device; optional, batch == 1): the entry count lives in device memory -- n is the capacity,
-// the first min(*d_n, n) entries count, and nothing about the launches depends on the count
+// d_n (densify_device, densify_device_raw, detect_device; optional): the entry counts live in device memory, one per item -- n is the capacity
+// and the stride of every item, the first min(d_n[item], n) entries of an item count, and nothing about the launches depends on the counts
 int densify_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
                    uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, const uint32_t* d_n = nullptr);
 int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
@@ -354,32 +356,41 @@ void cluster_gate_context_created(int device);      // almeida.hip: the cluster 
 void cluster_gate_context_destroyed(int device);
 int almeida_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float aspect, float fov_y_deg,
                    int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat);
-// one problem whose record count lives in device memory: the estimate over the first min(*d_n, n_max) records; every launch is sized from n_max.
-// lsq_min_n: the least-squares fit of fewer records than this is the identity (RANSAC has its own rule: fewer than 3 inliers)
+// `batch` problems of n_max records each whose record counts live in device memory: item j's estimate over its first min(d_n[j], n_max)
+// records; every launch is sized from n_max.  One problem may take any solver, a batch the one-workgroup solver (n_max <= 8192) or the
+// launch-per-step one.  lsq_min_n: the least-squares fit of fewer records than this is the identity (RANSAC has its own rule: fewer than 3 inliers)
 int almeida_device_n(ofps_hip_ctx* ctx, const float4* d_entries, size_t n_max, const uint32_t* d_n, float aspect, float fov_y_deg,
                      int use_ransac, size_t num_iters, float inlier_deg, size_t num_samples, uint64_t seed, float4* d_quat,
-                     uint32_t lsq_min_n = 0);
+                     uint32_t lsq_min_n = 0, int batch = 1);
 
-// sad_gate.hip: hip_sad's contrast gate.  The flags buffer of a frame: [counts][kept count][keep flags]
-inline size_t gate_flags_bytes(size_t nblk) { return ((nblk * sizeof(uint32_t) + 15) & ~size_t(15)) + 16 + ((nblk + 15) & ~size_t(15)); }
+// sad_gate.hip: hip_sad's contrast gate.  The flags buffer of a frame: [counts][kept count][keep flags]; of a batch of `items` frames:
+// [items x nblk counts][items kept counts][items x nblk keep flags], item-major
+inline size_t gate_kept_bytes(size_t items) { return (items * sizeof(uint32_t) + 15) & ~size_t(15); }
+inline size_t gate_flags_bytes(size_t nblk, size_t items = 1) {
+    return ((items * nblk * sizeof(uint32_t) + 15) & ~size_t(15)) + gate_kept_bytes(items) + ((items * nblk + 15) & ~size_t(15));
+}
 inline uint32_t* gate_counts(char* flags) { return reinterpret_cast<uint32_t*>(flags); }
-inline uint32_t* gate_kept(char* flags, size_t nblk) { return reinterpret_cast<uint32_t*>(flags + ((nblk * sizeof(uint32_t) + 15) & ~size_t(15))); }
-inline uint8_t* gate_keep(char* flags, size_t nblk) { return reinterpret_cast<uint8_t*>(gate_kept(flags, nblk)) + 16; }
+inline uint32_t* gate_kept(char* flags, size_t nblk, size_t items = 1) {
+    return reinterpret_cast<uint32_t*>(flags + ((items * nblk * sizeof(uint32_t) + 15) & ~size_t(15)));
+}
+inline uint8_t* gate_keep(char* flags, size_t nblk, size_t items = 1) { return reinterpret_cast<uint8_t*>(gate_kept(flags, nblk, items)) + gate_kept_bytes(items); }
 
 // sad_consistency.hip: hip_sad's forward-backward consistency check (include/ofps_hip.h N1c)
 constexpr int kSadConsistencyMax = 129;                     // 2 * 64 + 1: above every residual of the largest search range
 int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);        // limit in [1, 129]
-// residual and / or keep byte per block from the two directions' integer winners, on stream st; d_keep_in (optional, may be d_out_keep) is ANDed in
+// residual and / or keep byte per block from the two directions' integer winners, on stream st; d_keep_in (optional, may be d_out_keep) is ANDed in.
+// items > 1: every array holds items x nblk, item-major; one launch, no partner block outside its item
 int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
-                                 const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st);
+                                 const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st, int items = 1);
 
 // sad_median.hip: hip_sad's median test (include/ofps_hip.h N1v)
 constexpr int kSadMedianMax = 255;
 int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);             // limit in [1, 255]
 // doubled residual and / or keep byte per block from the integer winners, on stream st; d_keep_in (optional: absent = all ones) is ANDed in
-// and may NOT be d_out_keep: a verdict reads its neighbours' incoming flags
+// and may NOT be d_out_keep: a verdict reads its neighbours' incoming flags.  items > 1: every array holds items x nblk, item-major; one
+// launch, no neighbour outside its item
 int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t* d_keep_in, int W, int H, int block, int limit,
-                            uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st);
+                            uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st, int items = 1);
 
 // sad_gate.hip: one pair's filtered search -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device -- in the
 // steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  The one-pair entry points run them all on ctx->stream
@@ -389,7 +400,11 @@ struct SadFilter {
     int W, H, stride, block, range;
     int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
-    size_t nblk = 0;
+    // the batched form (sad_flow_filtered_batch_device): pair k = (d_prev + k * prev_pitch, d_cur + k * cur_pitch), every per-block array
+    // below holds pairs x nblk, item-major, and every step stays one launch (1: the one-pair kernels, as ever)
+    int pairs = 1;
+    size_t prev_pitch = 0, cur_pitch = 0;
+    size_t nblk = 0;                     // per pair
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
     char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
     int *d_fwd = nullptr, *d_bwd = nullptr;      // S_CONS_FWD (limit > 0 or median > 0), S_CONS_BWD (limit > 0): the two directions' integer winners
@@ -398,8 +413,9 @@ struct SadFilter {
     uint8_t* d_med_keep = nullptr;       // S_MED_KEEP, this ticket's block: the median test's outgoing flags (median > 0)
     bool on() const { return gate > 0 || limit > 0 || median > 0; }
     bool winners() const { return limit > 0 || median > 0; }       // both read the forward search's INTEGER winners, whatever the motion scale
-    uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk) : nullptr; }
-    uint8_t* keep() const { return gate_keep(d_flags, nblk); }      // the incoming flags: contrast gate AND consistency check
+    size_t total() const { return (size_t)pairs * nblk; }
+    uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk, pairs) : nullptr; }
+    uint8_t* keep() const { return gate_keep(d_flags, nblk, pairs); }       // the incoming flags: contrast gate AND consistency check
     int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
     // the scratch slots; S_GATE_FLAGS holds `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
     int reserve(ofps_hip_ctx* ctx, int tix = 0, int tickets = 1);
@@ -407,13 +423,18 @@ struct SadFilter {
     int contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st);                    // gate > 0: counts and keep flags of `cur`, which they depend on alone
     // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] [median flags read from those, into
     // d_med_keep ->] kept records [and triples] in raster order -> count
+    // pairs > 1: d_out and d_out_best hold pairs slots of nblk, item k's kept ones lead slot k; d_count holds pairs counts
     int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
 };
+// S_GATE_FLAGS / S_MED_KEEP hold `tickets` blocks, this call's is number `tix`; `who` leads every error text
+int sad_flow_filtered_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, size_t prev_pitch, const uint8_t* d_cur, size_t cur_pitch, int pairs,
+                                   int W, int H, int stride, int block, int range, int min_pixels, int limit, int median, float4* d_out,
+                                   int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets);
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
                              int min_pixels, int limit, int median, float4* d_out, int* d_out_best, uint32_t* d_count);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
-// are read on the device.  d_n (optional, batch == 1): the record count in device memory, n the capacity.  d_out may equal d_entries.
+// are read on the device.  d_n (optional): the record counts in device memory, one per item, n the capacity.  d_out may equal d_entries.
 // d_quat_echo (optional): the quaternions are stored there as well (a ticket's result block)
 int compensate_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const uint32_t* d_n, float aspect, float fov_y_deg,
                       const float4* d_quat, float4* d_out, float4* d_quat_echo);
@@ -422,8 +443,8 @@ int compensate_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int 
 // TailSide: the detector's chain runs on `stream` beside the estimator -- forked on `fork_on` (recorded on the compute stream here unless it
 // `recorded` a point there already), joined through `join`.  Only when both stages run and nothing is compensated.
 struct TailSide { hipStream_t stream; hipEvent_t fork_on; bool recorded; hipEvent_t join; };
-// d_n (optional, batch == 1): the record count lives in device memory, n is the capacity, and the estimator takes its device-count form
-// (lsq_min_n: almeida_device_n).  seed0: item 0's seed, item j gets seed0 + j.  may_compensate: the context's detect-compensation mode
+// d_n (optional): the record counts live in device memory, d_n[j] item j's, n is the capacity and the stride of every item, and the
+// estimator takes its device-count form (lsq_min_n: almeida_device_n).  seed0: item 0's seed, item j gets seed0 + j.  may_compensate: the context's detect-compensation mode
 // counts here.  d_result [batch][4], d_quat [batch], d_field: device memory or a ticket's device-addressable block.  -> *out_dim (optional)
 int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batch, const uint32_t* d_n, uint32_t lsq_min_n,
                       const ofps_hip_frame_params* prm, uint64_t seed0, bool may_compensate, int* d_result, float4* d_quat, float2* d_field,

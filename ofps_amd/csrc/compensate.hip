@@ -24,14 +24,15 @@ namespace ofps {
 constexpr int kCompThreads = 256;
 constexpr unsigned kCompMaxBlocks = 2048;        // per item; the loop strides over the rest
 
-// n_dev != nullptr: the record count lives in device memory (the dense decoders' tail), n is the capacity the grid was sized from.
+// n_dev != nullptr: the record counts live in device memory, one per item (the dense decoders' tail, the filtered SAD tails), n is the
+// capacity the grid was sized from and the stride of every item.
 // quat_echo != nullptr: the item's quaternion is also stored there (a ticket's page-locked result block: the estimator wrote to device
 // memory so that this kernel reads it from there).
 __global__ __launch_bounds__(kCompThreads) void compensate_kernel(const float4* in, size_t n, const uint32_t* __restrict__ n_dev, Camera cam,
                                                                   const float4* __restrict__ quat, float4* out, float4* __restrict__ quat_echo) {
     const size_t item = blockIdx.y;
     size_t cnt = n;
-    if (n_dev) { const uint32_t c = *n_dev; cnt = c < n ? c : n; }
+    if (n_dev) { const uint32_t c = n_dev[item]; cnt = c < n ? c : n; }
     const float4 qv = quat[item];                                        // (w, i, j, k)
     const Quat inv = {qv.x, -qv.y, -qv.z, -qv.w};                        // orc_quat_inverse
     const Mat3 M = mat3_uniform(quat_to_mat3(inv));                      // orc_quat_to_homogeneous, 3 x 3 part
@@ -51,7 +52,6 @@ __global__ __launch_bounds__(kCompThreads) void compensate_kernel(const float4* 
 int compensate_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, const uint32_t* d_n, float aspect, float fov_y_deg,
                       const float4* d_quat, float4* d_out, float4* d_quat_echo) {
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "compensate: batch %d out of range", batch);
-    OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "compensate: a device-side count is for one item (batch %d)", batch);
     OFPS_REQUIRE(ctx, n < (1ull << 31), "compensate: too many entries");
     OFPS_REQUIRE(ctx, aspect > 0.0f && fov_y_deg > 0.0f && fov_y_deg < 180.0f, "compensate: bad camera (aspect=%g fov_y=%g)",
                  (double)aspect, (double)fov_y_deg);

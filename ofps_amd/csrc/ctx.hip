@@ -109,6 +109,9 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_SAD_PREFILTER")) {
         if (!unset && (iv < 0 || iv > kSadPrefilterMax)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kSadPrefilterMax);
         o.sad_prefilter = unset ? dflt.sad_prefilter : iv;
+    } else if (!strcmp(name, "OFPS_HIP_SAD_BATCH_FILTER")) {
+        if (!unset && strcmp(value, "0") && strcmp(value, "1")) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' is not 0|1", name, value);
+        o.sad_batch_filter = unset ? dflt.sad_batch_filter : iv;
     } else if (!strcmp(name, "OFPS_HIP_MULTI_RCCL")) {
         o.multi_rccl = unset ? 0 : (iv != 0);
     } else if (!strcmp(name, "OFPS_HIP_ALMEIDA_TEST_FAULT") || !strcmp(name, "OFPS_HIP_LK_TEST_FALL") ||
@@ -133,7 +136,7 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_SAD_KERNEL", "OFPS_HIP_DENSIFY_NO_SMALL", "OFPS_HIP_ALMEIDA_PATH", "OFPS_HIP_ALMEIDA_EPT", "OFPS_HIP_ALMEIDA_BLOCK",
     "OFPS_HIP_ALMEIDA_HIER", "OFPS_HIP_ALMEIDA_FAST", "OFPS_HIP_ALMEIDA_ONE_XCD", "OFPS_HIP_ALMEIDA_PROF", "OFPS_HIP_LK_PROF", "OFPS_HIP_LK_SERIAL", "OFPS_HIP_FB_PREPARE_AHEAD", "OFPS_HIP_MULTI_RCCL",
     "OFPS_HIP_SAD_MOTION_SCALE", "OFPS_HIP_DETECT_COMPENSATE", "OFPS_HIP_SAD_GATE", "OFPS_HIP_SAD_CONSISTENCY", "OFPS_HIP_SAD_LEVELS",
-    "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN"};
+    "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN", "OFPS_HIP_SAD_BATCH_FILTER"};
 
 }  // namespace ofps
 

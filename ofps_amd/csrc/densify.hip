@@ -40,22 +40,22 @@ __global__ __launch_bounds__(256) void cell_kernel(const float4* __restrict__ en
                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                    uint32_t* __restrict__ out_cells, uint32_t* __restrict__ begin,
                                                    uint32_t* __restrict__ end, size_t cells, const uint32_t* __restrict__ n_dev) {
-    // n_dev (optional; this and the kernels below): the entry count lives on the device.  The launches are sized for n, the capacity, and
-    // work on the first min(*n_dev, n) entries; such calls have one item, so the item * n offsets below are 0 either way.
-    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
-    const size_t item = blockIdx.y;
+    // n_dev (optional; this and the kernels below): the entry counts live on the device, one per item.  The launches are sized for n, the
+    // capacity and the stride of every item (at), and work on the first min(n_dev[item], n) entries of each.
+    const size_t item = blockIdx.y, at = item * n;
+    if (n_dev) { const size_t nd = (size_t)n_dev[item]; n = nd < n ? nd : n; }
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     // clear the per-cell [begin, end) tables bounds_kernel fills later on this stream (saves two memset launches)
     for (size_t c = i; c < cells; c += (size_t)gridDim.x * 256) { begin[item * cells + c] = 0; end[item * cells + c] = 0; }
     if (i >= n) return;
-    const float4 e = entries[item * n + i];
+    const float4 e = entries[at + i];
     uint32_t x, y;
     densifier_cell(e.x, e.y, w, h, x, y);
-    keys[item * n + i] = y * (uint32_t)w + x;
-    vals[item * n + i] = (uint32_t)i;
+    keys[at + i] = y * (uint32_t)w + x;
+    vals[at + i] = (uint32_t)i;
     if (out_cells) {
-        out_cells[2 * (item * n + i)] = x;
-        out_cells[2 * (item * n + i) + 1] = y;
+        out_cells[2 * (at + i)] = x;
+        out_cells[2 * (at + i) + 1] = y;
     }
 }
 
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(256) void cell_kernel(const float4* __restrict__ en
 __global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t* __restrict__ keys, size_t n, int shift,
                                                          int ntiles, uint32_t* __restrict__ hist, const uint32_t* __restrict__ n_dev) {
     __shared__ uint32_t cnt[256];
-    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
-    const size_t item = blockIdx.y;
+    const size_t item = blockIdx.y, at = item * n;
+    if (n_dev) { const size_t nd = (size_t)n_dev[item]; n = nd < n ? nd : n; }
     const int tile = blockIdx.x;
     cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t* __restr
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const size_t i = base + r * 256 + threadIdx.x;
-        if (i < n) atomicAdd(&cnt[(keys[item * n + i] >> shift) & 0xFF], 1u);
+        if (i < n) atomicAdd(&cnt[(keys[at + i] >> shift) & 0xFF], 1u);
     }
     __syncthreads();
     hist[(item * 256 + threadIdx.x) * ntiles + tile] = cnt[threadIdx.x];
@@ -122,10 +122,10 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
                                                            const uint32_t* __restrict__ digit_total,
                                                            uint32_t* __restrict__ keys_out,
                                                            uint32_t* __restrict__ vals_out, const uint32_t* __restrict__ n_dev) {
-    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     __shared__ uint32_t slot_cnt[16][256];      // [round*4 + wave][digit]
     __shared__ uint32_t dbase[256];             // exclusive prefix over the digit totals of this item
-    const size_t item = blockIdx.y;
+    const size_t item = blockIdx.y, at = item * n;
+    if (n_dev) { const size_t nd = (size_t)n_dev[item]; n = nd < n ? nd : n; }
     const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < 16 * 256; i += 256) (&slot_cnt[0][0])[i] = 0;
     {   // exclusive prefix over the 256 digit totals: wave scans + the four wave totals (one barrier)
@@ -145,8 +145,8 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
     for (int r = 0; r < 4; ++r) {
         const size_t i = base + r * 256 + tid;
         ok[r] = i < n;
-        key[r] = ok[r] ? keys_in[item * n + i] : 0xFFFFFFFFu;
-        val[r] = ok[r] ? vals_in[item * n + i] : 0u;
+        key[r] = ok[r] ? keys_in[at + i] : 0xFFFFFFFFu;
+        val[r] = ok[r] ? vals_in[at + i] : 0u;
         const uint32_t d = (key[r] >> shift) & 0xFF;
         // lanes holding the same digit (inactive tail lanes are excluded through `ok`)
         unsigned long long same = __ballot(ok[r]);
@@ -171,8 +171,8 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
         if (!ok[r]) continue;
         const uint32_t d = (key[r] >> shift) & 0xFF;
         const size_t pos = (size_t)dbase[d] + hist[(item * 256 + d) * ntiles + tile] + slot_cnt[r * 4 + wave][d] + rank[r];
-        keys_out[item * n + pos] = key[r];
-        vals_out[item * n + pos] = val[r];
+        keys_out[at + pos] = key[r];
+        vals_out[at + pos] = val[r];
     }
 }
 
@@ -180,11 +180,11 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
 __global__ __launch_bounds__(256) void bounds_kernel(const uint32_t* __restrict__ keys, size_t n, size_t cells,
                                                      uint32_t* __restrict__ cell_begin, uint32_t* __restrict__ cell_end,
                                                      const uint32_t* __restrict__ n_dev) {
-    if (n_dev) { const size_t nd = (size_t)*n_dev; n = nd < n ? nd : n; }
     const size_t item = blockIdx.y;
+    const uint32_t* k = keys + item * n;
+    if (n_dev) { const size_t nd = (size_t)n_dev[item]; n = nd < n ? nd : n; }
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint32_t* k = keys + item * n;
     const uint32_t c = k[i];
     if (i == 0 || k[i - 1] != c) cell_begin[item * cells + c] = (uint32_t)i;
     if (i == n - 1 || k[i + 1] != c) cell_end[item * cells + c] = (uint32_t)(i + 1);
@@ -247,7 +247,8 @@ constexpr size_t kSmallLds = (size_t)kSmallMaxN * sizeof(float2) + (size_t)kSmal
 __global__ __launch_bounds__(1024) void densify_small_kernel(const float4* __restrict__ entries, uint32_t n, int w, int h,
                                                              float2* __restrict__ out_field, uint32_t* __restrict__ cell_begin,
                                                              uint32_t* __restrict__ cell_end, const uint32_t* __restrict__ n_dev) {
-    if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; }               // (one item: see cell_kernel)
+    const size_t at = (size_t)blockIdx.x * n;                                    // the item's entries: n is the capacity and the stride
+    if (n_dev) { const uint32_t nd = n_dev[blockIdx.x]; n = nd < n ? nd : n; }
     extern __shared__ __attribute__((aligned(16))) uint8_t small_lds[];
     float2* mot = reinterpret_cast<float2*>(small_lds);                          // [kSmallMaxN] motion of entry i
     uint16_t* sorted = reinterpret_cast<uint16_t*>(mot + kSmallMaxN);            // [kSmallMaxN] entry index by (cell, input order)
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(1024) void densify_small_kernel(const float4* __res
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {                                           // all of a thread's entries requested at once: the
         const uint32_t i = (uint32_t)(wave * ROUNDS + r) * 64u + (uint32_t)lane;  // ballots below would expose one round trip per round
-        ent[r] = entries[item * n + (i < n ? i : (n ? n - 1 : 0))];      // (n == 0: a device-side count; nothing of the record is used)
+        ent[r] = entries[at + (i < n ? i : (n ? n - 1 : 0))];      // (n == 0: a device-side count; nothing of the record is used)
     }
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
@@ -662,8 +663,8 @@ int densify_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int bat
 int densify_device_raw(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, int w, int h, float2* d_field,
                        uint32_t* d_cells, uint32_t** out_begin, uint32_t** out_end, float2* d_sum, float* d_cnt,
                        const float* d_weights, const uint32_t* d_n) {
-    // d_n (optional, batch == 1): the entry count on the device; n is then the capacity, and the path and every grid are chosen from it
-    OFPS_REQUIRE(ctx, d_n == nullptr || batch == 1, "densify: a device-side count is for one item (batch %d)", batch);
+    // d_n (optional): the entry counts on the device, one per item; n is then every item's capacity and stride, and the path and every grid
+    // are chosen from it
     const size_t cells = (size_t)w * (size_t)h;
     OFPS_REQUIRE(ctx, w >= 1 && h >= 1 && cells <= 65536, "densify: grid %dx%d unsupported (1..65536 cells)", w, h);
     OFPS_REQUIRE(ctx, batch >= 1 && batch <= 65535, "densify: batch %d out of range", batch);

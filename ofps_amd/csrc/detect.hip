@@ -102,7 +102,7 @@ static int block_dim_host(float min_size, size_t subdivide) {          // lib.rs
     return (int)d;
 }
 
-// d_n (optional, batch == 1): the entry count on the device -- n is the capacity (densify.hip)
+// d_n (optional): the entry counts on the device, one per item -- n is the capacity and the stride of every item (densify.hip)
 int detect_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float min_size, size_t subdivide,
                   float target_motion, int* d_result, float2* d_out_field, int* out_dim, const uint32_t* d_n) {
     const int dim = block_dim_host(min_size, subdivide);

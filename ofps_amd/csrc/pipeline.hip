@@ -325,9 +325,18 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const size_t pitch = (size_t)dstride * H;
     const size_t nblk = ofps_hip_sad_block_count(W, H, prm->block);
     const int tix = (int)(tno % kTickets);
+    // the batch filter switch (include/ofps_hip.h N1b) with a criterion on: the filtered batched search and the tail's per-item device counts;
+    // the ticket follows the settings the context has now.  Else everything below is what it is without the switch
+    const auto& o = ctx->opt;
+    const bool filtered = o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0);
+    if (filtered) {                                              // refused before anything is uploaded
+        SadFilter chk{W, H, dstride, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, /*want_triples=*/false};
+        rc = chk.plan(ctx, "push_frames_async");
+        if (rc != OFPS_HIP_OK) return rc;
+    }
     // capacity: both buffers and the per-ticket outputs are sized for the largest batch seen (grow-only; growing waits
     // for work in flight)
-    constexpr size_t kOutBytes = sizeof(TailRecord);             // per frame
+    const size_t out_bytes = sizeof(TailRecord) + (filtered ? sizeof(uint32_t) : 0);      // per frame; filtered: the n kept counts behind the n quaternions
     const size_t cap_frames = (size_t)n + 1;
     auto& fs = ctx->scratch[ofps::S_BATCH_FRAMES];
     size_t per_buf = fs.cap / kTickets / (pitch ? pitch : 1);
@@ -355,13 +364,13 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     auto* bufs = static_cast<uint8_t*>(fs.p);
     uint8_t* buf = bufs + (size_t)tix * per_buf * pitch;        // [slot 0 = previous frame][n frames]
     auto* d_ent_all = static_cast<float4*>(ofps::scratch(ctx, ofps::S_BATCH_ENTRIES, kTickets * (size_t)n * nblk * sizeof(float4)));
-    auto* d_out_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_BATCH_OUT, kTickets * (size_t)n * kOutBytes));
+    auto* d_out_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_BATCH_OUT, kTickets * (size_t)n * out_bytes));
     if (!d_ent_all || !d_out_all) return OFPS_HIP_ENOMEM;
     const size_t ent_per_ticket = ctx->scratch[ofps::S_BATCH_ENTRIES].cap / kTickets / sizeof(float4);
     const size_t out_per_ticket = ctx->scratch[ofps::S_BATCH_OUT].cap / kTickets;
     float4* d_ent = d_ent_all + (size_t)tix * ent_per_ticket;
     char* d_out = d_out_all + (size_t)tix * out_per_ticket;
-    rc = host_block_reserve(ctx, &t.pinned, &t.pinned_cap, (size_t)n * kOutBytes);
+    rc = host_block_reserve(ctx, &t.pinned, &t.pinned_cap, (size_t)n * out_bytes);
     if (rc != OFPS_HIP_OK) return rc;
     hipStream_t s = ctx->stream, up = ctx->pipe.copy_stream;
     // ---- copy stream: the n frames in one transfer (the buffer's previous tenant, ticket tno - 2, has been collected:
@@ -393,10 +402,19 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const int first = has_prev ? 0 : 1;                           // the stream's very first frame has no pair
     const int pairs = n - first;
     t.n = n; t.first_has_prev = has_prev ? 1 : 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.n_vectors = nblk;
+    t.filtered = filtered && pairs > 0;
     if (pairs > 0) {
         float4* ent0 = d_ent + (size_t)first * nblk;
-        rc = ofps::sad_pairs_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
-                                    prm->block, prm->range, ent0, nullptr);
+        // filtered: item j's kept records lead its slot of the record buffer, its count is word j behind the quaternions.  Searches, flags
+        // and the compaction run on the compute stream, in front of the tail that reads the counts there
+        uint32_t* d_cnt = filtered ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
+        if (filtered)
+            rc = sad_flow_filtered_batch_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
+                                                prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
+                                                "push_frames_async", tix, kTickets);
+        else
+            rc = ofps::sad_pairs_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
+                                        prm->block, prm->range, ent0, nullptr);
         if (rc != OFPS_HIP_OK) return rc;
         auto* d_res = reinterpret_cast<int(*)[4]>(d_out);                           // [n][4]
         float4* d_quat = reinterpret_cast<float4*>(d_out + (size_t)n * kBatchResult); // [n]
@@ -407,11 +425,12 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         }
         // one estimator launch, [one compensation launch,] one detector chain over the batch, item j seeded seed + j.  The multi-device
         // dispatcher's worker contexts (halo_mode 1) keep the raw detector whatever their detect-compensation mode
-        rc = frame_tail_device(ctx, ent0, nblk, pairs, nullptr, 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode, d_res[first],
-                               d_quat + first, d_field, nullptr, nullptr);
+        // filtered: the tail's device-count forms with one count per item; fewer than 3 kept -> identity, as in the filtered per-frame path
+        rc = frame_tail_device(ctx, ent0, nblk, pairs, d_cnt, filtered ? 3 : 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode,
+                               d_res[first], d_quat + first, d_field, nullptr, nullptr);
         if (rc != OFPS_HIP_OK) return rc;
-        if (prm->run_detector || prm->run_estimator) {
-            rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * kOutBytes, s);
+        if (filtered || prm->run_detector || prm->run_estimator) {         // (the kept counts travel in this read-back)
+            rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * out_bytes, s);
             if (rc != OFPS_HIP_OK) return rc;
         }
         if (out_entries) {
@@ -451,6 +470,10 @@ int ofps_hip_frames_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* o
         o.have_vectors = has ? 1 : 0;
         o.n_vectors = has ? t->n_vectors : 0;
         if (!has) continue;
+        if (t->filtered) {
+            const auto* kept = reinterpret_cast<const uint32_t*>(static_cast<const char*>(t->pinned) + (size_t)t->n * sizeof(TailRecord));
+            if (kept[j] < o.n_vectors) o.n_vectors = kept[j];
+        }
         if (t->run_detector) { o.has_motion = res[j][0]; o.area = (size_t)res[j][1]; o.dim = res[j][2]; }
         if (t->run_estimator) memcpy(o.quat, quat[j], sizeof(o.quat));
     }

@@ -19,9 +19,8 @@ namespace ofps {
 
 // fwd / bwd: (dx, dy, sad) triples in integer pixels, only dx and dy are read.  keep_in (optional, may alias out_keep: a lane reads and
 // writes its own byte only) is ANDed in.  Garbage winners (|d| > 64) give an unspecified flag: k' is clamped on both sides.
-__global__ __launch_bounds__(256) void sad_consistency_kernel(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B,
-                                                              int limit, const uint8_t* keep_in, uint32_t* __restrict__ out_residual,
-                                                              uint8_t* out_keep) {
+__device__ __forceinline__ void sad_consistency_block(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B, int limit,
+                                                      const uint8_t* keep_in, uint32_t* __restrict__ out_residual, uint8_t* out_keep) {
     const uint32_t nblk = (uint32_t)nbx * (uint32_t)nby;
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= nblk) return;
@@ -47,6 +46,21 @@ __global__ __launch_bounds__(256) void sad_consistency_kernel(const int* __restr
     }
 }
 
+__global__ __launch_bounds__(256) void sad_consistency_kernel(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B,
+                                                              int limit, const uint8_t* keep_in, uint32_t* __restrict__ out_residual,
+                                                              uint8_t* out_keep) {
+    sad_consistency_block(fwd, bwd, nbx, nby, B, limit, keep_in, out_residual, out_keep);
+}
+
+// the batched form: blockIdx.y is the item, every array nbx * nby elements per item.  The partner block is clamped into the item's own lattice
+__global__ __launch_bounds__(256) void sad_consistency_items_kernel(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B,
+                                                                    int limit, const uint8_t* keep_in, uint32_t* __restrict__ out_residual,
+                                                                    uint8_t* out_keep) {
+    const size_t at = (size_t)blockIdx.y * ((size_t)nbx * nby);
+    sad_consistency_block(fwd + 3 * at, bwd + 3 * at, nbx, nby, B, limit, keep_in ? keep_in + at : nullptr, out_residual ? out_residual + at : nullptr,
+                          out_keep ? out_keep + at : nullptr);
+}
+
 int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* who) {
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "%s: block=%d outside [1,64]", who, block);
     OFPS_REQUIRE(ctx, limit >= 1 && limit <= kSadConsistencyMax, "%s: consistency limit %d outside [1, %d]", who, limit, kSadConsistencyMax);
@@ -54,16 +68,21 @@ int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* w
 }
 
 int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
-                                 const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st) {
+                                 const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st, int items) {
     const int rc = sad_consistency_check(ctx, block, limit, "sad_consistency");
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, W >= 1 && H >= 1, "sad_consistency: bad geometry W=%d H=%d", W, H);
     const int nbx = W / block, nby = H / block;
     if (nbx == 0 || nby == 0) return OFPS_HIP_OK;
     OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "sad_consistency: too many blocks");
+    OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "sad_consistency: %d items", items);
     const size_t nblk = (size_t)nbx * nby;
-    hipLaunchKernelGGL(sad_consistency_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_fwd_best, d_bwd_best, nbx, nby, block,
-                       limit, d_keep_in, d_out_residual, d_out_keep);
+    if (items > 1)
+        hipLaunchKernelGGL(sad_consistency_items_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_fwd_best, d_bwd_best,
+                           nbx, nby, block, limit, d_keep_in, d_out_residual, d_out_keep);
+    else
+        hipLaunchKernelGGL(sad_consistency_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_fwd_best, d_bwd_best, nbx, nby, block,
+                           limit, d_keep_in, d_out_residual, d_out_keep);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }

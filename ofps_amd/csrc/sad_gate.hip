@@ -10,16 +10,20 @@
 // result does not depend on the order).
 // block_keep_kernel: count >= min_pixels -> one byte per block, the flag the ordered compactions of mask.hip take.
 // compact_best_kernel: the (dx, dy, SAD) triples compacted by the same flags in the same order.
+// block_contrast_items_kernel, compact_items_kernel: the batched forms (include/ofps_hip.h N1b) -- the item in a grid dimension, one launch
+// over a whole batch of pairs; the compaction segmented: one workgroup per item, records + triples + one count per item.
 //
 // Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate, the consistency check (sad_consistency.hip)
-// and / or the median test (sad_median.hip) in front of one compaction and one device-side count -- for the one-pair entry points and the fused per-frame path.
+// and / or the median test (sad_median.hip) in front of one compaction and one device-side count -- for the one-pair entry points, the fused
+// per-frame path and, over `pairs` pairs at once, ofps_hip_sad_flow_filtered_dev and the batched stream forms (pipeline.hip).
 #include "common.hpp"
 #include "mask_tile.hpp"
 
 namespace ofps {
 
-__global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx,
-                                                             int nby, int lattice, uint32_t* __restrict__ counts) {
+// one workgroup's tile of one frame: what both kernels below run
+__device__ __forceinline__ void block_contrast_tile(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx, int nby,
+                                                    int lattice, uint32_t* __restrict__ counts) {
     __shared__ uint8_t g[MG_H][MG_W + 2];
     __shared__ short hx[MG_H][MS_W + 2];
     __shared__ unsigned long long rowbits[MS_H][2];          // thresholded window, one bit per column
@@ -57,6 +61,18 @@ __global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __re
     if (lattice) counts[(size_t)by * nbx + bx] = c; else if (c) atomicAdd(&counts[(size_t)by * nbx + bx], c);
 }
 
+__global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx,
+                                                             int nby, int lattice, uint32_t* __restrict__ counts) {
+    block_contrast_tile(gray, W, H, stride, block, nbx, nby, lattice, counts);
+}
+
+// the batched form: blockIdx.z is the item, its frame `pitch` bytes behind the previous item's, its counts nbx * nby behind
+__global__ __launch_bounds__(256) void block_contrast_items_kernel(const uint8_t* __restrict__ gray, size_t pitch, int W, int H, int stride,
+                                                                   int block, int nbx, int nby, int lattice, uint32_t* __restrict__ counts) {
+    const size_t item = blockIdx.z;
+    block_contrast_tile(gray + item * pitch, W, H, stride, block, nbx, nby, lattice, counts + item * (size_t)nbx * nby);
+}
+
 __global__ __launch_bounds__(256) void block_keep_kernel(const uint32_t* __restrict__ counts, uint32_t n, uint32_t min_pixels,
                                                          uint8_t* __restrict__ keep) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -89,6 +105,63 @@ __global__ __launch_bounds__(1024) void compact_best_kernel(const int* __restric
     }
 }
 
+// The segmented ordered compaction of the batched filtered search: workgroup `item` scans its own n flags with the scheme above -- one path
+// for every n -- and writes its kept records [and triples] to the head of its own n-record slot and their number to counts[item].
+__global__ __launch_bounds__(1024) void compact_items_kernel(const float4* __restrict__ in, const int* __restrict__ in_best,
+                                                             const uint8_t* __restrict__ keep_flags, uint32_t n, float4* __restrict__ out,
+                                                             int* __restrict__ out_best, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t wtot[16];
+    __shared__ uint32_t base_sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t item = blockIdx.x, i_base = item * n;
+    in += i_base; out += i_base; keep_flags += i_base;
+    const bool triples = in_best && out_best;
+    if (triples) { in_best += 3 * i_base; out_best += 3 * i_base; }
+    if (tid == 0) base_sh = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < n; i0 += 1024) {
+        const uint32_t i = i0 + tid;
+        const bool keep = i < n && keep_flags[i];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        int v0 = 0, v1 = 0, v2 = 0;
+        if (keep) {
+            v = in[i];
+            if (triples) { v0 = in_best[3 * (size_t)i]; v1 = in_best[3 * (size_t)i + 1]; v2 = in_best[3 * (size_t)i + 2]; }
+        }
+        const unsigned long long bal = __ballot(keep);
+        const uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base_sh;
+        for (int k = 0; k < wave; ++k) off += wtot[k];
+        if (keep) {                                           // off + rank <= i: inside the item's slot
+            out[off + rank] = v;
+            if (triples) { int* o = out_best + 3 * (size_t)(off + rank); o[0] = v0; o[1] = v1; o[2] = v2; }
+        }
+        __syncthreads();
+        if (tid == 0) { uint32_t t = 0; for (int k = 0; k < 16; ++k) t += wtot[k]; base_sh += t; }
+        __syncthreads();
+    }
+    if (tid == 0) counts[item] = base_sh;
+}
+
+// items > 1: frame k lies k * pitch bytes behind d_luma, its counts k * nblk behind d_counts; one launch over all of them
+static int block_contrast_items_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, size_t pitch, int items, int W, int H, int stride, int block,
+                                       uint32_t* d_counts, hipStream_t st) {
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
+    OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
+    OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "block_contrast: %d items", items);
+    const int nbx = W / block, nby = H / block;
+    if (nbx == 0 || nby == 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, (long long)nbx * nby * items < (1ll << 31), "block_contrast: too many blocks");
+    const int lattice = block == 8 || block == 16;
+    if (!lattice) OFPS_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)items * nbx * nby * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(block_contrast_items_kernel, dim3((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H, items), dim3(256), 0, st, d_luma, pitch, W, H,
+                       stride, block, nbx, nby, lattice, d_counts);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
 int block_contrast_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, int W, int H, int stride, int block, uint32_t* d_counts, hipStream_t st) {
     OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
@@ -117,14 +190,16 @@ int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     if (rc == OFPS_HIP_OK && median > 0) rc = sad_median_check(ctx, block, median, who);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "%s: bad geometry W=%d H=%d stride=%d", who, W, H, stride);
+    OFPS_REQUIRE(ctx, pairs >= 1 && pairs <= 65535, "%s: %d pairs outside [1, 65535]", who, pairs);
     nblk = ofps_hip_sad_block_count(W, H, block);
+    OFPS_REQUIRE(ctx, pairs == 1 || total() < (size_t(1) << 31), "%s: too many blocks (%d pairs of %zu)", who, pairs, nblk);
     return OFPS_HIP_OK;
 }
 
 int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
     if (!on()) return OFPS_HIP_OK;
-    const size_t fbytes = gate_flags_bytes(nblk), tri = nblk * 3 * sizeof(int);
-    d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, nblk * sizeof(float4)));
+    const size_t fbytes = gate_flags_bytes(nblk, pairs), tri = total() * 3 * sizeof(int);
+    d_raw = static_cast<float4*>(scratch(ctx, S_GATE_RAW, total() * sizeof(float4)));
     auto* flags = static_cast<char*>(scratch(ctx, S_GATE_FLAGS, tickets * fbytes));
     if (!d_raw || !flags) return OFPS_HIP_ENOMEM;
     d_flags = flags + tix * fbytes;
@@ -134,11 +209,11 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
     }
     if (limit > 0) {
         d_bwd = static_cast<int*>(scratch(ctx, S_CONS_BWD, tri));
-        d_bwd_ent = static_cast<float4*>(scratch(ctx, S_CONS_BWD_ENT, nblk * sizeof(float4)));     // the search kernels always write records
+        d_bwd_ent = static_cast<float4*>(scratch(ctx, S_CONS_BWD_ENT, total() * sizeof(float4)));     // the search kernels always write records
         if (!d_bwd || !d_bwd_ent) return OFPS_HIP_ENOMEM;
     }
     if (median > 0) {
-        const size_t mbytes = (nblk + 15) & ~size_t(15);
+        const size_t mbytes = (total() + 15) & ~size_t(15);
         auto* mk = static_cast<uint8_t*>(scratch(ctx, S_MED_KEEP, tickets * mbytes));
         if (!mk) return OFPS_HIP_ENOMEM;
         d_med_keep = mk + tix * mbytes;
@@ -149,38 +224,47 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
 }
 
 int SadFilter::search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out) {
-    if (!winners()) return sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
+    if (!winners()) return sad_pairs_device(ctx, d_prev, prev_pitch, d_cur, cur_pitch, pairs, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
     // check or median test on (the two hazards: sad_consistency.hip): the forward search leaves its integer winners in d_fwd whatever the motion scale -- at
     // scale 4 as d_int_best, the refinement then writes d_triples or nothing -- and the backward search, integer only, runs right behind it
     const bool qpel = ctx->opt.sad_motion_scale == 4;
-    const int rc = sad_pairs_device(ctx, d_prev, 0, d_cur, 0, 1, W, H, stride, block, range, d_raw, qpel ? d_triples : d_fwd, /*integer_only=*/false,
-                                    qpel ? d_fwd : nullptr);
+    const int rc = sad_pairs_device(ctx, d_prev, prev_pitch, d_cur, cur_pitch, pairs, W, H, stride, block, range, d_raw, qpel ? d_triples : d_fwd,
+                                    /*integer_only=*/false, qpel ? d_fwd : nullptr);
     if (rc != OFPS_HIP_OK || limit == 0) return rc;
-    return sad_pairs_device(ctx, d_cur, 0, d_prev, 0, 1, W, H, stride, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
+    return sad_pairs_device(ctx, d_cur, cur_pitch, d_prev, prev_pitch, pairs, W, H, stride, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
 }
 
 int SadFilter::contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st) {
     if (gate <= 0 || !nblk) return OFPS_HIP_OK;
-    const int rc = block_contrast_device(ctx, d_cur, W, H, stride, block, gate_counts(d_flags), st);
+    const int rc = pairs == 1 ? block_contrast_device(ctx, d_cur, W, H, stride, block, gate_counts(d_flags), st)
+                              : block_contrast_items_device(ctx, d_cur, cur_pitch, pairs, W, H, stride, block, gate_counts(d_flags), st);
     if (rc != OFPS_HIP_OK) return rc;
-    hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, gate_counts(d_flags), (uint32_t)nblk, (uint32_t)gate, keep());
+    // a flag depends on its own count alone: the batch's pairs * nblk counts are one array to this kernel
+    hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((total() + 255) / 256)), dim3(256), 0, st, gate_counts(d_flags), (uint32_t)total(), (uint32_t)gate, keep());
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
 
 int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count) {
     if (!on()) return OFPS_HIP_OK;
-    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream)
+    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream, pairs)
                        : OFPS_HIP_OK;
     if (rc != OFPS_HIP_OK) return rc;
     // one pass: the median test reads the other criteria's flags (none on: all ones) and writes its own array
-    if (median > 0) rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, W, H, block, median, nullptr, d_med_keep, ctx->stream);
+    if (median > 0)
+        rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, W, H, block, median, nullptr, d_med_keep, ctx->stream, pairs);
     if (rc != OFPS_HIP_OK) return rc;
     if (nblk == 0) {
-        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, pairs * sizeof(uint32_t), ctx->stream));
         return OFPS_HIP_OK;
     }
     const uint8_t* flags = median > 0 ? d_med_keep : keep();
+    if (pairs > 1) {                                          // one workgroup per item, whatever nblk: records, triples and counts[item] in one launch
+        hipLaunchKernelGGL(compact_items_kernel, dim3((unsigned)pairs), dim3(1024), 0, ctx->stream, d_raw, d_out_best ? d_triples : nullptr, flags,
+                           (uint32_t)nblk, d_out, d_out_best, d_count);
+        OFPS_HIP_TRY(ctx, hipGetLastError());
+        return OFPS_HIP_OK;
+    }
     rc = nblk <= kCompactSmallMax ? compact_small_device(ctx, d_raw, flags, nblk, d_out, d_count)
                                   : compact_entries_device(ctx, d_raw, flags, nblk, d_out, d_count);
     if (rc != OFPS_HIP_OK) return rc;
@@ -202,9 +286,45 @@ int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uin
     return rc == OFPS_HIP_OK ? f.finish(ctx, d_out, d_out_best, d_count) : rc;
 }
 
+// `pairs` pairs, pair k = (d_prev + k * prev_pitch, d_cur + k * cur_pitch), everything on ctx->stream, the launch count independent of `pairs`:
+// item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k] is their number
+int sad_flow_filtered_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, size_t prev_pitch, const uint8_t* d_cur, size_t cur_pitch, int pairs,
+                                   int W, int H, int stride, int block, int range, int min_pixels, int limit, int median, float4* d_out,
+                                   int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets) {
+    SadFilter f{W, H, stride, block, range, min_pixels, limit, median, d_out_best != nullptr};
+    f.pairs = pairs; f.prev_pitch = prev_pitch; f.cur_pitch = cur_pitch;
+    int rc = f.plan(ctx, who);
+    if (rc == OFPS_HIP_OK) rc = f.reserve(ctx, tix, tickets);
+    if (rc == OFPS_HIP_OK) rc = f.search(ctx, d_prev, d_cur, d_out);
+    if (rc == OFPS_HIP_OK) rc = f.contrast_flags(ctx, d_cur, ctx->stream);
+    return rc == OFPS_HIP_OK ? f.finish(ctx, d_out, d_out_best, d_counts) : rc;
+}
+
 }  // namespace ofps
 
 extern "C" {
+
+int ofps_hip_sad_flow_filtered_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                   int block, int range, int min_pixels, int limit, int median, void* d_out_entries, void* d_out_best,
+                                   void* d_out_counts) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_frames && d_out_entries && d_out_counts, "sad_flow_filtered_dev: null device pointer");
+    OFPS_REQUIRE(ctx, n_frames >= 2, "sad_flow_filtered_dev: need at least 2 frames (got %d)", n_frames);
+    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow_filtered_dev: bad geometry W=%d H=%d stride=%d", W, H, stride);
+    OFPS_REQUIRE(ctx, frame_pitch >= (size_t)stride * (size_t)H, "sad_flow_filtered_dev: frame_pitch smaller than a frame");
+    OFPS_REQUIRE(ctx, ref_mode == 0 || ref_mode == 1, "sad_flow_filtered_dev: ref_mode must be 0 or 1");
+    OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow_filtered_dev: contrast gate %d is negative", min_pixels);
+    OFPS_REQUIRE(ctx, limit >= 0, "sad_flow_filtered_dev: consistency limit %d is negative", limit);
+    OFPS_REQUIRE(ctx, median >= 0, "sad_flow_filtered_dev: median limit %d is negative", median);
+    OFPS_REQUIRE(ctx, min_pixels > 0 || limit > 0 || median > 0,
+                 "sad_flow_filtered_dev: contrast gate, consistency limit and median limit are all 0 (the unfiltered form is ofps_hip_sad_flow_dev)");
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto* f = static_cast<const uint8_t*>(d_frames);
+    // the current frame of pair k is frame k + 1 in both modes: the gate reads it, the backward search starts from it
+    return ofps::sad_flow_filtered_batch_device(ctx, f, ref_mode ? 0 : frame_pitch, f + frame_pitch, frame_pitch, n_frames - 1, W, H, stride, block,
+                                                range, min_pixels, limit, median, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                                static_cast<uint32_t*>(d_out_counts), "sad_flow_filtered_dev", 0, 1);
+}
 
 int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts) {
     if (!ctx) return OFPS_HIP_EINVAL;
@@ -240,6 +360,15 @@ int ofps_hip_set_sad_gate(ofps_hip_ctx* ctx, int min_pixels) {
 }
 
 int ofps_hip_get_sad_gate(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.sad_gate : OFPS_HIP_EINVAL; }
+
+int ofps_hip_set_sad_batch_filter(ofps_hip_ctx* ctx, int on) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, on == 0 || on == 1, "set_sad_batch_filter: %d is not 0|1", on);
+    ctx->opt.sad_batch_filter = on;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_sad_batch_filter(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.sad_batch_filter : OFPS_HIP_EINVAL; }
 
 int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
                                 int min_pixels, void* d_out_entries, void* d_out_best, void* d_out_count) {

@@ -41,8 +41,8 @@ __device__ __forceinline__ unsigned long long half_pel_distance(const int (&s)[8
 // best: (dx, dy, sad) triples in integer pixels, only dx and dy are read.  keep_in (optional: absent = all ones) must NOT alias out_keep: a
 // lane reads its neighbours' bytes.  An unkept or off-lattice neighbour sorts to the end as INT_MAX -- a kept winner that holds INT_MAX
 // itself ties with it, and a tie leaves the first n sorted values what they are.  The residual saturates at 2^32 - 1.
-__global__ __launch_bounds__(256) void sad_median_kernel(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
-                                                         uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
+__device__ __forceinline__ void sad_median_block(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
+                                                 uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
     const uint32_t nblk = (uint32_t)nbx * (uint32_t)nby;
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= nblk) return;
@@ -73,6 +73,20 @@ __global__ __launch_bounds__(256) void sad_median_kernel(const int* __restrict__
     if (out_keep) out_keep[k] = r2 < limit2 && (!keep_in || keep_in[k] != 0) ? 1 : 0;
 }
 
+__global__ __launch_bounds__(256) void sad_median_kernel(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
+                                                         uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
+    sad_median_block(best, keep_in, nbx, nby, limit2, out_residual2, out_keep);
+}
+
+// the batched form: blockIdx.y is the item, every array nbx * nby elements per item.  A neighbour index is formed inside the item's own
+// lattice (x in [0, nbx), y in [0, nby)) and never reaches another item's blocks
+__global__ __launch_bounds__(256) void sad_median_items_kernel(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
+                                                               uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
+    const size_t at = (size_t)blockIdx.y * ((size_t)nbx * nby);
+    sad_median_block(best + 3 * at, keep_in ? keep_in + at : nullptr, nbx, nby, limit2, out_residual2 ? out_residual2 + at : nullptr,
+                     out_keep ? out_keep + at : nullptr);
+}
+
 int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who) {
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "%s: block=%d outside [1,64]", who, block);
     OFPS_REQUIRE(ctx, limit >= 1 && limit <= kSadMedianMax, "%s: median limit %d outside [1, %d]", who, limit, kSadMedianMax);
@@ -80,7 +94,7 @@ int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who) {
 }
 
 int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t* d_keep_in, int W, int H, int block, int limit,
-                            uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st) {
+                            uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st, int items) {
     const int rc = sad_median_check(ctx, block, limit, "sad_median");
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, W >= 1 && H >= 1, "sad_median: bad geometry W=%d H=%d", W, H);
@@ -88,9 +102,14 @@ int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t*
     const int nbx = W / block, nby = H / block;
     if (nbx == 0 || nby == 0) return OFPS_HIP_OK;
     OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "sad_median: too many blocks");
+    OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "sad_median: %d items", items);
     const size_t nblk = (size_t)nbx * nby;
-    hipLaunchKernelGGL(sad_median_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_best, d_keep_in, nbx, nby,
-                       2u * (uint32_t)limit, d_out_residual2, d_out_keep);
+    if (items > 1)
+        hipLaunchKernelGGL(sad_median_items_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_best, d_keep_in, nbx,
+                           nby, 2u * (uint32_t)limit, d_out_residual2, d_out_keep);
+    else
+        hipLaunchKernelGGL(sad_median_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_best, d_keep_in, nbx, nby,
+                           2u * (uint32_t)limit, d_out_residual2, d_out_keep);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }

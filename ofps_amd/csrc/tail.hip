@@ -1,7 +1,7 @@
 // tail.hip -- the tail of every fused entry point: estimator -> [compensation ->] detector on device-resident records, the results stored by
 // the stages' last kernels where the caller says (a ticket's device-addressable block, or scratch it reads back).  The per-frame SAD path
 // (pipeline.hip: one item, the count on the host or -- filtered -- on the device, the detector beside the estimator), its batched form
-// (n items; the multi-device workers among them) and the dense decoders' fused form (dense_decoder.hip: the count on the device) differ in
+// (n items, their counts on the host or -- filtered -- one per item on the device; the multi-device workers among them) and the dense decoders' fused form (dense_decoder.hip: the count on the device) differ in
 // the arguments alone.  No kernel lives here.
 #include "common.hpp"
 
@@ -32,10 +32,10 @@ int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batc
     }
     float4* d_q = compensate ? d_comp : d_quat;
     int rc = OFPS_HIP_OK;
-    // a device-side count: every launch is sized from the capacity n, the first *d_n records count
+    // device-side counts: every launch is sized from the capacity n, the first d_n[j] records of item j count
     if (prm->run_estimator)
         rc = d_n ? almeida_device_n(ctx, d_rec, n, d_n, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters, prm->inlier_deg,
-                                    prm->num_samples, seed0, d_q, lsq_min_n)
+                                    prm->num_samples, seed0, d_q, lsq_min_n, batch)
                  : almeida_device(ctx, d_rec, n, batch, prm->aspect, prm->fov_y_deg, prm->use_ransac, prm->num_iters, prm->inlier_deg,
                                   prm->num_samples, seed0, d_q);
     if (rc == OFPS_HIP_OK && compensate) rc = compensate_device(ctx, d_rec, n, batch, d_n, prm->aspect, prm->fov_y_deg, d_q, d_comp + batch, d_quat);

@@ -223,6 +223,23 @@ class HipContext:
                                                            min_pixels, limit, median_limit, C.c_void_p(d_out_entries),
                                                            C.c_void_p(d_out_best or 0), C.c_void_p(d_out_count)))
 
+    def sad_flow_filtered_dev(self, d_frames: int, n_frames: int, W: int, H: int, stride: int, frame_pitch: int, ref_mode: int, block: int,
+                              search_range: int, min_pixels: int, limit: int, median: int, d_out_entries: int, d_out_best: int | None,
+                              d_out_counts: int):
+        """The batched search of sad_flow_dev through contrast gate, consistency check and / or median test with explicit values (include/
+        ofps_hip.h N1b): item k's kept records [and triples] first in its nblk-sized slot, its count in d_out_counts[k] (u32).  Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_filtered_dev(self._h, C.c_void_p(d_frames), n_frames, W, H, stride, frame_pitch, ref_mode, block,
+                                                             search_range, min_pixels, limit, median, C.c_void_p(d_out_entries),
+                                                             C.c_void_p(d_out_best or 0), C.c_void_p(d_out_counts)))
+
+    def set_sad_batch_filter(self, on: int):
+        """0 = push_frames_async and the multi-device workers' pushes ignore gate, check and median test (default); 1 = they follow the
+        context's three settings: frames_wait's n_vectors is the kept count per frame, the kept records lead each frame's slot."""
+        self._check(self._lib.ofps_hip_set_sad_batch_filter(self._h, int(on)))
+
+    def get_sad_batch_filter(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_batch_filter(self._h))
+
     def set_sad_levels(self, levels: int):
         """hip_sad's search levels (include/ofps_hip.h N1h): 1 = the plain search (default); 2 | 3 = the search runs on the frames halved
         levels - 1 times and every finer level repairs the doubled vectors in a +-3 window: reach 2 * range + 3, 4 * range + 9."""
