@@ -239,12 +239,13 @@ __global__ __launch_bounds__(256) void sad_qsad_kernel(const SadParams p) {
 //   * the strip's (NB*B+2R) x (B+2R) window is staged once per wave with 16-byte coalesced loads; every
 //     window row is read once (B/4 ds_read2_b32 per lane) and feeds up to B*B/4 packed SADs;
 //   * the odd column dx = +R (2R+1 is never a multiple of 4) is a short second pass: lane = (block,
-//     chunk of KE dy) with v_sad_u8 on dword-aligned window data (R % 4 == 0) -- 4 % extra SAD-unit
-//     time instead of a ninth dx group that wastes 3 of its 4 shifts and one lane in 64;
+//     chunk of KE2 dy below +R) with v_sad_u8 on dword-aligned window data (R % 4 == 0), dy = +R shared by the
+//     block's lanes -- 3 % extra SAD-unit time instead of a ninth dx group that wastes 3 of its 4 shifts and
+//     one lane in 64;
 //   * lane-local argmin key = SAD<<16 | d2 (dy^2 added to the row minimum), walked in ascending dy with a strict <: inside one dx group
 //     |dx| is distinct, so equal (SAD, d2) in one lane means different dy and the walk keeps the spec's
-//     (SAD, d2, dy, dx) order; masked columns saturate through a clamped add; vertical clipping is a
-//     scalar branch (uniform per strip); a 64-bit key finishes the order across the NG lanes of a block;
+//     (SAD, d2, dy, dx) order; masked columns saturate through a clamped add; vertical clipping is
+//     uniform per strip: a strip the frame clips walks dy in chunks and skips the chunks outside it (StripClip); a 64-bit key finishes the order across the NG lanes of a block;
 //   * workgroup -> strip mapping is XCD-aware: the 8 XCDs (workgroup w runs on XCD w % 8) each take a
 //     contiguous range of strips, so vertically adjacent strips share their halo rows in one L2.
 template <int B, int R>
@@ -262,7 +263,9 @@ struct StripCfg {
     static constexpr int NB = 64 / NG;                       // blocks per wave
     static constexpr int BW = B / 4;
     static constexpr int TILE_H = B + 2 * R;
-    static constexpr int KE = (NCAND + NG - 1) / NG;         // dy per lane in the dx = +R pass
+    static constexpr int KE = (NCAND + NG - 1) / NG;         // dy per lane when the chunks of the dx = +R column cover all 2R+1 dy (pruned kernel)
+    static constexpr int KE2 = (2 * R + NG - 1) / NG;        // dy per lane in the dx = +R pass: its chunks cover dy = -R .. R-1
+    static constexpr int ERL = (B + NG - 1) / NG;            // block rows per lane for the last candidate of that pass, dy = +R
     static constexpr int EDGE_COL = (2 * R) / 4;             // dword offset of the dx = +R block inside a block's window
     // staging granule: the window origin bx0*B - R must be a multiple of it (NB*B and R both are)
     static constexpr int GRAN = ((NB * B) % 16 == 0 && R % 16 == 0) ? 16 : (((NB * B) % 8 == 0 && R % 8 == 0) ? 8 : 4);
@@ -283,7 +286,9 @@ struct StripCfg {
     // (which has bandwidth to spare); staging, the current block and the argmin state are shared by the passes.
     static constexpr int SPLIT = (NCAND + 32) / 33;
     static constexpr int NP = (NCAND + SPLIT - 1) / SPLIT;
-    static constexpr int MIN_WAVES = (2 * NP + B * BW + 40 <= 168) ? 3 : 2;
+    // (8x8 +-8 is the one entry that fits 64 VGPRs, 8 waves per SIMD: say so, or the dx = +R pass's second read of its block rows
+    // costs it the eighth wave for one register)
+    static constexpr int MIN_WAVES = (B == 8 && R == 8) ? 8 : ((2 * NP + B * BW + 40 <= 168) ? 3 : 2);
     // small ranges: (d2 << 6 | dy index) fits the low 16 bits of the lane key, so the key alone identifies the
     // candidate and the scan needs no separate index tracking
     static constexpr bool COMPACT_KEY = ((2 * R * R) << 6) + NCAND < 65536 && NCAND <= 64;
@@ -306,8 +311,8 @@ struct StripWalk {
     static constexpr int ROWS_PER_BASE = (255 - StripCfg<B, R>::BW) / StripCfg<B, R>::SW + 1;
 };
 
-template <int B, int R, int I0, int RR>
-__device__ __forceinline__ void strip_row(unsigned long long (&acc)[StripCfg<B, R>::NP], const uint32_t (&c)[B][B / 4],
+template <int B, int R, int I0, int N, int RR>
+__device__ __forceinline__ void strip_row(unsigned long long (&acc)[N], const uint32_t (&c)[B][B / 4],
                                           const uint32_t* lds, uint32_t& base) {
     using C = StripCfg<B, R>;
     constexpr int G = StripWalk<B, R>::ROWS_PER_BASE;
@@ -319,7 +324,7 @@ __device__ __forceinline__ void strip_row(unsigned long long (&acc)[StripCfg<B, 
 #pragma unroll
     for (int q = 0; q < C::BW; ++q) win[q] = reinterpret_cast<const U64A4*>(lds + base + (RR % G) * C::SW + q)->v;
 #pragma unroll
-    for (int ii = 0; ii < C::NP; ++ii) {
+    for (int ii = 0; ii < N; ++ii) {
         const int y = RR - ii;                                  // window row I0+RR belongs to candidate I0+ii, block row y
         if (I0 + ii < C::NCAND && y >= 0 && y < B) {
 #pragma unroll
@@ -329,15 +334,15 @@ __device__ __forceinline__ void strip_row(unsigned long long (&acc)[StripCfg<B, 
 }
 
 // lds: the workgroup's LDS array; tile_off: dword index of this lane's window origin inside it
-template <int B, int R, int I0, int... RR>
-__device__ __forceinline__ void strip_rows(unsigned long long (&acc)[StripCfg<B, R>::NP], const uint32_t (&c)[B][B / 4],
+template <int B, int R, int I0, int N, int... RR>
+__device__ __forceinline__ void strip_rows(unsigned long long (&acc)[N], const uint32_t (&c)[B][B / 4],
                                            const uint32_t* lds, uint32_t tile_off, std::integer_sequence<int, RR...>) {
     uint32_t base = tile_off + I0 * StripCfg<B, R>::SW;
     asm volatile("" : "+v"(base));
-    (strip_row<B, R, I0, RR>(acc, c, lds, base), ...);
+    (strip_row<B, R, I0, N, RR>(acc, c, lds, base), ...);
 }
 
-// One dy pass: accumulate candidates I0 .. I0+NP-1 and fold them into the lane's running (key, dy index).
+// One dy pass: accumulate candidates I0 .. I0+N-1 and fold them into the lane's running (key, dy index).
 // key = SAD<<16 | dx^2 is minimised over the 4 dx first; dy^2 (a compile-time constant per step) is added to
 // the row minimum afterwards -- adding the same constant to four keys does not change their order, and
 // dx^2 + dy^2 < 65536 cannot carry into the SAD field; a clipped column holds all-ones and the clamped add
@@ -355,18 +360,18 @@ __device__ __forceinline__ void strip_rows(unsigned long long (&acc)[StripCfg<B,
 constexpr int kSadColKeys = OFPS_SAD_COLKEYS;
 constexpr int kColSlotDwords = kSadColKeys == 2 ? 4 * 64 : 0;       // LDS per wave for the column minima
 
-template <int B, int R, int I0>
+template <int B, int R, int I0, int N = StripCfg<B, R>::NP>
 __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const uint32_t* lds, uint32_t tile_off,
                                            const uint32_t (&colk)[4], const uint32_t (&colk_pos)[4], int y0, int H, uint32_t& bkey, int& bi,
                                            uint32_t (&colmin)[4], uint32_t* amin) {
     using C = StripCfg<B, R>;
-    unsigned long long acc[C::NP];
+    unsigned long long acc[N];
 #pragma unroll
-    for (int ii = 0; ii < C::NP; ++ii) acc[ii] = 0;
-    constexpr int ROWS = ((I0 + C::NP < C::NCAND ? C::NP : C::NCAND - I0) + B - 1);
-    strip_rows<B, R, I0>(acc, c, lds, tile_off, std::make_integer_sequence<int, ROWS>{});
+    for (int ii = 0; ii < N; ++ii) acc[ii] = 0;
+    constexpr int ROWS = ((I0 + N < C::NCAND ? N : C::NCAND - I0) + B - 1);
+    strip_rows<B, R, I0, N>(acc, c, lds, tile_off, std::make_integer_sequence<int, ROWS>{});
 #pragma unroll
-    for (int ii = 0; ii < C::NP; ++ii) asm volatile("" : "+v"(acc[ii]));
+    for (int ii = 0; ii < N; ++ii) asm volatile("" : "+v"(acc[ii]));
     if constexpr (kSadColKeys != 0 && (C::RANK_KEY || C::COMPACT_KEY)) {
         // per-column keys: SAD << 16 | low, low = dy^2 << 1 | (dy > 0) (RANK_KEY) or dy^2 << 6 | dy index (COMPACT_KEY): the order
         // (SAD, dy^2, dy) inside a column.  A dy clipped by the frame (uniform over the strip) takes the all-ones constant, which
@@ -388,11 +393,11 @@ __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const 
         };
         if constexpr (kSadColKeys == 1) {
 #pragma unroll
-            for (int ii = 0; ii < C::NP; ii += 2) {                          // two dy per v_min3_u32 and column
+            for (int ii = 0; ii < N; ii += 2) {                          // two dy per v_min3_u32 and column
                 if (I0 + ii >= C::NCAND) break;
                 uint32_t ka[4], kb[4];
                 keys_of(ii, low_of(ii), ka);
-                if (ii + 1 < C::NP && I0 + ii + 1 < C::NCAND) {
+                if (ii + 1 < N && I0 + ii + 1 < C::NCAND) {
                     keys_of(ii + 1, low_of(ii + 1), kb);
 #pragma unroll
                     for (int j = 0; j < 4; ++j)      // (left to itself hipcc forms v_min3_u32 for half of these and two v_min_u32 for the rest)
@@ -404,7 +409,7 @@ __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const 
             }
         } else {
 #pragma unroll
-            for (int ii = 0; ii < C::NP; ++ii) {
+            for (int ii = 0; ii < N; ++ii) {
                 if (I0 + ii >= C::NCAND) break;
                 uint32_t k[4];
                 keys_of(ii, low_of(ii), k);
@@ -415,7 +420,7 @@ __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const 
         return;
     }
 #pragma unroll
-    for (int ii = 0; ii < C::NP; ++ii) {
+    for (int ii = 0; ii < N; ++ii) {
         const int i = I0 + ii;
         const int dy = -R + i;
         if (i < C::NCAND && y0 + dy >= 0 && y0 + dy + B <= H) {          // uniform over the strip: scalar branch
@@ -445,6 +450,30 @@ __device__ __forceinline__ void strip_passes(const uint32_t (&c)[B][B / 4], cons
                                              const uint32_t (&colk)[4], const uint32_t (&colk_pos)[4], int y0, int H, uint32_t& bkey, int& bi,
                                              uint32_t (&colmin)[4], uint32_t* amin, std::integer_sequence<int, S...>) {
     (strip_pass<B, R, S * StripCfg<B, R>::NP>(c, lds, tile_off, colk, colk_pos, y0, H, bkey, bi, colmin, amin), ...);
+}
+
+// Strips that the frame clips (the block rows within R lines of the top or bottom edge) walk dy in chunks instead: the valid
+// candidate rows [ilo, ihi] are uniform over the wave and known before the walk, a chunk without a valid dy is skipped by a scalar
+// branch, a partly valid one runs whole and low_of masks the rest as in the straight-line pass.  Chunk k starts at 8k up to dy = 0
+// and at 8k + 1 above it, so the usual clips fall on chunk edges: a top row (dy >= 0 only), a bottom row with H % B == 8
+// (dy <= 8: 1080p at B = 16), the tops of 8-line blocks.  The window rows between chunks are read again (the LDS unit has
+// the time); slots and keys are those of the straight-line pass, so the minimum is the same whichever form fed it.
+template <int B, int R>
+struct StripClip {
+    static constexpr int NCH = (2 * R) / 8 > 0 ? (2 * R) / 8 : 1;
+    static constexpr int start(int k) { return k >= NCH ? StripCfg<B, R>::NCAND : (8 * k > R ? 8 * k + 1 : 8 * k); }
+};
+
+template <int B, int R, int... K>
+__device__ __forceinline__ void strip_clipped(const uint32_t (&c)[B][B / 4], const uint32_t* lds, uint32_t tile_off,
+                                              const uint32_t (&colk)[4], const uint32_t (&colk_pos)[4], int y0, int H, int ilo, int ihi,
+                                              uint32_t& bkey, int& bi, uint32_t (&colmin)[4], uint32_t* amin, std::integer_sequence<int, K...>) {
+    using L = StripClip<B, R>;
+    auto chunk = [&](auto k) {
+        constexpr int S = L::start(decltype(k)::value), E = L::start(decltype(k)::value + 1);
+        if (ihi >= S && ilo < E) strip_pass<B, R, S, E - S>(c, lds, tile_off, colk, colk_pos, y0, H, bkey, bi, colmin, amin);
+    };
+    (chunk(std::integral_constant<int, K>{}), ...);
 }
 
 constexpr int kStripWaves = 4;      // independent waves (strips) per workgroup; no workgroup barrier
@@ -547,8 +576,15 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
 #pragma unroll
         for (int j = 0; j < 4; ++j) amin[64 * j] = 0xFFFFFFFFu;
     }
-    strip_passes<B, R>(c, tiles, (uint32_t)(wave * C::TILE_DWORDS + b * C::BW + g), colk, colk_pos, y0, p.H, bkey, bi, colmin, amin,
-                       std::make_integer_sequence<int, C::SPLIT>{});
+    // candidate rows inside the frame: i = dy + R in [ilo, ihi], uniform over the strip
+    const int ilo = __builtin_amdgcn_readfirstlane(R - y0 > 0 ? R - y0 : 0);
+    const int ihi = __builtin_amdgcn_readfirstlane(p.H - B - y0 < R ? R + p.H - B - y0 : 2 * R);
+    const uint32_t lane_off = (uint32_t)(wave * C::TILE_DWORDS + b * C::BW + g);
+    if (ilo == 0 && ihi == 2 * R)
+        strip_passes<B, R>(c, tiles, lane_off, colk, colk_pos, y0, p.H, bkey, bi, colmin, amin, std::make_integer_sequence<int, C::SPLIT>{});
+    else
+        strip_clipped<B, R>(c, tiles, lane_off, colk, colk_pos, y0, p.H, ilo, ihi, bkey, bi, colmin, amin,
+                            std::make_integer_sequence<int, StripClip<B, R>::NCH>{});
     if constexpr (kSadColKeys != 0 && (C::RANK_KEY || C::COMPACT_KEY)) {
         // column minima -> the lane key of the product layout (SAD << 16 | d2 << KSHIFT | code / dy index), once per strip
 #pragma unroll
@@ -591,31 +627,60 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
         best = ((unsigned long long)((bkey & 0xFFFF0000u) | d2) << 32) | (unsigned long long)(uint32_t)(((dy + R) << 8) | (dx + R));
     }
     // ---- dx = +R pass (after the main scan, so acc[] is dead and the wave stays within 168 VGPRs):
-    // lane = (block b, dy chunk g): KE consecutive dy, one v_sad_u8 per dword
-    uint32_t eacc[C::KE];
+    // lane = (block b, dy chunk g): KE2 consecutive dy below +R, one v_sad_u8 per dword.  The chunks cover dy = -R .. R-1; the odd
+    // last candidate dy = +R is shared by the block's NG lanes, ERL block rows each, and joined by a butterfly add: no SAD is
+    // issued for a dy beyond the range when NG * KE2 == 2R (every table entry but +-20 and +-28).
+    uint32_t eacc[C::KE2];
 #pragma unroll
-    for (int i = 0; i < C::KE; ++i) eacc[i] = 0;
+    for (int i = 0; i < C::KE2; ++i) eacc[i] = 0;
+    uint32_t elast = 0;
+    const uint32_t* ecol = tile + b * C::BW + C::EDGE_COL;
     {
-        const uint32_t* ecol = tile + b * C::BW + C::EDGE_COL;
-        const int erow0 = g * C::KE;
+        // the lane's rows of the current block for dy = +R: the block is in VGPRs under compile-time row indices only, so the
+        // (lane-dependent) rows are read again -- ERL short loads that hit the cache the block was just read through
+        const int yl = g * C::ERL;
+        uint32_t cl[C::ERL][C::BW];
+        {
+            const int bxc = blk_on ? bx : p.nbx - 1;
+            const uint8_t* cp = cur + (size_t)y0 * p.stride + bxc * B;
+#pragma unroll
+            for (int r = 0; r < C::ERL; ++r) {
+                const int y = (C::NG * C::ERL > B && yl + r > B - 1) ? B - 1 : yl + r;     // idle lanes re-read the last row
+                const uint8_t* rp = cp + (size_t)y * p.stride;
+                if constexpr (C::BW % 4 == 0) {
+#pragma unroll
+                    for (int q4 = 0; q4 < C::BW; q4 += 4) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(rp + 4 * q4);
+                        cl[r][q4 + 0] = v.x; cl[r][q4 + 1] = v.y; cl[r][q4 + 2] = v.z; cl[r][q4 + 3] = v.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int q2 = 0; q2 < C::BW; q2 += 2) {
+                        const uint2 v = *reinterpret_cast<const uint2*>(rp + 4 * q2);
+                        cl[r][q2 + 0] = v.x; cl[r][q2 + 1] = v.y;
+                    }
+                }
+            }
+        }
+        const int erow0 = g * C::KE2;
         // one-row software prefetch; the empty asm with a memory clobber keeps hipcc from hoisting all
-        // B+KE-1 rows of LDS reads above the loop (80 extra live VGPRs next to acc[] and c[][])
+        // B+KE2-1 rows of LDS reads above the loop (80 extra live VGPRs next to acc[] and c[][])
         uint32_t nxt[C::BW];
 #pragma unroll
         for (int q = 0; q < C::BW; ++q) nxt[q] = ecol[erow0 * C::SW + q];
 #pragma unroll
-        for (int rr = 0; rr < B + C::KE - 1; ++rr) {
+        for (int rr = 0; rr < B + C::KE2 - 1; ++rr) {
             uint32_t ref[C::BW];
 #pragma unroll
             for (int q = 0; q < C::BW; ++q) ref[q] = nxt[q];
-            if (rr + 1 < B + C::KE - 1) {
-                // the last chunks overshoot the window by up to KE*NG - NCAND rows (those dy are masked): the tile has the rows
+            if (rr + 1 < B + C::KE2 - 1) {
+                // where NG * KE2 > 2R the last chunks overshoot the window (those dy are masked): the tile has the rows
                 const int row = erow0 + rr + 1;
 #pragma unroll
                 for (int q = 0; q < C::BW; ++q) nxt[q] = ecol[row * C::SW + q];
             }
 #pragma unroll
-            for (int i = 0; i < C::KE; ++i) {
+            for (int i = 0; i < C::KE2; ++i) {
                 const int y = rr - i;
                 if (y >= 0 && y < B) {
 #pragma unroll
@@ -624,20 +689,47 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
             }
             asm volatile("" : "+v"(eacc[0]) : : "memory");
         }
+        // (the sums are final here: without the pins hipcc sinks the SADs of a chunk's later dy below the validity test of their
+        // candidate, which keeps all B+KE2-1 window rows live and costs the third wave per SIMD)
+#pragma unroll
+        for (int i = 1; i < C::KE2; ++i) asm volatile("" : "+v"(eacc[i]));
+        // dy = +R: window rows 2R + y for the lane's block rows y (clamped like the loads; an idle lane's sum is dropped)
+#pragma unroll
+        for (int r = 0; r < C::ERL; ++r) {
+            const int y = (C::NG * C::ERL > B && yl + r > B - 1) ? B - 1 : yl + r;
+#pragma unroll
+            for (int q = 0; q < C::BW; ++q) elast = __builtin_amdgcn_sad_u8(ecol[(2 * R + y) * C::SW + q], cl[r][q], elast);
+        }
+        if constexpr (C::NG * C::ERL > B) elast = yl < B ? elast : 0u;
+#pragma unroll
+        for (int m = 1; m < C::NG; m <<= 1) elast += (uint32_t)__shfl_xor((int)elast, m, 64);
     }
 
-    // ---- candidates of the dx = +R pass (ascending dy, strict <)
+    // ---- candidates of the dx = +R pass: a 32-bit key (SAD << 16 | d2) and the dy index over the lane's chunk in ascending dy with a
+    // strict <, then dy = +R (the same key in every lane of the block: a minimum does not mind), one 64-bit key at the end.
+    // Equal (SAD, d2) inside the column means dy = -+|dy|, and the walk keeps the first: the spec's order.
     {
         const bool xok = blk_on && bx * B + R + B <= p.W;
+        const int chi = ihi < 2 * R - 1 ? ihi : 2 * R - 1;                  // the chunks stop below dy = +R
+        uint32_t ek = 0xFFFFFFFFu;
+        int ei = 0;
 #pragma unroll
-        for (int i = 0; i < C::KE; ++i) {
-            const int dy = -R + g * C::KE + i;
-            const bool v = xok && dy <= R && y0 + dy >= 0 && y0 + dy + B <= p.H;
-            const unsigned long long k64 =
-                ((unsigned long long)((eacc[i] << 16) | (uint32_t)(R * R + dy * dy)) << 32) |
-                (unsigned long long)(uint32_t)(((dy + R) << 8) | (2 * R));
-            best = (v && k64 < best) ? k64 : best;
+        for (int i = 0; i < C::KE2; ++i) {
+            const int idx = g * C::KE2 + i, dy = idx - R;
+            const bool v = (unsigned)(idx - ilo) <= (unsigned)(chi - ilo);
+            const uint32_t k = v ? ((eacc[i] << 16) | (uint32_t)(R * R + dy * dy)) : 0xFFFFFFFFu;
+            const bool lt = k < ek;
+            ek = lt ? k : ek;
+            ei = lt ? idx : ei;
         }
+        if (ihi == 2 * R) {                                                 // uniform over the strip
+            const uint32_t k = (elast << 16) | (uint32_t)(2 * R * R);
+            const bool lt = k < ek;
+            ek = lt ? k : ek;
+            ei = lt ? 2 * R : ei;
+        }
+        const unsigned long long k64 = ((unsigned long long)ek << 32) | (unsigned long long)(uint32_t)((ei << 8) | (2 * R));
+        best = (xok && ek != 0xFFFFFFFFu && k64 < best) ? k64 : best;
     }
     // ---- min over the NG lanes of each block (aligned power-of-two segments: xor butterfly)
 #pragma unroll
