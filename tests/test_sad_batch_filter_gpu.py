@@ -481,3 +481,51 @@ def test_multi_device_follows_the_switch_variable(monkeypatch):
         np.testing.assert_array_equal(_bits(ent[k, :n]), _bits(want[k]["entries"]))
         assert res[k]["motion"] == want[k]["motion"]
         assert np.abs(res[k]["quat"] - want[k]["quat"]).max() <= QUAT_BOUND
+
+
+# ------------------------------------------------------------------------- per-item device counts behind the densifier's two-pass sort
+# 17 x 17 and 23 x 23 detector fields: more than 256 cells, so the densifier behind the batched tail is the general path with two digits,
+# one launch over all items of the ticket, each item's count read from device memory.  (The other batched stream tests use gc.FRAME_DETECTOR:
+# 9 x 9, the one-workgroup densifier.)
+FINE_DETECTORS = {"side17": (dict(min_size=0.014, subdivide=2, target_motion=0.003), 17, (None, None, 9, 172)),
+                  "side23": (dict(min_size=0.05, subdivide=5, target_motion=0.003), 23, (None, None, None, 191))}
+
+
+@pytest.mark.parametrize("use_ransac", (False, True), ids=["lsq", "ransac"])
+@pytest.mark.parametrize("detector", list(FINE_DETECTORS))
+def test_batched_stream_with_device_counts_and_a_two_pass_detector_sort(ctx, monkeypatch, detector, use_ransac):
+    """bc.mixed_frames() as ONE ticket of five under the gate that keeps none, two, some and all blocks: records, counts and island of the
+    batched push against five single pushes, bit for bit, and the island against the oracle on the kept records.  The batched form returns
+    the island's area and side only (ofps_hip_frame_result); the island FIELD is compared where the library returns one: the single push
+    against the oracle."""
+    import oracle
+    det, side, areas = FINE_DETECTORS[detector]
+    assert oracle.block_dim(det["min_size"], det["subdivide"]) == side and side * side > 256
+    monkeypatch.setattr(gc, "FRAME_DETECTOR", det)       # _prm reads it at every call
+    f = np.ascontiguousarray(bc.mixed_frames())
+    seeds = [gc.SEED + j for j in range(len(f))]
+    with _settings(ctx, gate=gc.TWO_BLOCK_GATE, batch_filter=1):
+        ctx.reset_frames()
+        want = [ctx.push_frame(fr, want_entries=True, want_field=True, **_prm(use_ransac, s)) for fr, s in zip(f, seeds)]
+        ctx.reset_frames()
+    # the same ticket unfiltered first: it leaves a whole sort of nblk records behind in every item's segment of the sorting scratch, so a stage
+    # that looked past an item's count would find well-formed keys of another frame there, not (perhaps) zeros
+    full = _batches(ctx, f, (len(f),), (gc.SEED,), use_ransac)
+    with _settings(ctx, gate=gc.TWO_BLOCK_GATE, batch_filter=1):
+        got = _batches(ctx, f, (len(f),), (gc.SEED,), use_ransac)
+    what = f"{detector} {'ransac' if use_ransac else 'lsq'}"
+    _check_stream(got, [dict(w, motion=None if w["motion"] is None else (w["motion"][0], side)) for w in want], what)
+    assert not got[0]["have"] and [g["n"] for g in got[1:]] == [0, bc.MIXED_KEPT_2, 144, gc.NBLK]
+    for k in range(1, len(f)):
+        m = f"{what} frame {k}"
+        isl = oracle.detect_motion(bc.vectors(f[k - 1], f[k], gc.BLOCK, gc.RANGE)[0], **det)
+        assert full[k]["n"] == gc.NBLK and full[k]["motion"] == (None if isl is None else (isl[0], side)), m + ": unfiltered"
+        keep = bc.keep_of(f[k - 1], f[k], gc.BLOCK, gc.RANGE, gc.TWO_BLOCK_GATE, 0, 0)
+        np.testing.assert_array_equal(_bits(got[k]["entries"]), _bits(bc.vectors(f[k - 1], f[k], gc.BLOCK, gc.RANGE)[0][keep]), err_msg=m)
+        isl = oracle.detect_motion(np.ascontiguousarray(got[k]["entries"]), **det)
+        assert gc.area_of(isl) == (areas[k - 1] or 0), m
+        assert got[k]["motion"] == (None if isl is None else (isl[0], side)), m + ": batched island"
+        assert (want[k]["motion"] is None) == (isl is None), m
+        if isl is not None:
+            assert want[k]["motion"][0] == isl[0], m
+            np.testing.assert_array_equal(_bits(want[k]["motion"][1]), _bits(isl[1]), err_msg=m + ": the single push's island field")
