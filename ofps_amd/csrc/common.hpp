@@ -292,15 +292,41 @@ int check_hip(ofps_hip_ctx* ctx, hipError_t e, const char* what);
 void* scratch(ofps_hip_ctx* ctx, int slot, size_t bytes);
 
 // ---- device-side stage entry points shared between translation units (all enqueue on ctx->stream)
+// The two frame sets of one search: pair k reads prev_base + k*prev_pitch and cur_base + k*cur_pitch; a set with pitch 0 is one frame that
+// every pair reads.  `pairs` travels beside it.  The refine kernels take one by value (sad_hier.hip: RefineParams): the member order is layout.
+struct SadFrames {
+    const uint8_t* prev_base;
+    const uint8_t* cur_base;
+    size_t prev_pitch, cur_pitch;
+    int W, H, stride;
+    // the n_frames - 1 pairs of a frame sequence: ref_mode 0 (k, k + 1), ref_mode 1 (0, k + 1).  The current frame of pair k is frame k + 1 in both
+    static SadFrames sequence(const uint8_t* frames, size_t frame_pitch, int ref_mode, int W, int H, int stride) {
+        return {frames, frames + frame_pitch, ref_mode ? 0 : frame_pitch, frame_pitch, W, H, stride};
+    }
+    SadFrames swapped() const { return {cur_base, prev_base, cur_pitch, prev_pitch, W, H, stride}; }       // the backward search's sets
+    // What a stage that copies the sets of `pairs` pairs (mean removal, the levels' halving) has to copy, and where the copies lie.  Consecutive
+    // pairs of one sequence (cur = prev + one frame) are a chain: pairs + 1 frames copied once, all counted in nprev; else two sets
+    struct Sets {
+        bool chain, prev_many, cur_many;
+        long long nprev, ncur;
+        long long cur_first() const { return chain ? 1 : nprev; }      // where the copies of cur begin: one frame behind prev for a chain, else behind the nprev frames
+        // the same sets inside `buf`, frames `pitch` apart; a pitch of 0 stays 0
+        SadFrames in(const uint8_t* buf, size_t pitch, int W, int H, int stride) const {
+            return {buf, buf + (size_t)cur_first() * pitch, prev_many ? pitch : 0, cur_many ? pitch : 0, W, H, stride};
+        }
+    };
+    Sets sets(int pairs) const {
+        const bool chain = prev_pitch != 0 && prev_pitch == cur_pitch && cur_base == prev_base + prev_pitch;
+        return {chain, prev_pitch != 0, cur_pitch != 0, chain ? (long long)pairs + 1 : (prev_pitch ? pairs : 1), chain ? 0 : (cur_pitch ? pairs : 1)};
+    }
+};
 // integer_only: no quarter-pel refinement whatever the context's motion scale (the consistency check's backward search).
 // d_int_best (motion scale 4 only): the integer winners are written here, not to S_SAD_QBEST / d_out_best, and are still there behind the
 // refinement, which then writes its triples to d_out_best (or nowhere)
-int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
-                     size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
-                     void* d_out_best, bool integer_only = false, void* d_int_best = nullptr);
+int sad_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_out_entries, void* d_out_best,
+                     bool integer_only = false, void* d_int_best = nullptr);
 // the plain integer search alone (N1): what sad_pairs_device runs at one search level, and the top search of sad_hier_pairs_device
-int sad_search_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                      int W, int H, int stride, int block, int range, void* d_out_entries, void* d_out_best);
+int sad_search_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_out_entries, void* d_out_best);
 // sad_hier.hip (include/ofps_hip.h N1h): the integer winners of a search over `levels` > 1 levels; never refines to quarter-pel and never
 // looks at the context's levels or predictor mode, so it cannot come back to itself through the top search.  d_out_best may be null
 constexpr int kSadHierRefine = 3;                           // the refinement's radius: 49 candidates in a 64-lane wave
@@ -308,17 +334,15 @@ constexpr int kSadHierPredictors = 6;                       // N1p: parent, four
 constexpr int kSadHierMaxReach = 127;                       // 8 * reach + 6 <= 1023: the quarter-pel key's 10-bit fields
 int sad_hier_reach(int range, int levels);                  // R_0, or -1
 int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
-int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                          int W, int H, int stride, int block, int range, int levels, int predictors, void* d_out_entries, void* d_out_best);
+int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int levels, int predictors, void* d_out_entries,
+                          void* d_out_best);
 // sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
 constexpr int kSadPrefilterMax = 16;
 int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
                          int dst_stride, long long frames, int radius);
-// a search's two frame sets -> S_SAD_PREF; bases, pitches and stride are replaced by the filtered frames'
-int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const uint8_t** prev_base, size_t* prev_pitch, const uint8_t** cur_base,
-                               size_t* cur_pitch, int pairs, int W, int H, int* stride);
-int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
-                           int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
+// a search's two frame sets -> S_SAD_PREF; *filtered: the filtered frames, in the shape of `f`
+int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const SadFrames& f, int pairs, SadFrames* filtered);
+int sad_qpel_refine_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best);
 // d_n (densify_device, densify_device_raw, detect_device; optional): the entry counts live in device memory, one per item -- n is the capacity
 // and the stride of every item, the first min(d_n[item], n) entries of an item count, and nothing about the launches depends on the counts
@@ -379,7 +403,7 @@ inline uint8_t* gate_keep(char* flags, size_t nblk, size_t items = 1) { return r
 constexpr int kSadConsistencyMax = 129;                     // 2 * 64 + 1: above every residual of the largest search range
 int sad_consistency_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);        // limit in [1, 129]
 // residual and / or keep byte per block from the two directions' integer winners, on stream st; d_keep_in (optional, may be d_out_keep) is ANDed in.
-// items > 1: every array holds items x nblk, item-major; one launch, no partner block outside its item
+// Every array holds items x nblk, item-major; one launch, no partner block outside its item
 int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const int* d_bwd_best, int W, int H, int block, int limit,
                                  const uint8_t* d_keep_in, uint32_t* d_out_residual, uint8_t* d_out_keep, hipStream_t st, int items = 1);
 
@@ -387,23 +411,21 @@ int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const
 constexpr int kSadMedianMax = 255;
 int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who);             // limit in [1, 255]
 // doubled residual and / or keep byte per block from the integer winners, on stream st; d_keep_in (optional: absent = all ones) is ANDed in
-// and may NOT be d_out_keep: a verdict reads its neighbours' incoming flags.  items > 1: every array holds items x nblk, item-major; one
-// launch, no neighbour outside its item
+// and may NOT be d_out_keep: a verdict reads its neighbours' incoming flags.  Every array holds items x nblk, item-major; one launch, no
+// neighbour outside its item
 int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t* d_keep_in, int W, int H, int block, int limit,
                             uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st, int items = 1);
 
-// sad_gate.hip: one pair's filtered search -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device -- in the
-// steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  The one-pair entry points run them all on ctx->stream
-// (sad_flow_filtered_device); the fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  With gate == 0,
-// limit == 0 and median == 0 search() is the plain search into d_out and no other step reserves or enqueues anything.
+// sad_gate.hip: the filtered search of `pairs` pairs -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device --
+// in the steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  sad_flow_filtered_device runs them all on ctx->stream; the
+// fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  Every per-block array holds pairs x nblk, item-major,
+// and every step is one launch whatever `pairs`.  With gate == 0, limit == 0 and median == 0 search() is the plain search into d_out and no
+// other step reserves or enqueues anything.
 struct SadFilter {
-    int W, H, stride, block, range;
+    SadFrames fr;                        // plan() and reserve() read the geometry alone: the bases may be filled in behind them (pipeline.hip)
+    int pairs, block, range;
     int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
-    // the batched form (sad_flow_filtered_batch_device): pair k = (d_prev + k * prev_pitch, d_cur + k * cur_pitch), every per-block array
-    // below holds pairs x nblk, item-major, and every step stays one launch (1: the one-pair kernels, as ever)
-    int pairs = 1;
-    size_t prev_pitch = 0, cur_pitch = 0;
     size_t nblk = 0;                     // per pair
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
     char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
@@ -417,21 +439,18 @@ struct SadFilter {
     uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk, pairs) : nullptr; }
     uint8_t* keep() const { return gate_keep(d_flags, nblk, pairs); }       // the incoming flags: contrast gate AND consistency check
     int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
-    // the scratch slots; S_GATE_FLAGS holds `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
+    // the scratch slots; S_GATE_FLAGS / S_MED_KEEP hold `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
     int reserve(ofps_hip_ctx* ctx, int tix = 0, int tickets = 1);
-    int search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out);      // on ctx->stream; d_out: the unfiltered search's records
-    int contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st);                    // gate > 0: counts and keep flags of `cur`, which they depend on alone
+    int search(ofps_hip_ctx* ctx, float4* d_out);         // on ctx->stream; d_out: the unfiltered search's records.  The backward search reads fr.swapped()
+    int contrast_flags(ofps_hip_ctx* ctx, hipStream_t st);        // gate > 0: counts and keep flags of the current frames, which they depend on alone
     // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] [median flags read from those, into
-    // d_med_keep ->] kept records [and triples] in raster order -> count
-    // pairs > 1: d_out and d_out_best hold pairs slots of nblk, item k's kept ones lead slot k; d_count holds pairs counts
+    // d_med_keep ->] kept records [and triples] in raster order -> count.  d_out and d_out_best hold pairs slots of nblk, item k's kept ones
+    // lead slot k; d_count holds pairs counts
     int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
 };
-// S_GATE_FLAGS / S_MED_KEEP hold `tickets` blocks, this call's is number `tix`; `who` leads every error text
-int sad_flow_filtered_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, size_t prev_pitch, const uint8_t* d_cur, size_t cur_pitch, int pairs,
-                                   int W, int H, int stride, int block, int range, int min_pixels, int limit, int median, float4* d_out,
-                                   int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets);
-int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                             int min_pixels, int limit, int median, float4* d_out, int* d_out_best, uint32_t* d_count);
+// the five steps on ctx->stream, the launch count independent of `pairs`; `who` leads every error text, tix / tickets: SadFilter::reserve
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
+                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional): the record counts in device memory, one per item, n the capacity.  d_out may equal d_entries.

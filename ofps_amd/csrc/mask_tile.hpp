@@ -1,5 +1,6 @@
 // mask_tile.hpp -- the arithmetic of cv-decoder's contrast mask for ONE 64x16 tile, shared by the kernel that writes the pixel mask
-// (mask.hip: contrast_mask_kernel) and the one that only counts it per lattice block (sad_gate.hip: block_contrast_kernel).
+// (mask.hip: contrast_mask_kernel) and the one that only counts it per lattice block (sad_gate.hip: block_contrast_kernel,
+// whose grid z is the frame of a batch; the tile functions see one frame).
 //
 //   Sobel(gray, CV_32F, dx=1, dy=1, ksize 5, BORDER_DEFAULT) -> threshold(> 20) -> dilate(MORPH_ELLIPSE 11x11)
 //

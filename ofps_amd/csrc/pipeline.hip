@@ -98,13 +98,13 @@ int pipe_upload(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride
 struct Push {
     ofps_hip_ctx* ctx;
     const ofps_hip_frame_params* prm;
-    ofps::SadFilter f;                   // contrast gate, consistency check and median test as the context has them at this push; all 0: the plain search
+    ofps::SadFilter f;                   // contrast gate, consistency check and median test as the context has them at this push; all 0: the plain search.
+                                         // Made with the geometry alone -- claim() refuses before anything is uploaded -- upload() fills in the pair's frames
     PipeStream::Ticket* t = nullptr;
     int tix = 0;
     long frame_no = 0;                   // the frame this push uploads
     int cur_slot = 0, prev_slot = 0;
     bool cur_by_event = false;           // this frame's upload ran on the copy stream and has an event of its own
-    const uint8_t *prev = nullptr, *cur = nullptr;
     float4* d_ent = nullptr;             // this ticket's records: what the caller gets
     char* d_out = nullptr;               // ... and its kPipeOutBytes
     PipeOut* out = nullptr;              // where the tail stores result and quaternion: the ticket's page-locked block, or d_out
@@ -124,11 +124,11 @@ struct Push {
     int upload(const uint8_t* luma, int stride) {
         PipeStream& ps = ctx->pipe;
         uint8_t* slots; size_t pitch; int dstride;
-        const int rc = pipe_upload(ctx, luma, f.W, f.H, stride, /*overlap=*/ps.ring.other_pending(), &slots, &pitch, &dstride);
+        const int rc = pipe_upload(ctx, luma, f.fr.W, f.fr.H, stride, /*overlap=*/ps.ring.other_pending(), &slots, &pitch, &dstride);
         if (rc != OFPS_HIP_OK) return rc;
         frame_no = ps.frames - 1;
         cur_slot = (int)(frame_no % kSlots); prev_slot = (int)((frame_no + kSlots - 1) % kSlots);
-        cur = slots + (size_t)cur_slot * pitch; prev = slots + (size_t)prev_slot * pitch;
+        f.fr.cur_base = slots + (size_t)cur_slot * pitch; f.fr.prev_base = slots + (size_t)prev_slot * pitch;
         cur_by_event = !ps.uploaded_on_compute[cur_slot];
         for (int slot : {prev_slot, cur_slot}) {
             if (ps.uploaded_on_compute[slot] || (frame_no == 0 && slot == prev_slot)) continue;
@@ -156,11 +156,11 @@ struct Push {
             // well), else the compute stream's position, which is right behind the upload
             if (!cur_by_event) OFPS_HIP_TRY(ctx, hipEventRecord(ps.fork, s));
             OFPS_HIP_TRY(ctx, hipStreamWaitEvent(ps.aux_stream, cur_by_event ? ps.uploaded[cur_slot] : ps.fork, 0));
-            rc = f.contrast_flags(ctx, cur, ps.aux_stream);
+            rc = f.contrast_flags(ctx, ps.aux_stream);
             if (rc != OFPS_HIP_OK) return rc;
             OFPS_HIP_TRY(ctx, hipEventRecord(ps.gate_done, ps.aux_stream));
         }
-        rc = f.search(ctx, prev, cur, d_ent);
+        rc = f.search(ctx, d_ent);
         if (rc != OFPS_HIP_OK) return rc;
         // the older slot may be overwritten once this search is through; the same event forks the unfiltered tail's detector
         // (one barrier packet between the search and the estimator instead of two)
@@ -236,7 +236,8 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    Push p{ctx, prm, {W, H, (W + 63) & ~63, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency, ctx->opt.sad_median, /*want_triples=*/false}};
+    Push p{ctx, prm, {{nullptr, nullptr, 0, 0, W, H, (W + 63) & ~63}, 1, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
+                      ctx->opt.sad_median, /*want_triples=*/false}};
     rc = p.claim();                                     // refused before anything is uploaded
     if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
     if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)
@@ -330,7 +331,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const auto& o = ctx->opt;
     const bool filtered = o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0);
     if (filtered) {                                              // refused before anything is uploaded
-        SadFilter chk{W, H, dstride, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, /*want_triples=*/false};
+        SadFilter chk{{nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, /*want_triples=*/false};
         rc = chk.plan(ctx, "push_frames_async");
         if (rc != OFPS_HIP_OK) return rc;
     }
@@ -408,13 +409,11 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         // filtered: item j's kept records lead its slot of the record buffer, its count is word j behind the quaternions.  Searches, flags
         // and the compaction run on the compute stream, in front of the tail that reads the counts there
         uint32_t* d_cnt = filtered ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
+        const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
         if (filtered)
-            rc = sad_flow_filtered_batch_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
-                                                prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
-                                                "push_frames_async", tix, kTickets);
-        else
-            rc = ofps::sad_pairs_device(ctx, buf + (size_t)first * pitch, pitch, buf + (size_t)(first + 1) * pitch, pitch, pairs, W, H, dstride,
-                                        prm->block, prm->range, ent0, nullptr);
+            rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
+                                          "push_frames_async", tix, kTickets);
+        else rc = sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0, nullptr);
         if (rc != OFPS_HIP_OK) return rc;
         auto* d_res = reinterpret_cast<int(*)[4]>(d_out);                           // [n][4]
         float4* d_quat = reinterpret_cast<float4*>(d_out + (size_t)n * kBatchResult); // [n]

@@ -1177,40 +1177,36 @@ size_t ofps_hip_sad_block_count(int W, int H, int block) {
 
 namespace {
 // what every search asks of its frames and parameters, in one place: sad_pairs_device and sad_search_device say the same words
-int sad_check_args(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int W, int H,
-                   int stride, int block, int range) {
-    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "sad_flow: bad geometry W=%d H=%d stride=%d", W, H, stride);
-    OFPS_REQUIRE(ctx, stride % 4 == 0 && ((uintptr_t)prev_base % 4) == 0 && ((uintptr_t)cur_base % 4) == 0 &&
-                          prev_pitch % 4 == 0 && cur_pitch % 4 == 0,
-                 "sad_flow: rows must be 4-byte aligned (stride=%d)", stride);
+int sad_check_args(ofps_hip_ctx* ctx, const ofps::SadFrames& f, int block, int range) {
+    OFPS_REQUIRE(ctx, f.W > 0 && f.H > 0 && f.stride >= f.W, "sad_flow: bad geometry W=%d H=%d stride=%d", f.W, f.H, f.stride);
+    OFPS_REQUIRE(ctx, f.stride % 4 == 0 && ((uintptr_t)f.prev_base % 4) == 0 && ((uintptr_t)f.cur_base % 4) == 0 &&
+                          f.prev_pitch % 4 == 0 && f.cur_pitch % 4 == 0,
+                 "sad_flow: rows must be 4-byte aligned (stride=%d)", f.stride);
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64 && range >= 0 && range <= 64,
                  "sad_flow: block=%d range=%d outside [1,64]/[0,64]", block, range);
     return OFPS_HIP_OK;
 }
 
-SadParams sad_params(const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int W, int H, int stride, int block,
-                     void* d_out_entries, void* d_out_best) {
+SadParams sad_params(const ofps::SadFrames& f, int block, void* d_out_entries, void* d_out_best) {
     SadParams p{};
-    p.prev_base = prev_base; p.cur_base = cur_base;
-    p.prev_pitch = prev_pitch; p.cur_pitch = cur_pitch;
-    p.W = W; p.H = H; p.stride = stride;
-    p.nbx = W / block; p.nby = H / block;
-    p.nx = 1.0f / (float)W; p.ny = 1.0f / (float)H;
+    p.prev_base = f.prev_base; p.cur_base = f.cur_base;
+    p.prev_pitch = f.prev_pitch; p.cur_pitch = f.cur_pitch;
+    p.W = f.W; p.H = f.H; p.stride = f.stride;
+    p.nbx = f.W / block; p.nby = f.H / block;
+    p.nx = 1.0f / (float)f.W; p.ny = 1.0f / (float)f.H;
     p.out_entries = static_cast<float4*>(d_out_entries);
     p.out_best = static_cast<int*>(d_out_best);
     return p;
 }
 
 // the launches of one plain search: kernel selection by geometry, alignment and the context's mode
-int sad_launch(ofps_hip_ctx* ctx, const SadParams& p, int pairs, int block, int range) {
-    const uint8_t* prev_base = p.prev_base; const uint8_t* cur_base = p.cur_base;
-    const size_t prev_pitch = p.prev_pitch, cur_pitch = p.cur_pitch;
-    const int stride = p.stride;
+int sad_launch(ofps_hip_ctx* ctx, const ofps::SadFrames& f, int pairs, int block, int range, void* d_out_entries, void* d_out_best) {
+    const SadParams p = sad_params(f, block, d_out_entries, d_out_best);
     hipStream_t s = ctx->stream;
     const int key = block * 1000 + range;
     const bool force_block = ctx->opt.sad_force_block != 0;     // OFPS_HIP_SAD_KERNEL=block (A/B profiling)
-    const bool strip_ok = !force_block && stride % 16 == 0 && ((uintptr_t)prev_base % 16) == 0 &&
-                          ((uintptr_t)cur_base % 16) == 0 && prev_pitch % 16 == 0 && cur_pitch % 16 == 0 &&
+    const bool strip_ok = !force_block && f.stride % 16 == 0 && ((uintptr_t)f.prev_base % 16) == 0 &&
+                          ((uintptr_t)f.cur_base % 16) == 0 && f.prev_pitch % 16 == 0 && f.cur_pitch % 16 == 0 &&
                           (long long)p.nbx * p.nby * pairs < (1ll << 28) && (long long)p.nbx * p.nby < (1ll << 20);
     switch (key) {
         // strip kernels need 16-byte aligned rows; otherwise (or with OFPS_HIP_SAD_KERNEL=block, A/B
@@ -1257,55 +1253,48 @@ int sad_launch(ofps_hip_ctx* ctx, const SadParams& p, int pairs, int block, int 
 }  // namespace
 
 namespace ofps {
-int sad_search_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                      int W, int H, int stride, int block, int range, void* d_out_entries, void* d_out_best) {
-    const int rc = sad_check_args(ctx, prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, range);
+int sad_search_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_out_entries, void* d_out_best) {
+    const int rc = sad_check_args(ctx, f, block, range);
     if (rc != OFPS_HIP_OK) return rc;
-    const SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
-    if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
-    OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
+    const int nbx = f.W / block, nby = f.H / block;
+    if (nbx == 0 || nby == 0 || pairs <= 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, pairs <= 65535 && nby <= 65535, "sad_flow: grid too large");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return sad_launch(ctx, p, pairs, block, range);
+    return sad_launch(ctx, f, pairs, block, range, d_out_entries, d_out_best);
 }
 
-// Shared by the batched entry point and the per-frame pipeline (pipeline.hip): `pairs` searches,
-// pair k between prev_base + k*prev_pitch and cur_base + k*cur_pitch.
-int sad_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base,
-                     size_t cur_pitch, int pairs, int W, int H, int stride, int block, int range, void* d_out_entries,
-                     void* d_out_best, bool integer_only, void* d_int_best) {
-    int rc = sad_check_args(ctx, prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, range);
+// Shared by the batched entry point and the per-frame pipeline (pipeline.hip): `pairs` searches over the frame sets `f`.
+int sad_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_out_entries, void* d_out_best,
+                     bool integer_only, void* d_int_best) {
+    int rc = sad_check_args(ctx, f, block, range);
     if (rc != OFPS_HIP_OK) return rc;
     // search levels (sad_hier.hip): the integer search below becomes top search + refinements; everything around it stays
     const int levels = ctx->opt.sad_levels, predictors = ctx->opt.sad_predictors;     // read once: every level of this search runs in one mode
     const int prefilter = ctx->opt.sad_prefilter;                                     // ... and on one kind of frames
-    if (levels > 1 && (rc = ofps::sad_hier_check(ctx, W, H, block, range, levels)) != OFPS_HIP_OK) return rc;
-    SadParams p = sad_params(prev_base, prev_pitch, cur_base, cur_pitch, W, H, stride, block, d_out_entries, d_out_best);
-    if (p.nbx == 0 || p.nby == 0 || pairs <= 0) return OFPS_HIP_OK;
-    OFPS_REQUIRE(ctx, pairs <= 65535 && p.nby <= 65535, "sad_flow: grid too large");
+    if (levels > 1 && (rc = ofps::sad_hier_check(ctx, f.W, f.H, block, range, levels)) != OFPS_HIP_OK) return rc;
+    const int nbx = f.W / block, nby = f.H / block;
+    if (nbx == 0 || nby == 0 || pairs <= 0) return OFPS_HIP_OK;
+    OFPS_REQUIRE(ctx, pairs <= 65535 && nby <= 65535, "sad_flow: grid too large");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // motion scale 4: the refinement (sad_qpel.hip) starts from the integer winners, so they are kept even when the caller wants none
     // (consistency check, sad_consistency.hip: its backward search is integer_only; its forward search keeps the integer winners in d_int_best)
     const bool qpel = ctx->opt.sad_motion_scale == 4 && !integer_only;
-    if (qpel && d_int_best) p.out_best = static_cast<int*>(d_int_best);
-    else if (qpel && !p.out_best) {
-        p.out_best = static_cast<int*>(ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * p.nbx * p.nby * 3 * sizeof(int)));
-        if (!p.out_best) return OFPS_HIP_ENOMEM;
+    void* d_best = d_out_best;                                  // where the integer winners go
+    if (qpel && d_int_best) d_best = d_int_best;
+    else if (qpel && !d_best) {
+        d_best = ofps::scratch(ctx, ofps::S_SAD_QBEST, (size_t)pairs * nbx * nby * 3 * sizeof(int));
+        if (!d_best) return OFPS_HIP_ENOMEM;
     }
     // mean removal (sad_prefilter.hip): everything below -- levels, plain launch, quarter-pel -- reads the filtered frames in S_SAD_PREF
-    if (prefilter > 0) {
-        rc = ofps::sad_prefilter_pairs_device(ctx, prefilter, &prev_base, &prev_pitch, &cur_base, &cur_pitch, pairs, W, H, &stride);
-        if (rc != OFPS_HIP_OK) return rc;
-        p.prev_base = prev_base; p.cur_base = cur_base; p.prev_pitch = prev_pitch; p.cur_pitch = cur_pitch; p.stride = stride;
-    }
+    SadFrames s = f;
+    if (prefilter > 0 && (rc = ofps::sad_prefilter_pairs_device(ctx, prefilter, f, pairs, &s)) != OFPS_HIP_OK) return rc;
     // with levels > 1 the level-0 winners land where the plain search's would (d_int_best included), and the quarter-pel key takes the reach
-    if (levels > 1)
-        rc = ofps::sad_hier_pairs_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block, range, levels,
-                                         predictors, d_out_entries, p.out_best);
-    else rc = sad_launch(ctx, p, pairs, block, range);
+    if (levels > 1) rc = ofps::sad_hier_pairs_device(ctx, s, pairs, block, range, levels, predictors, d_out_entries, d_best);
+    else rc = sad_launch(ctx, s, pairs, block, range, d_out_entries, d_best);
     if (rc != OFPS_HIP_OK) return rc;
     if (qpel)
-        return ofps::sad_qpel_refine_device(ctx, prev_base, prev_pitch, cur_base, cur_pitch, pairs, W, H, stride, block,
-                                            levels > 1 ? ofps::sad_hier_reach(range, levels) : range, d_out_entries, p.out_best, d_out_best);
+        return ofps::sad_qpel_refine_device(ctx, s, pairs, block, levels > 1 ? ofps::sad_hier_reach(range, levels) : range, d_out_entries, d_best,
+                                            d_out_best);
     return OFPS_HIP_OK;
 }
 }  // namespace ofps
@@ -1320,9 +1309,8 @@ int ofps_hip_sad_flow_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames,
     OFPS_REQUIRE(ctx, n_frames >= 2, "sad_flow: need at least 2 frames (got %d)", n_frames);
     OFPS_REQUIRE(ctx, frame_pitch >= (size_t)stride * (size_t)H, "sad_flow: frame_pitch smaller than a frame");
     OFPS_REQUIRE(ctx, ref_mode == 0 || ref_mode == 1, "sad_flow: ref_mode must be 0 or 1");
-    const auto* f = static_cast<const uint8_t*>(d_frames);
-    return ofps::sad_pairs_device(ctx, f, ref_mode ? 0 : frame_pitch, f + frame_pitch, frame_pitch, n_frames - 1, W, H, stride,
-                                  block, range, d_out_entries, d_out_best);
+    return ofps::sad_pairs_device(ctx, ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride),
+                                  n_frames - 1, block, range, d_out_entries, d_out_best);
 }
 
 int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride,
@@ -1347,8 +1335,9 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0 || ctx->opt.sad_median > 0) {
         auto* d_kept = static_cast<uint32_t*>(ofps::scratch(ctx, ofps::S_RESULT, sizeof(uint32_t)));
         if (!d_kept) return OFPS_HIP_ENOMEM;
-        rc = ofps::sad_flow_filtered_device(ctx, d_frames, d_frames + pitch, W, H, dstride, block, range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
-                                            ctx->opt.sad_median, reinterpret_cast<float4*>(d_ent), out_best ? d_best : nullptr, d_kept);
+        rc = ofps::sad_flow_filtered_device(ctx, {d_frames, d_frames + pitch, 0, 0, W, H, dstride}, 1, block, range, ctx->opt.sad_gate,
+                                            ctx->opt.sad_consistency, ctx->opt.sad_median, reinterpret_cast<float4*>(d_ent),
+                                            out_best ? d_best : nullptr, d_kept, "sad_flow");
         if (rc != OFPS_HIP_OK) return rc;
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
     } else {

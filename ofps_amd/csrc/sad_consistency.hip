@@ -2,9 +2,9 @@
 // the search in the other direction, started where its own winner points, comes back -- the round-trip test of flow and stereo pipelines.
 // It drops what the contrast gate (sad_gate.hip) keeps: content that left the frame or was occluded, repeated texture, noise winners.
 //
-// Nothing here searches.  The backward winners are ofps::sad_pairs_device with the two frame bases exchanged (the search kernels of
-// sad.hip are the parent's, untouched); this file holds what is behind the two searches:
-// sad_consistency_kernel: one lane per block: F[k] -> partner block k' -> G[k'] -> residual = max(|dx + ex|, |dy + ey|) -> keep byte.
+// Nothing here searches.  The backward winners are ofps::sad_pairs_device over SadFrames::swapped() (the search kernels of sad.hip are the
+// parent's, untouched); this file holds what is behind the two searches:
+// sad_consistency_kernel: one lane per block of one item (blockIdx.y; one pair is item 0): F[k] -> partner block k' -> G[k'] -> residual = max(|dx + ex|, |dy + ey|) -> keep byte.
 //   12 + 12 bytes read per block (the gather hits the 12 bytes of a near neighbour: |d| <= 64 px is at most 8 blocks away), 1-5 written.
 // The keep bytes feed the ordered compactions the gate already uses (mask.hip, compact_best_kernel): one compaction, one count.
 //
@@ -46,16 +46,10 @@ __device__ __forceinline__ void sad_consistency_block(const int* __restrict__ fw
     }
 }
 
+// blockIdx.y is the item, every array nbx * nby elements per item.  The partner block is clamped into the item's own lattice
 __global__ __launch_bounds__(256) void sad_consistency_kernel(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B,
                                                               int limit, const uint8_t* keep_in, uint32_t* __restrict__ out_residual,
                                                               uint8_t* out_keep) {
-    sad_consistency_block(fwd, bwd, nbx, nby, B, limit, keep_in, out_residual, out_keep);
-}
-
-// the batched form: blockIdx.y is the item, every array nbx * nby elements per item.  The partner block is clamped into the item's own lattice
-__global__ __launch_bounds__(256) void sad_consistency_items_kernel(const int* __restrict__ fwd, const int* __restrict__ bwd, int nbx, int nby, int B,
-                                                                    int limit, const uint8_t* keep_in, uint32_t* __restrict__ out_residual,
-                                                                    uint8_t* out_keep) {
     const size_t at = (size_t)blockIdx.y * ((size_t)nbx * nby);
     sad_consistency_block(fwd + 3 * at, bwd + 3 * at, nbx, nby, B, limit, keep_in ? keep_in + at : nullptr, out_residual ? out_residual + at : nullptr,
                           out_keep ? out_keep + at : nullptr);
@@ -77,12 +71,8 @@ int sad_consistency_flags_device(ofps_hip_ctx* ctx, const int* d_fwd_best, const
     OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "sad_consistency: too many blocks");
     OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "sad_consistency: %d items", items);
     const size_t nblk = (size_t)nbx * nby;
-    if (items > 1)
-        hipLaunchKernelGGL(sad_consistency_items_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_fwd_best, d_bwd_best,
-                           nbx, nby, block, limit, d_keep_in, d_out_residual, d_out_keep);
-    else
-        hipLaunchKernelGGL(sad_consistency_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_fwd_best, d_bwd_best, nbx, nby, block,
-                           limit, d_keep_in, d_out_residual, d_out_keep);
+    hipLaunchKernelGGL(sad_consistency_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_fwd_best, d_bwd_best, nbx,
+                       nby, block, limit, d_keep_in, d_out_residual, d_out_keep);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
@@ -146,9 +136,9 @@ int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const v
     const int rc = ofps::sad_consistency_check(ctx, block, limit, "sad_flow");           // (the filter itself takes 0 for "no check")
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
-    return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                          min_pixels, limit, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                          static_cast<uint32_t*>(d_out_count));
+    return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
+                                          range, min_pixels, limit, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 
 }  // extern "C"

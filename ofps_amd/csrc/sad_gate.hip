@@ -10,8 +10,9 @@
 // result does not depend on the order).
 // block_keep_kernel: count >= min_pixels -> one byte per block, the flag the ordered compactions of mask.hip take.
 // compact_best_kernel: the (dx, dy, SAD) triples compacted by the same flags in the same order.
-// block_contrast_items_kernel, compact_items_kernel: the batched forms (include/ofps_hip.h N1b) -- the item in a grid dimension, one launch
-// over a whole batch of pairs; the compaction segmented: one workgroup per item, records + triples + one count per item.
+// Every kernel but the compactions takes the item (the pair of a batch, include/ofps_hip.h N1b) from a grid dimension or sees the batch as one
+// array: one launch per step whatever the number of pairs, and one pair is item 0.
+// compact_items_kernel: a batch's compaction, segmented: one workgroup per item, records + triples + one count per item.
 //
 // Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate, the consistency check (sad_consistency.hip)
 // and / or the median test (sad_median.hip) in front of one compaction and one device-side count -- for the one-pair entry points, the fused
@@ -21,7 +22,7 @@
 
 namespace ofps {
 
-// one workgroup's tile of one frame: what both kernels below run
+// one workgroup's tile of one frame
 __device__ __forceinline__ void block_contrast_tile(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx, int nby,
                                                     int lattice, uint32_t* __restrict__ counts) {
     __shared__ uint8_t g[MG_H][MG_W + 2];
@@ -61,14 +62,9 @@ __device__ __forceinline__ void block_contrast_tile(const uint8_t* __restrict__ 
     if (lattice) counts[(size_t)by * nbx + bx] = c; else if (c) atomicAdd(&counts[(size_t)by * nbx + bx], c);
 }
 
-__global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __restrict__ gray, int W, int H, int stride, int block, int nbx,
-                                                             int nby, int lattice, uint32_t* __restrict__ counts) {
-    block_contrast_tile(gray, W, H, stride, block, nbx, nby, lattice, counts);
-}
-
-// the batched form: blockIdx.z is the item, its frame `pitch` bytes behind the previous item's, its counts nbx * nby behind
-__global__ __launch_bounds__(256) void block_contrast_items_kernel(const uint8_t* __restrict__ gray, size_t pitch, int W, int H, int stride,
-                                                                   int block, int nbx, int nby, int lattice, uint32_t* __restrict__ counts) {
+// blockIdx.z is the item, its frame `pitch` bytes behind the previous item's, its counts nbx * nby behind
+__global__ __launch_bounds__(256) void block_contrast_kernel(const uint8_t* __restrict__ gray, size_t pitch, int W, int H, int stride, int block,
+                                                             int nbx, int nby, int lattice, uint32_t* __restrict__ counts) {
     const size_t item = blockIdx.z;
     block_contrast_tile(gray + item * pitch, W, H, stride, block, nbx, nby, lattice, counts + item * (size_t)nbx * nby);
 }
@@ -145,9 +141,9 @@ __global__ __launch_bounds__(1024) void compact_items_kernel(const float4* __res
     if (tid == 0) counts[item] = base_sh;
 }
 
-// items > 1: frame k lies k * pitch bytes behind d_luma, its counts k * nblk behind d_counts; one launch over all of them
-static int block_contrast_items_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, size_t pitch, int items, int W, int H, int stride, int block,
-                                       uint32_t* d_counts, hipStream_t st) {
+// frame k lies k * pitch bytes behind d_luma, its counts k * nblk behind d_counts; one launch over all `items`
+int block_contrast_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, size_t pitch, int items, int W, int H, int stride, int block, uint32_t* d_counts,
+                          hipStream_t st) {
     OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
     OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "block_contrast: %d items", items);
@@ -156,21 +152,7 @@ static int block_contrast_items_device(ofps_hip_ctx* ctx, const uint8_t* d_luma,
     OFPS_REQUIRE(ctx, (long long)nbx * nby * items < (1ll << 31), "block_contrast: too many blocks");
     const int lattice = block == 8 || block == 16;
     if (!lattice) OFPS_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)items * nbx * nby * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(block_contrast_items_kernel, dim3((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H, items), dim3(256), 0, st, d_luma, pitch, W, H,
-                       stride, block, nbx, nby, lattice, d_counts);
-    OFPS_HIP_TRY(ctx, hipGetLastError());
-    return OFPS_HIP_OK;
-}
-
-int block_contrast_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, int W, int H, int stride, int block, uint32_t* d_counts, hipStream_t st) {
-    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && stride >= W, "block_contrast: bad geometry W=%d H=%d stride=%d", W, H, stride);
-    OFPS_REQUIRE(ctx, block >= 1 && block <= 64, "block_contrast: block=%d outside [1,64]", block);
-    const int nbx = W / block, nby = H / block;
-    if (nbx == 0 || nby == 0) return OFPS_HIP_OK;
-    OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "block_contrast: too many blocks");
-    const int lattice = block == 8 || block == 16;
-    if (!lattice) OFPS_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)nbx * nby * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(block_contrast_kernel, dim3((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H), dim3(256), 0, st, d_luma, W, H, stride,
+    hipLaunchKernelGGL(block_contrast_kernel, dim3((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H, items), dim3(256), 0, st, d_luma, pitch, W, H, stride,
                        block, nbx, nby, lattice, d_counts);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
@@ -183,15 +165,15 @@ static int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const ch
     return OFPS_HIP_OK;
 }
 
-// ---- SadFilter (common.hpp): the steps of one pair's filtered search
+// ---- SadFilter (common.hpp): the steps of the filtered search
 int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     int rc = limit > 0 ? sad_consistency_check(ctx, block, limit, who) : OFPS_HIP_OK;
     if (rc == OFPS_HIP_OK && gate > 0) rc = sad_gate_check(ctx, block, gate, who);
     if (rc == OFPS_HIP_OK && median > 0) rc = sad_median_check(ctx, block, median, who);
     if (rc != OFPS_HIP_OK) return rc;
-    OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W, "%s: bad geometry W=%d H=%d stride=%d", who, W, H, stride);
+    OFPS_REQUIRE(ctx, fr.W > 0 && fr.H > 0 && fr.stride >= fr.W, "%s: bad geometry W=%d H=%d stride=%d", who, fr.W, fr.H, fr.stride);
     OFPS_REQUIRE(ctx, pairs >= 1 && pairs <= 65535, "%s: %d pairs outside [1, 65535]", who, pairs);
-    nblk = ofps_hip_sad_block_count(W, H, block);
+    nblk = ofps_hip_sad_block_count(fr.W, fr.H, block);
     OFPS_REQUIRE(ctx, pairs == 1 || total() < (size_t(1) << 31), "%s: too many blocks (%d pairs of %zu)", who, pairs, nblk);
     return OFPS_HIP_OK;
 }
@@ -223,21 +205,19 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
     return want_triples && !d_triples ? OFPS_HIP_ENOMEM : OFPS_HIP_OK;
 }
 
-int SadFilter::search(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, float4* d_out) {
-    if (!winners()) return sad_pairs_device(ctx, d_prev, prev_pitch, d_cur, cur_pitch, pairs, W, H, stride, block, range, on() ? d_raw : d_out, d_triples);
+int SadFilter::search(ofps_hip_ctx* ctx, float4* d_out) {
+    if (!winners()) return sad_pairs_device(ctx, fr, pairs, block, range, on() ? d_raw : d_out, d_triples);
     // check or median test on (the two hazards: sad_consistency.hip): the forward search leaves its integer winners in d_fwd whatever the motion scale -- at
     // scale 4 as d_int_best, the refinement then writes d_triples or nothing -- and the backward search, integer only, runs right behind it
     const bool qpel = ctx->opt.sad_motion_scale == 4;
-    const int rc = sad_pairs_device(ctx, d_prev, prev_pitch, d_cur, cur_pitch, pairs, W, H, stride, block, range, d_raw, qpel ? d_triples : d_fwd,
-                                    /*integer_only=*/false, qpel ? d_fwd : nullptr);
+    const int rc = sad_pairs_device(ctx, fr, pairs, block, range, d_raw, qpel ? d_triples : d_fwd, /*integer_only=*/false, qpel ? d_fwd : nullptr);
     if (rc != OFPS_HIP_OK || limit == 0) return rc;
-    return sad_pairs_device(ctx, d_cur, cur_pitch, d_prev, prev_pitch, pairs, W, H, stride, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
+    return sad_pairs_device(ctx, fr.swapped(), pairs, block, range, d_bwd_ent, d_bwd, /*integer_only=*/true);
 }
 
-int SadFilter::contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream_t st) {
+int SadFilter::contrast_flags(ofps_hip_ctx* ctx, hipStream_t st) {
     if (gate <= 0 || !nblk) return OFPS_HIP_OK;
-    const int rc = pairs == 1 ? block_contrast_device(ctx, d_cur, W, H, stride, block, gate_counts(d_flags), st)
-                              : block_contrast_items_device(ctx, d_cur, cur_pitch, pairs, W, H, stride, block, gate_counts(d_flags), st);
+    const int rc = block_contrast_device(ctx, fr.cur_base, fr.cur_pitch, pairs, fr.W, fr.H, fr.stride, block, gate_counts(d_flags), st);
     if (rc != OFPS_HIP_OK) return rc;
     // a flag depends on its own count alone: the batch's pairs * nblk counts are one array to this kernel
     hipLaunchKernelGGL(block_keep_kernel, dim3((unsigned)((total() + 255) / 256)), dim3(256), 0, st, gate_counts(d_flags), (uint32_t)total(), (uint32_t)gate, keep());
@@ -247,19 +227,22 @@ int SadFilter::contrast_flags(ofps_hip_ctx* ctx, const uint8_t* d_cur, hipStream
 
 int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count) {
     if (!on()) return OFPS_HIP_OK;
-    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, W, H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream, pairs)
+    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, fr.W, fr.H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream, pairs)
                        : OFPS_HIP_OK;
     if (rc != OFPS_HIP_OK) return rc;
     // one pass: the median test reads the other criteria's flags (none on: all ones) and writes its own array
     if (median > 0)
-        rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, W, H, block, median, nullptr, d_med_keep, ctx->stream, pairs);
+        rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, fr.W, fr.H, block, median, nullptr, d_med_keep, ctx->stream, pairs);
     if (rc != OFPS_HIP_OK) return rc;
     if (nblk == 0) {
         OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, pairs * sizeof(uint32_t), ctx->stream));
         return OFPS_HIP_OK;
     }
     const uint8_t* flags = median > 0 ? d_med_keep : keep();
-    if (pairs > 1) {                                          // one workgroup per item, whatever nblk: records, triples and counts[item] in one launch
+    // The compaction is the one step that keeps a path per shape.  compact_items_kernel runs ONE workgroup per item whatever nblk: right for a
+    // batch of small lattices, but one pair through it would scan a 4K frame's 129,600 blocks on one compute unit, and in one launch where the
+    // paths below take up to three.  That would change speed and launch count; the one-pair path stays on the grid-wide compactions of mask.hip
+    if (pairs > 1) {                                          // records, triples and counts[item] in one launch
         hipLaunchKernelGGL(compact_items_kernel, dim3((unsigned)pairs), dim3(1024), 0, ctx->stream, d_raw, d_out_best ? d_triples : nullptr, flags,
                            (uint32_t)nblk, d_out, d_out_best, d_count);
         OFPS_HIP_TRY(ctx, hipGetLastError());
@@ -275,29 +258,17 @@ int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_
     return OFPS_HIP_OK;
 }
 
-// One pair, everything on ctx->stream: search[es], [contrast flags of `cur`,] [the check's flags,] [the median test's flags,] one compaction, one count.
-int sad_flow_filtered_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int block, int range,
-                             int min_pixels, int limit, int median, float4* d_out, int* d_out_best, uint32_t* d_count) {
-    SadFilter f{W, H, stride, block, range, min_pixels, limit, median, d_out_best != nullptr};
-    int rc = f.plan(ctx, "sad_flow");
-    if (rc == OFPS_HIP_OK) rc = f.reserve(ctx);
-    if (rc == OFPS_HIP_OK) rc = f.search(ctx, d_prev, d_cur, d_out);
-    if (rc == OFPS_HIP_OK) rc = f.contrast_flags(ctx, d_cur, ctx->stream);
-    return rc == OFPS_HIP_OK ? f.finish(ctx, d_out, d_out_best, d_count) : rc;
-}
-
-// `pairs` pairs, pair k = (d_prev + k * prev_pitch, d_cur + k * cur_pitch), everything on ctx->stream, the launch count independent of `pairs`:
-// item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k] is their number
-int sad_flow_filtered_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, size_t prev_pitch, const uint8_t* d_cur, size_t cur_pitch, int pairs,
-                                   int W, int H, int stride, int block, int range, int min_pixels, int limit, int median, float4* d_out,
-                                   int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets) {
-    SadFilter f{W, H, stride, block, range, min_pixels, limit, median, d_out_best != nullptr};
-    f.pairs = pairs; f.prev_pitch = prev_pitch; f.cur_pitch = cur_pitch;
-    int rc = f.plan(ctx, who);
-    if (rc == OFPS_HIP_OK) rc = f.reserve(ctx, tix, tickets);
-    if (rc == OFPS_HIP_OK) rc = f.search(ctx, d_prev, d_cur, d_out);
-    if (rc == OFPS_HIP_OK) rc = f.contrast_flags(ctx, d_cur, ctx->stream);
-    return rc == OFPS_HIP_OK ? f.finish(ctx, d_out, d_out_best, d_counts) : rc;
+// `pairs` pairs of `f`, everything on ctx->stream: search[es], [contrast flags of the current frames,] [the check's flags,] [the median test's
+// flags,] one compaction, one count per pair.  Item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k]
+// is their number
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
+                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets) {
+    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, d_out_best != nullptr};
+    int rc = flt.plan(ctx, who);
+    if (rc == OFPS_HIP_OK) rc = flt.reserve(ctx, tix, tickets);
+    if (rc == OFPS_HIP_OK) rc = flt.search(ctx, d_out);
+    if (rc == OFPS_HIP_OK) rc = flt.contrast_flags(ctx, ctx->stream);
+    return rc == OFPS_HIP_OK ? flt.finish(ctx, d_out, d_out_best, d_counts) : rc;
 }
 
 }  // namespace ofps
@@ -319,18 +290,16 @@ int ofps_hip_sad_flow_filtered_dev(ofps_hip_ctx* ctx, const void* d_frames, int 
     OFPS_REQUIRE(ctx, min_pixels > 0 || limit > 0 || median > 0,
                  "sad_flow_filtered_dev: contrast gate, consistency limit and median limit are all 0 (the unfiltered form is ofps_hip_sad_flow_dev)");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto* f = static_cast<const uint8_t*>(d_frames);
-    // the current frame of pair k is frame k + 1 in both modes: the gate reads it, the backward search starts from it
-    return ofps::sad_flow_filtered_batch_device(ctx, f, ref_mode ? 0 : frame_pitch, f + frame_pitch, frame_pitch, n_frames - 1, W, H, stride, block,
-                                                range, min_pixels, limit, median, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                                static_cast<uint32_t*>(d_out_counts), "sad_flow_filtered_dev", 0, 1);
+    return ofps::sad_flow_filtered_device(ctx, ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride),
+                                          n_frames - 1, block, range, min_pixels, limit, median, static_cast<float4*>(d_out_entries),
+                                          static_cast<int*>(d_out_best), static_cast<uint32_t*>(d_out_counts), "sad_flow_filtered_dev");
 }
 
 int ofps_hip_block_contrast_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_counts) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_luma && d_out_counts, "block_contrast_dev: null device pointer");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ofps::block_contrast_device(ctx, static_cast<const uint8_t*>(d_luma), W, H, stride, block, static_cast<uint32_t*>(d_out_counts), ctx->stream);
+    return ofps::block_contrast_device(ctx, static_cast<const uint8_t*>(d_luma), 0, 1, W, H, stride, block, static_cast<uint32_t*>(d_out_counts), ctx->stream);
 }
 
 int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_counts) {
@@ -345,7 +314,7 @@ int ofps_hip_block_contrast(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H
     auto* d_flags = static_cast<char*>(ofps::scratch(ctx, ofps::S_GATE_FLAGS, ofps::gate_flags_bytes(nblk)));
     if (!d_gray || !d_flags) return OFPS_HIP_ENOMEM;
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_gray, W, luma, stride, W, H, ctx->stream));
-    const int rc = ofps::block_contrast_device(ctx, d_gray, W, H, W, block, ofps::gate_counts(d_flags), ctx->stream);
+    const int rc = ofps::block_contrast_device(ctx, d_gray, 0, 1, W, H, W, block, ofps::gate_counts(d_flags), ctx->stream);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, ofps::gate_counts(d_flags), nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -377,9 +346,9 @@ int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int rc = ofps::sad_gate_check(ctx, block, min_pixels, "sad_flow");             // (the filter itself takes 0 for "no gate")
     if (rc != OFPS_HIP_OK) return rc;
-    return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                          min_pixels, 0, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                          static_cast<uint32_t*>(d_out_count));
+    return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
+                                          range, min_pixels, 0, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 
 }  // extern "C"

@@ -18,15 +18,10 @@
 
 namespace {
 
-struct HierLevel {                  // one level of one search's two frame sets
-    const uint8_t* prev_base;       // pair k: prev = prev_base + k*prev_pitch, cur = cur_base + k*cur_pitch
-    const uint8_t* cur_base;
-    size_t prev_pitch, cur_pitch;
-    int W, H, stride;
-};
+using ofps::SadFrames;
 
 struct RefineParams {
-    HierLevel f;
+    SadFrames f;                    // one level of one search's two frame sets
     int nbx, nby, B;                // this level's lattice
     int pnbx, pnby;                 // the parent lattice
     long long total;                // blocks of the whole batch
@@ -401,7 +396,7 @@ int down2_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W,
 
 // (the level's reach R_l biases the last two fields of the definition's key and so never changes its order: the kernel does not need it)
 // predictors: OFPS_HIP_SAD_PRED_PARENT the kernel above alone, OFPS_HIP_SAD_PRED_NEIGHBOURS sad_hier_refine_pred_kernel (N1p)
-int refine_device(ofps_hip_ctx* ctx, const HierLevel& f, int pairs, int block, const int* d_parent, int pnbx, int pnby, int predictors,
+int refine_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, const int* d_parent, int pnbx, int pnby, int predictors,
                   int* d_out_best, float4* d_out_entries) {
     RefineParams p{};
     p.f = f;
@@ -460,23 +455,20 @@ int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int le
 // Called by sad_pairs_device in place of the plain search's launches when the context's levels > 1.  Pyramids and the winners of the levels
 // above 0 live in S_HIER_*: written and read on ctx->stream only, by this search alone -- the next search (the consistency check's backward
 // one, the next ticket's) is ordered behind it by that stream.
-int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch, int pairs,
-                          int W, int H, int stride, int block, int range, int levels, int predictors, void* d_out_entries, void* d_out_best) {
-    int rc = sad_hier_check(ctx, W, H, block, range, levels);
+int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int levels, int predictors, void* d_out_entries,
+                          void* d_out_best) {
+    int rc = sad_hier_check(ctx, f.W, f.H, block, range, levels);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, levels > 1 && pairs >= 1 && d_out_entries, "sad_flow: levels=%d pairs=%d is no search over levels", levels, pairs);
-    // the frames to halve: consecutive pairs of one sequence (cur = prev + one frame) are halved once, not as two sets
-    const bool chain = prev_pitch != 0 && prev_pitch == cur_pitch && cur_base == prev_base + prev_pitch;
-    const long long nprev = chain ? pairs + 1 : (prev_pitch ? pairs : 1), ncur = chain ? 0 : (cur_pitch ? pairs : 1);
-    HierLevel lv[3];
+    // the frames to halve: a chain once, not as two sets (SadFrames::sets); every level above 0 has the shape of level 0
+    const SadFrames::Sets sets = f.sets(pairs);
+    SadFrames lv[3];
     size_t pyr_off[3] = {0, 0, 0}, best_off[3] = {0, 0, 0}, pyr_bytes = 0, best_bytes = 0;
-    lv[0] = HierLevel{prev_base, cur_base, prev_pitch, cur_pitch, W, H, stride};
-    for (int l = 1; l < levels; ++l) {
+    lv[0] = f;
+    for (int l = 1; l < levels; ++l) {                       // the geometry; the bases follow the reservation
         lv[l].W = lv[l - 1].W >> 1; lv[l].H = lv[l - 1].H >> 1;
         lv[l].stride = (lv[l].W + 63) & ~63;                 // 64-byte rows, so 16-byte frame pitches: the top search gets the strip kernel
-        const size_t pitch = (size_t)lv[l].stride * lv[l].H;
-        lv[l].prev_pitch = prev_pitch ? pitch : 0; lv[l].cur_pitch = cur_pitch ? pitch : 0;
-        pyr_off[l] = pyr_bytes; pyr_bytes += (size_t)(nprev + ncur) * pitch;
+        pyr_off[l] = pyr_bytes; pyr_bytes += (size_t)(sets.nprev + sets.ncur) * lv[l].stride * lv[l].H;
         best_off[l] = best_bytes;
         best_bytes += (((size_t)pairs * (lv[l].W / block) * (lv[l].H / block) * 3 * sizeof(int)) + 255) & ~size_t(255);
     }
@@ -489,17 +481,16 @@ int sad_hier_pairs_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t pr
     for (int l = 1; l < levels; ++l) {
         uint8_t* dp = pyr + pyr_off[l];
         const size_t pitch = (size_t)lv[l].stride * lv[l].H;
-        uint8_t* dc = chain ? dp + pitch : dp + (size_t)nprev * pitch;
-        lv[l].prev_base = dp; lv[l].cur_base = dc;
-        const HierLevel& s = lv[l - 1];
-        rc = down2_device(ctx, s.prev_base, s.prev_pitch, s.W, s.H, s.stride, dp, pitch, lv[l].stride, nprev);
-        if (rc == OFPS_HIP_OK && !chain) rc = down2_device(ctx, s.cur_base, s.cur_pitch, s.W, s.H, s.stride, dc, pitch, lv[l].stride, ncur);
+        lv[l] = sets.in(dp, pitch, lv[l].W, lv[l].H, lv[l].stride);
+        const SadFrames& s = lv[l - 1];
+        rc = down2_device(ctx, s.prev_base, s.prev_pitch, s.W, s.H, s.stride, dp, pitch, lv[l].stride, sets.nprev);
+        if (rc == OFPS_HIP_OK && !sets.chain)
+            rc = down2_device(ctx, s.cur_base, s.cur_pitch, s.W, s.H, s.stride, dp + (size_t)sets.cur_first() * pitch, pitch, lv[l].stride, sets.ncur);
         if (rc != OFPS_HIP_OK) return rc;
     }
     // top: the plain search, never sad_pairs_device -- no quarter-pel refinement of the top winners, no way back here
     int* parent = reinterpret_cast<int*>(bestbuf + best_off[top]);
-    rc = sad_search_device(ctx, lv[top].prev_base, lv[top].prev_pitch, lv[top].cur_base, lv[top].cur_pitch, pairs, lv[top].W, lv[top].H,
-                           lv[top].stride, block, range, top_ent, parent);
+    rc = sad_search_device(ctx, lv[top], pairs, block, range, top_ent, parent);
     if (rc != OFPS_HIP_OK) return rc;
     for (int l = top - 1; l >= 0; --l) {
         int* out = l == 0 ? static_cast<int*>(d_out_best) : reinterpret_cast<int*>(bestbuf + best_off[l]);
@@ -574,7 +565,7 @@ int ofps_hip_sad_refine_pred_dev(ofps_hip_ctx* ctx, const void* d_prev, const vo
     OFPS_REQUIRE(ctx, stride % 4 == 0 && ((uintptr_t)d_prev % 4) == 0 && ((uintptr_t)d_cur % 4) == 0,
                  "sad_refine: rows must be 4-byte aligned (stride=%d)", stride);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const HierLevel f{static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride};
+    const SadFrames f{static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride};
     return refine_device(ctx, f, 1, block, static_cast<const int*>(d_parent_best), nbx_parent, nby_parent, predictors, static_cast<int*>(d_out_best),
                          static_cast<float4*>(d_out_entries));
 }

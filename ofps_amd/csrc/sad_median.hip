@@ -4,7 +4,7 @@
 // round-trip-consistent match at the wrong place (repeated texture, a block clipped by the frame edge, the mask's dilation ring).
 //
 // Nothing here searches.  This file holds what is behind the search[es] and the other criteria's flags:
-// sad_median_kernel: one lane per block: up to 8 neighbours' (dx, dy) and incoming keep bytes -> two sorts of 8 in registers -> the two middle
+// sad_median_kernel: one lane per block of one item (blockIdx.y; one pair is item 0): up to 8 neighbours' (dx, dy) and incoming keep bytes -> two sorts of 8 in registers -> the two middle
 //   order statistics per component -> residual in half-pixels -> keep byte.  At most 8 * (8 + 1) + 8 + 1 bytes read per block (neighbouring
 //   lanes read the same lines), 1-5 written.  A latency-sized launch: no LDS, no tiling.
 // One pass: every verdict reads the INCOMING flags of its neighbours, so the outgoing flags are another array (SadFilter: S_MED_KEEP).
@@ -73,15 +73,10 @@ __device__ __forceinline__ void sad_median_block(const int* __restrict__ best, c
     if (out_keep) out_keep[k] = r2 < limit2 && (!keep_in || keep_in[k] != 0) ? 1 : 0;
 }
 
+// blockIdx.y is the item, every array nbx * nby elements per item.  A neighbour index is formed inside the item's own lattice (x in [0, nbx),
+// y in [0, nby)) and never reaches another item's blocks
 __global__ __launch_bounds__(256) void sad_median_kernel(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
                                                          uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
-    sad_median_block(best, keep_in, nbx, nby, limit2, out_residual2, out_keep);
-}
-
-// the batched form: blockIdx.y is the item, every array nbx * nby elements per item.  A neighbour index is formed inside the item's own
-// lattice (x in [0, nbx), y in [0, nby)) and never reaches another item's blocks
-__global__ __launch_bounds__(256) void sad_median_items_kernel(const int* __restrict__ best, const uint8_t* __restrict__ keep_in, int nbx, int nby,
-                                                               uint32_t limit2, uint32_t* __restrict__ out_residual2, uint8_t* __restrict__ out_keep) {
     const size_t at = (size_t)blockIdx.y * ((size_t)nbx * nby);
     sad_median_block(best + 3 * at, keep_in ? keep_in + at : nullptr, nbx, nby, limit2, out_residual2 ? out_residual2 + at : nullptr,
                      out_keep ? out_keep + at : nullptr);
@@ -104,12 +99,8 @@ int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t*
     OFPS_REQUIRE(ctx, (long long)nbx * nby < (1ll << 31), "sad_median: too many blocks");
     OFPS_REQUIRE(ctx, items >= 1 && items <= 65535, "sad_median: %d items", items);
     const size_t nblk = (size_t)nbx * nby;
-    if (items > 1)
-        hipLaunchKernelGGL(sad_median_items_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_best, d_keep_in, nbx,
-                           nby, 2u * (uint32_t)limit, d_out_residual2, d_out_keep);
-    else
-        hipLaunchKernelGGL(sad_median_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_best, d_keep_in, nbx, nby,
-                           2u * (uint32_t)limit, d_out_residual2, d_out_keep);
+    hipLaunchKernelGGL(sad_median_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)items), dim3(256), 0, st, d_best, d_keep_in, nbx, nby,
+                       2u * (uint32_t)limit, d_out_residual2, d_out_keep);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
@@ -174,9 +165,9 @@ int ofps_hip_sad_flow_median_dev(ofps_hip_ctx* ctx, const void* d_prev, const vo
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
     OFPS_REQUIRE(ctx, limit >= 0, "sad_flow: consistency limit %d is negative", limit);
-    return ofps::sad_flow_filtered_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, block, range,
-                                          min_pixels, limit, median_limit, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
-                                          static_cast<uint32_t*>(d_out_count));
+    return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
+                                          range, min_pixels, limit, median_limit, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 
 }  // extern "C"

@@ -184,25 +184,20 @@ int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch
 }
 
 // Called by sad_pairs_device in front of its launches when the context's sad_prefilter > 0: the two frame sets are filtered into S_SAD_PREF and
-// the bases, pitches and stride are replaced by the filtered ones (64-byte rows, so the search behind it takes the strip kernel whatever the
-// caller's alignment was).  Consecutive pairs of one sequence (cur = prev + one frame) are filtered once over pairs + 1 frames; a set with
-// pitch 0 is one frame.  S_SAD_PREF is written and read on ctx->stream only, anew by every search, which that stream orders.
-int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const uint8_t** prev_base, size_t* prev_pitch, const uint8_t** cur_base,
-                               size_t* cur_pitch, int pairs, int W, int H, int* stride) {
-    const bool chain = *prev_pitch != 0 && *prev_pitch == *cur_pitch && *cur_base == *prev_base + *prev_pitch;
-    const long long nprev = chain ? (long long)pairs + 1 : (*prev_pitch ? pairs : 1), ncur = chain ? 0 : (*cur_pitch ? pairs : 1);
-    const int fstride = (W + 63) & ~63;
-    const size_t fpitch = (size_t)fstride * H;
-    auto* buf = static_cast<uint8_t*>(scratch(ctx, S_SAD_PREF, (size_t)(nprev + ncur) * fpitch));
+// *filtered describes them there (64-byte rows, so the search behind it takes the strip kernel whatever the caller's alignment was).  What
+// is filtered and where it lands: SadFrames::sets -- a chain once over pairs + 1 frames, a set with pitch 0 as one frame.  S_SAD_PREF is
+// written and read on ctx->stream only, anew by every search, which that stream orders.
+int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const SadFrames& f, int pairs, SadFrames* filtered) {
+    const SadFrames::Sets sets = f.sets(pairs);
+    const int fstride = (f.W + 63) & ~63;
+    const size_t fpitch = (size_t)fstride * f.H;
+    auto* buf = static_cast<uint8_t*>(scratch(ctx, S_SAD_PREF, (size_t)(sets.nprev + sets.ncur) * fpitch));
     if (!buf) return OFPS_HIP_ENOMEM;
-    uint8_t* fcur = chain ? buf + fpitch : buf + (size_t)nprev * fpitch;
-    int rc = sad_prefilter_device(ctx, *prev_base, *prev_pitch, W, H, *stride, buf, fpitch, fstride, nprev, radius);
-    if (rc == OFPS_HIP_OK && !chain) rc = sad_prefilter_device(ctx, *cur_base, *cur_pitch, W, H, *stride, fcur, fpitch, fstride, ncur, radius);
-    if (rc != OFPS_HIP_OK) return rc;
-    *prev_base = buf; *cur_base = fcur;
-    *prev_pitch = *prev_pitch ? fpitch : 0; *cur_pitch = *cur_pitch ? fpitch : 0;
-    *stride = fstride;
-    return OFPS_HIP_OK;
+    int rc = sad_prefilter_device(ctx, f.prev_base, f.prev_pitch, f.W, f.H, f.stride, buf, fpitch, fstride, sets.nprev, radius);
+    if (rc == OFPS_HIP_OK && !sets.chain)
+        rc = sad_prefilter_device(ctx, f.cur_base, f.cur_pitch, f.W, f.H, f.stride, buf + (size_t)sets.cur_first() * fpitch, fpitch, fstride, sets.ncur, radius);
+    if (rc == OFPS_HIP_OK) *filtered = sets.in(buf, fpitch, f.W, f.H, fstride);
+    return rc;
 }
 
 }  // namespace ofps

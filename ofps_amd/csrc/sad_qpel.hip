@@ -238,19 +238,18 @@ void launch_qpel(const QpelParams& p, hipStream_t s) {
 namespace ofps {
 // Enqueued by sad_pairs_device behind the integer search when the context's motion scale is 4.  d_in_best: the search's
 // (dx, dy, sad); d_out_best: null, or where (Dx, Dy, SAD) go (may be d_in_best itself).
-int sad_qpel_refine_device(ofps_hip_ctx* ctx, const uint8_t* prev_base, size_t prev_pitch, const uint8_t* cur_base, size_t cur_pitch,
-                           int pairs, int W, int H, int stride, int block, int range, void* d_entries, const void* d_in_best,
+int sad_qpel_refine_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, void* d_entries, const void* d_in_best,
                            void* d_out_best) {
     OFPS_REQUIRE(ctx, block >= 1 && block <= 64 && range >= 0 && range <= kSadHierMaxReach, "sad_qpel: block=%d range=%d outside [1,64]/[0,127]",
                  block, range);                 // range above 64: the reach of a search over levels (sad_hier.hip); the key's fields hold 8 * 127 + 6
     OFPS_REQUIRE(ctx, d_entries && d_in_best, "sad_qpel: null device pointer");
     QpelParams p{};
-    p.prev_base = prev_base; p.cur_base = cur_base;
-    p.prev_pitch = prev_pitch; p.cur_pitch = cur_pitch;
-    p.W = W; p.H = H; p.stride = stride;
-    p.nbx = W / block; p.nby = H / block; p.B = block; p.R = range;
+    p.prev_base = f.prev_base; p.cur_base = f.cur_base;
+    p.prev_pitch = f.prev_pitch; p.cur_pitch = f.cur_pitch;
+    p.W = f.W; p.H = f.H; p.stride = f.stride;
+    p.nbx = f.W / block; p.nby = f.H / block; p.B = block; p.R = range;
     p.total = (long long)p.nbx * p.nby * pairs;
-    p.nx = 1.0f / (float)W; p.ny = 1.0f / (float)H;
+    p.nx = 1.0f / (float)f.W; p.ny = 1.0f / (float)f.H;
     p.out_entries = static_cast<float4*>(d_entries);
     p.in_best = static_cast<const int*>(d_in_best);
     p.out_best = static_cast<int*>(d_out_best);

@@ -115,3 +115,24 @@ def test_header_and_ctypes_table_declare_the_new_symbols():
     from ofps_amd.runtime import HipContext
     for m in ("sad_flow_filtered_dev", "set_sad_batch_filter", "get_sad_batch_filter"):
         assert callable(getattr(HipContext, m, None)), m
+
+
+def test_mean_removal_with_levels_keeps_some_blocks_of_every_item():
+    """the premise of the GPU suite's "prefilter4-levels2" mode, from the restatements alone: winners of the search over 2 levels on the
+    mean-removed frames (radius 4), forward and backward, through the criteria on the RAW frames (the gate reads the unfiltered current
+    frame) -- every item keeps some blocks and drops some, in both ref_modes, under all three criteria and under the median test alone"""
+    import indep_sad_hier as ih
+    import indep_sad_prefilter as ip
+    f = gc.frames()
+    filtered = [ip.prefilter(x, 4) for x in f]
+    for ref_mode in (0, 1):
+        counts = {(bc.GATE, bc.LIMIT, bc.MEDIAN): [], (0, 0, bc.MEDIAN): []}
+        for k in range(len(f) - 1):
+            a, b = (0 if ref_mode else k), k + 1
+            F = ih.search(filtered[a], filtered[b], gc.BLOCK, gc.RANGE, 2, top=ip.full_search)[1]
+            G = ih.search(filtered[b], filtered[a], gc.BLOCK, gc.RANGE, 2, top=ip.full_search)[1]
+            for crit, got in counts.items():
+                got.append(int(bc.keep_of(f[a], f[b], gc.BLOCK, gc.RANGE, *crit, F=F, G=G).sum()))
+        print(f"ref_mode {ref_mode}: {counts}")
+        for crit, got in counts.items():
+            assert gc.NBLK == 240 and all(0 < n < gc.NBLK for n in got), (ref_mode, crit, got)

@@ -165,6 +165,8 @@ MODES = {  # settings of the search, range
     "prefilter4": (dict(prefilter=4), gc.RANGE),
     "pruned": (dict(pruned=True), 16),                   # the pruned kernel's geometry: block 16, range 16
     "scale4-levels2": (dict(scale=4, levels=2), gc.RANGE),
+    # mean removal's output is itself a pair of frame sets the level loop lays out (tests/test_sad_batch_filter_cpu.py: the kept counts)
+    "prefilter4-levels2": (dict(prefilter=4, levels=2), gc.RANGE),
 }
 
 
