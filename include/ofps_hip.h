@@ -306,6 +306,68 @@ int ofps_hip_sad_flow_filtered_dev(ofps_hip_ctx* ctx, const void* d_frames, int 
 int ofps_hip_set_sad_batch_filter(ofps_hip_ctx* ctx, int on);   /* 0 = the batched forms ignore gate, check and median test (default) */
 int ofps_hip_get_sad_batch_filter(ofps_hip_ctx* ctx);
 
+/* ---- N1i: hip_sad's intra test and scene-cut rule -- a block that matches nothing yields no record (csrc/sad_intra.hip) ----
+ * A block whose content has no counterpart in the previous frame -- a scene cut, uncovered background, an object that appears, a flash --
+ * still has a best match among the search's candidates, and N1 reports it as a normal record.  An encoder's mode decision compares the
+ * match's cost with the cost of coding the block from itself; the decoder this build mirrors yields no vector for such a block and none on
+ * an intra frame (av-decoder/src/lib.rs:396-419).  Build-defined, like N1g, N1c and N1v; all-integer, so bit-exact on every device.  For a
+ * frame pair, lattice `block` = B in [1, 64], nbx = W / B, nby = H / B, full blocks only:
+ *   A(k), the activity of block k of the RAW current frame: S = the sum of its n = B*B pixels p, m = (S + n/2) / n (integer division: the
+ *     mean rounded half up), A(k) = the sum of |p - m|: a uint32, at most 522,240 (B = 64, half 0 and half 255).  The contrast gate (N1g)
+ *     reads the raw frame as well; with mean removal (N1m) on, the SAD below is the filtered frames' and A stays the raw frame's;
+ *   SAD(k): the SAD of the INTEGER forward winner of block k, the triple N1c and N1v read: in front of the quarter-pel refinement at
+ *     motion scale 4, the level-0 winner with search levels (N1h);
+ *   ratio q in [1, 255], in sixteenths: block k is INTRA iff 16 * SAD(k) >= q * A(k), evaluated in 64-bit signed arithmetic whatever the
+ *     triple holds.  Equality is intra; a flat block (A = 0, SAD = 0) is intra.  q = 16 is the encoder's literal rule; uncorrelated content
+ *     wins at SAD ~ A, so useful values lie below it;
+ *   flags: keep(k) = gate(k) AND NOT intra(k), gate(k) the contrast gate's flag (gate off: all ones).  The consistency check ANDs its flag
+ *     onto that, the median test reads the result as its incoming flags (gate AND NOT intra AND check).  One compaction, one count;
+ *   scene cut, P in [0, 100] percent: n_cand = the number of blocks of the pair with gate(k) = 1, n_intra = the number of those that are
+ *     intra (check and median test do not enter).  With P > 0 the pair is a CUT iff 100 * n_intra >= P * n_cand -- so n_cand = 0 is a cut --
+ *     and a cut pair yields zero records: n_vectors = 0, have_vectors as before; estimator and detector take their paths for fewer than 3
+ *     and for no records (identity, no motion: N1g).  P has no effect while q = 0; setting it then is accepted;
+ *   Kept records and out_best triples keep raster order and are the unfiltered call's records and triples bit for bit, quarter-pel or not.
+ * q = 0 = off, the default: every entry point then uses the launches, streams, scratch and bytes of a build without the test.  Values
+ * outside [0, 255] (q) and [0, 100] (P) are OFPS_HIP_EINVAL at the setters.  The options OFPS_HIP_SAD_INTRA and OFPS_HIP_SAD_CUT
+ * (environment / ofps_hip_set_option) set the same fields.
+ * ofps_hip_block_activity[_dev]: A alone, uint32 per block in raster order, any block in [1, 64], any stride >= W.  Every pixel is read once;
+ *   no address outside the frame is formed: the ragged right and bottom margins belong to no block.  The _dev form enqueues only.
+ * ofps_hip_sad_intra[_dev]: verdict and cut alone on caller-held data: (dx, dy, sad) triples (only the SAD is read, as a signed 32-bit
+ *   number), activities, keep_in (one byte per block, non-zero = gate(k) = 1, or NULL = all ones), ratio in [1, 255], cut in [0, 100] ->
+ *   out_keep (keep(k), all zero for a cut; the _dev form's may be d_keep_in) and, unless NULL, out_counts = [n_cand, n_intra].  The _dev
+ *   form enqueues only.
+ * With the context's q > 0:
+ *   ofps_hip_sad_flow: *n_out = the kept count, the kept records first (capacity nblk, as for the gate); gate, check and median test are
+ *     applied as well when they are on.
+ *   ofps_hip_push_frame[_async] / ofps_hip_frame_wait: the gate's path with one more producer of keep flags -- the activities of the current
+ *     frame are made beside the search on the second stream (with the contrast count, if the gate is on); on the compute stream behind the
+ *     search and the join: the verdicts and the pair's two counters, [check, median test,] [the cut rule's veto, one launch, only with
+ *     P > 0,] then ONE compaction and the count in device memory; no host synchronisation is added.  n_vectors = the
+ *     kept count, 0 for a cut; have_vectors stays 1 for every frame that ran a search.  A ticket follows the values the context has when it
+ *     is pushed.
+ * ofps_hip_sad_flow_intra_dev: ofps_hip_sad_flow_filtered_dev's shape (frames, pairs, both ref_modes, slots and counts) with two more
+ *   explicit values: intra in [1, 255] and cut in [0, 100]; min_pixels, limit and median may all be 0; the context's five fields are not
+ *   looked at.  Everything else of the context applies as to any search: motion scale 4, search levels and predictors, mean removal, PRUNED.
+ * The batched forms, as for N1g / N1c / N1v: ofps_hip_sad_flow_dev and ofps_hip_multi_sad_flow / _run_resident / _fetch ignore both fields
+ * and always produce nblk records per pair, and so do the explicit-argument forms _gated_dev, _checked_dev, _median_dev and _filtered_dev;
+ * ofps_hip_push_frames_async and the ofps_hip_multi_* workers' pushes follow them with the batch filter switch on (N1b).  Out of scope:
+ * replacing an intra block's vector; an activity on the filtered frame; reporting the cut through ofps_hip_frame_result (its layout is
+ * ABI); the dense decoders. */
+int ofps_hip_block_activity(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int block, uint32_t* out_activity /* nblk */);
+int ofps_hip_block_activity_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, int block, void* d_out_activity);
+int ofps_hip_sad_intra(ofps_hip_ctx* ctx, const int32_t* best, const uint32_t* activity, const uint8_t* keep_in /* nblk or NULL = all ones */,
+                       int W, int H, int block, int ratio, int cut, uint8_t* out_keep /* nblk */, uint32_t* out_counts /* [n_cand, n_intra] or NULL */);
+int ofps_hip_sad_intra_dev(ofps_hip_ctx* ctx, const void* d_best, const void* d_activity, const void* d_keep_in /* or NULL */, int W, int H,
+                           int block, int ratio, int cut, void* d_out_keep, void* d_out_counts /* two uint32, or NULL */);
+int ofps_hip_set_sad_intra(ofps_hip_ctx* ctx, int ratio);    /* sixteenths; 0 = off (default) */
+int ofps_hip_get_sad_intra(ofps_hip_ctx* ctx);
+int ofps_hip_set_sad_cut(ofps_hip_ctx* ctx, int percent);    /* 0 = off (default); no effect while the intra ratio is 0 */
+int ofps_hip_get_sad_cut(ofps_hip_ctx* ctx);
+int ofps_hip_sad_flow_intra_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch,
+                                int ref_mode, int block, int range, int min_pixels, int limit, int median, int intra /* >= 1 */, int cut,
+                                void* d_out_entries /* pairs * nblk * 4 f32 */, void* d_out_best /* pairs * nblk * 3 i32, or NULL */,
+                                void* d_out_counts /* pairs uint32 */);
+
 /* ---- N1h: hip_sad's search levels -- coarse-to-fine search for motion beyond the search range (csrc/sad_hier.hip) ----
  * The plain search cannot return a vector that was never a candidate: range 16 at 1080p ends at about one degree of camera rotation per
  * frame.  With levels = L in {2, 3} the search runs on the frames halved L - 1 times and every finer level repairs the doubled vectors in a

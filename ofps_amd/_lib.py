@@ -64,6 +64,16 @@ PROTOTYPES = {
                                                  C.c_int, C.c_int, _vp, _vp, _vp]),
     "ofps_hip_set_sad_batch_filter": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_batch_filter": (C.c_int, [_ctx]),
+    "ofps_hip_block_activity": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u32p]),
+    "ofps_hip_block_activity_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "ofps_hip_sad_intra": (C.c_int, [_ctx, _i32p, _u32p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _u32p]),
+    "ofps_hip_sad_intra_dev": (C.c_int, [_ctx, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ofps_hip_set_sad_intra": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_intra": (C.c_int, [_ctx]),
+    "ofps_hip_set_sad_cut": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_cut": (C.c_int, [_ctx]),
+    "ofps_hip_sad_flow_intra_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "ofps_hip_set_sad_levels": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_levels": (C.c_int, [_ctx]),
     "ofps_hip_sad_reach": (C.c_int, [C.c_int, C.c_int]),

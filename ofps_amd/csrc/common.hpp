@@ -108,7 +108,7 @@ struct PipeStream {
         int gated = 0;                   // pushed with the contrast gate or the consistency check on: n_vectors is the kept count in the page-locked block
         size_t n_vectors = 0;
     };
-    hipEvent_t gate_done = nullptr;      // contrast gate (sad_gate.hip): the keep flags of the newest frame, made on aux_stream beside the search (created with the first gated push)
+    hipEvent_t gate_done = nullptr;      // contrast gate and intra test (sad_gate.hip): the keep flags and activities of the newest frame, made on aux_stream beside the search (created with the first gated push)
     TicketRing<Ticket, kTickets> ring;
     void release() {
         for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); }
@@ -208,6 +208,8 @@ struct ofps_hip_ctx {
         int sad_levels = 1;              // OFPS_HIP_SAD_LEVELS / ofps_hip_set_sad_levels: 1 the plain search, 2 | 3 coarse-to-fine: the search runs on the frames halved levels - 1 times, a +-3 refinement per finer level (sad_hier.hip)
         int sad_predictors = 0;          // OFPS_HIP_SAD_PREDICTORS / ofps_hip_set_sad_predictors: 0 a refined block's one predictor is its parent's winner, 1 the parent's, its four lattice neighbours' and zero (sad_hier.hip, N1p); no effect at levels 1
         int sad_median = 0;              // OFPS_HIP_SAD_MEDIAN / ofps_hip_set_sad_median: 0 off, N in [1, 255] only blocks whose integer winner lies less than N pixels from the median of their kept lattice neighbours' (sad_median.hip, N1v)
+        int sad_intra = 0;               // OFPS_HIP_SAD_INTRA / ofps_hip_set_sad_intra: 0 off, q in [1, 255] (sixteenths) only blocks whose integer winner's SAD lies below q/16 of the block's activity in the raw current frame (sad_intra.hip, N1i)
+        int sad_cut = 0;                 // OFPS_HIP_SAD_CUT / ofps_hip_set_sad_cut: 0 off, P in [1, 100] a pair with at least P percent of its gated blocks intra yields no record; no effect while sad_intra is 0 (sad_intra.hip, N1i)
         int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
@@ -234,7 +236,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 54;
+    static constexpr int kNumScratch = 56;
     Scratch scratch[kNumScratch];
 };
 
@@ -271,9 +273,10 @@ enum ScratchSlot {
     S_HIER_BEST,            // ... the winners of every level above 0
     S_HIER_ENT,             // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
     S_SAD_PREF,             // hip_sad's mean removal (sad_prefilter.hip): the filtered frames of one search's two frame sets.  Compute stream only, written anew by every search
-    S_MED_KEEP              // hip_sad's median test (sad_median.hip): the outgoing keep flags, u8 per block, one per ticket in flight in the fused path (the incoming ones stay in S_GATE_FLAGS)
+    S_MED_KEEP,             // hip_sad's median test (sad_median.hip): the outgoing keep flags, u8 per block, one per ticket in flight in the fused path (the incoming ones stay in S_GATE_FLAGS)
+    S_INTRA                 // hip_sad's intra test (sad_intra.hip): [activity, u32 per block][candidate and intra counters, 2 x u32 per item], one per ticket in flight in the fused path
 };
-static_assert(S_MED_KEEP < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_INTRA < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -416,15 +419,30 @@ int sad_median_check(ofps_hip_ctx* ctx, int block, int limit, const char* who); 
 int sad_median_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint8_t* d_keep_in, int W, int H, int block, int limit,
                             uint32_t* d_out_residual2, uint8_t* d_out_keep, hipStream_t st, int items = 1);
 
+// sad_intra.hip: hip_sad's intra test and scene-cut rule (include/ofps_hip.h N1i)
+constexpr int kSadIntraMax = 255, kSadCutMax = 100;
+int sad_intra_check(ofps_hip_ctx* ctx, int block, int ratio, int cut, const char* who);     // ratio in [1, 255], cut in [0, 100]
+// A(k) of every block of `items` frames `pitch` bytes apart, u32 per block, item-major, on stream st; one launch
+int block_activity_device(ofps_hip_ctx* ctx, const uint8_t* d_luma, size_t pitch, int items, int W, int H, int stride, int block, uint32_t* d_out,
+                          hipStream_t st);
+// keep byte per block = incoming flag (d_keep_in: optional, absent = all ones, may be d_out_keep) AND NOT intra, from the integer winners' SADs
+// and the activities; d_counts (optional): [candidates, intra candidates] per item, zeroed here unless the caller has (zero_counts).  Every
+// array holds items x nblk, item-major
+int sad_intra_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint32_t* d_activity, const uint8_t* d_keep_in, int W, int H, int block,
+                           int ratio, uint8_t* d_out_keep, uint32_t* d_counts, hipStream_t st, int items = 1, bool zero_counts = true);
+// cut > 0: the flags of every item whose counters say 100 * intra >= cut * candidates are cleared; one launch.  cut == 0: nothing
+int sad_cut_device(ofps_hip_ctx* ctx, const uint32_t* d_counts, size_t nblk, int cut, uint8_t* d_flags, hipStream_t st, int items = 1);
+
 // sad_gate.hip: the filtered search of `pairs` pairs -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device --
 // in the steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  sad_flow_filtered_device runs them all on ctx->stream; the
-// fused per-frame path (pipeline.hip) makes the contrast flags on its auxiliary stream.  Every per-block array holds pairs x nblk, item-major,
+// fused per-frame path (pipeline.hip) makes the contrast flags and the activities on its auxiliary stream, beside the search.  Every per-block array holds pairs x nblk, item-major,
 // and every step is one launch whatever `pairs`.  With gate == 0, limit == 0 and median == 0 search() is the plain search into d_out and no
-// other step reserves or enqueues anything.
+// other step reserves or enqueues anything; the same holds for intra == 0 (cut alone does nothing).
 struct SadFilter {
     SadFrames fr;                        // plan() and reserve() read the geometry alone: the bases may be filled in behind them (pipeline.hip)
     int pairs, block, range;
     int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
+    int intra, cut;                      // the intra test's ratio in sixteenths, 0 = off; the scene-cut rule's percentage, 0 = off and no effect while intra == 0
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
     size_t nblk = 0;                     // per pair
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
@@ -433,24 +451,27 @@ struct SadFilter {
     float4* d_bwd_ent = nullptr;         // S_CONS_BWD_ENT
     int* d_triples = nullptr;            // the triples that belong to d_raw: S_GATE_BEST, or d_fwd itself (integer winners kept, motion scale 1)
     uint8_t* d_med_keep = nullptr;       // S_MED_KEEP, this ticket's block: the median test's outgoing flags (median > 0)
-    bool on() const { return gate > 0 || limit > 0 || median > 0; }
-    bool winners() const { return limit > 0 || median > 0; }       // both read the forward search's INTEGER winners, whatever the motion scale
+    uint32_t *d_act = nullptr, *d_intra_counts = nullptr;       // S_INTRA, this ticket's block: the current frames' activities and the items' two counters (intra > 0)
+    bool on() const { return gate > 0 || limit > 0 || median > 0 || intra > 0; }
+    bool winners() const { return limit > 0 || median > 0 || intra > 0; }       // all three read the forward search's INTEGER winners, whatever the motion scale
     size_t total() const { return (size_t)pairs * nblk; }
     uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk, pairs) : nullptr; }
-    uint8_t* keep() const { return gate_keep(d_flags, nblk, pairs); }       // the incoming flags: contrast gate AND consistency check
+    uint8_t* keep() const { return gate_keep(d_flags, nblk, pairs); }       // the incoming flags: contrast gate AND NOT intra AND consistency check
     int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
     // the scratch slots; S_GATE_FLAGS / S_MED_KEEP hold `tickets` blocks, this plan's is number `tix`.  May reallocate: behind whatever drains the slots' readers
     int reserve(ofps_hip_ctx* ctx, int tix = 0, int tickets = 1);
     int search(ofps_hip_ctx* ctx, float4* d_out);         // on ctx->stream; d_out: the unfiltered search's records.  The backward search reads fr.swapped()
-    int contrast_flags(ofps_hip_ctx* ctx, hipStream_t st);        // gate > 0: counts and keep flags of the current frames, which they depend on alone
-    // on ctx->stream behind search and flags: [consistency flags, the gate's ANDed in in place ->] [median flags read from those, into
-    // d_med_keep ->] kept records [and triples] in raster order -> count.  d_out and d_out_best hold pairs slots of nblk, item k's kept ones
+    // what depends on the current frames alone, on stream st: gate > 0: contrast counts and keep flags; intra > 0: activities, and the counters zeroed
+    int contrast_flags(ofps_hip_ctx* ctx, hipStream_t st);
+    // on ctx->stream behind search and contrast_flags: [intra flags and counters, the gate's ANDed in in place ->] [consistency flags, those
+    // ANDed in in place ->] [median flags read from those, into d_med_keep ->] [the cut rule's veto on the final flags ->] kept records [and triples] in raster order -> count.  d_out and d_out_best hold pairs slots of nblk, item k's kept ones
     // lead slot k; d_count holds pairs counts
     int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
 };
 // the five steps on ctx->stream, the launch count independent of `pairs`; `who` leads every error text, tix / tickets: SadFilter::reserve
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
-                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1);
+                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1, int intra = 0,
+                             int cut = 0);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional): the record counts in device memory, one per item, n the capacity.  d_out may equal d_entries.

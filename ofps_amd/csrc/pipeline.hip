@@ -19,7 +19,7 @@ using ofps::PipeStream;
 using ofps::TailRecord;
 struct PipeOut {                 // a ticket's result block: page-locked, and in device scratch at the head of its kPipeOutBytes
     TailRecord r;
-    uint32_t kept[4];            // contrast gate, consistency check or median test on: the kept record count (sad_gate.hip); not read back, not looked at, with all off
+    uint32_t kept[4];            // contrast gate, consistency check, median test or intra test on: the kept record count (sad_gate.hip); not read back, not looked at, with all off
 };
 constexpr size_t kPipeOutPlain = offsetof(PipeOut, kept);       // what a ticket without the gate reads back
 constexpr size_t kPipeField = 4096;                             // the detector's field in the device copy, behind the block
@@ -98,7 +98,7 @@ int pipe_upload(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride
 struct Push {
     ofps_hip_ctx* ctx;
     const ofps_hip_frame_params* prm;
-    ofps::SadFilter f;                   // contrast gate, consistency check and median test as the context has them at this push; all 0: the plain search.
+    ofps::SadFilter f;                   // contrast gate, consistency check, median test, intra test and cut rule as the context has them at this push; all 0: the plain search.
                                          // Made with the geometry alone -- claim() refuses before anything is uploaded -- upload() fills in the pair's frames
     PipeStream::Ticket* t = nullptr;
     int tix = 0;
@@ -138,8 +138,9 @@ struct Push {
         return OFPS_HIP_OK;
     }
 
-    // The search of pair (prev, cur) -> the [kept] records in d_ent [and their count in device memory, f.kept()].  Gate on: the keep flags
-    // depend on the new frame only -- they are made on the auxiliary stream, forked on that frame's upload, beside the search (never in front
+    // The search of pair (prev, cur) -> the [kept] records in d_ent [and their count in device memory, f.kept()].  Gate or intra test on: the
+    // contrast flags and the activities depend on the new frame only -- they are made on the auxiliary stream, forked on that frame's upload,
+    // beside the search (never in front
     // of it on the compute stream).  Check on: both searches read prev_slot, so its event is recorded behind both.
     int search() {
         PipeStream& ps = ctx->pipe;
@@ -150,7 +151,7 @@ struct Push {
         d_ent += (size_t)tix * f.nblk; d_out += (size_t)tix * kPipeOutBytes;
         int rc = f.reserve(ctx, tix, kTickets);          // S_GATE_FLAGS per ticket: the detector may still read ticket k's count while ticket k + 1 compacts
         if (rc != OFPS_HIP_OK) return rc;
-        if (f.gate > 0) {
+        if (f.gate > 0 || f.intra > 0) {
             if (!ps.gate_done) OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&ps.gate_done, hipEventDisableTiming));
             // fork on the upload: its own event when it ran on the copy stream (the flags are then made beside the previous ticket's tail as
             // well), else the compute stream's position, which is right behind the upload
@@ -166,7 +167,7 @@ struct Push {
         // (one barrier packet between the search and the estimator instead of two)
         OFPS_HIP_TRY(ctx, hipEventRecord(ps.slot_read[prev_slot], s));
         ps.slot_read_valid[prev_slot] = true;
-        if (f.gate > 0) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ps.gate_done, 0));
+        if (f.gate > 0 || f.intra > 0) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, ps.gate_done, 0));
         return f.finish(ctx, d_ent, nullptr, f.kept());
     }
 
@@ -237,7 +238,7 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
     Push p{ctx, prm, {{nullptr, nullptr, 0, 0, W, H, (W + 63) & ~63}, 1, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
-                      ctx->opt.sad_median, /*want_triples=*/false}};
+                      ctx->opt.sad_median, ctx->opt.sad_intra, ctx->opt.sad_cut, /*want_triples=*/false}};
     rc = p.claim();                                     // refused before anything is uploaded
     if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
     if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)
@@ -329,9 +330,9 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     // the batch filter switch (include/ofps_hip.h N1b) with a criterion on: the filtered batched search and the tail's per-item device counts;
     // the ticket follows the settings the context has now.  Else everything below is what it is without the switch
     const auto& o = ctx->opt;
-    const bool filtered = o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0);
+    const bool filtered = o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0 || o.sad_intra > 0);
     if (filtered) {                                              // refused before anything is uploaded
-        SadFilter chk{{nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, /*want_triples=*/false};
+        SadFilter chk{{nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, o.sad_intra, o.sad_cut, /*want_triples=*/false};
         rc = chk.plan(ctx, "push_frames_async");
         if (rc != OFPS_HIP_OK) return rc;
     }
@@ -412,7 +413,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
         if (filtered)
             rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
-                                          "push_frames_async", tix, kTickets);
+                                          "push_frames_async", tix, kTickets, o.sad_intra, o.sad_cut);
         else rc = sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0, nullptr);
         if (rc != OFPS_HIP_OK) return rc;
         auto* d_res = reinterpret_cast<int(*)[4]>(d_out);                           // [n][4]

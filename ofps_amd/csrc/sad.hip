@@ -1329,15 +1329,15 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (!d_frames || !d_ent || !d_best) return OFPS_HIP_ENOMEM;
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames, dstride, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_frames + pitch, dstride, cur, stride, W, H, ctx->stream));
-    // contrast gate, consistency check and / or median test (sad_gate.hip: SadFilter): the kept records first, their count from the device with them
+    // contrast gate, consistency check, median test and / or intra test (sad_gate.hip: SadFilter): the kept records first, their count from the device with them
     uint32_t kept = UINT32_MAX;
     int rc;
-    if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0 || ctx->opt.sad_median > 0) {
+    if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0 || ctx->opt.sad_median > 0 || ctx->opt.sad_intra > 0) {
         auto* d_kept = static_cast<uint32_t*>(ofps::scratch(ctx, ofps::S_RESULT, sizeof(uint32_t)));
         if (!d_kept) return OFPS_HIP_ENOMEM;
         rc = ofps::sad_flow_filtered_device(ctx, {d_frames, d_frames + pitch, 0, 0, W, H, dstride}, 1, block, range, ctx->opt.sad_gate,
                                             ctx->opt.sad_consistency, ctx->opt.sad_median, reinterpret_cast<float4*>(d_ent),
-                                            out_best ? d_best : nullptr, d_kept, "sad_flow");
+                                            out_best ? d_best : nullptr, d_kept, "sad_flow", 0, 1, ctx->opt.sad_intra, ctx->opt.sad_cut);
         if (rc != OFPS_HIP_OK) return rc;
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
     } else {

@@ -14,9 +14,9 @@
 // array: one launch per step whatever the number of pairs, and one pair is item 0.
 // compact_items_kernel: a batch's compaction, segmented: one workgroup per item, records + triples + one count per item.
 //
-// Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate, the consistency check (sad_consistency.hip)
-// and / or the median test (sad_median.hip) in front of one compaction and one device-side count -- for the one-pair entry points, the fused
-// per-frame path and, over `pairs` pairs at once, ofps_hip_sad_flow_filtered_dev and the batched stream forms (pipeline.hip).
+// Host side: ofps::SadFilter (common.hpp), the one filtered search of hip_sad -- this gate, the consistency check (sad_consistency.hip),
+// the median test (sad_median.hip) and / or the intra test (sad_intra.hip) in front of one compaction and one device-side count -- for the
+// one-pair entry points, the fused per-frame path and, over `pairs` pairs at once, ofps_hip_sad_flow_filtered_dev and the batched stream forms (pipeline.hip).
 #include "common.hpp"
 #include "mask_tile.hpp"
 
@@ -170,6 +170,8 @@ int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     int rc = limit > 0 ? sad_consistency_check(ctx, block, limit, who) : OFPS_HIP_OK;
     if (rc == OFPS_HIP_OK && gate > 0) rc = sad_gate_check(ctx, block, gate, who);
     if (rc == OFPS_HIP_OK && median > 0) rc = sad_median_check(ctx, block, median, who);
+    if (rc == OFPS_HIP_OK && intra > 0) rc = sad_intra_check(ctx, block, intra, cut, who);
+    if (rc == OFPS_HIP_OK && intra == 0 && (cut < 0 || cut > kSadCutMax)) rc = set_error(ctx, OFPS_HIP_EINVAL, "%s: scene cut %d outside [0, %d]", who, cut, kSadCutMax);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, fr.W > 0 && fr.H > 0 && fr.stride >= fr.W, "%s: bad geometry W=%d H=%d stride=%d", who, fr.W, fr.H, fr.stride);
     OFPS_REQUIRE(ctx, pairs >= 1 && pairs <= 65535, "%s: %d pairs outside [1, 65535]", who, pairs);
@@ -200,6 +202,13 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
         if (!mk) return OFPS_HIP_ENOMEM;
         d_med_keep = mk + tix * mbytes;
     }
+    if (intra > 0) {
+        const size_t abytes = (total() * sizeof(uint32_t) + 15) & ~size_t(15), ibytes = abytes + (((size_t)pairs * 2 * sizeof(uint32_t) + 15) & ~size_t(15));
+        auto* ia = static_cast<char*>(scratch(ctx, S_INTRA, tickets * ibytes));
+        if (!ia) return OFPS_HIP_ENOMEM;
+        d_act = reinterpret_cast<uint32_t*>(ia + tix * ibytes);
+        d_intra_counts = reinterpret_cast<uint32_t*>(ia + tix * ibytes + abytes);
+    }
     // the records' triples: the forward search's integer winners themselves when they are kept and nothing refines them
     if (want_triples) d_triples = winners() && ctx->opt.sad_motion_scale != 4 ? d_fwd : static_cast<int*>(scratch(ctx, S_GATE_BEST, tri));
     return want_triples && !d_triples ? OFPS_HIP_ENOMEM : OFPS_HIP_OK;
@@ -216,7 +225,13 @@ int SadFilter::search(ofps_hip_ctx* ctx, float4* d_out) {
 }
 
 int SadFilter::contrast_flags(ofps_hip_ctx* ctx, hipStream_t st) {
-    if (gate <= 0 || !nblk) return OFPS_HIP_OK;
+    if (!nblk) return OFPS_HIP_OK;
+    if (intra > 0) {                                          // the intra test's share: the raw current frames' activities, the counters at zero
+        const int rc = block_activity_device(ctx, fr.cur_base, fr.cur_pitch, pairs, fr.W, fr.H, fr.stride, block, d_act, st);
+        if (rc != OFPS_HIP_OK) return rc;
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_intra_counts, 0, (size_t)pairs * 2 * sizeof(uint32_t), st));
+    }
+    if (gate <= 0) return OFPS_HIP_OK;
     const int rc = block_contrast_device(ctx, fr.cur_base, fr.cur_pitch, pairs, fr.W, fr.H, fr.stride, block, gate_counts(d_flags), st);
     if (rc != OFPS_HIP_OK) return rc;
     // a flag depends on its own count alone: the batch's pairs * nblk counts are one array to this kernel
@@ -227,18 +242,28 @@ int SadFilter::contrast_flags(ofps_hip_ctx* ctx, hipStream_t st) {
 
 int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count) {
     if (!on()) return OFPS_HIP_OK;
-    int rc = limit > 0 ? sad_consistency_flags_device(ctx, d_fwd, d_bwd, fr.W, fr.H, block, limit, gate > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream, pairs)
-                       : OFPS_HIP_OK;
+    int rc = OFPS_HIP_OK;
+    // the intra test: the forward winners' SADs against the activities contrast_flags() made of the RAW current frames (as the gate reads
+    // them), the verdict ANDed onto the gate's flags
+    if (intra > 0 && nblk) {
+        rc = sad_intra_flags_device(ctx, d_fwd, d_act, gate > 0 ? keep() : nullptr, fr.W, fr.H, block, intra, keep(), d_intra_counts, ctx->stream, pairs,
+                                    /*zero_counts=*/false);
+        if (rc != OFPS_HIP_OK) return rc;
+    }
+    if (limit > 0)
+        rc = sad_consistency_flags_device(ctx, d_fwd, d_bwd, fr.W, fr.H, block, limit, gate > 0 || intra > 0 ? keep() : nullptr, nullptr, keep(), ctx->stream, pairs);
     if (rc != OFPS_HIP_OK) return rc;
     // one pass: the median test reads the other criteria's flags (none on: all ones) and writes its own array
     if (median > 0)
-        rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 ? keep() : nullptr, fr.W, fr.H, block, median, nullptr, d_med_keep, ctx->stream, pairs);
+        rc = sad_median_flags_device(ctx, d_fwd, gate > 0 || limit > 0 || intra > 0 ? keep() : nullptr, fr.W, fr.H, block, median, nullptr, d_med_keep, ctx->stream, pairs);
     if (rc != OFPS_HIP_OK) return rc;
     if (nblk == 0) {
         OFPS_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, pairs * sizeof(uint32_t), ctx->stream));
         return OFPS_HIP_OK;
     }
-    const uint8_t* flags = median > 0 ? d_med_keep : keep();
+    uint8_t* flags = median > 0 ? d_med_keep : keep();
+    // a cut item loses every flag: gate and intra verdicts alone decide that, whatever check and median test said since
+    if (intra > 0 && (rc = sad_cut_device(ctx, d_intra_counts, nblk, cut, flags, ctx->stream, pairs)) != OFPS_HIP_OK) return rc;
     // The compaction is the one step that keeps a path per shape.  compact_items_kernel runs ONE workgroup per item whatever nblk: right for a
     // batch of small lattices, but one pair through it would scan a 4K frame's 129,600 blocks on one compute unit, and in one launch where the
     // paths below take up to three.  That would change speed and launch count; the one-pair path stays on the grid-wide compactions of mask.hip
@@ -258,12 +283,12 @@ int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_
     return OFPS_HIP_OK;
 }
 
-// `pairs` pairs of `f`, everything on ctx->stream: search[es], [contrast flags of the current frames,] [the check's flags,] [the median test's
+// `pairs` pairs of `f`, everything on ctx->stream: search[es], [contrast flags and / or activities of the current frames,] [the intra test's flags,] [the check's flags,] [the median test's
 // flags,] one compaction, one count per pair.  Item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k]
 // is their number
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
-                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets) {
-    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, d_out_best != nullptr};
+                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets, int intra, int cut) {
+    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, intra, cut, d_out_best != nullptr};
     int rc = flt.plan(ctx, who);
     if (rc == OFPS_HIP_OK) rc = flt.reserve(ctx, tix, tickets);
     if (rc == OFPS_HIP_OK) rc = flt.search(ctx, d_out);

@@ -78,6 +78,12 @@ class HipSadDecoder(Properties):
               # build-defined: 0 = off; N = only blocks whose integer vector lies less than N pixels from the median of their kept lattice
               # neighbours' (include/ofps_hip.h N1v)
               ("Median test", "usize", "median_test", 0, 255),
+              # build-defined: 0 = off; q (sixteenths) = only blocks whose integer vector's SAD lies below q/16 of the block's own activity
+              # (sum of |pixel - block mean|) in the current frame: the encoder's intra decision (include/ofps_hip.h N1i)
+              ("Intra test", "usize", "intra_test", 0, 255),
+              # build-defined: 0 = off; P = a frame with at least P percent of its (gated) blocks intra yields no vector at all, as the
+              # reference's decoder does on an intra frame.  No effect while "Intra test" is 0
+              ("Scene cut", "usize", "scene_cut", 0, 100),
               # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
               # include/ofps_hip.h N1c).  Costs a second search per frame
               # build-defined: 0 = the search compares the frames as they are; r = both frames minus their box mean of radius r, for streams
@@ -100,6 +106,8 @@ class HipSadDecoder(Properties):
         self.contrast_gate = 0
         self.consistency = 0
         self.median_test = 0
+        self.intra_test = 0
+        self.scene_cut = 0
         self.levels = 1
         self.neighbour_predictors = False
         self.prefilter = 0
@@ -143,6 +151,8 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_gate(self.contrast_gate)
         self.ctx.set_sad_consistency(self.consistency)
         self.ctx.set_sad_median(self.median_test)
+        self.ctx.set_sad_intra(self.intra_test)
+        self.ctx.set_sad_cut(self.scene_cut)
         self.ctx.set_sad_levels(self.levels)
         self.ctx.set_sad_predictors(1 if self.neighbour_predictors else 0)
         self.ctx.set_sad_prefilter(self.prefilter)

@@ -240,6 +240,73 @@ class HipContext:
     def get_sad_batch_filter(self) -> int:
         return int(self._lib.ofps_hip_get_sad_batch_filter(self._h))
 
+    def set_sad_intra(self, ratio: int):
+        """hip_sad's intra test (include/ofps_hip.h N1i): 0 = off (default); q in [1, 255] (sixteenths) = a block whose integer winner's SAD
+        reaches q/16 of the block's activity in the raw current frame (16 * SAD >= q * A) yields no record (sad_flow, push_frame[_async])."""
+        self._check(self._lib.ofps_hip_set_sad_intra(self._h, ratio))
+
+    def get_sad_intra(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_intra(self._h))
+
+    def set_sad_cut(self, percent: int):
+        """hip_sad's scene-cut rule (N1i): 0 = off (default); P in [1, 100] = a pair with at least P percent of its gated blocks intra yields
+        no record at all.  No effect while the intra ratio is 0."""
+        self._check(self._lib.ofps_hip_set_sad_cut(self._h, percent))
+
+    def get_sad_cut(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_cut(self._h))
+
+    def block_activity(self, luma: np.ndarray, block: int, stride: int | None = None) -> np.ndarray:
+        """Sum of |pixel - rounded block mean| per full lattice block of `luma` -> uint32 [H // block, W // block].  stride: as for
+        block_contrast."""
+        if stride is None:
+            g = np.ascontiguousarray(luma, np.uint8)
+            stride = g.shape[1]
+        else:
+            g = luma
+            assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
+        H, W = g.shape
+        out = np.zeros((H // block, W // block), np.uint32)
+        buf = out if out.size else np.zeros(1, np.uint32)
+        self._check(self._lib.ofps_hip_block_activity(self._h, C.cast(C.c_void_p(g.ctypes.data), C.POINTER(C.c_uint8)), W, H, stride, block,
+                                                      buf.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def block_activity_dev(self, d_luma: int, W: int, H: int, stride: int, block: int, d_out_activity: int):
+        self._check(self._lib.ofps_hip_block_activity_dev(self._h, C.c_void_p(d_luma), W, H, stride, block, C.c_void_p(d_out_activity)))
+
+    def sad_intra(self, best: np.ndarray, activity: np.ndarray, keep_in: np.ndarray | None, W: int, H: int, block: int, ratio: int, cut: int = 0,
+                  want_counts=True):
+        """Verdict and cut rule alone on a [nblk, 3] array of (dx, dy, sad) integer winners, the blocks' activities and the gate's keep
+        bytes (None = all ones) -> (keep uint8 [nblk], [n_cand, n_intra] uint32 or None)."""
+        b = np.ascontiguousarray(best, np.int32)
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        a = np.ascontiguousarray(activity, np.uint32).reshape(-1)
+        assert b.shape == (nb, 3) and a.shape == (nb,)
+        k = None if keep_in is None else np.ascontiguousarray(keep_in, np.uint8)
+        assert k is None or k.shape == (nb,)
+        keep = np.zeros(max(nb, 1), np.uint8)
+        counts = np.zeros(2, np.uint32) if want_counts else None
+        u8, u32 = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        self._check(self._lib.ofps_hip_sad_intra(self._h, b.ctypes.data_as(C.POINTER(C.c_int32)), a.ctypes.data_as(u32),
+                                                 None if k is None else k.ctypes.data_as(u8), W, H, block, ratio, cut, keep.ctypes.data_as(u8),
+                                                 counts.ctypes.data_as(u32) if want_counts else None))
+        return keep[:nb], counts
+
+    def sad_intra_dev(self, d_best: int, d_activity: int, d_keep_in: int | None, W: int, H: int, block: int, ratio: int, cut: int,
+                      d_out_keep: int, d_out_counts: int | None):
+        self._check(self._lib.ofps_hip_sad_intra_dev(self._h, C.c_void_p(d_best), C.c_void_p(d_activity), C.c_void_p(d_keep_in or 0), W, H, block,
+                                                     ratio, cut, C.c_void_p(d_out_keep), C.c_void_p(d_out_counts or 0)))
+
+    def sad_flow_intra_dev(self, d_frames: int, n_frames: int, W: int, H: int, stride: int, frame_pitch: int, ref_mode: int, block: int,
+                           search_range: int, min_pixels: int, limit: int, median: int, intra: int, cut: int, d_out_entries: int,
+                           d_out_best: int | None, d_out_counts: int):
+        """sad_flow_filtered_dev with the intra test (intra in [1, 255]) and the cut rule (cut in [0, 100]) as two more explicit values
+        (include/ofps_hip.h N1i); min_pixels, limit and median may all be 0.  Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_intra_dev(self._h, C.c_void_p(d_frames), n_frames, W, H, stride, frame_pitch, ref_mode, block,
+                                                          search_range, min_pixels, limit, median, intra, cut, C.c_void_p(d_out_entries),
+                                                          C.c_void_p(d_out_best or 0), C.c_void_p(d_out_counts)))
+
     def set_sad_levels(self, levels: int):
         """hip_sad's search levels (include/ofps_hip.h N1h): 1 = the plain search (default); 2 | 3 = the search runs on the frames halved
         levels - 1 times and every finer level repairs the doubled vectors in a +-3 window: reach 2 * range + 3, 4 * range + 9."""

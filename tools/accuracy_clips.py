@@ -20,6 +20,10 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               with --sad-prefilter R [R ...] also hip_sad_m<R>: hip_sad with its "Mean removal" property at R (include/ofps_hip.h N1m)
               with --sad-median N [N ...] also hip_sad_v<N>: hip_sad with its "Median test" property at N (include/ofps_hip.h N1v); with
               --sad-consistency C also hip_sad_cv<N>: on top of "Consistency check" = C
+              with --sad-intra Q [Q ...] also hip_sad_i<Q>: hip_sad with its "Intra test" property at Q (include/ofps_hip.h N1i); --sad-cut P sets
+              "Scene cut" = P in those columns; with --sad-prefilter R also hip_sad_fi<Q>: on top of "Mean removal" = R (the first R)
+  cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
+              cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
               toggles by 20 grey levels every 4 frames (a quarter of the pairs straddle a step); flicker = +12 on odd frames, -12 on even
               ones (every pair differs by 24); ramp = odd frames gain 30 x/(W-1) - 10 y/(H-1) - 8 (a gradient that comes and goes); all
@@ -157,8 +161,12 @@ def relight_clip(frames, lighting):
     return np.clip(np.floor(f + 0.5), 0, 255).astype(np.uint8)
 
 
+CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
+
+
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
-        fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=()):
+        fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
+        cut_clip=False):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -202,6 +210,12 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         if sad_consistency:
             props_cv = {"Consistency check": sad_consistency, "Median test": limit}
             combos[2:2] = [(f"hip_sad_cv{limit}", HipSadDecoder, False, props_cv), (f"hip_sad_cv{limit}", HipSadDecoder, True, props_cv)]
+    for ratio in sad_intra:         # hip_sad with its "Intra test" property at Q (include/ofps_hip.h N1i), "Scene cut" at --sad-cut
+        props_i = {"Intra test": ratio, "Scene cut": sad_cut}
+        combos[2:2] = [(f"hip_sad_i{ratio}", HipSadDecoder, False, props_i), (f"hip_sad_i{ratio}", HipSadDecoder, True, props_i)]
+        if sad_prefilter:           # ... and on top of "Mean removal" at the first --sad-prefilter radius: filtered SAD against raw activity
+            props_fi = dict(props_i, **{"Mean removal": sad_prefilter[0]})
+            combos[2:2] = [(f"hip_sad_fi{ratio}", HipSadDecoder, False, props_fi), (f"hip_sad_fi{ratio}", HipSadDecoder, True, props_fi)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
@@ -215,11 +229,18 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
             clips.append((name + tag, geom, clip_seed, False, light))
             if sad_gate:
                 clips.append((name + "_flat_third" + tag, geom, clip_seed, True, light))
+    if cut_clip and (not only or CUT_CLIP in only):                 # behind every other clip: their seeds stay what they are
+        for light in lighting:
+            clips.append((CUT_CLIP + ("" if light == "none" else "@" + light), clip_table(quick)["pan_0.2"], CUT_SEEDS[0], False, light))
     rendered = (None, None)
     for name, (W, H, fov, eul, dis), clip_seed, flat, light in clips:
         t0 = time.perf_counter()
         if rendered[0] != (name.split("@")[0].replace("_flat_third", ""), clip_seed):
             rendered = ((name.split("@")[0].replace("_flat_third", ""), clip_seed), synth.rotation_clip(eul, W, H, fov, seed=clip_seed, distractor=dis))
+            if rendered[0][0] == CUT_CLIP:                          # the second half of the frames from another canvas
+                other = synth.rotation_clip(eul, W, H, fov, seed=CUT_SEEDS[1], distractor=dis)[0]
+                half = len(other) // 2
+                rendered = (rendered[0], (np.concatenate([rendered[1][0][:half], other[half:]]), rendered[1][1]))
         frames, truth = rendered[1]
         if flat:
             frames = flat_third(frames)
@@ -234,6 +255,8 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
             assert len(q) == len(truth), (len(q), len(truth))
             key = f"{dname}+{'ransac' if ransac else 'lsq'}"
             row[key] = dict(stats(q, truth), ms_per_frame=round(dt * 1e3, 3))
+            if name.split("@")[0] == CUT_CLIP:                      # pair k relates frames k and k + 1: the cut lies in pair len(frames) // 2 - 1
+                row[key]["cut_pair_err_deg"] = float(synth.quat_angle_deg(q[len(frames) // 2 - 1], truth[len(frames) // 2 - 1]))
             per_pair[key] = q
         if with_oracle:
             import oracle
@@ -265,7 +288,8 @@ def table(res):
         cols[2:2] = ["hip_sad_g+lsq", "hip_sad_g+ransac"]
     radii = sorted({int(k.split("+")[0].rsplit("m", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_m", "hip_sad_hm"))})
     limits = sorted({int(k.split("+")[0].rsplit("v", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_v", "hip_sad_cv"))})
-    for tag in tuple(f"hip_sad_{t}{limit}" for limit in reversed(limits) for t in ("cv", "v")) + (
+    ratios = sorted({int(k.split("+")[0].rsplit("i", 1)[1]) for r in res.values() for k in r if k.startswith("hip_sad_i")})
+    for tag in tuple(f"hip_sad_{t}{ratio}" for ratio in reversed(ratios) for t in ("fi", "i")) + tuple(f"hip_sad_{t}{limit}" for limit in reversed(limits) for t in ("cv", "v")) + (
             "hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp") + tuple(
             f"hip_sad_{t}{radius}" for radius in reversed(radii) for t in ("hm", "m")):
         if any(tag + "+lsq" in r for r in res.values()):
@@ -294,6 +318,13 @@ def table(res):
     for name, r in res.items():
         lines.append(f"{name},{r['frames']}," + ",".join(f"{r[c]['drift_deg']:.4f}" if c in r else "" for c in cols))
     lines.append("")
+    if any(CUT_CLIP in name for name in res):
+        lines.append("error of the pair across the scene cut, degrees (the planted rotation of that pair is the clip's rate)")
+        lines.append("clip," + ",".join(cols))
+        for name, r in res.items():
+            if CUT_CLIP in name:
+                lines.append(f"{name}," + ",".join(f"{r[c]['cut_pair_err_deg']:.5f}" if c in r and "cut_pair_err_deg" in r[c] else "" for c in cols))
+        lines.append("")
     lines.append("HIP chain vs CPU oracle chain on the same frames: largest |dq| component (sad+lsq: every pair; lk+lsq: the first pairs); tracking-loop ms per frame (host loop incl. PCIe)")
     lines.append("clip,sad+lsq_max_abs_dq,lk+lsq_max_abs_dq,lk_pairs_checked,ms_per_frame_hip_sad+lsq,ms_per_frame_hip_lk+lsq,ms_per_frame_hip_sad+ransac")
     for name, r in res.items():
@@ -328,13 +359,17 @@ def main():
                     help="add the hip_sad_m<R> columns (hip_sad with \"Mean removal\" = R; with --sad-levels N also hip_sad_hm<R>: on top of \"Search levels\")")
     ap.add_argument("--sad-median", nargs="*", type=int, default=[], metavar="N",
                     help="add the hip_sad_v<N> columns (hip_sad with \"Median test\" = N; with --sad-consistency C also hip_sad_cv<N>: on top of \"Consistency check\")")
+    ap.add_argument("--sad-intra", nargs="*", type=int, default=[], metavar="Q",
+                    help="add the hip_sad_i<Q> columns (hip_sad with \"Intra test\" = Q sixteenths; --sad-cut P sets \"Scene cut\" = P in them)")
+    ap.add_argument("--sad-cut", type=int, default=0, metavar="P", help="\"Scene cut\" of the hip_sad_i<Q> columns, percent (0 = off)")
+    ap.add_argument("--cut-clip", action="store_true", help="add pan_0.2_cut: pan_0.2 with the second half of its frames from another canvas seed")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
     ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
               sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
-              sad_median=tuple(args.sad_median))
+              sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip)
     txt = table(res)
     print(txt)
     if args.out:
