@@ -636,6 +636,55 @@ int ofps_hip_detect_dev(ofps_hip_ctx* ctx, const void* d_entries, size_t n_per_i
                         float min_size, size_t subdivide, float target_motion,
                         void* d_out_result, void* d_out_field);
 
+/* ---- A5i: every moving island, not the largest alone (csrc/detect.hip; build-defined, off by default) ----
+ * A5 answers "is there an island of at least min_size, and which cells does the largest cover" -- the reference's detect_motion, which
+ * stays as it is.  The labelling behind it knows every 8-connected component; this extension hands them out.  Build-defined: the
+ * reference has no counterpart, the definition below is this library's.
+ * Inputs: those of ofps_hip_detect plus max_islands = K in [1, 6400] (6400: the most components a 160 x 160 grid holds).
+ *   dim = ofps_hip_block_dim(min_size, subdivide), cells = dim * dim; f = the densified field, the detector's own densify call;
+ *   cell i = y * dim + x is lit iff sqrtf(f.x * f.x + f.y * f.y) >= target_motion (the detector's expression, no contraction);
+ *   a component is an 8-connected set of lit cells; its seed is its smallest cell index, its area its cell count; it qualifies iff
+ *   (float)area / (float)cells >= min_size (the detector's test);
+ *   the islands are the qualifying components ordered by area descending, then seed ascending -- a total order.  Island 0 is the
+ *   detector's winner (strict >, first in raster order).  Listed: ranks 0 .. min(n_islands, K) - 1.
+ * Outputs:
+ *   counts, int32[4]: n_islands (all qualifying components, also beyond K), n_components (all, any size), dim, n_listed;
+ *   table, int32[8] per listed island in rank order: seed, area, x0, y0, x1, y1, sum_x, sum_y -- the inclusive bounding box in cells and
+ *     the integer sums of the cells' x and y; the centroid in frame coordinates is ((sum_x / area) + 0.5) / dim, the caller's to compute.
+ *     Rows at and behind n_listed are unspecified;
+ *   labels (optional), uint16 per cell: the rank of the cell's island if it is listed, else 0xFFFF;
+ *   field (optional), 2 f32 per cell: f[i] where cell i belongs to a listed island and is not that island's seed, else (0, 0) -- the
+ *     reference never copies a seed cell (block-motion-detector/src/lib.rs:79-102) and every island keeps that rule, so with K = 1 the
+ *     field equals ofps_hip_detect's out_field bit for bit, with or without motion.
+ * Everything but the field is integer and order-independent (integer atomics and owned writes), no float is summed: bit-exact by
+ * construction.  Always: has_motion == (n_islands >= 1) and area == table[0].area.
+ * ofps_hip_detect_islands_dev: item j reads n_per_item records at j * n_per_item, as ofps_hip_detect_dev does; counts 4 int32, table
+ * 8 * max_islands int32, labels dim * dim uint16 and field 2 * dim * dim f32 per item; enqueues and returns.
+ * K outside [1, 6400] and dim outside [1, 160]: OFPS_HIP_EINVAL.  out_labels is uint16_t[dim * dim] (typed void*).
+ *
+ * The fused per-frame entry points -- ofps_hip_push_frame[_async], ofps_hip_push_frames_async, ofps_hip_lk_push_frame_fused[_async] --
+ * follow the context's max_islands (ofps_hip_set_detect_islands; the option OFPS_HIP_DETECT_ISLANDS sets the same field; 0 = off, the
+ * default: every entry point enqueues exactly what a build without this extension enqueues).  A ticket follows the value the context
+ * had when it was pushed.  With K > 0 and run_detector set, the tail computes counts, table and labels behind the detector, on its
+ * stream, from the records the detector reads (detect-compensation mode 1: the compensated records; device-side counts: the first
+ * d_n[j] records): one launch and one copy into a page-locked block of the ticket, no host synchronisation between push and wait.  The
+ * wait copies them into memory the context owns -- a later push cannot disturb them -- and ofps_hip_frame_islands returns those of
+ * `item` of the most recently collected fused ticket: item 0 for the single-frame forms, 0 .. n - 1 after ofps_hip_frames_wait.  A frame
+ * that yielded no vectors (a stream's first) has n_islands = n_components = 0.  OFPS_HIP_EINVAL: the ticket was pushed with K = 0 or
+ * without the detector; item out of range; capacity (in records) < n_listed.  ofps_hip_frame_result and the fused out_field do not
+ * change: out_field stays the largest island's.
+ * Out of scope: the worker contexts of ofps_hip_multi_* ignore max_islands. */
+int ofps_hip_detect_islands(ofps_hip_ctx* ctx, const float* entries, size_t n, float min_size, size_t subdivide, float target_motion,
+                            int max_islands, int32_t out_counts[4], int32_t* out_table /* 8*max_islands */,
+                            void* out_labels /* uint16 x dim*dim, or NULL */, float* out_field /* 2*dim*dim or NULL */);
+int ofps_hip_detect_islands_dev(ofps_hip_ctx* ctx, const void* d_entries, size_t n_per_item, int batch, float min_size, size_t subdivide,
+                                float target_motion, int max_islands, void* d_out_counts /* batch*4 */,
+                                void* d_out_table /* batch*max_islands*8 */, void* d_out_labels /* or NULL */, void* d_out_field /* or NULL */);
+int ofps_hip_set_detect_islands(ofps_hip_ctx* ctx, int max_islands);   /* 0 = off (default); option OFPS_HIP_DETECT_ISLANDS */
+int ofps_hip_get_detect_islands(ofps_hip_ctx* ctx);
+int ofps_hip_frame_islands(ofps_hip_ctx* ctx, int item, int32_t out_counts[4], int32_t* out_table, int capacity /* records */,
+                           void* out_labels /* uint16 x dim*dim, or NULL */);
+
 /* ---- A6-A12: Almeida estimator ("hip_almeida" Estimator) ----
  * out_quat = (w,i,j,k) of the returned UnitQuaternion; out_tr = translation (always 0,
  * almeida-estimator/src/lib.rs:120).  seed drives the counter-based RANSAC sampler (the reference draws from

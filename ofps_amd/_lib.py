@@ -124,6 +124,11 @@ PROTOTYPES = {
     "ofps_hip_detect": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_float, C.c_size_t, C.c_float,
                                   C.POINTER(C.c_int), _szp, C.POINTER(C.c_int), _f32p]),
     "ofps_hip_detect_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_size_t, C.c_float, _vp, _vp]),
+    "ofps_hip_detect_islands": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_float, C.c_size_t, C.c_float, C.c_int, _i32p, _i32p, _vp, _f32p]),
+    "ofps_hip_detect_islands_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_size_t, C.c_float, C.c_int, _vp, _vp, _vp, _vp]),
+    "ofps_hip_set_detect_islands": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_detect_islands": (C.c_int, [_ctx]),
+    "ofps_hip_frame_islands": (C.c_int, [_ctx, C.c_int, _i32p, _i32p, C.c_int, _vp]),
     "ofps_hip_almeida": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_size_t,
                                    C.c_float, C.c_size_t, C.c_uint64, _f32p, _f32p]),
     "ofps_hip_almeida_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.c_size_t,

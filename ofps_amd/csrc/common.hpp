@@ -66,6 +66,18 @@ inline void destroy(hipEvent_t e) { if (e) (void)hipEventDestroy(e); }
 inline void destroy(hipStream_t s) { if (s) (void)hipStreamDestroy(s); }
 inline void free_host(void* p) { if (p) (void)hipHostFree(p); }
 
+// A5i (detect.hip): what a fused ticket pushed with max_islands = K > 0 and the detector on carries beside its result block.  One block
+// per item: [counts, int32 x 4][table, int32 x 8 x K][labels, u16 x dim x dim, padded to 16 bytes], made in device scratch by the islands
+// kernel and copied to `pinned` behind it, on the stream the detector ran on.  Items in front of `first` yielded no vectors (a stream's
+// first frame): nothing was enqueued for them, their islands are none.  K == 0: the ticket has no islands
+constexpr int kMaxIslands = 6400;        // the most 8-connected components a 160 x 160 grid holds
+inline size_t islands_block_bytes(int K, int dim) { return 16 + (size_t)K * 32 + (((size_t)dim * dim * sizeof(uint16_t) + 15) & ~size_t(15)); }
+struct IslandsTicket {
+    void* pinned = nullptr; size_t cap = 0;
+    int K = 0, items = 0, first = 0, dim = 0;
+    void release() { free_host(pinned); }
+};
+
 // Farneback's state across calls (farneback.hip).  hip_flow in the stream forms: the pyramid + polynomial expansion of a pair's second
 // frame is the next pair's first, and the NEW frame's is made on the upload's stream beside the previous pair's flow.  Frames of the
 // stream carry ids (never reused); `cache.id[i]` is the frame whose expansion planes are in R slot i of the S_FB_WORK allocation of
@@ -107,11 +119,12 @@ struct PipeStream {
         int have_vectors = 0, run_detector = 0, run_estimator = 0;
         int gated = 0;                   // pushed with the contrast gate or the consistency check on: n_vectors is the kept count in the page-locked block
         size_t n_vectors = 0;
+        IslandsTicket isl;               // A5i
     };
     hipEvent_t gate_done = nullptr;      // contrast gate and intra test (sad_gate.hip): the keep flags and activities of the newest frame, made on aux_stream beside the search (created with the first gated push)
     TicketRing<Ticket, kTickets> ring;
     void release() {
-        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); }
+        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); t.isl.release(); }
         for (int k = 0; k < kSlots; ++k) { destroy(uploaded[k]); destroy(slot_read[k]); }
         destroy(copy_stream); destroy(aux_stream); destroy(fork); destroy(join); destroy(gate_done);
     }
@@ -137,9 +150,10 @@ struct BatchStream {
         int n = 0, first_has_prev = 0, run_detector = 0, run_estimator = 0;
         int filtered = 0;                // pushed with the batch filter switch and a criterion on: n kept counts follow the quaternions in the page-locked block
         size_t n_vectors = 0;
+        IslandsTicket isl;               // A5i
     };
     TicketRing<Ticket, kTickets> ring;
-    void release() { for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); destroy(t.prev_copied); } }
+    void release() { for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); destroy(t.prev_copied); t.isl.release(); } }
 };
 
 // dense decoders, hip_lk and hip_flow (dense_decoder.hip: ofps_hip_lk_push_frame[_async] / ofps_hip_lk_frame_wait): frame k lives in
@@ -163,12 +177,13 @@ struct DenseStream {
         // fused form (ofps_hip_lk_push_frame_fused[_async]): the tail's results sit behind the records, at tail_off of the block
         int fused = 0, run_detector = 0, run_estimator = 0, dim = 0;
         size_t tail_off = 0;
+        IslandsTicket isl;               // A5i
     };
     TicketRing<Ticket, kTickets> ring;
     void* decode_pinned = nullptr; size_t decode_pinned_cap = 0;     // ofps_hip_lk_decode's block: a pair's records + their count (one wait)
     void release() {
         free_host(decode_pinned);
-        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); }
+        for (auto& t : ring.entry) { free_host(t.pinned); destroy(t.done); destroy(t.uploaded); t.isl.release(); }
         destroy(copy_stream);
     }
     hipError_t sync_side_streams() { return copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess; }
@@ -212,6 +227,7 @@ struct ofps_hip_ctx {
         int sad_cut = 0;                 // OFPS_HIP_SAD_CUT / ofps_hip_set_sad_cut: 0 off, P in [1, 100] a pair with at least P percent of its gated blocks intra yields no record; no effect while sad_intra is 0 (sad_intra.hip, N1i)
         int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
+        int detect_islands = 0;          // OFPS_HIP_DETECT_ISLANDS / ofps_hip_set_detect_islands: 0 the fused entry points' detector answers for the largest island alone, K in [1, 6400] a ticket that runs the detector lists up to K islands as well (detect.hip, A5i)
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -225,6 +241,9 @@ struct ofps_hip_ctx {
     ofps::BatchStream batch;
     ofps::DenseStream dense;
     ofps::FarnebackState fb;
+    // A5i: the islands of the most recently collected fused ticket, in host memory the context owns (detect.hip: islands_collect): `items`
+    // blocks of islands_block_bytes(K, dim).  K == 0: that ticket had none
+    struct IslandsLast { char* data = nullptr; size_t cap = 0; int K = 0, items = 0, dim = 0; } isl_last;
     uint32_t lk_epoch = 0;               // lk_levels_kernel: tag of the last launch in the tile flags (S_LK_FLAGS)
     uint64_t lk_flags_gen = 0;           // generation of the flag buffer the tags refer to
 
@@ -236,7 +255,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 56;
+    static constexpr int kNumScratch = 58;
     Scratch scratch[kNumScratch];
 };
 
@@ -274,9 +293,11 @@ enum ScratchSlot {
     S_HIER_ENT,             // ... and the top search's records, which nobody reads.  All three: compute stream only, written anew by every search
     S_SAD_PREF,             // hip_sad's mean removal (sad_prefilter.hip): the filtered frames of one search's two frame sets.  Compute stream only, written anew by every search
     S_MED_KEEP,             // hip_sad's median test (sad_median.hip): the outgoing keep flags, u8 per block, one per ticket in flight in the fused path (the incoming ones stay in S_GATE_FLAGS)
-    S_INTRA                 // hip_sad's intra test (sad_intra.hip): [activity, u32 per block][candidate and intra counters, 2 x u32 per item], one per ticket in flight in the fused path
+    S_INTRA,                // hip_sad's intra test (sad_intra.hip): [activity, u32 per block][candidate and intra counters, 2 x u32 per item], one per ticket in flight in the fused path
+    S_ISL_WORK,             // the islands kernel (detect.hip, A5i): per item [qualifying roots' keys, u64][rank of every root, u16 per cell]
+    S_ISL_OUT               // ... and the blocks of a fused ticket or a host-pointer call ([counts][table][labels] per item), copied out behind the kernel on its stream
 };
-static_assert(S_INTRA < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_ISL_OUT < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -486,9 +507,17 @@ struct TailSide { hipStream_t stream; hipEvent_t fork_on; bool recorded; hipEven
 // d_n (optional): the record counts live in device memory, d_n[j] item j's, n is the capacity and the stride of every item, and the
 // estimator takes its device-count form (lsq_min_n: almeida_device_n).  seed0: item 0's seed, item j gets seed0 + j.  may_compensate: the context's detect-compensation mode
 // counts here.  d_result [batch][4], d_quat [batch], d_field: device memory or a ticket's device-addressable block.  -> *out_dim (optional)
+// isl (optional; the ticket's, with K = the context's max_islands at this push, 0 = off): behind the detector, on its stream, the islands of
+// the field it read -> the ticket's page-locked blocks, items isl->first .. isl->first + batch - 1 (detect.hip).  Nothing is enqueued with K == 0
 int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batch, const uint32_t* d_n, uint32_t lsq_min_n,
                       const ofps_hip_frame_params* prm, uint64_t seed0, bool may_compensate, int* d_result, float4* d_quat, float2* d_field,
-                      const TailSide* side, int* out_dim);
+                      const TailSide* side, int* out_dim, IslandsTicket* isl = nullptr);
+// detect.hip, A5i.  A push arms its ticket: K = the context's max_islands when the detector runs and its grid is valid, else 0; `items` frames
+void islands_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, const ofps_hip_frame_params* prm, int items);
+// the islands of the `batch` fields detect_device has just left in S_FIELD, on ctx->stream -> isl->pinned, items isl->first ..
+int islands_ticket_device(ofps_hip_ctx* ctx, int batch, int dim, float min_size, float target_motion, IslandsTicket* isl);
+// a fused wait: the collected ticket's blocks -> the context's own host memory (what ofps_hip_frame_islands answers from)
+int islands_collect(ofps_hip_ctx* ctx, const IslandsTicket& isl);
 
 // ---- transfers (transfer.hip)
 bool device_address_of(const void* host_ptr, void** dev_ptr);        // the device address of page-locked host memory, or false for pageable memory

@@ -91,6 +91,9 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_DETECT_COMPENSATE")) {
         if (!unset && iv != 0 && iv != 1) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d is not 0|1", name, iv);
         o.detect_compensate = unset ? dflt.detect_compensate : iv;
+    } else if (!strcmp(name, "OFPS_HIP_DETECT_ISLANDS")) {
+        if (!unset && (iv < 0 || iv > kMaxIslands)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kMaxIslands);
+        o.detect_islands = unset ? dflt.detect_islands : iv;
     } else if (!strcmp(name, "OFPS_HIP_SAD_GATE")) {
         if (!unset && iv < 0) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d is negative", name, iv);
         o.sad_gate = unset ? dflt.sad_gate : iv;
@@ -143,7 +146,7 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_ALMEIDA_HIER", "OFPS_HIP_ALMEIDA_FAST", "OFPS_HIP_ALMEIDA_ONE_XCD", "OFPS_HIP_ALMEIDA_PROF", "OFPS_HIP_LK_PROF", "OFPS_HIP_LK_SERIAL", "OFPS_HIP_FB_PREPARE_AHEAD", "OFPS_HIP_MULTI_RCCL",
     "OFPS_HIP_SAD_MOTION_SCALE", "OFPS_HIP_DETECT_COMPENSATE", "OFPS_HIP_SAD_GATE", "OFPS_HIP_SAD_CONSISTENCY", "OFPS_HIP_SAD_LEVELS",
     "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN", "OFPS_HIP_SAD_BATCH_FILTER",
-    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT"};
+    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS"};
 
 }  // namespace ofps
 
@@ -238,6 +241,7 @@ void ofps_hip_destroy(ofps_hip_ctx* ctx) {
     for (auto& s : ctx->scratch)
         if (s.p) (void)hipFree(s.p);
     ctx->pipe.release(); ctx->batch.release(); ctx->dense.release(); ctx->fb.release();
+    free(ctx->isl_last.data);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);

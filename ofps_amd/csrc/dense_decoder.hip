@@ -306,6 +306,8 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
     // frame's slot is simply uploaded again by the next push) -- ADVICE r4
     const long frames_after = ds.frames + 1;
     int have_vectors = 0;
+    if (tail) ofps::islands_ticket_arm(ctx, &t.isl, tail, 1);           // A5i: the ticket follows the context's max_islands at this push
+    else t.isl.K = 0;
     size_t tail_off = 0;
     if (frames_after >= 2) {                                        // cv-decoder/src/lib.rs:156-158: flow needs two frames
         const size_t rec_bytes = kBlockHeader + g.max_records * sizeof(float4);
@@ -344,7 +346,7 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
             // their own: d_rec is what the copy above reads
             rc = ofps::frame_tail_device(ctx, d_rec, g.max_records, 1, d_cnt, /*lsq_min_n=*/0, tail, tail->seed, /*may_compensate=*/true,
                                          reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float4*>(blk + tail_off + kTailQuat),
-                                         reinterpret_cast<float2*>(blk + tail_off + kTailField), nullptr, nullptr);
+                                         reinterpret_cast<float2*>(blk + tail_off + kTailField), nullptr, nullptr, &t.isl);
             if (rc != OFPS_HIP_OK) return rc;
         }
         have_vectors = 1;
@@ -451,6 +453,8 @@ int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_r
     out->have_vectors = t->have_vectors;
     if (out_w) *out_w = t->gw;
     if (out_h) *out_h = t->gh;
+    const int isl_rc = ofps::islands_collect(ctx, t->isl);             // (a plain ticket: none)
+    if (isl_rc != OFPS_HIP_OK) return isl_rc;
     if (!t->have_vectors) return OFPS_HIP_OK;
     const char* blk = static_cast<const char*>(t->pinned);
     uint32_t cnt = 0;

@@ -115,6 +115,7 @@ struct Push {
         t = &ctx->pipe.ring.at(tno);
         tix = (int)(tno % kTickets);
         OFPS_REQUIRE(ctx, !t->pending, "push_frame_async: ticket %ld has not been collected (at most %d frames in flight)", tno - kTickets, kTickets);
+        ofps::islands_ticket_arm(ctx, &t->isl, prm, 1);             // A5i: the ticket follows the context's max_islands at this push
         return f.plan(ctx, "push_frame_async");
     }
 
@@ -182,7 +183,7 @@ struct Push {
         out = ofps::device_address_of(t->pinned, &mapped) ? static_cast<PipeOut*>(mapped) : reinterpret_cast<PipeOut*>(d_out);
         const ofps::TailSide side{ps.aux_stream, f.on() ? ps.fork : ps.slot_read[prev_slot], /*recorded=*/!f.on(), ps.join};
         return ofps::frame_tail_device(ctx, d_ent, f.nblk, 1, f.kept(), /*lsq_min_n=*/3, prm, prm->seed, /*may_compensate=*/true, out->r.result,
-                                       reinterpret_cast<float4*>(out->r.quat), reinterpret_cast<float2*>(d_out + kPipeField), &side, &dim);
+                                       reinterpret_cast<float4*>(out->r.quat), reinterpret_cast<float2*>(d_out + kPipeField), &side, &dim, &t->isl);
     }
 
     int read_back(float* out_entries, float* out_field) {
@@ -285,7 +286,7 @@ int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* ou
         }
         if (t->run_estimator) memcpy(out->quat, host->r.quat, sizeof(out->quat));
     }
-    return OFPS_HIP_OK;
+    return ofps::islands_collect(ctx, t->isl);
 }
 
 // ---- batched read-ahead form: n consecutive frames of the stream per ticket.  What a decoder that runs n frames ahead
@@ -405,6 +406,8 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const int pairs = n - first;
     t.n = n; t.first_has_prev = has_prev ? 1 : 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.n_vectors = nblk;
     t.filtered = filtered && pairs > 0;
+    if (halo_mode) t.isl.K = 0;                                  // the multi-device workers list no islands (include/ofps_hip.h A5i)
+    else islands_ticket_arm(ctx, &t.isl, prm, n);
     if (pairs > 0) {
         float4* ent0 = d_ent + (size_t)first * nblk;
         // filtered: item j's kept records lead its slot of the record buffer, its count is word j behind the quaternions.  Searches, flags
@@ -427,7 +430,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         // dispatcher's worker contexts (halo_mode 1) keep the raw detector whatever their detect-compensation mode
         // filtered: the tail's device-count forms with one count per item; fewer than 3 kept -> identity, as in the filtered per-frame path
         rc = frame_tail_device(ctx, ent0, nblk, pairs, d_cnt, filtered ? 3 : 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode,
-                               d_res[first], d_quat + first, d_field, nullptr, nullptr);
+                               d_res[first], d_quat + first, d_field, nullptr, nullptr, &t.isl);
         if (rc != OFPS_HIP_OK) return rc;
         if (filtered || prm->run_detector || prm->run_estimator) {         // (the kept counts travel in this read-back)
             rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * out_bytes, s);
@@ -477,7 +480,7 @@ int ofps_hip_frames_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* o
         if (t->run_detector) { o.has_motion = res[j][0]; o.area = (size_t)res[j][1]; o.dim = res[j][2]; }
         if (t->run_estimator) memcpy(o.quat, quat[j], sizeof(o.quat));
     }
-    return OFPS_HIP_OK;
+    return ofps::islands_collect(ctx, t->isl);
 }
 
 int ofps_hip_push_frame(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride,

@@ -9,7 +9,7 @@ namespace ofps {
 
 int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batch, const uint32_t* d_n, uint32_t lsq_min_n,
                       const ofps_hip_frame_params* prm, uint64_t seed0, bool may_compensate, int* d_result, float4* d_quat, float2* d_field,
-                      const TailSide* side, int* out_dim) {
+                      const TailSide* side, int* out_dim, IslandsTicket* isl) {
     const bool both = prm->run_detector && prm->run_estimator;
     // detect-compensation mode 1 (compensate.hip; the mode is the context's at this push): the detector reads the vectors compensated with the
     // frame's own quaternion, so its chain cannot run beside the estimator -- estimator, compensation and detector are enqueued on the compute
@@ -41,8 +41,13 @@ int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batc
     if (rc == OFPS_HIP_OK && compensate) rc = compensate_device(ctx, d_rec, n, batch, d_n, prm->aspect, prm->fov_y_deg, d_q, d_comp + batch, d_quat);
     if (rc != OFPS_HIP_OK || !prm->run_detector) return rc;
     if (fork) ctx->stream = side->stream;                         // the stage entry points enqueue on ctx->stream
+    int dim = 0;
     rc = detect_device(ctx, compensate ? d_comp + batch : d_rec, n, batch, prm->min_size, prm->subdivide, prm->target_motion, d_result, d_field,
-                       out_dim, d_n);
+                       &dim, d_n);
+    if (out_dim) *out_dim = dim;
+    // A5i: a ticket armed with max_islands > 0 lists the islands of the field the detector has just read, behind it on its stream: one launch
+    // and one copy to the ticket's page-locked blocks, inside the fork.  Nothing here with max_islands 0
+    if (rc == OFPS_HIP_OK && isl && isl->K > 0) rc = islands_ticket_device(ctx, batch, dim, prm->min_size, prm->target_motion, isl);
     ctx->stream = s;
     if (rc != OFPS_HIP_OK || !fork) return rc;
     OFPS_HIP_TRY(ctx, hipEventRecord(side->join, side->stream));

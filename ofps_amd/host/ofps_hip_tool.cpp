@@ -2,7 +2,7 @@
 //   extract <decoder> <arg> <out.mvec> [max_frames [Name=value[@frame] ...]]     motion-extract/src/main.rs:7-38 (decode -> .mvec); properties set by name,
 //                                                                               e.g. hip_sad: "Block size", "Search range", "Exact pruning", "Quarter pel"=true|false
 //   detect  <decoder> <arg> [max_frames]                detection loop, ofps-suite/src/app/detection.rs:92-168
-//   detect  --config <saved.json> [--perf-csv <dir>] [max_frames]
+//   detect  --config <saved.json> [--perf-csv <dir>] [--islands-csv <file>] [max_frames]     (--islands-csv: "Max islands" > 0 in the config)
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
@@ -124,17 +124,38 @@ int main(int argc, char** argv) {
             if (!f) throw Error(std::string("cannot open ") + argv[3]);
             std::stringstream ss; ss << f.rdbuf();
             const MotionDetectionConfig cfg = MotionDetectionConfig::from_json(ss.str());
-            std::string perf_dir;
+            std::string perf_dir, islands_csv;
             size_t max_frames = SIZE_MAX;
             for (int a = 4; a < argc; ++a) {
                 if (std::string(argv[a]) == "--perf-csv" && a + 1 < argc) perf_dir = argv[++a];
+                else if (std::string(argv[a]) == "--islands-csv" && a + 1 < argc) islands_csv = argv[++a];
                 else max_frames = std::strtoull(argv[a], nullptr, 10);
             }
             auto dec = create_decoder(cfg.decoder.selected_plugin, cfg.decoder.arg);
             auto det = create_detector(cfg.detector.selected_plugin, cfg.detector.arg);
             transfer_props(cfg.decoder_properties, *dec);             // detection.rs:100-109
             transfer_props(cfg.detector_properties, *det);
-            const DetectionRun run = run_detection(*dec, *det, max_frames);
+            // --islands-csv: one row per listed island and frame (include/ofps_hip.h A5i); K is the saved configuration's "Max islands"
+            std::ofstream isl_out;
+            std::function<void(size_t)> on_frame;
+            if (!islands_csv.empty()) {
+                auto* bm = dynamic_cast<HipBlockMotionDetection*>(det.get());
+                if (!bm || bm->max_islands == 0) throw Error("--islands-csv needs the hip_block_motion detector with \"Max islands\" above 0 in the configuration");
+                isl_out.open(islands_csv);
+                if (!isl_out) throw Error("cannot write " + islands_csv);
+                isl_out << "frame,rank,seed,area,x0,y0,x1,y1,cx,cy\n";
+                on_frame = [&isl_out, bm](size_t frame) {
+                    const int dim = ofps_hip_block_dim(bm->min_size, bm->subdivide);
+                    size_t rank = 0;
+                    char line[256];
+                    for (const auto& s : bm->islands()) {
+                        const double cx = ((double)s.sum_x / s.area + 0.5) / dim, cy = ((double)s.sum_y / s.area + 0.5) / dim;
+                        std::snprintf(line, sizeof(line), "%zu,%zu,%d,%d,%d,%d,%d,%d,%.6f,%.6f\n", frame, rank++, s.seed, s.area, s.x0, s.y0, s.x1, s.y1, cx, cy);
+                        isl_out << line;
+                    }
+                };
+            }
+            const DetectionRun run = run_detection(*dec, *det, max_frames, on_frame);
             if (!perf_dir.empty())
                 export_perf_csv(perf_dir, cfg.decoder.selected_plugin, {{"decoder", &run.decoder_ms}, {cfg.detector.selected_plugin, &run.detector_ms}});
             std::printf("{\"frames\": %zu, \"decoder_ms_mean\": %.4f, \"detector_ms_mean\": %.4f, \"max_frame_gap\": %zu, \"min_frames\": %zu, "

@@ -259,6 +259,16 @@ std::optional<std::pair<size_t, MotionField>> HipBlockMotionDetection::detect_mo
     const int dim = ofps_hip_block_dim(min_size, subdivide);
     if (dim < 1) return std::nullopt;
     MotionField mf((size_t)dim, (size_t)dim);
+    if (max_islands > 0) {
+        static_assert(sizeof(Island) == 8 * sizeof(int32_t), "one table row");
+        int32_t counts[4] = {0, 0, 0, 0};
+        islands_.assign(max_islands, Island{});
+        const int rc = ofps_hip_detect_islands(ctx_.get(), reinterpret_cast<const float*>(mv), n, min_size, subdivide, target_motion, (int)max_islands,
+                                               counts, reinterpret_cast<int32_t*>(islands_.data()), nullptr, mf.raw().data());
+        islands_.resize(rc == OFPS_HIP_OK ? (size_t)counts[3] : 0);
+        if (rc != OFPS_HIP_OK || counts[0] < 1) return std::nullopt;
+        return std::make_pair((size_t)islands_[0].area, std::move(mf));
+    }
     int has = 0, odim = 0;
     size_t area = 0;
     const int rc = ofps_hip_detect(ctx_.get(), reinterpret_cast<const float*>(mv), n, min_size, subdivide, target_motion, &has,
@@ -270,7 +280,8 @@ std::optional<std::pair<size_t, MotionField>> HipBlockMotionDetection::detect_mo
 std::vector<std::pair<std::string, PropertyMut>> HipBlockMotionDetection::props_mut() {   // lib.rs:29-46
     return {{"Min size", PropertyMut::float_(&min_size, 0.01f, 1.0f)},
             {"Subdivisions", PropertyMut::usize(&subdivide, 1, 16)},
-            {"Target motion", PropertyMut::float_(&target_motion, 0.0001f, 0.1f)}};
+            {"Target motion", PropertyMut::float_(&target_motion, 0.0001f, 0.1f)},
+            {"Max islands", PropertyMut::usize(&max_islands, 0, 256)}};
 }
 
 // ------------------------------------------------------------------ hip_almeida
@@ -581,7 +592,7 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-DetectionRun run_detection(Decoder& decoder, Detector& detector, size_t max_frames) {
+DetectionRun run_detection(Decoder& decoder, Detector& detector, size_t max_frames, const std::function<void(size_t)>& on_frame) {
     DetectionRun run;
     MotionVectors mv;
     while (run.frames < max_frames) {
@@ -593,6 +604,7 @@ DetectionRun run_detection(Decoder& decoder, Detector& detector, size_t max_fram
         t0 = std::chrono::steady_clock::now();
         const auto motion = detector.detect_motion(mv.data(), mv.size());                        // :146-148
         run.detector_ms.push_back(ms_since(t0));
+        if (on_frame) on_frame(run.frames - 1);
         if (motion) {                                                 // :150-155
             if (!run.motion_ranges.empty() && run.motion_ranges.back().second == run.frames) run.motion_ranges.back().second += 1;
             else run.motion_ranges.emplace_back(run.frames, run.frames + 1);

@@ -9,6 +9,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <istream>
 #include <memory>
 #include <optional>
@@ -213,10 +214,16 @@ class HipBlockMotionDetection : public Detector {                    // block-mo
 public:
     explicit HipBlockMotionDetection(int device = 0) : ctx_(device) {}
     float min_size = 0.05f; size_t subdivide = 3; float target_motion = 0.003f;
+    // build-defined (include/ofps_hip.h A5i): 0 = the reference's detector; K = up to K qualifying islands per frame -- detect_motion then
+    // returns the largest one's area with the union of the listed islands' fields, and islands() the table
+    size_t max_islands = 0;
+    struct Island { int32_t seed, area, x0, y0, x1, y1, sum_x, sum_y; };
+    const std::vector<Island>& islands() const { return islands_; }  // the last frame's listed islands, in rank order
     std::optional<std::pair<size_t, MotionField>> detect_motion(const MotionEntry* mv, size_t n) override;
     std::vector<std::pair<std::string, PropertyMut>> props_mut() override;
 private:
     HipContext ctx_;
+    std::vector<Island> islands_;
 };
 
 class HipAlmeidaEstimator : public Estimator {                       // almeida-estimator/src/lib.rs:57-121
@@ -278,7 +285,9 @@ struct DetectionRun {
 // `dir`, one millisecond value per line (csv::Writer::serialize of an f32: no header).
 void export_perf_csv(const std::string& dir, const std::string& decoder_name,
                      const std::vector<std::pair<std::string, const std::vector<double>*>>& stages);
-DetectionRun run_detection(Decoder& decoder, Detector& detector, size_t max_frames = SIZE_MAX);
+// on_frame (optional): called with the frame's index behind every detect_motion (the tool's --islands-csv reads the detector there)
+DetectionRun run_detection(Decoder& decoder, Detector& detector, size_t max_frames = SIZE_MAX,
+                           const std::function<void(size_t)>& on_frame = nullptr);
 // Tracking loop of ofps-suite/src/app/tracking/worker.rs:62-69,305-412 (one estimator).
 struct TrackingRun {
     size_t frames = 0;

@@ -270,13 +270,34 @@ class HipBlockMotionDetection(Properties):
     _PROPS = (("Min size", "float", "min_size", 0.01, 1.0), ("Subdivisions", "usize", "subdivide", 1, 16),
               ("Target motion", "float", "target_motion", 0.0001, 0.1))
 
+    # build-defined (include/ofps_hip.h A5i): 0 = the reference's detector; K = up to K qualifying islands per frame -- detect_motion then
+    # returns the largest one's area with the union of the listed islands' fields, and last_islands holds the table.  props() stays the
+    # reference's three names; the extension is listed by ext_props() and set through the same set_prop
+    _EXT_PROPS = (("Max islands", "usize", "max_islands", 0, 256),)
+
     def __init__(self, device: int = 0):
         self.ctx = HipContext(device)
         self.min_size, self.subdivide, self.target_motion = 0.05, 3, 0.003
+        self.max_islands = 0
+        self.last_islands = None          # int32 [n_listed, 8]: seed, area, x0, y0, x1, y1, sum_x, sum_y of the last frame (Max islands > 0)
+
+    def ext_props(self):
+        return [(name, kind, getattr(self, attr), lo, hi) for name, kind, attr, lo, hi in self._EXT_PROPS]
+
+    def set_prop(self, name: str, value) -> bool:
+        if name == "Max islands":
+            self.max_islands = min(max(int(value), 0), 256)
+            return True
+        return super().set_prop(name, value)
 
     def detect_motion(self, motion):
         """-> None | (area, MotionField)"""
-        r = self.ctx.detect(np.asarray(motion, np.float32).reshape(-1, 4), self.min_size, self.subdivide, self.target_motion)
+        mv = np.asarray(motion, np.float32).reshape(-1, 4)
+        if self.max_islands > 0:
+            r = self.ctx.detect_islands(mv, self.min_size, self.subdivide, self.target_motion, self.max_islands, want_labels=False)
+            self.last_islands = r["table"]
+            return None if r["n_islands"] == 0 else (int(r["table"][0, 1]), MotionField(r["field"]))
+        r = self.ctx.detect(mv, self.min_size, self.subdivide, self.target_motion)
         return None if r is None else (r[0], MotionField(r[1]))
 
 

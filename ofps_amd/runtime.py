@@ -629,12 +629,15 @@ class HipContext:
         return out.reshape(-1, 4)[:n.value], (gw.value, gh.value)
 
     # ---- the dense decoders with detector + estimator behind them in the same ticket (ofps_hip_lk_push_frame_fused[_async])
-    def _fused_result(self, res, ent, fld, grid):
+    def _fused_result(self, res, ent, fld, grid, islands=False):
         have = bool(res.have_vectors)
         n = int(res.n_vectors)
         motion = (int(res.area), fld) if res.has_motion else None
-        return {"have_vectors": have, "n_vectors": n, "motion": motion, "quat": np.array(list(res.quat), np.float32),
-                "entries": ent[:n] if (ent is not None and have) else None, "grid": grid}
+        out = {"have_vectors": have, "n_vectors": n, "motion": motion, "quat": np.array(list(res.quat), np.float32),
+               "entries": ent[:n] if (ent is not None and have) else None, "grid": grid}
+        if islands:
+            out["islands"] = self.frame_islands(0)
+        return out
 
     def lk_push_frame_fused_async(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
                                   farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True,
@@ -654,6 +657,8 @@ class HipContext:
         self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records)
         self._lk_dim = getattr(self, "_lk_dim", {})
         self._lk_dim[t.value] = self.block_dim(min_size, subdivide) if detector else 0
+        self._lk_isl = getattr(self, "_lk_isl", {})
+        self._lk_isl[t.value] = self._ticket_islands(detector)
         return t.value
 
     def lk_frame_fused_wait(self, ticket: int, want_entries=True, want_field=True) -> dict:
@@ -666,7 +671,7 @@ class HipContext:
         res = _lib.FrameResult(); gw = C.c_int(0); gh = C.c_int(0)
         self._check(self._lib.ofps_hip_lk_frame_fused_wait(self._h, ticket, C.byref(res), _fp(ent) if ent is not None else None,
                                                            _fp(fld) if fld is not None else None, C.byref(gw), C.byref(gh)))
-        return self._fused_result(res, ent, fld, (gw.value, gh.value))
+        return self._fused_result(res, ent, fld, (gw.value, gh.value), getattr(self, "_lk_isl", {}).pop(ticket, False))
 
     def lk_push_frame_fused(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
                             farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True, min_size=0.05,
@@ -687,7 +692,7 @@ class HipContext:
                                                            iters, max_w, max_h, flags, C.byref(prm), C.byref(res),
                                                            _fp(ent) if ent is not None else None, _fp(fld) if fld is not None else None,
                                                            C.byref(gw), C.byref(gh)))
-        return self._fused_result(res, ent, fld, (gw.value, gh.value))
+        return self._fused_result(res, ent, fld, (gw.value, gh.value), self._ticket_islands(detector))
 
     def lk_reset(self):
         self._check(self._lib.ofps_hip_lk_reset(self._h))
@@ -783,6 +788,60 @@ class HipContext:
         self._check(self._lib.ofps_hip_detect_dev(self._h, C.c_void_p(d_entries), n_per_item, batch, min_size, subdivide,
                                                   target_motion, C.c_void_p(d_out_result), C.c_void_p(d_out_field)))
 
+    # ---- A5i: every qualifying island (include/ofps_hip.h; csrc/detect.hip)
+    @staticmethod
+    def island_centroids(table: np.ndarray, dim: int) -> np.ndarray:
+        """table [n, 8] -> [n, 2] centroids in frame coordinates: ((sum / area) + 0.5) / dim"""
+        t = np.asarray(table, np.float64).reshape(-1, 8)
+        return (t[:, 6:8] / np.maximum(t[:, 1:2], 1) + 0.5) / max(dim, 1)
+
+    def detect_islands(self, entries, min_size=0.05, subdivide=3, target_motion=0.003, max_islands=16, want_labels=True, want_field=True) -> dict:
+        """-> dict(n_islands, n_components, dim, n_listed, table int32 [n_listed, 8] = seed, area, x0, y0, x1, y1, sum_x, sum_y in rank
+        order, labels uint16 [dim, dim] | None (0xFFFF = not listed), field f32 [dim, dim, 2] | None: the listed islands' cells but their seeds)"""
+        e = np.ascontiguousarray(entries, np.float32).reshape(-1, 4)
+        dim = max(self.block_dim(min_size, subdivide), 1)
+        counts = np.zeros(4, np.int32)
+        table = np.zeros((max(int(max_islands), 1), 8), np.int32)
+        labels = np.zeros((dim, dim), np.uint16) if want_labels else None
+        field = np.zeros((dim, dim, 2), np.float32) if want_field else None
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_detect_islands(self._h, _fp(e), e.shape[0], min_size, subdivide, target_motion, int(max_islands),
+                                                      counts.ctypes.data_as(i32), table.ctypes.data_as(i32),
+                                                      C.c_void_p(labels.ctypes.data) if want_labels else None, _fp(field) if want_field else None))
+        return {"n_islands": int(counts[0]), "n_components": int(counts[1]), "dim": int(counts[2]), "n_listed": int(counts[3]),
+                "table": table[:int(counts[3])].copy(), "labels": labels, "field": field}
+
+    def detect_islands_dev(self, d_entries: int, n_per_item: int, batch: int, min_size: float, subdivide: int, target_motion: float,
+                           max_islands: int, d_out_counts: int, d_out_table: int, d_out_labels: int | None = None, d_out_field: int | None = None):
+        """Device form: per item counts int32[4], table int32[8 * max_islands], labels uint16[dim * dim], field f32[2 * dim * dim].  Enqueue only."""
+        self._check(self._lib.ofps_hip_detect_islands_dev(self._h, C.c_void_p(d_entries), n_per_item, batch, min_size, subdivide, target_motion,
+                                                          int(max_islands), C.c_void_p(d_out_counts), C.c_void_p(d_out_table),
+                                                          C.c_void_p(d_out_labels or 0), C.c_void_p(d_out_field or 0)))
+
+    def set_detect_islands(self, max_islands: int):
+        """0 = off (default); K in [1, 6400]: a fused ticket that runs the detector lists up to K islands, read with frame_islands"""
+        self._check(self._lib.ofps_hip_set_detect_islands(self._h, int(max_islands)))
+
+    def get_detect_islands(self) -> int:
+        return int(self._lib.ofps_hip_get_detect_islands(self._h))
+
+    def frame_islands(self, item: int = 0, want_labels=True) -> dict:
+        """The islands of `item` of the most recently collected fused ticket (pushed with max_islands > 0 and the detector on)"""
+        counts = np.zeros(4, np.int32)
+        if getattr(self, "_isl_buf", None) is None:                      # sized for the largest answer, made once
+            self._isl_buf = (np.zeros((6400, 8), np.int32), np.zeros(160 * 160, np.uint16))
+        table, labels = self._isl_buf[0], (self._isl_buf[1] if want_labels else None)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_frame_islands(self._h, int(item), counts.ctypes.data_as(i32), table.ctypes.data_as(i32), table.shape[0],
+                                                     C.c_void_p(labels.ctypes.data) if want_labels else None))
+        dim = int(counts[2])
+        return {"n_islands": int(counts[0]), "n_components": int(counts[1]), "dim": dim, "n_listed": int(counts[3]),
+                "table": table[:int(counts[3])].copy(), "labels": labels[:dim * dim].reshape(dim, dim).copy() if want_labels else None}
+
+    def _ticket_islands(self, detector) -> bool:
+        """whether a ticket pushed now will carry islands: the context's max_islands at the push counts"""
+        return bool(detector) and self.get_detect_islands() > 0
+
     # ---- A6-A12
     def almeida(self, entries, aspect: float, fov_y_deg: float, use_ransac=False, num_iters=200, inlier_deg=0.05,
                 num_samples=1000, seed=0):
@@ -876,6 +935,8 @@ class HipContext:
         self._check(self._lib.ofps_hip_push_frame_async(self._h, luma.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, W, C.byref(prm),
                                                         _fp(out_entries) if out_entries is not None else None,
                                                         _fp(out_field) if out_field is not None else None, C.byref(t)))
+        self._pipe_isl = getattr(self, "_pipe_isl", {})
+        self._pipe_isl[int(t.value)] = self._ticket_islands(detector)
         return int(t.value)
 
     def push_frames_async(self, frames: np.ndarray, block=16, search_range=16, detector=True, min_size=0.05, subdivide=3,
@@ -892,20 +953,29 @@ class HipContext:
                                                          _fp(out_entries) if out_entries is not None else None, C.byref(t)))
         self._batch_n = getattr(self, "_batch_n", {})
         self._batch_n[t.value] = n
+        self._batch_isl = getattr(self, "_batch_isl", {})
+        self._batch_isl[t.value] = self._ticket_islands(detector)
         return t.value
 
     def frames_wait(self, ticket: int) -> list:
         n = self._batch_n.pop(ticket)
         res = (_lib.FrameResult * n)()
         self._check(self._lib.ofps_hip_frames_wait(self._h, ticket, res))
-        return [{"have_vectors": bool(r.have_vectors), "n_vectors": int(r.n_vectors),
-                 "motion": (int(r.area), int(r.dim)) if r.has_motion else None, "quat": np.array(list(r.quat), np.float32)} for r in res]
+        out = [{"have_vectors": bool(r.have_vectors), "n_vectors": int(r.n_vectors),
+                "motion": (int(r.area), int(r.dim)) if r.has_motion else None, "quat": np.array(list(r.quat), np.float32)} for r in res]
+        if getattr(self, "_batch_isl", {}).pop(ticket, False):
+            for j, o in enumerate(out):
+                o["islands"] = self.frame_islands(j)
+        return out
 
     def frame_wait(self, ticket: int) -> dict:
         res = _lib.FrameResult()
         self._check(self._lib.ofps_hip_frame_wait(self._h, ticket, C.byref(res)))
-        return {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors),
-                "motion": (int(res.area), int(res.dim)) if res.has_motion else None, "quat": np.array(list(res.quat), np.float32)}
+        out = {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors),
+               "motion": (int(res.area), int(res.dim)) if res.has_motion else None, "quat": np.array(list(res.quat), np.float32)}
+        if getattr(self, "_pipe_isl", {}).pop(ticket, False):
+            out["islands"] = self.frame_islands(0)
+        return out
 
     def push_frame(self, luma: np.ndarray, block=16, search_range=16, detector=True, min_size=0.05, subdivide=3,
                    target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16, use_ransac=False,
@@ -916,6 +986,7 @@ class HipContext:
         prm = _lib.FrameParams(block, search_range, int(detector), min_size, subdivide, target_motion, int(estimator),
                                aspect, fov_y_deg, int(use_ransac), num_iters, inlier_deg, num_samples, seed)
         res = _lib.FrameResult()
+        islands = self._ticket_islands(detector)
         nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
         ent = np.zeros((max(nb, 1), 4), np.float32) if want_entries else None
         dim = self.block_dim(min_size, subdivide)
@@ -924,9 +995,12 @@ class HipContext:
                                                   C.byref(res), _fp(ent) if want_entries else None,
                                                   _fp(fld) if want_field else None))
         motion = (int(res.area), fld) if res.has_motion else None
-        return {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors), "motion": motion,
-                "quat": np.array(list(res.quat), np.float32),
-                "entries": ent[:min(nb, int(res.n_vectors))] if (want_entries and res.have_vectors) else None}      # (the kept records with the contrast gate on)
+        out = {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors), "motion": motion,
+               "quat": np.array(list(res.quat), np.float32),
+               "entries": ent[:min(nb, int(res.n_vectors))] if (want_entries and res.have_vectors) else None}      # (the kept records with the contrast gate on)
+        if islands:
+            out["islands"] = self.frame_islands(0)
+        return out
 
 
 def device_count() -> int:
