@@ -368,6 +368,71 @@ int ofps_hip_sad_flow_intra_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_f
                                 void* d_out_entries /* pairs * nblk * 4 f32 */, void* d_out_best /* pairs * nblk * 3 i32, or NULL */,
                                 void* d_out_counts /* pairs uint32 */);
 
+/* ---- N1s: hip_sad's split blocks -- a block that holds two motions yields its four sub-blocks' vectors (csrc/sad_split.hip) ----
+ * A lattice block that straddles a motion boundary has no right vector: its winner belongs to one side, to neither, or to whatever fits the
+ * mixture, and every criterion above can only drop it.  The encoders whose vectors av-decoder reads split such a macroblock into
+ * partitions, and the decoder yields one record per partition (av-decoder/src/lib.rs:396-419).  Build-defined, like N1, N1q, N1g ... N1p;
+ * all-integer, so bit-exact on every device.  For a frame pair (prev, cur), lattice `block` = B, sub-block side b = B / 2, `threshold` = T
+ * in [1, 4080]:
+ *   frames: the ones the integer search read -- the mean-removed copies with N1m on; with search levels (N1h) the step acts on level 0;
+ *   parents: the integer winners (dx, dy, SAD) of the context's search, one per lattice block, after every other setting of the context
+ *     (PRUNED, levels, predictors, mean removal); R0 = ofps_hip_sad_reach(range, levels);
+ *   sub-block s in {0, 1, 2, 3} of block (bx, by), raster order: at (sx0, sy0) = (bx*B + (s & 1)*b, by*B + (s >> 1)*b);
+ *   predictor list, in this order: the winner of (bx, by); the winners of (bx - 1, by), (bx + 1, by), (bx, by - 1), (bx, by + 1), those that
+ *     exist in the lattice (a neighbour's keep flag is not looked at); (0, 0).  Predictors are not doubled.  Each is clamped on its own for
+ *     this sub-block: px = clamp(px, -sx0, W - b - sx0), py alike; the block's own winner is never changed by the clamp;
+ *   candidates d = p + e over all predictors p and e in [-3, 3]^2, valid iff 0 <= sx0 + dx <= W - b and the same in y;
+ *   cost = sum |cur - prev displaced by d| over the b x b sub-block;
+ *   winner = min of (SAD, dx*dx + dy*dy, dy + R0 + 3, dx + R0 + 3), lexicographic: a total order on d, so duplicate predictors and candidates
+ *     cannot change it (the kernel drops duplicate predictors);
+ *   consequence: the parent's winner is a valid candidate of each of its sub-blocks, so sum_s SAD_s <= SAD_parent and
+ *     gain = SAD_parent - sum_s SAD_s >= 0;
+ *   rule: a block is SPLIT iff 16 * gain >= T * B * B (64-bit signed): T counts sixteenths of a grey level per pixel of the block, as the
+ *     intra test's ratio counts sixteenths;
+ *   records: an unsplit kept block yields its one N1 record, bit for bit; a split kept block yields four records in sub-block order in its
+ *     place, by N1's float expressions with the sub-block's centre (sx0 + b/2, sy0 + b/2) and d_s; a block dropped by gate, check, median
+ *     test, intra test or cut rule yields nothing -- those criteria read the parents and are unchanged.  Block raster order; the count is
+ *     variable, between kept and 4 * kept.
+ * OFPS_HIP_EINVAL: B odd or b < 4 (B < 8); R0 + 3 > 127; T outside [0, 4080] at the setter and at the option OFPS_HIP_SAD_SPLIT
+ * (environment / ofps_hip_set_option), outside [1, 4080] at the explicit calls.  With motion scale 4 and T > 0 a search call returns
+ * OFPS_HIP_EUNSUPPORTED: quarter-pel sub-block vectors are a later step.  T = 0 = off, the default: every entry point then uses the
+ * launches, streams, scratch and bytes of a build without this section.
+ * ofps_hip_sad_record_capacity(ctx, W, H, block): the records out_entries must hold for a search call of this context: nblk with T = 0,
+ *   4 * nblk with T > 0.
+ * ofps_hip_sad_split[_dev]: the step alone on caller-held data, as ofps_hip_sad_refine is: best = the nblk parent triples (a predictor is
+ *   clamped to the frame whatever they hold: no access out of bounds), keep = one byte per block (non-zero = kept) or NULL = all ones,
+ *   reach = R0 in [0, 124] ->
+ *   out_sub_best: the four sub-blocks' (dx, dy, SAD), 12 int32 per block, for every kept block whether split or not (zeros for the others);
+ *   out_split: one byte per block; out_entries (or NULL): the raw slots, 4 records per block, slot 4 * blk + s; out_slot_flags (or NULL):
+ *   one byte per slot -- an unsplit kept block fills slot 0 alone, with its N1 record, a split one all four, a block that is not kept none;
+ *   a slot whose flag is 0 holds zeros.  An ordered compaction of the slots by their flags is the record stream above.  The _dev form
+ *   enqueues only; the packed kernels need 4-byte aligned rows (other rows take the byte-wise form).
+ * ofps_hip_sad_flow_split_dev: one pair in device memory: search + the three explicit criteria (min_pixels, limit, median; 0 = off each;
+ *   the context's own criteria and T are not looked at) + split with T in [1, 4080] + ONE compaction + the count on the device:
+ *   d_out_entries holds 4 * nblk records, d_out_count one uint32.  Enqueues only.
+ * With the context's T > 0:
+ *   ofps_hip_sad_flow: *n_out = the record count, out_entries has capacity 4 * nblk; out_best stays the PARENTS' triples, nblk of them,
+ *     compacted by the keep flags as before.
+ *   ofps_hip_push_frame[_async] / ofps_hip_frame_wait: the filtered path with the split step between the flags and the one compaction, on
+ *     the compute stream; out_entries has capacity 4 * nblk, n_vectors = the record count, detector and estimator read the split stream
+ *     through their device-count forms; no host synchronisation is added, and a ticket follows the T the context has when it is pushed.
+ * Ignoring T, as they first ignored the gate (a later step): the batched and multi-device forms -- ofps_hip_sad_flow_dev, _gated_dev,
+ * _checked_dev, _median_dev, _filtered_dev, _intra_dev, ofps_hip_push_frames_async, ofps_hip_multi_* -- which always produce at most nblk
+ * records per pair, and the dense decoders. */
+int ofps_hip_set_sad_split(ofps_hip_ctx* ctx, int threshold);   /* sixteenths; 0 = off (default) */
+int ofps_hip_get_sad_split(ofps_hip_ctx* ctx);
+size_t ofps_hip_sad_record_capacity(ofps_hip_ctx* ctx, int W, int H, int block);
+int ofps_hip_sad_split(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int block,
+                       const int32_t* best /* 3 * nblk */, const uint8_t* keep /* nblk or NULL = all ones */, int reach, int threshold,
+                       int32_t* out_sub_best /* 12 * nblk */, uint8_t* out_split /* nblk */, float* out_entries /* 16 * nblk or NULL */,
+                       uint8_t* out_slot_flags /* 4 * nblk or NULL */);
+int ofps_hip_sad_split_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, const void* d_best,
+                           const void* d_keep /* or NULL */, int reach, int threshold, void* d_out_sub_best, void* d_out_split,
+                           void* d_out_entries /* or NULL */, void* d_out_slot_flags /* or NULL */);
+int ofps_hip_sad_flow_split_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int block, int range,
+                                int min_pixels, int limit, int median, int threshold, void* d_out_entries /* 4 * nblk * 4 f32 */,
+                                void* d_out_count /* one uint32 */);
+
 /* ---- N1h: hip_sad's search levels -- coarse-to-fine search for motion beyond the search range (csrc/sad_hier.hip) ----
  * The plain search cannot return a vector that was never a candidate: range 16 at 1080p ends at about one degree of camera rotation per
  * frame.  With levels = L in {2, 3} the search runs on the frames halved L - 1 times and every finer level repairs the doubled vectors in a

@@ -74,6 +74,12 @@ PROTOTYPES = {
     "ofps_hip_get_sad_cut": (C.c_int, [_ctx]),
     "ofps_hip_sad_flow_intra_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_set_sad_split": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_sad_split": (C.c_int, [_ctx]),
+    "ofps_hip_sad_record_capacity": (C.c_size_t, [_ctx, C.c_int, C.c_int, C.c_int]),
+    "ofps_hip_sad_split": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u8p, C.c_int, C.c_int, _i32p, _u8p, _f32p, _u8p]),
+    "ofps_hip_sad_split_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "ofps_hip_sad_flow_split_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ofps_hip_set_sad_levels": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_sad_levels": (C.c_int, [_ctx]),
     "ofps_hip_sad_reach": (C.c_int, [C.c_int, C.c_int]),

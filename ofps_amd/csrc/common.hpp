@@ -225,6 +225,7 @@ struct ofps_hip_ctx {
         int sad_median = 0;              // OFPS_HIP_SAD_MEDIAN / ofps_hip_set_sad_median: 0 off, N in [1, 255] only blocks whose integer winner lies less than N pixels from the median of their kept lattice neighbours' (sad_median.hip, N1v)
         int sad_intra = 0;               // OFPS_HIP_SAD_INTRA / ofps_hip_set_sad_intra: 0 off, q in [1, 255] (sixteenths) only blocks whose integer winner's SAD lies below q/16 of the block's activity in the raw current frame (sad_intra.hip, N1i)
         int sad_cut = 0;                 // OFPS_HIP_SAD_CUT / ofps_hip_set_sad_cut: 0 off, P in [1, 100] a pair with at least P percent of its gated blocks intra yields no record; no effect while sad_intra is 0 (sad_intra.hip, N1i)
+        int sad_split = 0;               // OFPS_HIP_SAD_SPLIT / ofps_hip_set_sad_split: 0 one record per kept block, T in [1, 4080] (sixteenths of a grey level per pixel) a kept block whose four sub-blocks together match better by at least T yields their four records (sad_split.hip, N1s)
         int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int detect_islands = 0;          // OFPS_HIP_DETECT_ISLANDS / ofps_hip_set_detect_islands: 0 the fused entry points' detector answers for the largest island alone, K in [1, 6400] a ticket that runs the detector lists up to K islands as well (detect.hip, A5i)
@@ -255,7 +256,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 58;
+    static constexpr int kNumScratch = 59;
     Scratch scratch[kNumScratch];
 };
 
@@ -295,9 +296,10 @@ enum ScratchSlot {
     S_MED_KEEP,             // hip_sad's median test (sad_median.hip): the outgoing keep flags, u8 per block, one per ticket in flight in the fused path (the incoming ones stay in S_GATE_FLAGS)
     S_INTRA,                // hip_sad's intra test (sad_intra.hip): [activity, u32 per block][candidate and intra counters, 2 x u32 per item], one per ticket in flight in the fused path
     S_ISL_WORK,             // the islands kernel (detect.hip, A5i): per item [qualifying roots' keys, u64][rank of every root, u16 per cell]
-    S_ISL_OUT               // ... and the blocks of a fused ticket or a host-pointer call ([counts][table][labels] per item), copied out behind the kernel on its stream
+    S_ISL_OUT,              // ... and the blocks of a fused ticket or a host-pointer call ([counts][table][labels] per item), copied out behind the kernel on its stream
+    S_SPLIT                 // hip_sad's split step (sad_split.hip, N1s): [raw slots, 4 records per block][sub triples, 12 i32 per block][slot flags, 4 u8 per block][split flags, u8 per block].  Compute stream only, written anew by every search
 };
-static_assert(S_ISL_OUT < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_SPLIT < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -454,6 +456,17 @@ int sad_intra_flags_device(ofps_hip_ctx* ctx, const int* d_best, const uint32_t*
 // cut > 0: the flags of every item whose counters say 100 * intra >= cut * candidates are cleared; one launch.  cut == 0: nothing
 int sad_cut_device(ofps_hip_ctx* ctx, const uint32_t* d_counts, size_t nblk, int cut, uint8_t* d_flags, hipStream_t st, int items = 1);
 
+// sad_split.hip: hip_sad's split step (include/ofps_hip.h N1s)
+constexpr int kSadSplitMax = 4080;                          // sixteenths: 255 grey levels per pixel
+int sad_split_check(ofps_hip_ctx* ctx, int block, int reach, int threshold, const char* who);       // block even in [8, 64], reach + 3 <= 127, threshold in [1, 4080]
+inline size_t sad_split_bytes(size_t nblk) { return nblk * (4 * sizeof(float4) + 12 * sizeof(int) + 4 + 1); }
+// One pair of `f` (the frames the integer search read), on ctx->stream, one launch: per block with a non-zero keep flag (d_keep: optional,
+// absent = all ones) the four sub-blocks' winners -> d_sub_best (12 i32 per block), the verdict -> d_split (u8 per block), and, unless null,
+// the raw slots 4 * blk + s -> d_raw (records) and d_slot_flags (u8): an unsplit kept block fills slot 0 with its N1 record, a split one all
+// four, a block that is not kept none; slots whose flag is 0 hold zeros
+int sad_split_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int reach, int threshold, const int* d_best, const uint8_t* d_keep,
+                     int* d_sub_best, uint8_t* d_split, float4* d_raw, uint8_t* d_slot_flags);
+
 // sad_gate.hip: the filtered search of `pairs` pairs -- search [+ backward search] -> keep flags -> ordered compaction -> count on the device --
 // in the steps every caller takes: plan, reserve, search, [contrast_flags,] finish.  sad_flow_filtered_device runs them all on ctx->stream; the
 // fused per-frame path (pipeline.hip) makes the contrast flags and the activities on its auxiliary stream, beside the search.  Every per-block array holds pairs x nblk, item-major,
@@ -465,6 +478,7 @@ struct SadFilter {
     int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
     int intra, cut;                      // the intra test's ratio in sixteenths, 0 = off; the scene-cut rule's percentage, 0 = off and no effect while intra == 0
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
+    int split = 0;                       // the split step's threshold in sixteenths (N1s), 0 = off; one pair only
     size_t nblk = 0;                     // per pair
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
     char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
@@ -473,9 +487,14 @@ struct SadFilter {
     int* d_triples = nullptr;            // the triples that belong to d_raw: S_GATE_BEST, or d_fwd itself (integer winners kept, motion scale 1)
     uint8_t* d_med_keep = nullptr;       // S_MED_KEEP, this ticket's block: the median test's outgoing flags (median > 0)
     uint32_t *d_act = nullptr, *d_intra_counts = nullptr;       // S_INTRA, this ticket's block: the current frames' activities and the items' two counters (intra > 0)
-    bool on() const { return gate > 0 || limit > 0 || median > 0 || intra > 0; }
-    bool winners() const { return limit > 0 || median > 0 || intra > 0; }       // all three read the forward search's INTEGER winners, whatever the motion scale
+    int* d_sub_best = nullptr;           // S_SPLIT (split > 0): the raw slots' records (d_split_raw), the sub-blocks' triples, slot flags and split flags
+    float4* d_split_raw = nullptr;
+    uint8_t *d_slot_flags = nullptr, *d_split = nullptr;
+    bool criteria() const { return gate > 0 || limit > 0 || median > 0 || intra > 0; }         // something drops blocks
+    bool on() const { return criteria() || split > 0; }   // the record count is variable and lives on the device
+    bool winners() const { return limit > 0 || median > 0 || intra > 0 || split > 0; }       // all four read the forward search's INTEGER winners, whatever the motion scale
     size_t total() const { return (size_t)pairs * nblk; }
+    size_t capacity() const { return split > 0 ? 4 * nblk : nblk; }       // records d_out must hold, per pair
     uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk, pairs) : nullptr; }
     uint8_t* keep() const { return gate_keep(d_flags, nblk, pairs); }       // the incoming flags: contrast gate AND NOT intra AND consistency check
     int plan(ofps_hip_ctx* ctx, const char* who);         // validation, every text led by `who`; nothing is reserved or enqueued
@@ -485,14 +504,16 @@ struct SadFilter {
     // what depends on the current frames alone, on stream st: gate > 0: contrast counts and keep flags; intra > 0: activities, and the counters zeroed
     int contrast_flags(ofps_hip_ctx* ctx, hipStream_t st);
     // on ctx->stream behind search and contrast_flags: [intra flags and counters, the gate's ANDed in in place ->] [consistency flags, those
-    // ANDed in in place ->] [median flags read from those, into d_med_keep ->] [the cut rule's veto on the final flags ->] kept records [and triples] in raster order -> count.  d_out and d_out_best hold pairs slots of nblk, item k's kept ones
-    // lead slot k; d_count holds pairs counts
+    // ANDed in in place ->] [median flags read from those, into d_med_keep ->] [the cut rule's veto on the final flags ->] [the split step: raw
+    // slots and slot flags of the kept blocks ->] kept records [and triples] in raster order -> count.  d_out and d_out_best hold pairs slots of nblk, item k's kept ones
+    // lead slot k; d_count holds pairs counts.  split > 0: d_out holds capacity() records, d_out_best stays the parents' nblk triples
     int finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_t* d_count);               // d_out may not alias d_raw
+    int finish_split(ofps_hip_ctx* ctx, const uint8_t* flags, float4* d_out, int* d_out_best, uint32_t* d_count);     // finish()'s last step with split > 0
 };
 // the five steps on ctx->stream, the launch count independent of `pairs`; `who` leads every error text, tix / tickets: SadFilter::reserve
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
                              float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1, int intra = 0,
-                             int cut = 0);
+                             int cut = 0, int split = 0);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional): the record counts in device memory, one per item, n the capacity.  d_out may equal d_entries.

@@ -109,6 +109,9 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_SAD_CUT")) {
         if (!unset && (iv < 0 || iv > kSadCutMax)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kSadCutMax);
         o.sad_cut = unset ? dflt.sad_cut : iv;
+    } else if (!strcmp(name, "OFPS_HIP_SAD_SPLIT")) {
+        if (!unset && (iv < 0 || iv > kSadSplitMax)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kSadSplitMax);
+        o.sad_split = unset ? dflt.sad_split : iv;
     } else if (!strcmp(name, "OFPS_HIP_SAD_LEVELS")) {
         if (!unset && (iv < 1 || iv > 3)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' is not 1|2|3", name, value);
         o.sad_levels = unset ? dflt.sad_levels : iv;
@@ -146,7 +149,7 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_ALMEIDA_HIER", "OFPS_HIP_ALMEIDA_FAST", "OFPS_HIP_ALMEIDA_ONE_XCD", "OFPS_HIP_ALMEIDA_PROF", "OFPS_HIP_LK_PROF", "OFPS_HIP_LK_SERIAL", "OFPS_HIP_FB_PREPARE_AHEAD", "OFPS_HIP_MULTI_RCCL",
     "OFPS_HIP_SAD_MOTION_SCALE", "OFPS_HIP_DETECT_COMPENSATE", "OFPS_HIP_SAD_GATE", "OFPS_HIP_SAD_CONSISTENCY", "OFPS_HIP_SAD_LEVELS",
     "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN", "OFPS_HIP_SAD_BATCH_FILTER",
-    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS"};
+    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS", "OFPS_HIP_SAD_SPLIT"};
 
 }  // namespace ofps
 

@@ -146,10 +146,10 @@ struct Push {
     int search() {
         PipeStream& ps = ctx->pipe;
         hipStream_t s = ctx->stream;
-        d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_PIPE_ENTRIES, kTickets * f.nblk * sizeof(float4)));
+        d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_PIPE_ENTRIES, kTickets * f.capacity() * sizeof(float4)));
         d_out = static_cast<char*>(ofps::scratch(ctx, ofps::S_PIPE_OUT, kTickets * kPipeOutBytes));
         if (!d_ent || !d_out) return OFPS_HIP_ENOMEM;
-        d_ent += (size_t)tix * f.nblk; d_out += (size_t)tix * kPipeOutBytes;
+        d_ent += (size_t)tix * f.capacity(); d_out += (size_t)tix * kPipeOutBytes;
         int rc = f.reserve(ctx, tix, kTickets);          // S_GATE_FLAGS per ticket: the detector may still read ticket k's count while ticket k + 1 compacts
         if (rc != OFPS_HIP_OK) return rc;
         if (f.gate > 0 || f.intra > 0) {
@@ -182,7 +182,7 @@ struct Push {
         void* mapped = nullptr;
         out = ofps::device_address_of(t->pinned, &mapped) ? static_cast<PipeOut*>(mapped) : reinterpret_cast<PipeOut*>(d_out);
         const ofps::TailSide side{ps.aux_stream, f.on() ? ps.fork : ps.slot_read[prev_slot], /*recorded=*/!f.on(), ps.join};
-        return ofps::frame_tail_device(ctx, d_ent, f.nblk, 1, f.kept(), /*lsq_min_n=*/3, prm, prm->seed, /*may_compensate=*/true, out->r.result,
+        return ofps::frame_tail_device(ctx, d_ent, f.capacity(), 1, f.kept(), /*lsq_min_n=*/3, prm, prm->seed, /*may_compensate=*/true, out->r.result,
                                        reinterpret_cast<float4*>(out->r.quat), reinterpret_cast<float2*>(d_out + kPipeField), &side, &dim, &t->isl);
     }
 
@@ -192,7 +192,7 @@ struct Push {
         if ((prm->run_detector || prm->run_estimator) && out == reinterpret_cast<PipeOut*>(d_out)) rc = ofps::read_back_device(ctx, t->pinned, d_out, kPipeOutPlain, s);
         if (rc == OFPS_HIP_OK && f.on())                             // the kept count travels in the ticket's page-locked block
             rc = ofps::read_back_device(ctx, static_cast<PipeOut*>(t->pinned)->kept, f.kept(), sizeof(uint32_t), s);
-        if (rc == OFPS_HIP_OK && out_entries && f.nblk) rc = ofps::read_back_device(ctx, out_entries, d_ent, f.nblk * sizeof(float4), s);
+        if (rc == OFPS_HIP_OK && out_entries && f.nblk) rc = ofps::read_back_device(ctx, out_entries, d_ent, f.capacity() * sizeof(float4), s);
         if (rc == OFPS_HIP_OK && out_field && prm->run_detector)
             rc = ofps::read_back_device(ctx, out_field, d_out + kPipeField, (size_t)dim * dim * sizeof(float2), s);
         return rc;
@@ -200,7 +200,7 @@ struct Push {
 
     int commit(int* ticket) {
         OFPS_HIP_TRY(ctx, hipEventRecord(t->done, ctx->stream));
-        t->have_vectors = frame_no > 0; t->n_vectors = frame_no > 0 ? f.nblk : 0; t->gated = frame_no > 0 && f.on();
+        t->have_vectors = frame_no > 0; t->n_vectors = frame_no > 0 ? f.capacity() : 0; t->gated = frame_no > 0 && f.on();
         t->run_detector = prm->run_detector; t->run_estimator = prm->run_estimator;
         *ticket = ctx->pipe.ring.commit();
         return OFPS_HIP_OK;
@@ -239,7 +239,7 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
     Push p{ctx, prm, {{nullptr, nullptr, 0, 0, W, H, (W + 63) & ~63}, 1, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
-                      ctx->opt.sad_median, ctx->opt.sad_intra, ctx->opt.sad_cut, /*want_triples=*/false}};
+                      ctx->opt.sad_median, ctx->opt.sad_intra, ctx->opt.sad_cut, /*want_triples=*/false, ctx->opt.sad_split}};
     rc = p.claim();                                     // refused before anything is uploaded
     if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
     if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)

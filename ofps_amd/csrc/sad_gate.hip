@@ -173,6 +173,13 @@ int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     if (rc == OFPS_HIP_OK && intra > 0) rc = sad_intra_check(ctx, block, intra, cut, who);
     if (rc == OFPS_HIP_OK && intra == 0 && (cut < 0 || cut > kSadCutMax)) rc = set_error(ctx, OFPS_HIP_EINVAL, "%s: scene cut %d outside [0, %d]", who, cut, kSadCutMax);
     if (rc != OFPS_HIP_OK) return rc;
+    if (split > 0) {                                          // N1s: one pair, integer vectors, the sub-blocks' candidates inside the key's fields
+        const int reach = sad_hier_reach(range, ctx->opt.sad_levels);
+        if ((rc = sad_split_check(ctx, block, reach < 0 ? kSadHierMaxReach + 1 : reach, split, who)) != OFPS_HIP_OK) return rc;
+        OFPS_REQUIRE(ctx, pairs == 1, "%s: split blocks take one pair at a time (%d pairs)", who, pairs);
+        if (ctx->opt.sad_motion_scale == 4)
+            return set_error(ctx, OFPS_HIP_EUNSUPPORTED, "%s: split blocks (threshold %d) have no quarter-pel form: motion scale 4 needs threshold 0", who, split);
+    } else if (split < 0) return set_error(ctx, OFPS_HIP_EINVAL, "%s: split threshold %d is negative", who, split);
     OFPS_REQUIRE(ctx, fr.W > 0 && fr.H > 0 && fr.stride >= fr.W, "%s: bad geometry W=%d H=%d stride=%d", who, fr.W, fr.H, fr.stride);
     OFPS_REQUIRE(ctx, pairs >= 1 && pairs <= 65535, "%s: %d pairs outside [1, 65535]", who, pairs);
     nblk = ofps_hip_sad_block_count(fr.W, fr.H, block);
@@ -208,6 +215,14 @@ int SadFilter::reserve(ofps_hip_ctx* ctx, int tix, int tickets) {
         if (!ia) return OFPS_HIP_ENOMEM;
         d_act = reinterpret_cast<uint32_t*>(ia + tix * ibytes);
         d_intra_counts = reinterpret_cast<uint32_t*>(ia + tix * ibytes + abytes);
+    }
+    if (split > 0 && nblk) {
+        auto* sp = static_cast<char*>(scratch(ctx, S_SPLIT, sad_split_bytes(nblk)));
+        if (!sp) return OFPS_HIP_ENOMEM;
+        d_split_raw = reinterpret_cast<float4*>(sp);
+        d_sub_best = reinterpret_cast<int*>(sp + nblk * 4 * sizeof(float4));
+        d_slot_flags = reinterpret_cast<uint8_t*>(d_sub_best + 12 * nblk);
+        d_split = d_slot_flags + 4 * nblk;
     }
     // the records' triples: the forward search's integer winners themselves when they are kept and nothing refines them
     if (want_triples) d_triples = winners() && ctx->opt.sad_motion_scale != 4 ? d_fwd : static_cast<int*>(scratch(ctx, S_GATE_BEST, tri));
@@ -264,6 +279,7 @@ int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_
     uint8_t* flags = median > 0 ? d_med_keep : keep();
     // a cut item loses every flag: gate and intra verdicts alone decide that, whatever check and median test said since
     if (intra > 0 && (rc = sad_cut_device(ctx, d_intra_counts, nblk, cut, flags, ctx->stream, pairs)) != OFPS_HIP_OK) return rc;
+    if (split > 0) return finish_split(ctx, criteria() ? flags : nullptr, d_out, d_out_best, d_count);
     // The compaction is the one step that keeps a path per shape.  compact_items_kernel runs ONE workgroup per item whatever nblk: right for a
     // batch of small lattices, but one pair through it would scan a 4K frame's 129,600 blocks on one compute unit, and in one launch where the
     // paths below take up to three.  That would change speed and launch count; the one-pair path stays on the grid-wide compactions of mask.hip
@@ -283,12 +299,36 @@ int SadFilter::finish(ofps_hip_ctx* ctx, float4* d_out, int* d_out_best, uint32_
     return OFPS_HIP_OK;
 }
 
+// N1s behind the criteria's final flags (null: every block is kept): the split step over the frames the integer search read -> raw slots
+// 4 * blk + s and their flags -> the one compaction, over 4 * nblk slots: block raster order, a split block's four records in sub-block
+// order, the count on the device.  The cut rule's veto has cleared the flags by now.  d_out_best: the PARENTS' triples of the kept blocks
+int SadFilter::finish_split(ofps_hip_ctx* ctx, const uint8_t* flags, float4* d_out, int* d_out_best, uint32_t* d_count) {
+    // mean removal: the search filtered its pair into scratch that, with the check on, the backward search has since rewritten; the step
+    // filters the pair itself either way (one more filter pass, only with both settings on)
+    SadFrames s = fr;
+    int rc = OFPS_HIP_OK;
+    if (ctx->opt.sad_prefilter > 0 && (rc = sad_prefilter_pairs_device(ctx, ctx->opt.sad_prefilter, fr, 1, &s)) != OFPS_HIP_OK) return rc;
+    rc = sad_split_device(ctx, s, 1, block, sad_hier_reach(range, ctx->opt.sad_levels), split, d_fwd, flags, d_sub_best, d_split, d_split_raw, d_slot_flags);
+    if (rc != OFPS_HIP_OK) return rc;
+    // (four slots per block: a 1080p frame's 32,160 slots are past the size one workgroup scans well; the grid-wide compaction takes over earlier)
+    rc = 4 * nblk <= kCompactSmallMax / 4 ? compact_small_device(ctx, d_split_raw, d_slot_flags, 4 * nblk, d_out, d_count)
+                                          : compact_entries_device(ctx, d_split_raw, d_slot_flags, 4 * nblk, d_out, d_count);
+    if (rc != OFPS_HIP_OK || !d_out_best) return rc;
+    if (!flags) {
+        OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_out_best, d_triples, nblk * 3 * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+        return OFPS_HIP_OK;
+    }
+    hipLaunchKernelGGL(compact_best_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_triples, flags, (uint32_t)nblk, d_out_best);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
 // `pairs` pairs of `f`, everything on ctx->stream: search[es], [contrast flags and / or activities of the current frames,] [the intra test's flags,] [the check's flags,] [the median test's
 // flags,] one compaction, one count per pair.  Item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k]
 // is their number
 int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
-                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets, int intra, int cut) {
-    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, intra, cut, d_out_best != nullptr};
+                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets, int intra, int cut, int split) {
+    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, intra, cut, d_out_best != nullptr, split};
     int rc = flt.plan(ctx, who);
     if (rc == OFPS_HIP_OK) rc = flt.reserve(ctx, tix, tickets);
     if (rc == OFPS_HIP_OK) rc = flt.search(ctx, d_out);

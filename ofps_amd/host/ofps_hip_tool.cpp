@@ -1,6 +1,7 @@
 // ofps_hip_tool -- small CLI over the C++ host layer; the counterparts of the reference's non-GUI callers:
 //   extract <decoder> <arg> <out.mvec> [max_frames [Name=value[@frame] ...]]     motion-extract/src/main.rs:7-38 (decode -> .mvec); properties set by name,
-//                                                                               e.g. hip_sad: "Block size", "Search range", "Exact pruning", "Quarter pel"=true|false
+//                                                                               e.g. hip_sad: "Block size", "Search range", "Exact pruning", "Quarter pel"=true|false,
+//                                                                               "Split blocks"=T (then a frame holds between nblk and 4 * nblk vectors)
 //   detect  <decoder> <arg> [max_frames]                detection loop, ofps-suite/src/app/detection.rs:92-168
 //   detect  --config <saved.json> [--perf-csv <dir>] [--islands-csv <file>] [max_frames]     (--islands-csv: "Max islands" > 0 in the config)
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):

@@ -104,6 +104,11 @@ void HipContext::check(int rc) const {
 }
 
 // ------------------------------------------------------------------ hip_sad
+size_t sad_record_floats(size_t records) {
+    if (records > std::vector<float>().max_size() / 4) throw Error("hip_sad: a buffer of " + std::to_string(records) + " records is too large");
+    return 4 * records;
+}
+
 HipSadDecoder::HipSadDecoder(std::unique_ptr<std::istream> input, size_t width, size_t height, std::optional<double> fps,
                              int device)
     : ctx_(device), in_(std::move(input)), w_(width), h_(height), fps_(fps) {
@@ -133,14 +138,14 @@ bool HipSadDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_f
         out_frame->reserve(bytes);
         for (size_t i = 0; i < bytes; ++i) out_frame->push_back(RGBA{frame_[i], frame_[i], frame_[i], 255});
     }
-    const size_t nblk = ofps_hip_sad_block_count((int)w_, (int)h_, (int)block_);
-    out_.resize(4 * nblk);
     ofps_hip_frame_params prm{};
     prm.block = (int)block_;
     prm.range = (int)range_;
     ofps_hip_frame_result res{};
     ctx_.check(ofps_hip_set_sad_mode(ctx_.get(), pruned_ ? OFPS_HIP_SAD_PRUNED : OFPS_HIP_SAD_EXHAUSTIVE));
     ctx_.check(ofps_hip_set_sad_motion_scale(ctx_.get(), quarter_pel_ ? 4 : 1));
+    ctx_.check(ofps_hip_set_sad_split(ctx_.get(), (int)split_));
+    out_.resize(sad_record_floats(ofps_hip_sad_record_capacity(ctx_.get(), (int)w_, (int)h_, (int)block_)));   // nblk records, 4 * nblk with "Split blocks" on
     ctx_.check(ofps_hip_push_frame(ctx_.get(), frame_, (int)w_, (int)h_, (int)w_, &prm, &res, out_.data(), nullptr));
     if (!res.have_vectors) return false;                              // first frame: no pair yet
     const size_t base = field.size();
@@ -152,7 +157,10 @@ bool HipSadDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_f
 std::vector<std::pair<std::string, PropertyMut>> HipSadDecoder::props_mut() {
     return {{"Block size", PropertyMut::usize(&block_, 8, 16)}, {"Search range", PropertyMut::usize(&range_, 8, 32)},
             {"Exact pruning", PropertyMut::boolean(&pruned_)},        // same vectors; faster on smooth camera motion
-            {"Quarter pel", PropertyMut::boolean(&quarter_pel_)}};    // motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
+            {"Quarter pel", PropertyMut::boolean(&quarter_pel_)},     // motion_scale 4: H.264's sub-pel vectors (include/ofps_hip.h N1q)
+            // build-defined: 0 = off, T (sixteenths of a grey level per pixel) = a block whose four sub-blocks together match better by at
+            // least T yields their four vectors in its place: a variable number of vectors per frame (include/ofps_hip.h N1s); not with "Quarter pel"
+            {"Split blocks", PropertyMut::usize(&split_, 0, kSadSplitMax)}};
 }
 
 // ------------------------------------------------------------------ hip_lk

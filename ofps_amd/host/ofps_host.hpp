@@ -138,6 +138,9 @@ private:
 
 // ---- plugins on the HIP path
 // "hip_sad": raw 8-bit luma frames (W*H bytes, back to back) from a stream -> MotionEntry per block.
+constexpr size_t kSadSplitMax = 4080;      // "Split blocks": sixteenths of a grey level per pixel (include/ofps_hip.h N1s)
+size_t sad_record_floats(size_t records);  // the floats of a buffer of `records` motion records; throws Error when that many cannot be held
+
 class HipSadDecoder : public Decoder {
 public:
     HipSadDecoder(std::unique_ptr<std::istream> input, size_t width, size_t height, std::optional<double> fps, int device = 0);
@@ -152,6 +155,7 @@ private:
     size_t w_, h_, block_ = 16, range_ = 16;
     bool pruned_ = false;                  // OFPS_HIP_SAD_PRUNED: identical vectors, content-dependent run time
     bool quarter_pel_ = false;             // ofps_hip_set_sad_motion_scale(4): quarter-pel refinement of every block vector
+    size_t split_ = 0;                     // ofps_hip_set_sad_split: 0 = off, T = a block that holds two motions yields its four sub-blocks' vectors (N1s)
     std::optional<double> fps_;
     uint8_t* frame_ = nullptr;             // page-locked staging buffer for the frame being read
     std::vector<float> out_;

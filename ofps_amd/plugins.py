@@ -84,6 +84,9 @@ class HipSadDecoder(Properties):
               # build-defined: 0 = off; P = a frame with at least P percent of its (gated) blocks intra yields no vector at all, as the
               # reference's decoder does on an intra frame.  No effect while "Intra test" is 0
               ("Scene cut", "usize", "scene_cut", 0, 100),
+              # build-defined: 0 = off; T (sixteenths of a grey level per pixel) = a kept block whose four sub-blocks together match better
+              # than the block by at least T yields their four vectors in its place (include/ofps_hip.h N1s); not with "Quarter pel"
+              ("Split blocks", "usize", "split_blocks", 0, 4080),
               # build-defined as well: 0 = off; N = only blocks whose forward-backward round trip misses by less than N pixels (1 = exact;
               # include/ofps_hip.h N1c).  Costs a second search per frame
               # build-defined: 0 = the search compares the frames as they are; r = both frames minus their box mean of radius r, for streams
@@ -108,6 +111,7 @@ class HipSadDecoder(Properties):
         self.median_test = 0
         self.intra_test = 0
         self.scene_cut = 0
+        self.split_blocks = 0
         self.levels = 1
         self.neighbour_predictors = False
         self.prefilter = 0
@@ -153,6 +157,7 @@ class HipSadDecoder(Properties):
         self.ctx.set_sad_median(self.median_test)
         self.ctx.set_sad_intra(self.intra_test)
         self.ctx.set_sad_cut(self.scene_cut)
+        self.ctx.set_sad_split(self.split_blocks)
         self.ctx.set_sad_levels(self.levels)
         self.ctx.set_sad_predictors(1 if self.neighbour_predictors else 0)
         self.ctx.set_sad_prefilter(self.prefilter)

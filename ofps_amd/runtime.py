@@ -307,6 +307,63 @@ class HipContext:
                                                           search_range, min_pixels, limit, median, intra, cut, C.c_void_p(d_out_entries),
                                                           C.c_void_p(d_out_best or 0), C.c_void_p(d_out_counts)))
 
+    def set_sad_split(self, threshold: int):
+        """hip_sad's split blocks (include/ofps_hip.h N1s): 0 = off (default); T in [1, 4080] (sixteenths of a grey level per pixel) = a kept
+        block whose four sub-blocks together match better than the block by at least T yields their four records in its place (sad_flow,
+        push_frame[_async]); the record buffers then hold sad_record_capacity() = 4 * nblk records."""
+        self._check(self._lib.ofps_hip_set_sad_split(self._h, threshold))
+
+    def get_sad_split(self) -> int:
+        return int(self._lib.ofps_hip_get_sad_split(self._h))
+
+    def sad_record_capacity(self, W: int, H: int, block: int) -> int:
+        """The records a search call of this context may return: nblk, 4 * nblk with split blocks on."""
+        if "ofps_hip_sad_record_capacity" not in _lib.PROTOTYPES:      # a tool's --lib run against a build from before N1s: one record per block
+            return int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        return int(self._lib.ofps_hip_sad_record_capacity(self._h, W, H, block))
+
+    def sad_split(self, prev: np.ndarray, cur: np.ndarray, block: int, best: np.ndarray, keep: np.ndarray | None, reach: int, threshold: int,
+                  want_entries=True, stride: int | None = None) -> dict:
+        """The split step alone on a [nblk, 3] array of parent (dx, dy, sad) triples and keep bytes (None = all ones) -> dict(sub_best int32
+        [nblk, 4, 3], split uint8 [nblk], entries float32 [nblk, 4, 4] | None, slot_flags uint8 [nblk, 4] | None).  stride: None, or the row
+        pitch in bytes of both frames (views of wider buffers)."""
+        if stride is None:
+            prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
+            stride = prev.shape[1]
+        else:
+            for g in (prev, cur):
+                assert g.dtype == np.uint8 and g.ndim == 2 and (g.shape[0] == 1 or g.strides[0] == stride) and g.strides[1] == 1
+        assert prev.shape == cur.shape and prev.ndim == 2
+        H, W = prev.shape
+        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        b = np.ascontiguousarray(best, np.int32)
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        assert b.shape == (nb, 3) and (k is None or k.shape == (nb,))
+        sub = np.zeros((max(nb, 1), 4, 3), np.int32)
+        split = np.zeros(max(nb, 1), np.uint8)
+        ent = np.zeros((max(nb, 1), 4, 4), np.float32) if want_entries else None
+        slot = np.zeros((max(nb, 1), 4), np.uint8) if want_entries else None
+        u8, i32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_sad_split(self._h, C.cast(C.c_void_p(prev.ctypes.data), u8), C.cast(C.c_void_p(cur.ctypes.data), u8), W, H,
+                                                 stride, block, b.ctypes.data_as(i32), None if k is None else k.ctypes.data_as(u8), reach, threshold,
+                                                 sub.ctypes.data_as(i32), split.ctypes.data_as(u8), _fp(ent) if want_entries else None,
+                                                 slot.ctypes.data_as(u8) if want_entries else None))
+        return {"sub_best": sub[:nb], "split": split[:nb], "entries": ent[:nb] if want_entries else None,
+                "slot_flags": slot[:nb] if want_entries else None}
+
+    def sad_split_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, d_best: int, d_keep: int | None, reach: int,
+                      threshold: int, d_out_sub_best: int, d_out_split: int, d_out_entries: int | None = None, d_out_slot_flags: int | None = None):
+        self._check(self._lib.ofps_hip_sad_split_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, C.c_void_p(d_best),
+                                                     C.c_void_p(d_keep or 0), reach, threshold, C.c_void_p(d_out_sub_best), C.c_void_p(d_out_split),
+                                                     C.c_void_p(d_out_entries or 0), C.c_void_p(d_out_slot_flags or 0)))
+
+    def sad_flow_split_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, block: int, search_range: int, min_pixels: int, limit: int,
+                           median: int, threshold: int, d_out_entries: int, d_out_count: int):
+        """One pair in device memory: search + gate / check / median test (0 = off each) + split blocks (threshold in [1, 4080]) + one
+        compaction; d_out_entries holds 4 * nblk records, d_out_count one uint32.  Enqueue only."""
+        self._check(self._lib.ofps_hip_sad_flow_split_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, block, search_range,
+                                                          min_pixels, limit, median, threshold, C.c_void_p(d_out_entries), C.c_void_p(d_out_count)))
+
     def set_sad_levels(self, levels: int):
         """hip_sad's search levels (include/ofps_hip.h N1h): 1 = the plain search (default); 2 | 3 = the search runs on the frames halved
         levels - 1 times and every finer level repairs the doubled vectors in a +-3 window: reach 2 * range + 3, 4 * range + 9."""
@@ -424,12 +481,23 @@ class HipContext:
         return int(n.value)
 
     def sad_flow(self, prev: np.ndarray, cur: np.ndarray, block: int, search_range: int, want_best=False):
-        """-> records [n, 4] (and (dx, dy, SAD) triples [n, 3]): n = one per lattice block, or the kept blocks with the contrast gate and / or
-        the consistency check on"""
+        """-> records [n, 4] (and (dx, dy, SAD) triples [m, 3]): n = m = one per lattice block, or the kept blocks with the contrast gate and / or
+        the consistency check on.  With split blocks on (N1s) n lies between kept and 4 * kept and the triples stay the kept PARENTS', m = kept
+        (their number is not returned by the library: m = nblk unless a criterion drops blocks, when the caller counts them)"""
         prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
         assert prev.shape == cur.shape and prev.ndim == 2
         H, W = prev.shape
         nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        cap = self.sad_record_capacity(W, H, block)
+        if cap != nb:
+            ent = np.zeros((max(cap, 1), 4), np.float32)
+            best = np.zeros((max(nb, 1), 3), np.int32)
+            n_out = C.c_size_t(0)
+            self._check(self._lib.ofps_hip_sad_flow(self._h, prev.ctypes.data_as(C.POINTER(C.c_uint8)), cur.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, W,
+                                                    block, search_range, _fp(ent), best.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out)))
+            n = int(n_out.value)
+            assert n <= cap
+            return (ent[:n], best[:nb]) if want_best else ent[:n]
         ent = np.zeros((max(nb, 1), 4), np.float32)
         best = np.zeros((max(nb, 1), 3), np.int32)
         n_out = C.c_size_t(0)
@@ -987,7 +1055,7 @@ class HipContext:
                                aspect, fov_y_deg, int(use_ransac), num_iters, inlier_deg, num_samples, seed)
         res = _lib.FrameResult()
         islands = self._ticket_islands(detector)
-        nb = int(self._lib.ofps_hip_sad_block_count(W, H, block))
+        nb = self.sad_record_capacity(W, H, block) if want_entries else 0      # 4 * nblk with split blocks on (N1s)
         ent = np.zeros((max(nb, 1), 4), np.float32) if want_entries else None
         dim = self.block_dim(min_size, subdivide)
         fld = np.zeros((dim, dim, 2), np.float32) if want_field else None

@@ -22,6 +22,8 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               --sad-consistency C also hip_sad_cv<N>: on top of "Consistency check" = C
               with --sad-intra Q [Q ...] also hip_sad_i<Q>: hip_sad with its "Intra test" property at Q (include/ofps_hip.h N1i); --sad-cut P sets
               "Scene cut" = P in those columns; with --sad-prefilter R also hip_sad_fi<Q>: on top of "Mean removal" = R (the first R)
+              with --sad-split T [T ...] also hip_sad_b<T>: hip_sad with its "Split blocks" property at T (include/ofps_hip.h N1s); with
+              --sad-median N also hip_sad_xb<T>: on top of "Median test" = N (the first N)
   cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
               cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
@@ -166,7 +168,7 @@ CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
 
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
         fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
-        cut_clip=False):
+        cut_clip=False, sad_split=()):
     from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -216,6 +218,11 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
         if sad_prefilter:           # ... and on top of "Mean removal" at the first --sad-prefilter radius: filtered SAD against raw activity
             props_fi = dict(props_i, **{"Mean removal": sad_prefilter[0]})
             combos[2:2] = [(f"hip_sad_fi{ratio}", HipSadDecoder, False, props_fi), (f"hip_sad_fi{ratio}", HipSadDecoder, True, props_fi)]
+    for thr in sad_split:           # hip_sad with its "Split blocks" property at T (include/ofps_hip.h N1s); with --sad-median N also on top of "Median test" at the first N
+        combos[2:2] = [(f"hip_sad_b{thr}", HipSadDecoder, False, {"Split blocks": thr}), (f"hip_sad_b{thr}", HipSadDecoder, True, {"Split blocks": thr})]
+        if sad_median:
+            props_xb = {"Median test": sad_median[0], "Split blocks": thr}
+            combos[2:2] = [(f"hip_sad_xb{thr}", HipSadDecoder, False, props_xb), (f"hip_sad_xb{thr}", HipSadDecoder, True, props_xb)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
     res = {}
@@ -289,7 +296,8 @@ def table(res):
     radii = sorted({int(k.split("+")[0].rsplit("m", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_m", "hip_sad_hm"))})
     limits = sorted({int(k.split("+")[0].rsplit("v", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_v", "hip_sad_cv"))})
     ratios = sorted({int(k.split("+")[0].rsplit("i", 1)[1]) for r in res.values() for k in r if k.startswith("hip_sad_i")})
-    for tag in tuple(f"hip_sad_{t}{ratio}" for ratio in reversed(ratios) for t in ("fi", "i")) + tuple(f"hip_sad_{t}{limit}" for limit in reversed(limits) for t in ("cv", "v")) + (
+    splits = sorted({int(k.split("+")[0].rsplit("b", 1)[1]) for r in res.values() for k in r if k.startswith(("hip_sad_b", "hip_sad_xb"))})
+    for tag in tuple(f"hip_sad_{t}{thr}" for thr in reversed(splits) for t in ("xb", "b")) + tuple(f"hip_sad_{t}{ratio}" for ratio in reversed(ratios) for t in ("fi", "i")) + tuple(f"hip_sad_{t}{limit}" for limit in reversed(limits) for t in ("cv", "v")) + (
             "hip_sad_c", "hip_sad_qc", "hip_sad_h", "hip_sad_qh", "hip_sad_hp", "hip_sad_hpc", "hip_sad_qhp") + tuple(
             f"hip_sad_{t}{radius}" for radius in reversed(radii) for t in ("hm", "m")):
         if any(tag + "+lsq" in r for r in res.values()):
@@ -361,6 +369,8 @@ def main():
                     help="add the hip_sad_v<N> columns (hip_sad with \"Median test\" = N; with --sad-consistency C also hip_sad_cv<N>: on top of \"Consistency check\")")
     ap.add_argument("--sad-intra", nargs="*", type=int, default=[], metavar="Q",
                     help="add the hip_sad_i<Q> columns (hip_sad with \"Intra test\" = Q sixteenths; --sad-cut P sets \"Scene cut\" = P in them)")
+    ap.add_argument("--sad-split", nargs="*", type=int, default=[], metavar="T",
+                    help="add the hip_sad_b<T> columns (hip_sad with \"Split blocks\" = T sixteenths; with --sad-median N also hip_sad_xb<T>: on top of \"Median test\" = N)")
     ap.add_argument("--sad-cut", type=int, default=0, metavar="P", help="\"Scene cut\" of the hip_sad_i<Q> columns, percent (0 = off)")
     ap.add_argument("--cut-clip", action="store_true", help="add pan_0.2_cut: pan_0.2 with the second half of its frames from another canvas seed")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
@@ -369,7 +379,7 @@ def main():
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
               sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
-              sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip)
+              sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split))
     txt = table(res)
     print(txt)
     if args.out:

@@ -2,7 +2,9 @@
 """BASELINE configs[4]: 1080p@60 live stream over TCP, SAD decoder + block-motion detector + Almeida estimator
 fused per frame (ofps_hip_push_frame); steady-state latency = frame fully received -> island + quaternion on the
 host.  The feeder thread paces raw luma frames (8-byte header: u32 W, u32 H, then W*H bytes) through a loop-back
-socket, the way ofps::utils::open_file("tcp://...") feeds a decoder (ofps/src/utils.rs:92-118).  Prints JSON."""
+socket, the way ofps::utils::open_file("tcp://...") feeds a decoder (ofps/src/utils.rs:92-118).  Prints JSON.
+--split T: hip_sad's split blocks at threshold T (include/ofps_hip.h N1s); --lib <libofps_hip.so>: another build of the library (a build
+from before a feature runs without that feature's entry points)."""
 import argparse
 import json
 import os
@@ -15,6 +17,13 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if "--lib" in sys.argv:
+    import ctypes
+    import torch  # noqa: E402,F401  (before the library: both then share one HIP runtime, as ofps_amd._lib.load does)
+    from ofps_amd import _lib  # noqa: E402
+    _lib.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
+    for _name in [n for n in _lib.PROTOTYPES if not hasattr(ctypes.CDLL(_lib.LIB_PATH), n)]:
+        _lib.PROTOTYPES.pop(_name)
 from ofps_amd import synth  # noqa: E402
 from ofps_amd.runtime import HipContext  # noqa: E402
 
@@ -36,6 +45,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--ransac", action="store_true")
+    ap.add_argument("--split", type=int, default=0, metavar="T")
+    ap.add_argument("--lib", default=None)
     args = ap.parse_args()
     W, H = args.width, args.height
     clip = synth.luma_sequence(16, W, H, max_step=16)            # looped
@@ -57,6 +68,8 @@ def main():
     th = threading.Thread(target=feeder, daemon=True); th.start()
     sock = socket.create_connection(("127.0.0.1", port))
     ctx = HipContext(0)
+    if args.split:
+        ctx.set_sad_split(args.split)
     # the receive buffer IS the page-locked staging buffer (recv_into writes the frame where the DMA engine reads it):
     # no host copy, no pageable-memory staging inside hipMemcpy
     pinned = ctx.pinned_frame(H, W)
@@ -79,7 +92,8 @@ def main():
                                 f"({'RANSAC' if args.ransac else 'LSQ'}) per frame", "frames": args.frames,
                       "latency_ms": {"p50": round(float(np.percentile(lat, 50)), 3), "p90": round(float(np.percentile(lat, 90)), 3),
                                      "p99": round(float(np.percentile(lat, 99)), 3), "max": round(float(lat.max()), 3)},
-                      "frame_budget_ms": round(1e3 / args.fps, 2), "frames_with_motion_island": int(islands)}))
+                      "frame_budget_ms": round(1e3 / args.fps, 2), "frames_with_motion_island": int(islands), "split_blocks": args.split,
+                      "library": args.lib or "in-tree"}))
 
 
 if __name__ == "__main__":
