@@ -599,6 +599,13 @@ int ofps_hip_contrast_mask_dev(ofps_hip_ctx* ctx, const void* d_gray, int W, int
                                         conversion, mask and flow -- which therefore run on the ~150 x 84 frame -- and every unmasked
                                         pixel of that REDUCED frame is one record at ((x+.5)/gw, (y+.5)/gh) in raster order; no densifier.
                                         Excludes OFPS_HIP_LK_FULLRES_RECORDS. */
+#define OFPS_HIP_FLOW_SPARSE     32u /* "hip_klt" (N3 below) in place of the flow, mask and output stage: levels, radius and iters mean L, w and K;
+                                        out_w x out_h is the cell lattice of the frames the tracker reads and the capacity its slot count;
+                                        max_w / max_h are ignored unless OFPS_HIP_LK_REDUCED is set.  Frame formats, OFPS_HIP_LK_REDUCED,
+                                        the two tickets in flight, ofps_hip_lk_reset and the fused forms stay as they are; a ticket follows
+                                        the ofps_hip_set_klt values the context has when it is pushed.  Excludes OFPS_HIP_LK_CONTRAST_MASK,
+                                        OFPS_HIP_LK_FULLRES_RECORDS, OFPS_HIP_FLOW_FARNEBACK and OFPS_HIP_FLOW_USE_PREVIOUS
+                                        (OFPS_HIP_EINVAL before anything is uploaded) */
 /* The frames' pixel format, bits 8-9 of `flags` (one of the OFPS_HIP_FMT_* values below shifted left by 8; 0 = 8-bit luma, this build's
  * raw-stream input).  With a colour format `stride` is the row pitch in BYTES (>= W * channels) and every frame goes through
  * cvt_color(.., COLOR_BGR2GRAY)'s integer formula (cv-decoder/src/lib.rs:135) behind its upload -- after the resize when
@@ -664,6 +671,61 @@ int ofps_hip_farneback_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
  * pyramid and polynomial expansion are kept on the device and only the new frame goes through them (same results, bit for bit).
  * Diagnostics: how many calls of this context found the first frame's expansion already there. */
 int ofps_hip_flow_cache_hits(ofps_hip_ctx* ctx, uint64_t* count);
+/* ---- N3: sparse Lucas-Kanade on per-cell corner features ("hip_klt" Decoder; csrc/klt.hip) ----
+ * Between hip_sad's block vectors and the dense flows: sub-pixel vectors at one well-chosen point per lattice cell.  Build-defined (the
+ * reference has no counterpart; its report names sparse optical flow as future work).  Every sum over pixels is an exact integer and the
+ * few f64 operations are scalar and in a fixed order, so the result does not depend on a reduction order: bit-exact against the NumPy
+ * restatement tests/indep_klt.py.  Integers are signed 64-bit unless a smaller range is stated.
+ * Settings of the context (ofps_hip_set_klt): cell C in {8, 16, 32} (16), score_radius r in [1, 3] (2), min_score in [1, 2^31 - 1] (1),
+ *   min_eig e in [1, 65535] (1), max_residual R in [0, 4080], 0 = off (0).  Per call: levels L in [1, 6], radius w in [1, 7], iters K in
+ *   [1, 30]; window side n = 2w + 1.  Frames: 8-bit luma, W x H with W >> (L - 1) >= 8 and H >> (L - 1) >= 8, stride >= W.  Anything else is
+ *   OFPS_HIP_EINVAL.
+ * Features (in prev): gradients = the 3 x 3 Sobel pair on integers (gx = right - left, gy = lower - upper, weights 1 2 1); a pixel is
+ *   admissible iff r + 1 <= x <= W - r - 2 and the same in y; a, b, c = the sums of gx*gx, gx*gy, gy*gy over its (2r + 1)^2 window;
+ *   D = (a - c)^2 + 4 b^2; score = a + c - ceil(sqrt(D)), the root exact.  The lattice has ceil(W / C) x ceil(H / C) cells from (0, 0), the
+ *   slot index is raster order.  A cell's feature = its admissible pixel of largest score, ties to the smallest y, then the smallest x; a
+ *   cell with no admissible pixel, or whose best score is below min_score, has none (status 1).
+ * Pyramid: both frames' levels are ofps_hip_sad_down2's (N1h), as they are.
+ * Sampling: positions are integers in 1/256 pixel, q = 256 i + f per axis (i = q >> 8, arithmetic); S(img, q) = (the sum of weight * pixel
+ *   + 128) >> 8 over the four pixels (i, i + 1) x (j, j + 1), weights (256 - fx)(256 - fy), fx (256 - fy), (256 - fx) fy, fx fy, pixel indices
+ *   clamped into the level's frame: no sample is ever refused; values carry 8 fractional bits.
+ * Tracking the feature (x, y): dq = (0, 0); for l = L - 1 .. 0:
+ *   centre cq = (((2x + 1) * 128) >> l) - 128, y alike;
+ *   template I = S(prev_l, cq + 256 (i, j)), i, j in [-w - 1, w + 1]; Ix = I(i + 1, j) - I(i - 1, j), Iy alike, on the n x n interior;
+ *     A11, A12, A22 = the sums of Ix*Ix, Ix*Iy, Iy*Iy;
+ *   flat test: T = e * n * n * 262144; in f64 X = (double)(A11 - T), Y = (double)(A22 - T), Z = (double)A12; the feature is flat (status 2)
+ *     unless X * Y >= Z * Z and X + Y >= 0;  det = (double)A11 * (double)A22 - Z * Z; det <= 0 is flat as well;
+ *   up to K iterations: the feature has left the frame (status 3) unless 0 <= 256 x + dqx * 2^l <= 256 (W - 1) and the same in y (tested at
+ *     level-0 scale); J = S(cur_l, cq + dq + 256 (i, j)) on the n x n window; b1 = sum (J - I) Ix, b2 = sum (J - I) Iy; in f64, in this order:
+ *     num_x = (double)A22 * (double)b1 - Z * (double)b2, u_x = (-512.0 * num_x) / det; u_y alike with (double)A11 * (double)b2 - Z * (double)b1;
+ *     uq = clamp(rint(u), -256 w, 256 w), round half even; dq += uq; stop when uq = (0, 0);
+ *   if l > 0: dq = 2 dq.
+ *   After level 0 the frame test once more, then res = sum |J - I| at the final dq; with R > 0, res > 16 R n n is a residual loss (status 4);
+ *   otherwise the feature is kept (status 0).  Statuses 1, 2 and 3 report dq = (0, 0) and res = 0; status 4 reports its dq and res.
+ * Records (cv-decoder's convention, as N2): pos = ((x + 0.5f) / W, (y + 0.5f) / H), motion = (((float)dqx / 256.0f) / W,
+ *   ((float)dqy / 256.0f) / H), f32 divisions; the kept slots' records come first, in slot order, and their count is made on the device.
+ * ofps_hip_klt_features[_dev]: one frame -> int32 (x, y, score) per slot, (-1, -1, 0) = no feature.
+ * ofps_hip_klt_track[_dev]: the pair, n caller-given points as int32 (x, y) -> int32 (dqx, dqy, res, status) per point; min_eig and
+ *   max_residual are the context's.  A point outside the frame: OFPS_HIP_EINVAL in the host form, status 3 in the _dev form (no access
+ *   out of bounds).
+ * ofps_hip_klt_flow[_dev]: the pair -> records (capacity: the slot count), their count (_dev: one uint32 in device memory) and, unless
+ *   NULL, the raw slots: int32 (x, y, score, dqx, dqy, status) per slot, (-1, -1, 0, 0, 0, 1) for a cell without a feature.
+ * The _dev forms enqueue on the context's stream and synchronise nothing.  OFPS_HIP_FLOW_SPARSE (above) runs the same chain inside the
+ * dense decoders' stream and fused forms. */
+int ofps_hip_set_klt(ofps_hip_ctx* ctx, int cell, int score_radius, int min_score, int min_eig, int max_residual);
+int ofps_hip_get_klt(ofps_hip_ctx* ctx, int32_t* cell, int32_t* score_radius, int32_t* min_score, int32_t* min_eig, int32_t* max_residual);   /* any may be NULL */
+size_t ofps_hip_klt_slot_count(int W, int H, int cell);      /* ceil(W / cell) * ceil(H / cell); 0 for an invalid cell */
+int ofps_hip_klt_features(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int32_t* out_triples /* 3 * slots */);
+int ofps_hip_klt_features_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, void* d_out_triples);
+int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points /* 2 * n */,
+                       size_t n, int levels, int radius, int iters, int32_t* out_quads /* 4 * n */);
+int ofps_hip_klt_track_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                           int levels, int radius, int iters, void* d_out_quads);
+int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
+                      float* out_entries /* 4 * slots */, uint32_t* n_out, int32_t* out_slots /* 6 * slots, or NULL */);
+int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                          void* d_out_entries, void* d_out_count /* one uint32 */, void* d_out_slots /* or NULL */);
+
 /* ---- A1-A4: MotionFieldDensifier ---- */
 int ofps_hip_densify(ofps_hip_ctx* ctx, const float* entries, size_t n, int w, int h,
                      float* out_field /* 2*w*h, cell (x,y) at 2*(y*w+x) */,

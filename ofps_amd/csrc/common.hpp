@@ -229,6 +229,9 @@ struct ofps_hip_ctx {
         int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
         int detect_islands = 0;          // OFPS_HIP_DETECT_ISLANDS / ofps_hip_set_detect_islands: 0 the fused entry points' detector answers for the largest island alone, K in [1, 6400] a ticket that runs the detector lists up to K islands as well (detect.hip, A5i)
+        // ofps_hip_set_klt: hip_klt's lattice cell (8 | 16 | 32), score window radius [1, 3], smallest score of a feature, smallest eigenvalue of
+        // a template's structure tensor per pixel [1, 65535], residual limit in sixteenths of a grey level per pixel (0 = off) (klt.hip, N3)
+        int klt_cell = 16, klt_score_radius = 2, klt_min_score = 1, klt_min_eig = 1, klt_max_residual = 0;
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -256,7 +259,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 59;
+    static constexpr int kNumScratch = 62;
     Scratch scratch[kNumScratch];
 };
 
@@ -297,9 +300,12 @@ enum ScratchSlot {
     S_INTRA,                // hip_sad's intra test (sad_intra.hip): [activity, u32 per block][candidate and intra counters, 2 x u32 per item], one per ticket in flight in the fused path
     S_ISL_WORK,             // the islands kernel (detect.hip, A5i): per item [qualifying roots' keys, u64][rank of every root, u16 per cell]
     S_ISL_OUT,              // ... and the blocks of a fused ticket or a host-pointer call ([counts][table][labels] per item), copied out behind the kernel on its stream
-    S_SPLIT                 // hip_sad's split step (sad_split.hip, N1s): [raw slots, 4 records per block][sub triples, 12 i32 per block][slot flags, 4 u8 per block][split flags, u8 per block].  Compute stream only, written anew by every search
+    S_SPLIT,                // hip_sad's split step (sad_split.hip, N1s): [raw slots, 4 records per block][sub triples, 12 i32 per block][slot flags, 4 u8 per block][split flags, u8 per block].  Compute stream only, written anew by every search
+    S_KLT_PYR,              // hip_klt (klt.hip, N3): both frames' pyramid levels above 0.  Compute stream only, written anew by every call
+    S_KLT_WORK,             // ... [features, 3 i32 per slot][raw records per slot][keep flags, u8 per slot], in front of the compaction
+    S_KLT_HOST              // ... the host-pointer forms' device-side inputs and outputs
 };
-static_assert(S_SPLIT < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_KLT_HOST < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -362,6 +368,14 @@ int sad_hier_reach(int range, int levels);                  // R_0, or -1
 int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
 int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int levels, int predictors, void* d_out_entries,
                           void* d_out_best);
+// one pyramid step of one frame (what ofps_hip_sad_down2_dev enqueues): W x H -> (W >> 1) x (H >> 1)
+int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int src_stride, uint8_t* dst, int dst_stride);
+// klt.hip (include/ofps_hip.h N3): hip_klt on one pair of device frames with the context's settings -- the kept records first, in slot order, and
+// their count in device memory; d_out holds ofps_hip_klt_slot_count records, d_slots (optional) 6 int32 per slot.  Enqueues on ctx->stream only
+// the decoder's limits on one call: levels, radius, iters, a frame of 8 .. 32768 pixels a side whose top level is at least 8 x 8, stride >= W
+int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who);
+int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                    float4* d_out, uint32_t* d_count, int* d_slots);
 // sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
 constexpr int kSadPrefilterMax = 16;
 int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,

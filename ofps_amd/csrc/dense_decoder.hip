@@ -21,6 +21,7 @@ struct DenseGrid {              // what a process_frame returns for this geometr
     bool farneback = false;     // OFPS_HIP_FLOW_FARNEBACK: the flow is farneback.hip's (the "hip_flow" decoder), not the iterative LK
     bool use_previous = false;  // OFPS_HIP_FLOW_USE_PREVIOUS: the stream's previous flow is the initial flow (cv-decoder/src/lib.rs:161-165)
     bool reduced = false;       // OFPS_HIP_LK_REDUCED: cv-decoder's "Process Fullres" = false (:124-133,274-276)
+    bool sparse = false;        // OFPS_HIP_FLOW_SPARSE: hip_klt (klt.hip) in place of flow, mask and output stage; the record grid is its cell lattice
     int fmt = OFPS_HIP_FMT_LUMA, cn = 1;      // the arriving frames' pixel format (bits 8-9 of the flags)
     bool frontend = false;      // the arriving frames are resized and / or converted behind their upload (frontend.hip)
     size_t raw_row = 0;         // bytes per row of the staged arriving frame (W * cn rounded up to 4)
@@ -28,7 +29,20 @@ struct DenseGrid {              // what a process_frame returns for this geometr
 };
 
 constexpr unsigned kDenseFlagBits = OFPS_HIP_LK_CONTRAST_MASK | OFPS_HIP_LK_FULLRES_RECORDS | OFPS_HIP_FLOW_FARNEBACK | OFPS_HIP_FLOW_USE_PREVIOUS |
-                                 OFPS_HIP_LK_REDUCED | OFPS_HIP_FRAME_FORMAT_MASK;
+                                 OFPS_HIP_LK_REDUCED | OFPS_HIP_FLOW_SPARSE | OFPS_HIP_FRAME_FORMAT_MASK;
+// max_w / max_h are not looked at by hip_klt on full-size frames
+inline bool dense_cap_ok(unsigned flags, int max_w, int max_h) {
+    return ((flags & OFPS_HIP_FLOW_SPARSE) && !(flags & OFPS_HIP_LK_REDUCED)) || (max_w >= 1 && max_h >= 1);
+}
+
+// hip_klt has no mask, no per-pixel records and no flow to carry over: refused in front of every other test of the flags
+int dense_sparse_flags(ofps_hip_ctx* ctx, unsigned flags, const char* who) {
+    constexpr unsigned excluded = OFPS_HIP_LK_CONTRAST_MASK | OFPS_HIP_LK_FULLRES_RECORDS | OFPS_HIP_FLOW_FARNEBACK | OFPS_HIP_FLOW_USE_PREVIOUS;
+    OFPS_REQUIRE(ctx, !(flags & OFPS_HIP_FLOW_SPARSE) || !(flags & excluded),
+                 "%s: OFPS_HIP_FLOW_SPARSE excludes OFPS_HIP_LK_CONTRAST_MASK, OFPS_HIP_LK_FULLRES_RECORDS, OFPS_HIP_FLOW_FARNEBACK and "
+                 "OFPS_HIP_FLOW_USE_PREVIOUS (flags 0x%x)", who, flags);
+    return OFPS_HIP_OK;
+}
 
 int dense_grid_of(ofps_hip_ctx* ctx, int W, int H, int stride, int max_w, int max_h, unsigned flags, int levels, int radius, int iters, const char* who,
                   DenseGrid* g) {
@@ -39,6 +53,25 @@ int dense_grid_of(ofps_hip_ctx* ctx, int W, int H, int stride, int max_w, int ma
     const bool fullres_records = flags & OFPS_HIP_LK_FULLRES_RECORDS;
     g->fmt = (int)((flags & OFPS_HIP_FRAME_FORMAT_MASK) >> 8);
     g->cn = ofps::frame_format_channels(g->fmt);
+    g->sparse = flags & OFPS_HIP_FLOW_SPARSE;
+    if (g->sparse) {
+        const int rc = dense_sparse_flags(ctx, flags, who);
+        if (rc != OFPS_HIP_OK) return rc;
+        OFPS_REQUIRE(ctx, stride >= W * g->cn, "dense decoder: stride %d < %d bytes per row (%d x %d channels)", stride, W * g->cn, W, g->cn);
+        g->fw = W; g->fh = H;
+        if (g->reduced) {
+            ofps::cv_grid(W, H, max_w, max_h, &g->fw, &g->fh);
+            OFPS_REQUIRE(ctx, g->fw >= 1 && g->fh >= 1, "dense decoder: the capped grid of %dx%d under (%d, %d) is empty", W, H, max_w, max_h);
+        }
+        const int rc_klt = ofps::klt_check_call(ctx, g->fw, g->fh, g->fw, levels, radius, iters, who);       // the frames the tracker reads, rows dense
+        if (rc_klt != OFPS_HIP_OK) return rc_klt;
+        const int cell = ctx->opt.klt_cell;
+        g->gw = (g->fw + cell - 1) / cell; g->gh = (g->fh + cell - 1) / cell;
+        g->max_records = (size_t)g->gw * g->gh;
+        g->frontend = g->reduced || g->fmt != OFPS_HIP_FMT_LUMA;
+        g->raw_row = ((size_t)W * g->cn + 3) & ~(size_t)3;
+        return OFPS_HIP_OK;
+    }
     OFPS_REQUIRE(ctx, !g->use_previous || g->farneback, "OFPS_HIP_FLOW_USE_PREVIOUS without OFPS_HIP_FLOW_FARNEBACK (the iterative LK has no initial flow across pairs)");
     OFPS_REQUIRE(ctx, !(g->reduced && fullres_records), "OFPS_HIP_LK_REDUCED with OFPS_HIP_LK_FULLRES_RECORDS: the reduced mode has no full-resolution flow");
     OFPS_REQUIRE(ctx, stride >= W * g->cn, "dense decoder: stride %d < %d bytes per row (%d x %d channels)", stride, W * g->cn, W, g->cn);
@@ -97,6 +130,8 @@ int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t*
     // tail_rec / tail_cnt (fused form): where a tail finds the records and their count in DEVICE memory -- rec_dst / cnt_dst, which the
     // caller then points at device scratch, or the compaction's own output, which is then not copied to rec_dst at all
     if (tail_rec) { *tail_rec = rec_dst; *tail_cnt = cnt_dst; }
+    // hip_klt: features, pyramid, track, flags, the ordered compaction and the count, straight to rec_dst / cnt_dst
+    if (g.sparse) return ofps::klt_flow_device(ctx, d_prev, d_cur, W, H, W, levels, radius, iters, rec_dst, cnt_dst, nullptr);
     const size_t px = (size_t)W * H, cells = g.per_pixel ? 1 : (size_t)g.gw * g.gh;
     auto* d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_ENTRIES, px * sizeof(float4)));
     auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_FIELD, cells * sizeof(float2)));
@@ -199,8 +234,9 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
                unsigned flags, const ofps_hip_frame_params* tail, int* ticket, const char* who) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, frame && ticket, "%s: null pointer", who);
-    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "%s: bad geometry", who);
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && dense_cap_ok(flags, max_w, max_h), "%s: bad geometry", who);
     OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "%s: unknown flags 0x%x", who, flags);
+    if (const int rc_sparse = dense_sparse_flags(ctx, flags, who)) return rc_sparse;
     int dim = 0;
     if (tail) {
         // refused before anything is uploaded, the stream's first frame (which runs no tail) included
@@ -369,7 +405,7 @@ int ofps_hip_lk_decode(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cu
                        int* out_w, int* out_h) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "lk_decode: null host pointer");
-    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && max_w >= 1 && max_h >= 1, "lk_decode: bad geometry");
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && dense_cap_ok(flags, max_w, max_h), "lk_decode: bad geometry");
     OFPS_REQUIRE(ctx, (flags & ~kDenseFlagBits) == 0, "lk_decode: unknown flags 0x%x", flags);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     DenseGrid g;

@@ -1,0 +1,521 @@
+// klt.hip -- hip_klt (include/ofps_hip.h N3): one corner feature per lattice cell of the previous frame, tracked into the current
+// frame by a pyramidal Lucas-Kanade iteration.  Every sum over pixels is an integer; the handful of f64 operations per iteration are
+// scalar, in the definition's order and computed by every lane alike (the build compiles with -ffp-contract=off).
+//
+// klt_score_kernel: one workgroup = one cell.  The cell's pixels and an r + 1 halo are staged in LDS; a horizontal pass makes the
+//   (2r + 1)-column sums of gx*gx, gx*gy, gy*gy for the cell's columns over the cell's rows and r rows above and below, the Sobel
+//   values of the walked columns held in registers; a vertical pass sums 2r + 1 of those rows per pixel.  The cell's winner is the
+//   maximum of one 64-bit key, score << 32 | ~local index: a total order, so the reduction's order cannot change it.
+// klt_track_kernel: one wave = one slot, the lanes over the n * n <= 225 window pixels (four per lane), the (n + 2)^2 template samples
+//   of a level in LDS, the template's gradients in registers; A11, A12, A22, b1, b2 and the residual are 64-bit integer sums reduced
+//   across the wave by a butterfly, so every lane holds them and takes the same branches.  All levels in one launch.
+#include "common.hpp"
+
+#include <cmath>
+
+namespace {
+
+using namespace ofps;
+
+constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3;
+constexpr int kKltTemplate = (2 * kKltMaxRadius + 3) * (2 * kKltMaxRadius + 3);       // 17 x 17 samples
+constexpr int kKltTemplatePitch = (kKltTemplate + 3) & ~3;
+constexpr int kKltTrackWaves = 4;
+
+enum { KLT_KEPT = 0, KLT_NONE = 1, KLT_FLAT = 2, KLT_LEFT = 3, KLT_RESIDUAL = 4 };
+
+struct KltLevels {
+    const uint8_t* prev[kKltMaxLevels];
+    const uint8_t* cur[kKltMaxLevels];
+    int W[kKltMaxLevels], H[kKltMaxLevels], stride[kKltMaxLevels];
+};
+
+struct KltTrackParams {
+    KltLevels lv;
+    int L, w, K, min_eig, max_residual;
+    const int* pts;                      // n points, pt_stride ints apart: (x, y[, score])
+    int pt_stride, from_features, n;     // from_features: the points are the score kernel's triples, x < 0 = no feature (status 1)
+    int* out_quad;                       // 4 per slot or null
+    int* out_slots;                      // 6 per slot or null
+    float4* out_rec;                     // the slot's record (zeros unless kept) or null
+    uint8_t* out_flag;                   // 1 = kept; beside out_rec
+};
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    lo = __shfl_xor(lo, mask, 64);
+    hi = __shfl_xor(hi, mask, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+    for (int m = 1; m < 64; m <<= 1) v += (long long)shfl_xor_u64((unsigned long long)v, m);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = shfl_xor_u64(v, m); v = o > v ? o : v; }
+    return v;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ceil(sqrt(D)), exact: the f64 root is a first guess, the integer loops make it the floor whatever its last bit was
+__device__ __forceinline__ unsigned long long ceil_sqrt_u64(unsigned long long D) {
+    unsigned long long s = (unsigned long long)sqrt((double)D);
+    while (s * s > D) --s;
+    while ((s + 1) * (s + 1) <= D) ++s;
+    return s + (s * s < D ? 1 : 0);
+}
+
+template <int C>
+__global__ __launch_bounds__(C * C < 256 ? C * C : 256) void klt_score_kernel(const uint8_t* __restrict__ img, int W, int H, int stride, int r,
+                                                                              int min_score, int* __restrict__ out) {
+    constexpr int T = C * C < 256 ? C * C : 256;
+    constexpr int PWMAX = C + 2 * (kKltMaxScoreRadius + 1), HRMAX = C + 2 * kKltMaxScoreRadius;
+    __shared__ uint8_t P[PWMAX * PWMAX];
+    __shared__ int Hs[3][HRMAX * C];
+    __shared__ unsigned long long wkey[T / 64];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * C, y0 = blockIdx.y * C;
+    const int PW = C + 2 * (r + 1), HR = C + 2 * r;
+    // pixels outside the frame are replicated: they reach only pixels that are not admissible
+    for (int idx = tid; idx < PW * PW; idx += T) {
+        const int py = idx / PW, px = idx - py * PW;
+        const int gx = clampi(x0 - (r + 1) + px, 0, W - 1), gy = clampi(y0 - (r + 1) + py, 0, H - 1);
+        P[idx] = img[(size_t)gy * stride + gx];
+    }
+    __syncthreads();
+    // row hy of Hs is frame row y0 - r + hy = P row hy + 1; the window of column lx covers P columns lx + 1 .. lx + 2r + 1
+    for (int idx = tid; idx < HR * C; idx += T) {
+        const int hy = idx / C, lx = idx - hy * C;
+        const uint8_t* row = &P[(hy + 1) * PW + lx];
+        // column c of the walk: s = top + 2 mid + bottom (gx = s[c + 1] - s[c - 1]), d = bottom - top (gy = d[c - 1] + 2 d[c] + d[c + 1])
+        int s0 = (int)row[-PW] + 2 * (int)row[0] + (int)row[PW], d0 = (int)row[PW] - (int)row[-PW];
+        int s1 = (int)row[1 - PW] + 2 * (int)row[1] + (int)row[1 + PW], d1 = (int)row[1 + PW] - (int)row[1 - PW];
+        int a = 0, b = 0, c = 0;
+        for (int i = 0; i <= 2 * r; ++i) {
+            const uint8_t* q = row + i + 2;
+            const int s2 = (int)q[-PW] + 2 * (int)q[0] + (int)q[PW], d2 = (int)q[PW] - (int)q[-PW];
+            const int gx = s2 - s0, gy = d0 + 2 * d1 + d2;
+            a += gx * gx; b += gx * gy; c += gy * gy;
+            s0 = s1; d0 = d1; s1 = s2; d1 = d2;
+        }
+        Hs[0][idx] = a; Hs[1][idx] = b; Hs[2][idx] = c;
+    }
+    __syncthreads();
+    unsigned long long key = 0;
+    for (int idx = tid; idx < C * C; idx += T) {
+        const int ly = idx / C, lx = idx - ly * C;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x < r + 1 || x > W - r - 2 || y < r + 1 || y > H - r - 2) continue;
+        long long a = 0, b = 0, c = 0;
+        for (int j = 0; j <= 2 * r; ++j) {
+            const int h = (ly + j) * C + lx;
+            a += Hs[0][h]; b += Hs[1][h]; c += Hs[2][h];
+        }
+        const unsigned long long D = (unsigned long long)((a - c) * (a - c)) + 4ull * (unsigned long long)(b * b);
+        const long long score = a + c - (long long)ceil_sqrt_u64(D);
+        const unsigned long long k = ((unsigned long long)score << 32) | (unsigned long long)(~(unsigned)idx);
+        key = k > key ? k : key;
+    }
+    key = wave_max_u64(key);
+    if ((tid & 63) == 0) wkey[tid >> 6] = key;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < T / 64; ++k) key = wkey[k] > key ? wkey[k] : key;
+        int* o = out + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+        const long long score = (long long)(key >> 32);
+        if (key != 0 && score >= (long long)min_score) {
+            const int idx = (int)(~(unsigned)key);
+            o[0] = x0 + idx % C; o[1] = y0 + idx / C; o[2] = (int)score;
+        } else {
+            o[0] = -1; o[1] = -1; o[2] = 0;
+        }
+    }
+}
+
+// S(img, q): bilinear sample at a 1/256-pixel position, pixel indices clamped into the frame, 8 fractional bits
+__device__ __forceinline__ int klt_sample(const uint8_t* __restrict__ img, int W, int H, int stride, int qx, int qy) {
+    const int ix = qx >> 8, iy = qy >> 8, fx = qx & 255, fy = qy & 255;
+    const int xa = clampi(ix, 0, W - 1), xb = clampi(ix + 1, 0, W - 1);
+    const uint8_t* ra = img + (size_t)clampi(iy, 0, H - 1) * stride;
+    const uint8_t* rb = img + (size_t)clampi(iy + 1, 0, H - 1) * stride;
+    const int s = (256 - fx) * (256 - fy) * (int)ra[xa] + fx * (256 - fy) * (int)ra[xb] + (256 - fx) * fy * (int)rb[xa] + fx * fy * (int)rb[xb];
+    return (s + 128) >> 8;
+}
+
+// what one lane stores for a slot: statuses 1, 2 and 3 report dq = (0, 0) and res = 0
+__device__ __forceinline__ void klt_store(const KltTrackParams& p, long long slot, int x, int y, int score, int dqx, int dqy, long long res, int status) {
+    if (status != KLT_KEPT && status != KLT_RESIDUAL) { dqx = 0; dqy = 0; res = 0; }
+    if (p.out_quad) {
+        int* o = p.out_quad + 4 * (size_t)slot;
+        o[0] = dqx; o[1] = dqy; o[2] = (int)res; o[3] = status;
+    }
+    if (p.out_slots) {
+        int* o = p.out_slots + 6 * (size_t)slot;
+        o[0] = status == KLT_NONE ? -1 : x; o[1] = status == KLT_NONE ? -1 : y; o[2] = status == KLT_NONE ? 0 : score;
+        o[3] = dqx; o[4] = dqy; o[5] = status;
+    }
+    if (p.out_rec) {
+        const float W0 = (float)p.lv.W[0], H0 = (float)p.lv.H[0];
+        float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (status == KLT_KEPT) rec = make_float4(((float)x + 0.5f) / W0, ((float)y + 0.5f) / H0, ((float)dqx / 256.0f) / W0, ((float)dqy / 256.0f) / H0);
+        p.out_rec[slot] = rec;
+        p.out_flag[slot] = status == KLT_KEPT ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
+    if (slot >= p.n) return;                                  // the whole wave
+    int* I = tmpl + wave * kKltTemplatePitch;
+    const int* pt = p.pts + (size_t)slot * p.pt_stride;
+    const int x = pt[0], y = pt[1], score = p.from_features ? pt[2] : 0;
+    const int W0 = p.lv.W[0], H0 = p.lv.H[0];
+    const int w = p.w, n = 2 * w + 1, n2 = n * n, m = n + 2;
+    int status = KLT_KEPT, dqx = 0, dqy = 0;
+    long long res = 0;
+    if (p.from_features && x < 0) status = KLT_NONE;
+    else if (x < 0 || x >= W0 || y < 0 || y >= H0) status = KLT_LEFT;
+    if (status != KLT_KEPT) {                                 // no feature, or a point outside the frame: the wave leaves at once
+        if (lane == 0) klt_store(p, slot, x, y, score, 0, 0, 0, status);
+        return;
+    }
+    // the lane's window pixels lane + 64 k: their offsets from the window centre, and the template's value and gradients there
+    int pi[4], pj[4], ix[4], iy[4], ic[4];
+    for (int k = 0; k < 4; ++k) {
+        const int q = lane + 64 * k;
+        pj[k] = q / n; pi[k] = q - pj[k] * n;
+        ix[k] = iy[k] = ic[k] = 0;
+    }
+    int cqx = 0, cqy = 0;
+    for (int l = p.L - 1; l >= 0 && status == KLT_KEPT; --l) {
+        const uint8_t* __restrict__ prev = p.lv.prev[l];
+        const uint8_t* __restrict__ cur = p.lv.cur[l];
+        const int Wl = p.lv.W[l], Hl = p.lv.H[l], sl = p.lv.stride[l];
+        cqx = (((2 * x + 1) * 128) >> l) - 128;
+        cqy = (((2 * y + 1) * 128) >> l) - 128;
+        wave_sync();                                          // the previous level's template has been read
+        for (int idx = lane; idx < m * m; idx += 64) {
+            const int j = idx / m, i = idx - j * m;
+            I[idx] = klt_sample(prev, Wl, Hl, sl, cqx + 256 * (i - w - 1), cqy + 256 * (j - w - 1));
+        }
+        wave_sync();
+        long long a11 = 0, a12 = 0, a22 = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (lane + 64 * k < n2) {
+                const int c = (pj[k] + 1) * m + pi[k] + 1;
+                ix[k] = I[c + 1] - I[c - 1]; iy[k] = I[c + m] - I[c - m]; ic[k] = I[c];
+                a11 += (long long)ix[k] * ix[k]; a12 += (long long)ix[k] * iy[k]; a22 += (long long)iy[k] * iy[k];
+            }
+        }
+        a11 = wave_sum_i64(a11); a12 = wave_sum_i64(a12); a22 = wave_sum_i64(a22);
+        const long long T = (long long)p.min_eig * n2 * 262144ll;
+        const double X = (double)(a11 - T), Y = (double)(a22 - T), Z = (double)a12;
+        const double xy = X * Y, zz = Z * Z;
+        if (!(xy >= zz && X + Y >= 0.0)) { status = KLT_FLAT; break; }
+        const double A11 = (double)a11, A22 = (double)a22;
+        const double det = A11 * A22 - zz;
+        if (det <= 0.0) { status = KLT_FLAT; break; }
+        const double lim = 256.0 * w;
+        for (int it = 0; it < p.K; ++it) {
+            const long long fx = 256ll * x + (long long)dqx * (1ll << l), fy = 256ll * y + (long long)dqy * (1ll << l);
+            if (fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1)) { status = KLT_LEFT; break; }
+            long long b1 = 0, b2 = 0;
+            for (int k = 0; k < 4; ++k) {
+                if (lane + 64 * k < n2) {
+                    const int d = klt_sample(cur, Wl, Hl, sl, cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
+                    b1 += (long long)d * ix[k]; b2 += (long long)d * iy[k];
+                }
+            }
+            b1 = wave_sum_i64(b1); b2 = wave_sum_i64(b2);
+            const double B1 = (double)b1, B2 = (double)b2;
+            const double t1 = A22 * B1, t2 = Z * B2, t3 = A11 * B2, t4 = Z * B1;
+            const double num_x = t1 - t2, num_y = t3 - t4;
+            const double ux = (-512.0 * num_x) / det, uy = (-512.0 * num_y) / det;
+            const int uqx = (int)rint(fmin(fmax(ux, -lim), lim)), uqy = (int)rint(fmin(fmax(uy, -lim), lim));
+            dqx += uqx; dqy += uqy;
+            if (uqx == 0 && uqy == 0) break;
+        }
+        if (status != KLT_KEPT) break;
+        if (l > 0) { dqx *= 2; dqy *= 2; }
+    }
+    if (status == KLT_KEPT) {
+        const long long fx = 256ll * x + dqx, fy = 256ll * y + dqy;
+        if (fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1)) status = KLT_LEFT;
+    }
+    if (status == KLT_KEPT) {
+        long long sum = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (lane + 64 * k < n2) {
+                const int d = klt_sample(p.lv.cur[0], W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
+                sum += d < 0 ? -d : d;
+            }
+        }
+        res = wave_sum_i64(sum);
+        if (p.max_residual > 0 && res > 16ll * p.max_residual * n2) status = KLT_RESIDUAL;
+    }
+    if (lane == 0) klt_store(p, slot, x, y, score, dqx, dqy, res, status);
+}
+
+struct KltSettings { int cell, r, min_score, min_eig, max_residual; };
+
+KltSettings klt_settings(const ofps_hip_ctx* ctx) {
+    return {ctx->opt.klt_cell, ctx->opt.klt_score_radius, ctx->opt.klt_min_score, ctx->opt.klt_min_eig, ctx->opt.klt_max_residual};
+}
+
+int klt_check_settings(ofps_hip_ctx* ctx, int cell, int r, int min_score, int min_eig, int max_residual, const char* who) {
+    OFPS_REQUIRE(ctx, cell == 8 || cell == 16 || cell == 32, "%s: cell %d is not 8|16|32", who, cell);
+    OFPS_REQUIRE(ctx, r >= 1 && r <= kKltMaxScoreRadius, "%s: score_radius %d outside [1, %d]", who, r, kKltMaxScoreRadius);
+    OFPS_REQUIRE(ctx, min_score >= 1, "%s: min_score %d outside [1, 2^31 - 1]", who, min_score);
+    OFPS_REQUIRE(ctx, min_eig >= 1 && min_eig <= 65535, "%s: min_eig %d outside [1, 65535]", who, min_eig);
+    OFPS_REQUIRE(ctx, max_residual >= 0 && max_residual <= 4080, "%s: max_residual %d outside [0, 4080]", who, max_residual);
+    return OFPS_HIP_OK;
+}
+
+int klt_check_frame(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, const char* who) {
+    OFPS_REQUIRE(ctx, levels >= 1 && levels <= kKltMaxLevels, "%s: levels %d outside [1, %d]", who, levels, kKltMaxLevels);
+    OFPS_REQUIRE(ctx, W >= 8 && H >= 8 && W <= 32768 && H <= 32768 && stride >= W, "%s: bad geometry W=%d H=%d stride=%d", who, W, H, stride);
+    OFPS_REQUIRE(ctx, (W >> (levels - 1)) >= 8 && (H >> (levels - 1)) >= 8, "%s: a %d x %d frame has no %d levels of at least 8 x 8", who, W, H,
+                 levels);
+    return OFPS_HIP_OK;
+}
+
+int klt_check_track(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who) {
+    const int rc = klt_check_frame(ctx, W, H, stride, levels, who);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_REQUIRE(ctx, radius >= 1 && radius <= kKltMaxRadius, "%s: radius %d outside [1, %d]", who, radius, kKltMaxRadius);
+    OFPS_REQUIRE(ctx, iters >= 1 && iters <= kKltMaxIters, "%s: iters %d outside [1, %d]", who, iters, kKltMaxIters);
+    return OFPS_HIP_OK;
+}
+
+inline size_t klt_slots(int W, int H, int cell) { return (size_t)((W + cell - 1) / cell) * (size_t)((H + cell - 1) / cell); }
+inline size_t pad16(size_t b) { return (b + 15) & ~size_t(15); }
+
+int klt_features_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int H, int stride, const KltSettings& s, int* d_out) {
+    const dim3 grid((W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell);
+    if (s.cell == 8) hipLaunchKernelGGL(klt_score_kernel<8>, grid, dim3(64), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
+    else if (s.cell == 16) hipLaunchKernelGGL(klt_score_kernel<16>, grid, dim3(256), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
+    else hipLaunchKernelGGL(klt_score_kernel<32>, grid, dim3(256), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+// both frames' levels above 0 in S_KLT_PYR (ofps_hip_sad_down2's levels, as they are) -> *lv
+int klt_pyramid_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, KltLevels* lv) {
+    size_t off[kKltMaxLevels] = {}, bytes = 0;
+    lv->prev[0] = d_prev; lv->cur[0] = d_cur; lv->W[0] = W; lv->H[0] = H; lv->stride[0] = stride;
+    for (int l = 1; l < kKltMaxLevels; ++l) {
+        lv->prev[l] = lv->cur[l] = nullptr;
+        lv->W[l] = lv->H[l] = lv->stride[l] = 0;
+        if (l >= levels) continue;
+        lv->W[l] = lv->W[l - 1] >> 1; lv->H[l] = lv->H[l - 1] >> 1;
+        lv->stride[l] = (lv->W[l] + 63) & ~63;
+        off[l] = bytes; bytes += 2 * (size_t)lv->stride[l] * lv->H[l];
+    }
+    if (levels == 1) return OFPS_HIP_OK;
+    auto* pyr = static_cast<uint8_t*>(scratch(ctx, S_KLT_PYR, bytes));
+    if (!pyr) return OFPS_HIP_ENOMEM;
+    for (int l = 1; l < levels; ++l) {
+        uint8_t* dp = pyr + off[l];
+        uint8_t* dc = dp + (size_t)lv->stride[l] * lv->H[l];
+        int rc = sad_down2_device(ctx, lv->prev[l - 1], lv->W[l - 1], lv->H[l - 1], lv->stride[l - 1], dp, lv->stride[l]);
+        if (rc == OFPS_HIP_OK) rc = sad_down2_device(ctx, lv->cur[l - 1], lv->W[l - 1], lv->H[l - 1], lv->stride[l - 1], dc, lv->stride[l]);
+        if (rc != OFPS_HIP_OK) return rc;
+        lv->prev[l] = dp; lv->cur[l] = dc;
+    }
+    return OFPS_HIP_OK;
+}
+
+int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p) {
+    if (p.n <= 0) return OFPS_HIP_OK;
+    hipLaunchKernelGGL(klt_track_kernel, dim3((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves)), dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+}  // namespace
+
+namespace ofps {
+
+// what every call of the decoder refuses, the stage forms and the dense decoders' stream forms alike
+int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who) {
+    return klt_check_track(ctx, W, H, stride, levels, radius, iters, who);
+}
+
+// features of prev -> pyramid of both frames -> track -> status flags -> the ordered compaction -> count on the device.  Enqueues on
+// ctx->stream, synchronises nothing.  d_out: capacity = the slot count; d_slots (optional): 6 int32 per slot
+int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                    float4* d_out, uint32_t* d_count, int* d_slots) {
+    const KltSettings s = klt_settings(ctx);
+    const size_t ns = klt_slots(W, H, s.cell);
+    const size_t o_raw = pad16(ns * 3 * sizeof(int)), o_flag = o_raw + ns * sizeof(float4);
+    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_flag + pad16(ns)));
+    if (!work) return OFPS_HIP_ENOMEM;
+    auto* d_feat = reinterpret_cast<int*>(work);
+    auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
+    auto* d_flag = reinterpret_cast<uint8_t*>(work + o_flag);
+    int rc = klt_features_device(ctx, d_prev, W, H, stride, s, d_feat);
+    if (rc != OFPS_HIP_OK) return rc;
+    KltTrackParams p{};
+    rc = klt_pyramid_device(ctx, d_prev, d_cur, W, H, stride, levels, &p.lv);
+    if (rc != OFPS_HIP_OK) return rc;
+    p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
+    p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)ns;
+    p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
+    rc = klt_track_launch(ctx, p);
+    if (rc != OFPS_HIP_OK) return rc;
+    return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_count) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_count);
+}
+
+}  // namespace ofps
+
+extern "C" {
+
+int ofps_hip_set_klt(ofps_hip_ctx* ctx, int cell, int score_radius, int min_score, int min_eig, int max_residual) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    const int rc = klt_check_settings(ctx, cell, score_radius, min_score, min_eig, max_residual, "set_klt");
+    if (rc != OFPS_HIP_OK) return rc;
+    ctx->opt.klt_cell = cell; ctx->opt.klt_score_radius = score_radius; ctx->opt.klt_min_score = min_score;
+    ctx->opt.klt_min_eig = min_eig; ctx->opt.klt_max_residual = max_residual;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_klt(ofps_hip_ctx* ctx, int32_t* cell, int32_t* score_radius, int32_t* min_score, int32_t* min_eig, int32_t* max_residual) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    if (cell) *cell = ctx->opt.klt_cell;
+    if (score_radius) *score_radius = ctx->opt.klt_score_radius;
+    if (min_score) *min_score = ctx->opt.klt_min_score;
+    if (min_eig) *min_eig = ctx->opt.klt_min_eig;
+    if (max_residual) *max_residual = ctx->opt.klt_max_residual;
+    return OFPS_HIP_OK;
+}
+
+size_t ofps_hip_klt_slot_count(int W, int H, int cell) {
+    if (W < 1 || H < 1 || (cell != 8 && cell != 16 && cell != 32)) return 0;
+    return klt_slots(W, H, cell);
+}
+
+int ofps_hip_klt_features_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, void* d_out_triples) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_luma && d_out_triples, "klt_features: null device pointer");
+    const int rc = klt_check_frame(ctx, W, H, stride, 1, "klt_features");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return klt_features_device(ctx, static_cast<const uint8_t*>(d_luma), W, H, stride, klt_settings(ctx), static_cast<int*>(d_out_triples));
+}
+
+int ofps_hip_klt_features(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, int32_t* out_triples) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, luma && out_triples, "klt_features: null host pointer");
+    int rc = klt_check_frame(ctx, W, H, stride, 1, "klt_features");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KltSettings s = klt_settings(ctx);
+    const size_t ns = klt_slots(W, H, s.cell);
+    const int ss = (W + 63) & ~63;
+    auto* d_img = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)ss * H));
+    auto* d_out = static_cast<int*>(ofps::scratch(ctx, ofps::S_KLT_HOST, ns * 3 * sizeof(int)));
+    if (!d_img || !d_out) return OFPS_HIP_ENOMEM;
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_img, ss, luma, stride, W, H, ctx->stream));
+    rc = klt_features_device(ctx, d_img, W, H, ss, s, d_out);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_triples, d_out, ns * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_track_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                           int levels, int radius, int iters, void* d_out_quads) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_prev && d_cur && (n == 0 || (d_points && d_out_quads)), "klt_track: null device pointer");
+    OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
+    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_track");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return OFPS_HIP_OK;
+    KltTrackParams p{};
+    rc = klt_pyramid_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, levels, &p.lv);
+    if (rc != OFPS_HIP_OK) return rc;
+    p.L = levels; p.w = radius; p.K = iters; p.min_eig = ctx->opt.klt_min_eig; p.max_residual = ctx->opt.klt_max_residual;
+    p.pts = static_cast<const int*>(d_points); p.pt_stride = 2; p.from_features = 0; p.n = (int)n;
+    p.out_quad = static_cast<int*>(d_out_quads);
+    return klt_track_launch(ctx, p);
+}
+
+int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
+                       int levels, int radius, int iters, int32_t* out_quads) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, prev && cur && (n == 0 || (points && out_quads)), "klt_track: null host pointer");
+    OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
+    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_track");
+    if (rc != OFPS_HIP_OK) return rc;
+    for (size_t k = 0; k < n; ++k)
+        OFPS_REQUIRE(ctx, points[2 * k] >= 0 && points[2 * k] < W && points[2 * k + 1] >= 0 && points[2 * k + 1] < H,
+                     "klt_track: point %zu = (%d, %d) lies outside the %d x %d frame", k, points[2 * k], points[2 * k + 1], W, H);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return OFPS_HIP_OK;
+    const int ss = (W + 63) & ~63;
+    const size_t fb = (size_t)ss * H, o_quad = pad16(n * 2 * sizeof(int));
+    auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_quad + n * 4 * sizeof(int)));
+    if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io, points, n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    rc = ofps_hip_klt_track_dev(ctx, d_fr, d_fr + fb, W, H, ss, d_io, n, levels, radius, iters, d_io + o_quad);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_quads, d_io + o_quad, n * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                          void* d_out_entries, void* d_out_count, void* d_out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "klt_flow: null device pointer");
+    const int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ofps::klt_flow_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, levels, radius, iters,
+                                 static_cast<float4*>(d_out_entries), static_cast<uint32_t*>(d_out_count), static_cast<int*>(d_out_slots));
+}
+
+int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
+                      float* out_entries, uint32_t* n_out, int32_t* out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "klt_flow: null host pointer");
+    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
+    const int ss = (W + 63) & ~63;
+    const size_t fb = (size_t)ss * H, o_count = ns * sizeof(float4), o_slots = o_count + 16;
+    auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_slots + ns * 6 * sizeof(int)));
+    if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
+    OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
+    rc = ofps::klt_flow_device(ctx, d_fr, d_fr + fb, W, H, ss, levels, radius, iters, reinterpret_cast<float4*>(d_io),
+                               reinterpret_cast<uint32_t*>(d_io + o_count), out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr);
+    if (rc != OFPS_HIP_OK) return rc;
+    uint32_t count = 0;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(&count, d_io + o_count, sizeof(count), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_io + o_slots, ns * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (count > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "klt_flow: the device counted %u records in %zu slots", count, ns);
+    if (count) OFPS_HIP_TRY(ctx, hipMemcpy(out_entries, d_io, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost));
+    *n_out = count;
+    return OFPS_HIP_OK;
+}
+
+}  // extern "C"

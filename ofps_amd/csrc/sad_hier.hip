@@ -435,6 +435,11 @@ int refine_check(ofps_hip_ctx* ctx, const void* prev, const void* cur, const voi
 
 namespace ofps {
 
+// one frame -> its halved form, on ctx->stream: the level hip_klt's pyramid is made of (klt.hip)
+int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int src_stride, uint8_t* dst, int dst_stride) {
+    return down2_device(ctx, src, 0, W, H, src_stride, dst, 0, dst_stride, 1);
+}
+
 int sad_hier_reach(int range, int levels) {
     if (range < 0 || range > 64 || levels < 1 || levels > 3) return -1;
     int r = range;

@@ -205,10 +205,17 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
     // both were read by this very call (skip >= 1 on the first call)
     frames_read_ += skip + 1;
     if (frames_read_ < 2) return false;
-    const bool records_fullres = process_fullres_ && fullres_records_;
-    out_.resize(records_fullres ? 4 * w_ * h_ : 4 * std::min(max_w_, w_) * std::min(max_h_, h_));
+    const bool records_fullres = process_fullres_ && fullres_records_ && !klt_;
+    if (klt_) {                                                       // hip_klt: the settings a ticket follows, and one record slot per lattice cell
+        ctx_.check(ofps_hip_set_klt(ctx_.get(), (int)klt_->cell, (int)klt_->score_radius, (int)klt_->min_score, (int)klt_->min_eig,
+                                    (int)klt_->max_residual));
+        out_.resize(klt_record_floats(w_, h_, max_w_, max_h_, process_fullres_, klt_->cell));
+    } else {
+        out_.resize(records_fullres ? 4 * w_ * h_ : 4 * std::min(max_w_, w_) * std::min(max_h_, h_));
+    }
     size_t n_out = 0;
-    const unsigned flags = (contrast_mask_ ? OFPS_HIP_LK_CONTRAST_MASK : 0u) | (process_fullres_ ? 0u : OFPS_HIP_LK_REDUCED) |
+    const unsigned flags = klt_ ? OFPS_HIP_FLOW_SPARSE | (process_fullres_ ? 0u : OFPS_HIP_LK_REDUCED) | OFPS_HIP_FRAME_FORMAT(fmt_) :
+                           (contrast_mask_ ? OFPS_HIP_LK_CONTRAST_MASK : 0u) | (process_fullres_ ? 0u : OFPS_HIP_LK_REDUCED) |
                            (records_fullres ? OFPS_HIP_LK_FULLRES_RECORDS : 0u) | OFPS_HIP_FRAME_FORMAT(fmt_) |
                            (farneback_ ? OFPS_HIP_FLOW_FARNEBACK | OFPS_HIP_FLOW_USE_PREVIOUS : 0u);   // cv-decoder/src/lib.rs:161-165: its previous flow is the initial flow
     const size_t params[5] = {levels_, radius_, iters_, max_w_, max_h_};
@@ -236,10 +243,33 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
 }
 
 std::vector<std::pair<std::string, PropertyMut>> HipLkDecoder::props_mut() {   // cv-decoder/src/lib.rs:35-52 + the flow's knobs
+    if (klt_) return klt_props({&max_w_, &max_h_, &process_fullres_, &*klt_, &levels_, &radius_, &iters_});
     return {{"Width", PropertyMut::usize(&max_w_, 1, 2000)}, {"Height", PropertyMut::usize(&max_h_, 1, 2000)},
             {"Pyramid levels", PropertyMut::usize(&levels_, 1, 8)}, {"Window radius", PropertyMut::usize(&radius_, 1, farneback_ ? 7 : 15)},
             {"Iterations", PropertyMut::usize(&iters_, 1, 64)}, {"Contrast mask", PropertyMut::boolean(&contrast_mask_)},
             {"Process Fullres", PropertyMut::boolean(&process_fullres_)}, {"Fullres records", PropertyMut::boolean(&fullres_records_)}};
+}
+
+// ------------------------------------------------------------------ hip_klt
+size_t klt_record_floats(size_t w, size_t h, size_t max_w, size_t max_h, bool process_fullres, size_t cell) {
+    int fw = (int)w, fh = (int)h;
+    if (w == 0 || h == 0 || w > 32768 || h > 32768) throw Error("hip_klt: frame size " + std::to_string(w) + " x " + std::to_string(h) + " is out of range");
+    if (!process_fullres && (max_w == 0 || max_h == 0 || max_w > 32768 || max_h > 32768 ||
+                             ofps_hip_cv_grid((int)w, (int)h, (int)max_w, (int)max_h, &fw, &fh) != 0 || fw < 1 || fh < 1))
+        throw Error("hip_klt: the capped grid of the frame is empty");
+    const size_t slots = cell <= 32 ? ofps_hip_klt_slot_count(fw, fh, (int)cell) : 0;
+    if (slots == 0) throw Error("hip_klt: cell size " + std::to_string(cell) + " is not 8, 16 or 32");
+    return sad_record_floats(slots);
+}
+
+std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage& at) {
+    KltSettings& s = *at.settings;
+    return {{"Width", PropertyMut::usize(at.max_w, 1, 2000)}, {"Height", PropertyMut::usize(at.max_h, 1, 2000)},
+            {"Process Fullres", PropertyMut::boolean(at.process_fullres)},
+            {"Cell size", PropertyMut::usize(&s.cell, 8, 32)}, {"Score radius", PropertyMut::usize(&s.score_radius, 1, 3)},
+            {"Min score", PropertyMut::usize(&s.min_score, 1, kKltMaxScore)}, {"Min eigenvalue", PropertyMut::usize(&s.min_eig, 1, kKltMaxEig)},
+            {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)}, {"Levels", PropertyMut::usize(at.levels, 1, 6)},
+            {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)}};
 }
 
 // ------------------------------------------------------------------ .mvec
@@ -558,7 +588,7 @@ std::vector<MotionVectors> MultiDeviceSad::search(const uint8_t* frames, size_t 
 
 std::unique_ptr<Decoder> create_decoder(const std::string& name, const std::string& arg) {
     if (name == "mvec") return std::make_unique<MvecFileDecoder>(open_input(arg));
-    if (name == "hip_sad" || name == "hip_lk" || name == "hip_flow") {                      // "<path>?w=1920&h=1080&fps=60"
+    if (name == "hip_sad" || name == "hip_lk" || name == "hip_flow" || name == "hip_klt") {  // "<path>?w=1920&h=1080&fps=60"
         std::string path = arg;
         size_t w = 0, h = 0;
         int fmt = OFPS_HIP_FMT_LUMA;
@@ -581,6 +611,7 @@ std::unique_ptr<Decoder> create_decoder(const std::string& name, const std::stri
         }
         if (name == "hip_lk") return std::make_unique<HipLkDecoder>(open_input(path), w, h, fps, 0, false, fmt);
         if (name == "hip_flow") return std::make_unique<HipLkDecoder>(open_input(path), w, h, fps, 0, /*farneback=*/true, fmt);
+        if (name == "hip_klt") return std::make_unique<HipKltDecoder>(open_input(path), w, h, fps, 0, fmt);
         if (fmt != OFPS_HIP_FMT_LUMA) throw Error("hip_sad reads luma frames only");
         return std::make_unique<HipSadDecoder>(open_input(path), w, h, fps);
     }

@@ -161,6 +161,16 @@ private:
     std::vector<float> out_;
 };
 
+// "hip_klt" (include/ofps_hip.h N3): what the decoder below keeps for it, its property table, and the size of its record buffer
+constexpr size_t kKltMaxResidual = 4080, kKltMaxEig = 65535, kKltMaxScore = 2147483647;
+struct KltSettings { size_t cell = 16, score_radius = 2, min_score = 1, min_eig = 1, max_residual = 0; };
+// the storage behind hip_klt's properties; klt_props is the one table of their names and bounds (the decoder's props_mut returns it)
+struct KltPropStorage { size_t *max_w, *max_h; bool* process_fullres; KltSettings* settings; size_t *levels, *radius, *iters; };
+std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage& at);
+// the floats of hip_klt's record buffer: four per slot of the cell lattice over the frames the tracker reads (the capped grid's frames
+// with "Process Fullres" = false); throws Error for a cell size the library does not know or a lattice without a slot
+size_t klt_record_floats(size_t w, size_t h, size_t max_w, size_t max_h, bool process_fullres, size_t cell);
+
 // "hip_lk": dense per-pixel flow in cv-decoder's full-resolution mode (cv-decoder/src/lib.rs:82-294): one record per
 // visited cell of the (Width, Height)-capped grid; property names as in cv-decoder (:35-52).
 class HipLkDecoder : public Decoder {
@@ -182,7 +192,12 @@ public:
         return std::make_pair((size_t)gw, (size_t)gh);
     }
     std::vector<std::pair<std::string, PropertyMut>> props_mut() override;
+protected:
+    // "hip_klt" (HipKltDecoder below): OFPS_HIP_FLOW_SPARSE in place of the flow's flags, the context's klt settings set before every push, the
+    // record buffer sized from the cell lattice, klt_props as the property table
+    void enable_klt() { klt_ = KltSettings{}; levels_ = 4; radius_ = 7; iters_ = 10; contrast_mask_ = false; }
 private:
+    std::optional<KltSettings> klt_;
     HipContext ctx_;
     std::unique_ptr<std::istream> in_;
     size_t w_, h_, max_w_ = 150, max_h_ = 150, levels_ = 3, radius_ = 4, iters_ = 3;
@@ -199,6 +214,15 @@ private:
     unsigned on_device_flags_ = 0;     // ... pushed with these flags / parameters (a property change restarts the library's stream)
     size_t on_device_params_[5] = {0, 0, 0, 0, 0};
     bool farneback_ = false;
+};
+
+// "hip_klt" (include/ofps_hip.h N3): one corner feature per lattice cell of the previous frame, tracked into the new frame by a pyramidal
+// Lucas-Kanade iteration; hip_lk's stream of frames, formats and "Process Fullres", no mask and no down-sampling
+class HipKltDecoder : public HipLkDecoder {
+public:
+    HipKltDecoder(std::unique_ptr<std::istream> input, size_t width, size_t height, std::optional<double> fps, int device = 0,
+                  int frame_format = OFPS_HIP_FMT_LUMA)
+        : HipLkDecoder(std::move(input), width, height, fps, device, false, frame_format) { enable_klt(); }
 };
 
 // MvecFile of motion-loader/src/lib.rs:31-83 (pure host I/O, no GPU)
@@ -273,7 +297,7 @@ struct MotionDetectionConfig {
 void transfer_props(const std::vector<std::pair<std::string, Property>>& saved, Properties& plugin);
 
 // ---- creation by name (the part of PluginStore the hot path needs: ofps/src/plugins/mod.rs:396-453)
-std::unique_ptr<Decoder> create_decoder(const std::string& name, const std::string& arg);    // "hip_sad", "hip_lk", "hip_flow", "mvec"
+std::unique_ptr<Decoder> create_decoder(const std::string& name, const std::string& arg);    // "hip_sad", "hip_lk", "hip_flow", "hip_klt", "mvec"
 std::unique_ptr<Detector> create_detector(const std::string& name, const std::string& arg);  // "hip_block_motion"
 std::unique_ptr<Estimator> create_estimator(const std::string& name, const std::string& arg);// "hip_almeida"
 

@@ -270,6 +270,38 @@ class HipFlowDecoder(HipLkDecoder):
         return self._decode(field, dict(self._flow_kw(), farneback=True, use_previous=self.use_previous_flow))
 
 
+class HipKltDecoder(HipLkDecoder):
+    """The sparse decoder between hip_sad and the dense flows (include/ofps_hip.h N3, ofps_amd/csrc/klt.hip): one corner feature per cell
+    of a lattice over the previous frame, tracked into the new frame by a pyramidal Lucas-Kanade iteration at 1/256 pixel.  Frames, formats
+    and "Process Fullres" as HipLkDecoder; no contrast mask and no down-sampling: the kept features' records, in lattice order."""
+
+    _PROPS = (("Width", "usize", "max_w", 1, 2000), ("Height", "usize", "max_h", 1, 2000), ("Process Fullres", "bool", "process_fullres", None, None),
+              ("Cell size", "usize", "cell", 8, 32), ("Score radius", "usize", "score_radius", 1, 3), ("Min score", "usize", "min_score", 1, 2 ** 31 - 1),
+              ("Min eigenvalue", "usize", "min_eig", 1, 65535), ("Max residual", "usize", "max_residual", 0, 4080),
+              ("Levels", "usize", "levels", 1, 6), ("Window radius", "usize", "radius", 1, 7), ("Iterations", "usize", "iters", 1, 30))
+
+    def __init__(self, frames, framerate=None, device: int = 0, frame_format: int = HipContext.FMT_LUMA):
+        super().__init__(frames, framerate, device, frame_format)
+        self.levels, self.radius, self.iters = 4, 7, 10
+        self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual = 16, 2, 1, 1, 0
+        self.contrast_mask = False
+
+    def process_frame(self, field: list, out_frame=None, skip_frames: int = 0) -> bool:
+        for _ in range(skip_frames + 1):
+            self._prev = self._cur
+            try:
+                self._cur = np.ascontiguousarray(next(self._it), np.uint8)
+            except StopIteration:
+                raise EOFError("failed to grab frame") from None
+        if out_frame is not None:
+            out_frame[:] = [self._shown_frame()]
+        if self._prev is None or self._prev.shape != self._cur.shape:
+            self._on_device = None
+            return False
+        self.ctx.set_klt(self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual)
+        return self._decode(field, dict(reduced=not self.process_fullres, fmt=self.frame_format, sparse=True))
+
+
 class HipBlockMotionDetection(Properties):
     """Detector (ofps/src/detection.rs:11; block-motion-detector/src/lib.rs:13-46)."""
     _PROPS = (("Min size", "float", "min_size", 0.01, 1.0), ("Subdivisions", "usize", "subdivide", 1, 16),

@@ -581,11 +581,94 @@ class HipContext:
                 self.free(b)
         return flow
 
+    # ---- N3: hip_klt, sparse Lucas-Kanade on per-cell corner features
+    KLT_KEPT, KLT_NO_FEATURE, KLT_FLAT, KLT_LEFT_FRAME, KLT_RESIDUAL = 0, 1, 2, 3, 4
+
+    def set_klt(self, cell: int = 16, score_radius: int = 2, min_score: int = 1, min_eig: int = 1, max_residual: int = 0):
+        """hip_klt's settings (include/ofps_hip.h N3): lattice cell 8 | 16 | 32, score window radius [1, 3], smallest score of a feature,
+        smallest eigenvalue of a template's structure tensor per pixel [1, 65535], residual limit in sixteenths of a grey level per pixel
+        [0, 4080] (0 = off)."""
+        self._check(self._lib.ofps_hip_set_klt(self._h, cell, score_radius, min_score, min_eig, max_residual))
+
+    def get_klt(self) -> dict:
+        v = [C.c_int32(0) for _ in range(5)]
+        self._check(self._lib.ofps_hip_get_klt(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("cell", "score_radius", "min_score", "min_eig", "max_residual"), (int(x.value) for x in v)))
+
+    def klt_slot_count(self, W: int, H: int, cell: int | None = None) -> int:
+        return int(self._lib.ofps_hip_klt_slot_count(W, H, self.get_klt()["cell"] if cell is None else cell))
+
+    @staticmethod
+    def _luma_view(img: np.ndarray, stride: int | None):
+        if stride is None:
+            g = np.ascontiguousarray(img, np.uint8)
+            return g, g.shape[1]
+        assert img.dtype == np.uint8 and img.ndim == 2 and (img.shape[0] == 1 or img.strides[0] == stride) and img.strides[1] == 1
+        return img, stride
+
+    def klt_features(self, luma: np.ndarray, stride: int | None = None) -> np.ndarray:
+        """-> int32 [slots, 3]: (x, y, score) of every lattice cell's corner feature, (-1, -1, 0) for a cell without one.  stride: None, or
+        the row pitch in bytes of `luma` (a view of a wider buffer)."""
+        g, stride = self._luma_view(luma, stride)
+        H, W = g.shape
+        out = np.zeros((max(self.klt_slot_count(W, H), 1), 3), np.int32)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.ofps_hip_klt_features(self._h, C.cast(C.c_void_p(g.ctypes.data), u8), W, H, stride,
+                                                    out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out[:self.klt_slot_count(W, H)]
+
+    def klt_features_dev(self, d_luma: int, W: int, H: int, stride: int, d_out_triples: int):
+        self._check(self._lib.ofps_hip_klt_features_dev(self._h, C.c_void_p(d_luma), W, H, stride, C.c_void_p(d_out_triples)))
+
+    def klt_track(self, prev: np.ndarray, cur: np.ndarray, points: np.ndarray, levels: int, radius: int, iters: int,
+                  stride: int | None = None) -> np.ndarray:
+        """points int [n, 2] (x, y) inside the frame -> int32 [n, 4]: (dqx, dqy, res, status), dq in 1/256 pixel"""
+        p, stride = self._luma_view(prev, stride)
+        c, stride_c = self._luma_view(cur, stride)
+        assert p.shape == c.shape and stride == stride_c
+        H, W = p.shape
+        pts = np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+        out = np.zeros((max(len(pts), 1), 4), np.int32)
+        u8, i32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_track(self._h, C.cast(C.c_void_p(p.ctypes.data), u8), C.cast(C.c_void_p(c.ctypes.data), u8), W, H,
+                                                 stride, pts.ctypes.data_as(i32) if len(pts) else None, len(pts), levels, radius, iters,
+                                                 out.ctypes.data_as(i32)))
+        return out[:len(pts)]
+
+    def klt_track_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, d_points: int, n: int, levels: int, radius: int, iters: int,
+                      d_out_quads: int):
+        """Enqueue only; a point outside the frame comes back with status 3."""
+        self._check(self._lib.ofps_hip_klt_track_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, C.c_void_p(d_points), n,
+                                                     levels, radius, iters, C.c_void_p(d_out_quads)))
+
+    def klt_flow(self, prev: np.ndarray, cur: np.ndarray, levels: int, radius: int, iters: int, want_slots=False, stride: int | None = None):
+        """-> entries float32 [count, 4] (the kept features' records, in slot order) [, slots int32 [slots, 6]: (x, y, score, dqx, dqy, status)]"""
+        p, stride = self._luma_view(prev, stride)
+        c, stride_c = self._luma_view(cur, stride)
+        assert p.shape == c.shape and stride == stride_c
+        H, W = p.shape
+        ns = self.klt_slot_count(W, H)
+        ent = np.zeros((max(ns, 1), 4), np.float32)
+        slots = np.zeros((max(ns, 1), 6), np.int32) if want_slots else None
+        n = C.c_uint32(0)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.ofps_hip_klt_flow(self._h, C.cast(C.c_void_p(p.ctypes.data), u8), C.cast(C.c_void_p(c.ctypes.data), u8), W, H,
+                                                stride, levels, radius, iters, _fp(ent), C.byref(n),
+                                                slots.ctypes.data_as(C.POINTER(C.c_int32)) if want_slots else None))
+        return (ent[:n.value], slots[:ns]) if want_slots else ent[:n.value]
+
+    def klt_flow_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, levels: int, radius: int, iters: int, d_out_entries: int,
+                     d_out_count: int, d_out_slots: int | None = None):
+        """Enqueue only: d_out_entries holds klt_slot_count records, d_out_count one uint32, d_out_slots (optional) 6 int32 per slot."""
+        self._check(self._lib.ofps_hip_klt_flow_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, levels, radius, iters,
+                                                    C.c_void_p(d_out_entries), C.c_void_p(d_out_count), C.c_void_p(d_out_slots or 0)))
+
     LK_CONTRAST_MASK, LK_FULLRES_RECORDS, FLOW_FARNEBACK, FLOW_USE_PREVIOUS, LK_REDUCED = 1, 2, 4, 8, 16
+    FLOW_SPARSE = 32            # hip_klt (include/ofps_hip.h N3) in place of flow, mask and output stage; levels / radius / iters = L / w / K
     FMT_LUMA, FMT_BGR, FMT_RGBA, FMT_BGRA = 0, 1, 2, 3
 
-    def _lk_flags(self, contrast_mask, fullres_records, farneback, use_previous, reduced, fmt) -> int:
-        return ((self.LK_CONTRAST_MASK if contrast_mask else 0) | (self.LK_FULLRES_RECORDS if fullres_records else 0) |
+    def _lk_flags(self, contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse=False) -> int:
+        return ((self.FLOW_SPARSE if sparse else 0) | (self.LK_CONTRAST_MASK if contrast_mask else 0) | (self.LK_FULLRES_RECORDS if fullres_records else 0) |
                 (self.FLOW_FARNEBACK if farneback else 0) | (self.FLOW_USE_PREVIOUS if use_previous else 0) |
                 (self.LK_REDUCED if reduced else 0) | (int(fmt) << 8))
 
@@ -599,8 +682,10 @@ class HipContext:
         H, W = frame.shape[:2]
         return W, H, W * cn
 
-    @staticmethod
-    def _lk_capacity(W, H, max_w, max_h, fullres_records) -> int:
+    def _lk_capacity(self, W, H, max_w, max_h, fullres_records, reduced=False, sparse=False) -> int:
+        if sparse:                                            # hip_klt: the slot count of the frames the tracker reads
+            fw, fh = self.cv_grid(W, H, max_w, max_h) if reduced else (W, H)
+            return max(self.klt_slot_count(fw, fh), 1)
         return W * H if fullres_records else min(max_w, W) * min(max_h, H)
 
     def cv_grid(self, W: int, H: int, max_w: int = 150, max_h: int = 150):
@@ -638,29 +723,29 @@ class HipContext:
         return ow.value, oh.value
 
     def lk_decode(self, prev: np.ndarray, cur: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, farneback=False, use_previous=False,
-                  contrast_mask=False, fullres_records=False, reduced=False, fmt=0):
+                  contrast_mask=False, fullres_records=False, reduced=False, fmt=0, *, sparse=False):
         """-> (entries[n,4], (grid_w, grid_h)): what a hip_lk Decoder appends per frame (cv-decoder/src/lib.rs:82-294).
         reduced: cv-decoder's "Process Fullres" = false; fmt: the frames' pixel format (FMT_*; colour frames are [H, W, channels])."""
         prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
         assert prev.shape == cur.shape
         W, H, pitch = self._frame_geometry(prev, fmt)
-        out = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records), 4), np.float32)
+        out = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records, reduced, sparse), 4), np.float32)
         n = C.c_size_t(0); gw = C.c_int(0); gh = C.c_int(0)
         u8 = C.POINTER(C.c_uint8)
-        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse)
         self._check(self._lib.ofps_hip_lk_decode(self._h, prev.ctypes.data_as(u8), cur.ctypes.data_as(u8), W, H, pitch, levels, radius,
                                                  iters, max_w, max_h, flags, _fp(out), C.byref(n), C.byref(gw), C.byref(gh)))
         return out[:n.value].copy(), (gw.value, gh.value)
 
     def lk_push_frame(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
-                      fullres_records=False, farneback=False, use_previous=False, reduced=False, fmt=0):
+                      fullres_records=False, farneback=False, use_previous=False, reduced=False, fmt=0, *, sparse=False):
         """Stream form of lk_decode: the frame is uploaded once and is the next call's previous frame.
         -> None for the first frame of a stream, else (entries[n,4], (grid_w, grid_h))."""
         frame = np.ascontiguousarray(frame, np.uint8)
         W, H, pitch = self._frame_geometry(frame, fmt)
-        out = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records), 4), np.float32)
+        out = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records, reduced, sparse), 4), np.float32)
         n = C.c_size_t(0); gw = C.c_int(0); gh = C.c_int(0); have = C.c_int(0)
-        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse)
         self._check(self._lib.ofps_hip_lk_push_frame(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels, radius,
                                                      iters, max_w, max_h, flags, _fp(out), C.byref(n), C.byref(gw), C.byref(gh),
                                                      C.byref(have)))
@@ -669,17 +754,17 @@ class HipContext:
         return out[:n.value].copy(), (gw.value, gh.value)
 
     def lk_push_frame_async(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
-                            fullres_records=False, farneback=False, use_previous=False, reduced=False, fmt=0) -> int:
+                            fullres_records=False, farneback=False, use_previous=False, reduced=False, fmt=0, *, sparse=False) -> int:
         """Read-ahead form: returns a ticket once the upload, the flow and the output stage are enqueued.  `frame` must be
         C-contiguous u8 and stay alive (ideally page-locked: pinned_frame) until lk_frame_wait(ticket)."""
         assert frame.dtype == np.uint8 and frame.flags["C_CONTIGUOUS"]
         W, H, pitch = self._frame_geometry(frame, fmt)
-        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse)
         t = C.c_int(0)
         self._check(self._lib.ofps_hip_lk_push_frame_async(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels, radius,
                                                            iters, max_w, max_h, flags, C.byref(t)))
         self._lk_cap = getattr(self, "_lk_cap", {})
-        self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records)
+        self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records, reduced, sparse)
         return t.value
 
     def lk_frame_wait(self, ticket: int, out: np.ndarray | None = None):
@@ -710,19 +795,19 @@ class HipContext:
     def lk_push_frame_fused_async(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
                                   farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True,
                                   min_size=0.05, subdivide=3, target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16,
-                                  use_ransac=False, num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0) -> int:
+                                  use_ransac=False, num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, *, sparse=False) -> int:
         """Read-ahead form of lk_push_frame_fused: -> ticket once upload, flow, output stage, detector and estimator are enqueued.
         `frame` as for lk_push_frame_async; collect with lk_frame_fused_wait (or lk_frame_wait: the records alone)."""
         assert frame.dtype == np.uint8 and frame.flags["C_CONTIGUOUS"]
         W, H, pitch = self._frame_geometry(frame, fmt)
-        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse)
         prm = self._frame_params(0, 0, detector, min_size, subdivide, target_motion, estimator, aspect, fov_y_deg, use_ransac, num_iters,
                                  inlier_deg, num_samples, seed)
         t = C.c_int(0)
         self._check(self._lib.ofps_hip_lk_push_frame_fused_async(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels,
                                                                  radius, iters, max_w, max_h, flags, C.byref(prm), C.byref(t)))
         self._lk_cap = getattr(self, "_lk_cap", {})
-        self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records)
+        self._lk_cap[t.value] = self._lk_capacity(W, H, max_w, max_h, fullres_records, reduced, sparse)
         self._lk_dim = getattr(self, "_lk_dim", {})
         self._lk_dim[t.value] = self.block_dim(min_size, subdivide) if detector else 0
         self._lk_isl = getattr(self, "_lk_isl", {})
@@ -744,16 +829,16 @@ class HipContext:
     def lk_push_frame_fused(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
                             farneback=False, use_previous=False, reduced=False, fmt=0, fullres_records=False, detector=True, min_size=0.05,
                             subdivide=3, target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16, use_ransac=False,
-                            num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, want_entries=True, want_field=True) -> dict:
+                            num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, want_entries=True, want_field=True, *, sparse=False) -> dict:
         """One frame of a hip_lk / hip_flow stream -> records -> island + rotation in one call, the records staying on the device in
         between (ofps_hip_lk_push_frame_fused).  The same stream of frames as lk_push_frame."""
         frame = np.ascontiguousarray(frame, np.uint8)
         W, H, pitch = self._frame_geometry(frame, fmt)
-        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt)
+        flags = self._lk_flags(contrast_mask, fullres_records, farneback, use_previous, reduced, fmt, sparse)
         prm = self._frame_params(0, 0, detector, min_size, subdivide, target_motion, estimator, aspect, fov_y_deg, use_ransac, num_iters,
                                  inlier_deg, num_samples, seed)
         dim = self.block_dim(min_size, subdivide) if detector else 0
-        ent = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records), 4), np.float32) if want_entries else None
+        ent = np.zeros((self._lk_capacity(W, H, max_w, max_h, fullres_records, reduced, sparse), 4), np.float32) if want_entries else None
         fld = np.zeros((dim, dim, 2), np.float32) if (want_field and dim) else None
         res = _lib.FrameResult(); gw = C.c_int(0); gh = C.c_int(0)
         self._check(self._lib.ofps_hip_lk_push_frame_fused(self._h, frame.ctypes.data_as(C.POINTER(C.c_uint8)), W, H, pitch, levels, radius,

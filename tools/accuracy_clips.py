@@ -24,6 +24,9 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               "Scene cut" = P in those columns; with --sad-prefilter R also hip_sad_fi<Q>: on top of "Mean removal" = R (the first R)
               with --sad-split T [T ...] also hip_sad_b<T>: hip_sad with its "Split blocks" property at T (include/ofps_hip.h N1s); with
               --sad-median N also hip_sad_xb<T>: on top of "Median test" = N (the first N)
+              with --klt also hip_klt: the sparse decoder (include/ofps_hip.h N3) with its defaults -- cell 16, levels 4, window radius 7, 10
+              iterations, no residual limit; --klt-cell C [C ...] and --klt-residual R [R ...] add hip_klt_c<C>r<R> for every other pair of
+              "Cell size" and "Max residual"; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
   cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
               cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
@@ -168,8 +171,8 @@ CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
 
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
         fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
-        cut_clip=False, sad_split=()):
-    from ofps_amd.plugins import HipFlowDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
+        cut_clip=False, sad_split=(), klt=False, klt_cells=(16,), klt_residuals=(0,), skip=()):
+    from ofps_amd.plugins import HipFlowDecoder, HipKltDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
               # the reference's dense decoder runs Farneback over FIVE pyramid levels (cv-decoder/src/lib.rs:188-199): the same decoder with
@@ -225,6 +228,13 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
             combos[2:2] = [(f"hip_sad_xb{thr}", HipSadDecoder, False, props_xb), (f"hip_sad_xb{thr}", HipSadDecoder, True, props_xb)]
     if sad_only:
         combos = [c for c in combos if c[1] is HipSadDecoder]
+    if klt:             # the sparse decoder (include/ofps_hip.h N3): its defaults, and every other pair of "Cell size" and "Max residual" asked for
+        for cell in klt_cells:
+            for limit in klt_residuals:
+                tag = "hip_klt" if (cell, limit) == (16, 0) else f"hip_klt_c{cell}r{limit}"
+                props_k = {"Cell size": cell, "Max residual": limit}
+                combos += [(tag, HipKltDecoder, False, props_k), (tag, HipKltDecoder, True, props_k)]
+    combos = [c for c in combos if c[0] not in skip]
     res = {}
     clips = []
     for name, geom in clip_table(quick, fast_clips).items():
@@ -304,6 +314,8 @@ def table(res):
             cols[2:2] = [tag + "+lsq", tag + "+ransac"]
     if not any("hip_lk+lsq" in r for r in res.values()):       # --sad-only: no dense decoder ran
         cols = [c for c in cols if c.startswith(("hip_sad", "cpu_oracle"))]
+    klt_cols = sorted({k for r in res.values() for k in r if k.startswith("hip_klt")}, key=lambda k: (k.split("+")[0], k.endswith("ransac")))
+    cols[len(cols) - 1:len(cols) - 1] = klt_cols                   # in front of the CPU oracle's column
     lines = []
     lines.append("mean rotation error per frame, degrees (docs/statistics/err_av.csv's unit); clip rows, decoder+estimator columns")
     lines.append("clip,geometry,mean_rot_deg_per_frame,px_per_deg," + ",".join(cols))
@@ -375,11 +387,16 @@ def main():
     ap.add_argument("--cut-clip", action="store_true", help="add pan_0.2_cut: pan_0.2 with the second half of its frames from another canvas seed")
     ap.add_argument("--fast-clips", action="store_true", help="add 1080p pans of 1.5 and 3 degrees per frame: beyond the plain search's reach")
     ap.add_argument("--sad-only", action="store_true", help="only the hip_sad columns (the dense decoders take most of the run time)")
+    ap.add_argument("--klt", action="store_true", help="add the hip_klt columns: the sparse decoder with its defaults (also with --sad-only)")
+    ap.add_argument("--klt-cell", nargs="*", type=int, default=[16], metavar="C", help="with --klt: \"Cell size\" values; hip_klt_c<C>r<R> beside hip_klt")
+    ap.add_argument("--klt-residual", nargs="*", type=int, default=[0], metavar="R", help="with --klt: \"Max residual\" values (sixteenths of a grey level)")
+    ap.add_argument("--skip", nargs="*", default=[], metavar="NAME", help="decoder columns to leave out, e.g. hip_lk5 hip_flow")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
               sad_gate=args.sad_gate, sad_consistency=args.sad_consistency, sad_levels=args.sad_levels, fast_clips=args.fast_clips,
               sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
-              sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split))
+              sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split),
+              klt=args.klt, klt_cells=tuple(args.klt_cell), klt_residuals=tuple(args.klt_residual), skip=tuple(args.skip))
     txt = table(res)
     print(txt)
     if args.out:

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Times hip_klt (csrc/klt.hip, include/ofps_hip.h N3) on the device, with the plain hip_sad search and the dense hip_lk flow beside it in
+the same process.  Needs the GPU; prints one JSON line.
+
+Per geometry (1080p with cell 16, 4K with cell 8; levels 4, window radius 7, 10 iterations) and content (synth.luma_sequence: region-wise
+integer jumps; synth.camera_warp_pair: a smooth sub-pixel camera motion), on frames resident in device memory:
+  score    ofps_hip_klt_features_dev: one pass over the previous frame
+  pyramid  the 2 * (levels - 1) ofps_hip_sad_down2_dev launches both frames' levels cost
+  track    ofps_hip_klt_track_dev on the frame's own features: the pyramid and the track launch (track_alone = track - pyramid, derived)
+  flow     ofps_hip_klt_flow_dev: score + pyramid + track + status flags + ordered compaction + count, everything a decoder call enqueues
+  sad      ofps_hip_sad_flow_dev, 16 x 16 blocks, +-16, one pair: the plain search
+  lk       ofps_hip_lk_flow_dev with the bench's parameters (3 levels, radius 4, 3 steps), records out
+Protocol: time per call of a saturated queue -- `--calls` (50) calls between two HIP events on the context's stream --, the median of
+`--reps` (7) such windows behind `--warm` (2) windows that are not counted.  Beside the times: the slot count, the kept count and the
+status histogram of the flow (0 kept, 1 no feature, 2 flat, 3 left the frame, 4 residual)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ofps_amd import synth  # noqa: E402
+from ofps_amd.runtime import HipContext  # noqa: E402
+
+
+def window_ms(ctx, fn, calls, reps, warm):
+    out = []
+    for k in range(warm + reps):
+        ctx.timer_start()
+        for _ in range(calls):
+            fn()
+        ms = ctx.timer_stop() / calls
+        if k >= warm:
+            out.append(ms)
+    return {"median_us": round(float(np.median(out)) * 1e3, 2), "min_us": round(min(out) * 1e3, 2), "max_us": round(max(out) * 1e3, 2)}
+
+
+def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, reps, warm):
+    H, W = prev.shape
+    ctx.set_klt(cell, 2, 1, 1, max_residual)
+    ns = ctx.klt_slot_count(W, H)
+    d_fr = ctx.malloc(2 * W * H)
+    ctx.memcpy_h2d(d_fr, np.stack([prev, cur]))
+    d_prev, d_cur = d_fr, d_fr + W * H
+    d_tri, d_quad, d_rec, d_cnt, d_slots = ctx.malloc(12 * ns), ctx.malloc(16 * ns), ctx.malloc(16 * ns), ctx.malloc(16), ctx.malloc(24 * ns)
+    ctx.klt_features_dev(d_prev, W, H, W, d_tri)
+    ctx.sync()
+    tri = np.zeros((ns, 3), np.int32)
+    ctx.memcpy_d2h(tri, d_tri)
+    pts = np.ascontiguousarray(tri[tri[:, 0] >= 0][:, :2])
+    d_pts = ctx.malloc(max(pts.nbytes, 16))
+    ctx.memcpy_h2d(d_pts, pts)
+    pyr = []                                                  # the levels' own buffers for the pyramid-alone timing
+    w, h = W, H
+    for _ in range(1, levels):
+        w, h = w >> 1, h >> 1
+        s = (w + 63) & ~63
+        pyr.append((w, h, s, ctx.malloc(s * h), ctx.malloc(s * h)))
+
+    def pyramid():
+        sp, sc, sw, sh, ss = d_prev, d_cur, W, H, W
+        for (lw, lh, ls, dp, dc) in pyr:
+            ctx.sad_down2_dev(sp, sw, sh, ss, dp, ls)
+            ctx.sad_down2_dev(sc, sw, sh, ss, dc, ls)
+            sp, sc, sw, sh, ss = dp, dc, lw, lh, ls
+
+    nblk = (W // 16) * (H // 16)
+    d_sad = ctx.malloc(16 * nblk)
+    d_lk = ctx.malloc(16 * W * H)
+    t = {
+        "score": window_ms(ctx, lambda: ctx.klt_features_dev(d_prev, W, H, W, d_tri), calls, reps, warm),
+        "pyramid": window_ms(ctx, pyramid, calls, reps, warm),
+        "track": window_ms(ctx, lambda: ctx.klt_track_dev(d_prev, d_cur, W, H, W, d_pts, len(pts), levels, radius, iters, d_quad), calls, reps, warm),
+        "flow": window_ms(ctx, lambda: ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots), calls, reps, warm),
+        "sad_16x16_pm16": window_ms(ctx, lambda: ctx.sad_flow_dev(d_fr, 2, W, H, W, W * H, 0, 16, 16, d_sad, None), calls, reps, warm),
+        "lk_3_4_3": window_ms(ctx, lambda: ctx.lk_flow_dev(d_prev, d_cur, W, H, W, 3, 4, 3, None, d_lk), calls, reps, warm),
+    }
+    t["track_alone_derived_us"] = round(t["track"]["median_us"] - t["pyramid"]["median_us"], 2)
+    ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots)
+    ctx.sync()
+    slots = np.zeros((ns, 6), np.int32)
+    cnt = np.zeros(4, np.uint32)
+    ctx.memcpy_d2h(slots, d_slots)
+    ctx.memcpy_d2h(cnt, d_cnt)
+    u, c = np.unique(slots[:, 5], return_counts=True)
+    for p in [d_fr, d_tri, d_quad, d_rec, d_cnt, d_slots, d_pts, d_sad, d_lk] + [b for lv in pyr for b in lv[3:]]:
+        ctx.free(p)
+    return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
+            "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warm", type=int, default=2)
+    ap.add_argument("--levels", type=int, default=4)
+    ap.add_argument("--radius", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--max-residual", type=int, default=0)
+    ap.add_argument("--no-4k", action="store_true")
+    a = ap.parse_args()
+    ctx = HipContext(0)
+    rows = []
+    for W, H, cell in [(1920, 1080, 16)] + ([] if a.no_4k else [(3840, 2160, 8)]):
+        lum = synth.luma_sequence(2, W, H, max_step=6, seed=5)
+        warp = synth.camera_warp_pair(W, H, shift=(3.3 * W / 1920, -2.6 * H / 1080))
+        for name, (p, c) in (("luma_sequence", (lum[0], lum[1])), ("camera_warp_pair", (warp[0], warp[1]))):
+            rows.append(one(ctx, name, np.ascontiguousarray(p), np.ascontiguousarray(c), cell, a.levels, a.radius, a.iters, a.max_residual,
+                            a.calls, a.reps, a.warm))
+            print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    ctx.close()
+    print(json.dumps({"calls_per_window": a.calls, "windows": a.reps, "warm_windows": a.warm, "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()

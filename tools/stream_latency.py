@@ -3,7 +3,8 @@
 fused per frame (ofps_hip_push_frame); steady-state latency = frame fully received -> island + quaternion on the
 host.  The feeder thread paces raw luma frames (8-byte header: u32 W, u32 H, then W*H bytes) through a loop-back
 socket, the way ofps::utils::open_file("tcp://...") feeds a decoder (ofps/src/utils.rs:92-118).  Prints JSON.
---split T: hip_sad's split blocks at threshold T (include/ofps_hip.h N1s); --lib <libofps_hip.so>: another build of the library (a build
+--split T: hip_sad's split blocks at threshold T (include/ofps_hip.h N1s); --klt: the sparse decoder in place of hip_sad (ofps_hip_lk_push_frame_fused with
+OFPS_HIP_FLOW_SPARSE: cell 16, 4 levels, window radius 7, 10 iterations; include/ofps_hip.h N3); --lib <libofps_hip.so>: another build of the library (a build
 from before a feature runs without that feature's entry points)."""
 import argparse
 import json
@@ -46,6 +47,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--ransac", action="store_true")
     ap.add_argument("--split", type=int, default=0, metavar="T")
+    ap.add_argument("--klt", action="store_true")
     ap.add_argument("--lib", default=None)
     args = ap.parse_args()
     W, H = args.width, args.height
@@ -82,13 +84,16 @@ def main():
         recv_exact(sock, w * h, buf)
         t_arr = time.perf_counter()
         frame = pinned
-        r = ctx.push_frame(frame, block=16, search_range=16, use_ransac=args.ransac, seed=k)
+        if args.klt:
+            r = ctx.lk_push_frame_fused(frame, 4, 7, 10, sparse=True, use_ransac=args.ransac, seed=k, want_entries=False, want_field=False)
+        else:
+            r = ctx.push_frame(frame, block=16, search_range=16, use_ransac=args.ransac, seed=k)
         t_done = time.perf_counter()
         if k >= 10:                                               # steady state
             lat.append((t_done - t_arr) * 1e3)
         islands += r["motion"] is not None
     lat = np.array(lat)
-    print(json.dumps({"config": f"{W}x{H}@{args.fps:g} TCP loop-back, 16x16 +-16 SAD + block-motion + almeida "
+    print(json.dumps({"config": f"{W}x{H}@{args.fps:g} TCP loop-back, {'hip_klt (cell 16, 4 levels, radius 7, 10 iterations)' if args.klt else '16x16 +-16 SAD'} + block-motion + almeida "
                                 f"({'RANSAC' if args.ransac else 'LSQ'}) per frame", "frames": args.frames,
                       "latency_ms": {"p50": round(float(np.percentile(lat, 50)), 3), "p90": round(float(np.percentile(lat, 90)), 3),
                                      "p99": round(float(np.percentile(lat, 99)), 3), "max": round(float(lat.max()), 3)},
