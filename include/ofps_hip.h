@@ -726,6 +726,41 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
 int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
                           void* d_out_entries, void* d_out_count /* one uint32 */, void* d_out_slots /* or NULL */);
 
+/* ---- N3b: hip_klt on a batch of pairs, and in the batched stream forms (csrc/klt.hip, csrc/pipeline.hip) ----
+ * Nothing about the arithmetic is new.  Item k of a sequence of n_frames >= 2 frames, frame_pitch >= stride * H bytes apart, is the pair
+ * (k, k + 1) with ref_mode 0 and (0, k + 1) with ref_mode 1; pairs = n_frames - 1.  Per item the kept records (kept slots first, in slot
+ * order), their count and the raw slots equal ofps_hip_klt_flow on that pair with the context's settings, bit for bit.  Item k's records
+ * lead item k's slot of ofps_hip_klt_slot_count(W, H, cell) records; what lies at and behind its count is unspecified (the host form
+ * leaves it untouched); counts[k] is a uint32.  pairs * slots < 2^31.  The number of launches does not depend on pairs: one score launch
+ * over the distinct previous frames, one halving per level over the distinct frames, one track launch of pairs * slots waves, one segmented
+ * compaction (one workgroup per item).  Refused with OFPS_HIP_EINVAL before anything is enqueued or uploaded: what ofps_hip_klt_flow
+ * refuses, n_frames < 2, a ref_mode other than 0 | 1, frame_pitch < stride * H.  The _dev form enqueues on the context's stream and
+ * synchronises nothing.
+ *
+ * ofps_hip_set_batch_decoder: what ofps_hip_push_frames_async and the ofps_hip_multi_push_frames_async workers' pushes search with.
+ * OFPS_HIP_BATCH_DECODER_SAD (default): hip_sad, exactly as without this switch; levels, radius and iters are not read.
+ * OFPS_HIP_BATCH_DECODER_KLT: hip_klt with these levels, window radius and iterations (defaults 4, 7, 10) and the ofps_hip_set_klt values
+ * the context has at the push.  Then params->block and params->range are ignored; a frame's record capacity is the slot count and
+ * out_entries holds n * 4 * slots floats; frame j's n_vectors is its kept count, made on the device and read back behind the quaternions;
+ * detector, estimator, islands and compensation read the counts on the device, nothing is read back between push and wait; a least-squares
+ * fit of too few records is the identity, as in the fused sparse form of the dense decoders' stream; the stream's first frame, a geometry
+ * change and ofps_hip_reset_frames behave as with hip_sad; a frame the decoder refuses (N3) is OFPS_HIP_EINVAL before the upload.  Only
+ * luma frames.  Bounds against six ofps_hip_lk_push_frame_fused calls with OFPS_HIP_FLOW_SPARSE: records, counts and detector results
+ * equal bit for bit, the quaternion to 2e-6; frame j's RANSAC seed is params->seed + j.  ofps_hip_multi_sad_flow, _stage_frames,
+ * _run_resident and _fetch stay hip_sad.  The multi-device workers' contexts take the switch and the settings from the environment at
+ * ofps_hip_init alone: OFPS_HIP_BATCH_DECODER, OFPS_HIP_KLT_LEVELS, OFPS_HIP_KLT_RADIUS, OFPS_HIP_KLT_ITERS, OFPS_HIP_KLT_CELL,
+ * OFPS_HIP_KLT_SCORE_RADIUS, OFPS_HIP_KLT_MIN_SCORE, OFPS_HIP_KLT_MIN_EIG, OFPS_HIP_KLT_MAX_RESIDUAL (all ofps_hip_set_option names too).
+ * Additive: OFPS_HIP_API_VERSION stays. */
+int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                            int levels, int radius, int iters, float* out_entries /* pairs * 4 * slots */, uint32_t* out_counts /* pairs */,
+                            int32_t* out_slots /* pairs * 6 * slots, or NULL */);
+int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                int levels, int radius, int iters, void* d_out_entries /* pairs * slots float4 */,
+                                void* d_out_counts /* pairs uint32 */, void* d_out_slots /* pairs * 6 * slots int32, or NULL */);
+enum { OFPS_HIP_BATCH_DECODER_SAD = 0, OFPS_HIP_BATCH_DECODER_KLT = 1 };
+int ofps_hip_set_batch_decoder(ofps_hip_ctx* ctx, int decoder, int levels, int radius, int iters);   /* levels, radius, iters: read only for KLT */
+int ofps_hip_get_batch_decoder(ofps_hip_ctx* ctx, int32_t* decoder, int32_t* levels, int32_t* radius, int32_t* iters);   /* any may be NULL */
+
 /* ---- A1-A4: MotionFieldDensifier ---- */
 int ofps_hip_densify(ofps_hip_ctx* ctx, const float* entries, size_t n, int w, int h,
                      float* out_field /* 2*w*h, cell (x,y) at 2*(y*w+x) */,

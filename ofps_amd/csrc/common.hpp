@@ -232,6 +232,9 @@ struct ofps_hip_ctx {
         // ofps_hip_set_klt: hip_klt's lattice cell (8 | 16 | 32), score window radius [1, 3], smallest score of a feature, smallest eigenvalue of
         // a template's structure tensor per pixel [1, 65535], residual limit in sixteenths of a grey level per pixel (0 = off) (klt.hip, N3)
         int klt_cell = 16, klt_score_radius = 2, klt_min_score = 1, klt_min_eig = 1, klt_max_residual = 0;
+        // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
+        // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
+        int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;
         int multi_rccl = 0;              // OFPS_HIP_MULTI_RCCL: ofps_hip_multi_init fans the shared key frame out by ncclBroadcast (multi.hip)
         // fault injectors: only builds with -DOFPS_HIP_TEST_HOOKS (libofps_hip_testhooks.so) can set them, and only
         // through ofps_hip_set_option -- never from the environment
@@ -370,12 +373,22 @@ int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
                           void* d_out_best);
 // one pyramid step of one frame (what ofps_hip_sad_down2_dev enqueues): W x H -> (W >> 1) x (H >> 1)
 int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int src_stride, uint8_t* dst, int dst_stride);
+// ... of `frames` frames src_pitch bytes apart, their halved forms dst_pitch apart, in one launch
+int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
+                            int dst_stride, long long frames);
 // klt.hip (include/ofps_hip.h N3): hip_klt on one pair of device frames with the context's settings -- the kept records first, in slot order, and
 // their count in device memory; d_out holds ofps_hip_klt_slot_count records, d_slots (optional) 6 int32 per slot.  Enqueues on ctx->stream only
 // the decoder's limits on one call: levels, radius, iters, a frame of 8 .. 32768 pixels a side whose top level is at least 8 x 8, stride >= W
+constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3, kKltMaxMinEig = 65535, kKltMaxResidual = 4080;
 int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who);
 int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
                     float4* d_out, uint32_t* d_count, int* d_slots);
+// N3b: item k of `pairs` pairs of `f` = klt_flow_device on that pair, bit for bit, in a number of launches that does not depend on `pairs`:
+// one score launch over the distinct prev frames, one halving per level over the distinct frames, one track launch of pairs x slots waves, the
+// segmented compaction.  d_out: pairs slots of the slot count, item k's kept records lead slot k; d_counts: pairs counts; d_slots (optional):
+// 6 int32 per slot, item-major.  Works in S_KLT_PYR and S_KLT_WORK (compute stream only, consumed in front of the compaction: tickets share them)
+int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
+                          int* d_slots);
 // sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
 constexpr int kSadPrefilterMax = 16;
 int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
@@ -438,6 +451,10 @@ inline uint32_t* gate_kept(char* flags, size_t nblk, size_t items = 1) {
     return reinterpret_cast<uint32_t*>(flags + ((items * nblk * sizeof(uint32_t) + 15) & ~size_t(15)));
 }
 inline uint8_t* gate_keep(char* flags, size_t nblk, size_t items = 1) { return reinterpret_cast<uint8_t*>(gate_kept(flags, nblk, items)) + gate_kept_bytes(items); }
+
+// the segmented ordered compaction (compact_items_kernel): item k's records with a non-zero flag -> the head of slot k of d_out, their number ->
+// d_counts[k]; every array holds items x n, item-major; one workgroup per item, one launch, on ctx->stream.  d_out may not alias d_in
+int compact_items_device(ofps_hip_ctx* ctx, const float4* d_in, const uint8_t* d_flags, size_t n, int items, float4* d_out, uint32_t* d_counts);
 
 // sad_consistency.hip: hip_sad's forward-backward consistency check (include/ofps_hip.h N1c)
 constexpr int kSadConsistencyMax = 129;                     // 2 * 64 + 1: above every residual of the largest search range

@@ -124,6 +124,33 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_SAD_BATCH_FILTER")) {
         if (!unset && strcmp(value, "0") && strcmp(value, "1")) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' is not 0|1", name, value);
         o.sad_batch_filter = unset ? dflt.sad_batch_filter : iv;
+    } else if (!strcmp(name, "OFPS_HIP_BATCH_DECODER")) {
+        if (!unset && strcmp(value, "0") && strcmp(value, "1")) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' is not 0|1", name, value);
+        o.batch_decoder = unset ? dflt.batch_decoder : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_LEVELS")) {
+        if (!unset && (iv < 1 || iv > kKltMaxLevels)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [1, %d]", name, iv, kKltMaxLevels);
+        o.klt_levels = unset ? dflt.klt_levels : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_RADIUS")) {
+        if (!unset && (iv < 1 || iv > kKltMaxRadius)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [1, %d]", name, iv, kKltMaxRadius);
+        o.klt_radius = unset ? dflt.klt_radius : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_ITERS")) {
+        if (!unset && (iv < 1 || iv > kKltMaxIters)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [1, %d]", name, iv, kKltMaxIters);
+        o.klt_iters = unset ? dflt.klt_iters : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_CELL")) {
+        if (!unset && iv != 8 && iv != 16 && iv != 32) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d is not 8|16|32", name, iv);
+        o.klt_cell = unset ? dflt.klt_cell : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_SCORE_RADIUS")) {
+        if (!unset && (iv < 1 || iv > kKltMaxScoreRadius)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [1, %d]", name, iv, kKltMaxScoreRadius);
+        o.klt_score_radius = unset ? dflt.klt_score_radius : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_MIN_SCORE")) {
+        if (!unset && iv < 1) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d is below 1", name, iv);
+        o.klt_min_score = unset ? dflt.klt_min_score : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_MIN_EIG")) {
+        if (!unset && (iv < 1 || iv > kKltMaxMinEig)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [1, %d]", name, iv, kKltMaxMinEig);
+        o.klt_min_eig = unset ? dflt.klt_min_eig : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_MAX_RESIDUAL")) {
+        if (!unset && (iv < 0 || iv > kKltMaxResidual)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kKltMaxResidual);
+        o.klt_max_residual = unset ? dflt.klt_max_residual : iv;
     } else if (!strcmp(name, "OFPS_HIP_MULTI_RCCL")) {
         o.multi_rccl = unset ? 0 : (iv != 0);
     } else if (!strcmp(name, "OFPS_HIP_ALMEIDA_TEST_FAULT") || !strcmp(name, "OFPS_HIP_LK_TEST_FALL") ||
@@ -149,7 +176,9 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_ALMEIDA_HIER", "OFPS_HIP_ALMEIDA_FAST", "OFPS_HIP_ALMEIDA_ONE_XCD", "OFPS_HIP_ALMEIDA_PROF", "OFPS_HIP_LK_PROF", "OFPS_HIP_LK_SERIAL", "OFPS_HIP_FB_PREPARE_AHEAD", "OFPS_HIP_MULTI_RCCL",
     "OFPS_HIP_SAD_MOTION_SCALE", "OFPS_HIP_DETECT_COMPENSATE", "OFPS_HIP_SAD_GATE", "OFPS_HIP_SAD_CONSISTENCY", "OFPS_HIP_SAD_LEVELS",
     "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN", "OFPS_HIP_SAD_BATCH_FILTER",
-    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS", "OFPS_HIP_SAD_SPLIT"};
+    "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS", "OFPS_HIP_SAD_SPLIT",
+    "OFPS_HIP_KLT_CELL", "OFPS_HIP_KLT_SCORE_RADIUS", "OFPS_HIP_KLT_MIN_SCORE", "OFPS_HIP_KLT_MIN_EIG", "OFPS_HIP_KLT_MAX_RESIDUAL",
+    "OFPS_HIP_BATCH_DECODER", "OFPS_HIP_KLT_LEVELS", "OFPS_HIP_KLT_RADIUS", "OFPS_HIP_KLT_ITERS"};
 
 }  // namespace ofps
 

@@ -17,7 +17,6 @@ namespace {
 
 using namespace ofps;
 
-constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3;
 constexpr int kKltTemplate = (2 * kKltMaxRadius + 3) * (2 * kKltMaxRadius + 3);       // 17 x 17 samples
 constexpr int kKltTemplatePitch = (kKltTemplate + 3) & ~3;
 constexpr int kKltTrackWaves = 4;
@@ -39,6 +38,14 @@ struct KltTrackParams {
     int* out_slots;                      // 6 per slot or null
     float4* out_rec;                     // the slot's record (zeros unless kept) or null
     uint8_t* out_flag;                   // 1 = kept; beside out_rec
+};
+
+// the batch form's track launch (N3b): slot s belongs to item s / slots_per_item, whose frames of level l lie item * pitch[l] behind the
+// level's base (a pitch of 0: one frame for every item); shared_features: one set of triples, of the key frame, for every item
+struct KltTrackBatchParams {
+    KltTrackParams t;
+    size_t prev_pitch[kKltMaxLevels], cur_pitch[kKltMaxLevels];
+    int slots_per_item, shared_features;
 };
 
 __device__ __forceinline__ void wave_sync() {
@@ -74,9 +81,9 @@ __device__ __forceinline__ unsigned long long ceil_sqrt_u64(unsigned long long D
     return s + (s * s < D ? 1 : 0);
 }
 
+// one workgroup's cell of one frame; `out`: that frame's triples
 template <int C>
-__global__ __launch_bounds__(C * C < 256 ? C * C : 256) void klt_score_kernel(const uint8_t* __restrict__ img, int W, int H, int stride, int r,
-                                                                              int min_score, int* __restrict__ out) {
+__device__ __forceinline__ void klt_score_body(const uint8_t* __restrict__ img, int W, int H, int stride, int r, int min_score, int* __restrict__ out) {
     constexpr int T = C * C < 256 ? C * C : 256;
     constexpr int PWMAX = C + 2 * (kKltMaxScoreRadius + 1), HRMAX = C + 2 * kKltMaxScoreRadius;
     __shared__ uint8_t P[PWMAX * PWMAX];
@@ -141,6 +148,20 @@ __global__ __launch_bounds__(C * C < 256 ? C * C : 256) void klt_score_kernel(co
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(C * C < 256 ? C * C : 256) void klt_score_kernel(const uint8_t* __restrict__ img, int W, int H, int stride, int r,
+                                                                              int min_score, int* __restrict__ out) {
+    klt_score_body<C>(img, W, H, stride, r, min_score, out);
+}
+
+// N3b: frame blockIdx.z lies frame_pitch bytes further, its triples 3 * slots ints further
+template <int C>
+__global__ __launch_bounds__(C * C < 256 ? C * C : 256) void klt_score_batch_kernel(const uint8_t* __restrict__ img, size_t frame_pitch, int W, int H,
+                                                                                    int stride, int r, int min_score, int* __restrict__ out) {
+    klt_score_body<C>(img + (size_t)blockIdx.z * frame_pitch, W, H, stride, r, min_score,
+                      out + 3 * (size_t)blockIdx.z * ((size_t)gridDim.x * gridDim.y));
+}
+
 // S(img, q): bilinear sample at a 1/256-pixel position, pixel indices clamped into the frame, 8 fractional bits
 __device__ __forceinline__ int klt_sample(const uint8_t* __restrict__ img, int W, int H, int stride, int qx, int qy) {
     const int ix = qx >> 8, iy = qy >> 8, fx = qx & 255, fy = qy & 255;
@@ -172,13 +193,21 @@ __device__ __forceinline__ void klt_store(const KltTrackParams& p, long long slo
     }
 }
 
-__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const KltTrackParams p) {
-    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+// one wave's slot.  BATCH: the slot's item picks the frames (b: the launch's pitches) and, with shared features, its triple; the outputs are
+// indexed by the slot either way.  Everything behind the pointers is one text for both kernels
+template <bool BATCH>
+__device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
     if (slot >= p.n) return;                                  // the whole wave
     int* I = tmpl + wave * kKltTemplatePitch;
-    const int* pt = p.pts + (size_t)slot * p.pt_stride;
+    size_t item = 0;
+    long long pt_slot = slot;
+    if constexpr (BATCH) {                                    // slot < 2^31; the item is the same for the wave's lanes: a scalar
+        item = (size_t)__builtin_amdgcn_readfirstlane((int)slot / b->slots_per_item);
+        if (b->shared_features) pt_slot = slot - (long long)item * b->slots_per_item;
+    }
+    const int* pt = p.pts + (size_t)pt_slot * p.pt_stride;
     const int x = pt[0], y = pt[1], score = p.from_features ? pt[2] : 0;
     const int W0 = p.lv.W[0], H0 = p.lv.H[0];
     const int w = p.w, n = 2 * w + 1, n2 = n * n, m = n + 2;
@@ -199,8 +228,8 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const Kl
     }
     int cqx = 0, cqy = 0;
     for (int l = p.L - 1; l >= 0 && status == KLT_KEPT; --l) {
-        const uint8_t* __restrict__ prev = p.lv.prev[l];
-        const uint8_t* __restrict__ cur = p.lv.cur[l];
+        const uint8_t* __restrict__ prev = BATCH ? p.lv.prev[l] + item * b->prev_pitch[l] : p.lv.prev[l];
+        const uint8_t* __restrict__ cur = BATCH ? p.lv.cur[l] + item * b->cur_pitch[l] : p.lv.cur[l];
         const int Wl = p.lv.W[l], Hl = p.lv.H[l], sl = p.lv.stride[l];
         cqx = (((2 * x + 1) * 128) >> l) - 128;
         cqy = (((2 * y + 1) * 128) >> l) - 128;
@@ -254,10 +283,11 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const Kl
         if (fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1)) status = KLT_LEFT;
     }
     if (status == KLT_KEPT) {
+        const uint8_t* __restrict__ cur0 = BATCH ? p.lv.cur[0] + item * b->cur_pitch[0] : p.lv.cur[0];
         long long sum = 0;
         for (int k = 0; k < 4; ++k) {
             if (lane + 64 * k < n2) {
-                const int d = klt_sample(p.lv.cur[0], W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
+                const int d = klt_sample(cur0, W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
                 sum += d < 0 ? -d : d;
             }
         }
@@ -265,6 +295,16 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const Kl
         if (p.max_residual > 0 && res > 16ll * p.max_residual * n2) status = KLT_RESIDUAL;
     }
     if (lane == 0) klt_store(p, slot, x, y, score, dqx, dqy, res, status);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false>(p, nullptr, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_kernel(const KltTrackBatchParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true>(p.t, &p, tmpl);
 }
 
 struct KltSettings { int cell, r, min_score, min_eig, max_residual; };
@@ -277,8 +317,8 @@ int klt_check_settings(ofps_hip_ctx* ctx, int cell, int r, int min_score, int mi
     OFPS_REQUIRE(ctx, cell == 8 || cell == 16 || cell == 32, "%s: cell %d is not 8|16|32", who, cell);
     OFPS_REQUIRE(ctx, r >= 1 && r <= kKltMaxScoreRadius, "%s: score_radius %d outside [1, %d]", who, r, kKltMaxScoreRadius);
     OFPS_REQUIRE(ctx, min_score >= 1, "%s: min_score %d outside [1, 2^31 - 1]", who, min_score);
-    OFPS_REQUIRE(ctx, min_eig >= 1 && min_eig <= 65535, "%s: min_eig %d outside [1, 65535]", who, min_eig);
-    OFPS_REQUIRE(ctx, max_residual >= 0 && max_residual <= 4080, "%s: max_residual %d outside [0, 4080]", who, max_residual);
+    OFPS_REQUIRE(ctx, min_eig >= 1 && min_eig <= kKltMaxMinEig, "%s: min_eig %d outside [1, 65535]", who, min_eig);
+    OFPS_REQUIRE(ctx, max_residual >= 0 && max_residual <= kKltMaxResidual, "%s: max_residual %d outside [0, 4080]", who, max_residual);
     return OFPS_HIP_OK;
 }
 
@@ -343,6 +383,75 @@ int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p) {
     return OFPS_HIP_OK;
 }
 
+// ---- N3b: the batch form's three steps, each one launch (the pyramid: one per level) whatever the number of pairs
+// `frames` frames `pitch` bytes apart -> their triples, 3 * slots ints apart
+int klt_features_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_img, size_t pitch, int frames, int W, int H, int stride, const KltSettings& s,
+                              int* d_out) {
+    OFPS_REQUIRE(ctx, frames >= 1 && frames <= 65535, "klt_flow_batch: %d frames to score (at most 65535)", frames);
+    const dim3 grid((W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell, frames);
+    if (s.cell == 8) hipLaunchKernelGGL(klt_score_batch_kernel<8>, grid, dim3(64), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
+    else if (s.cell == 16) hipLaunchKernelGGL(klt_score_batch_kernel<16>, grid, dim3(256), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
+    else hipLaunchKernelGGL(klt_score_batch_kernel<32>, grid, dim3(256), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+// the levels above 0 of the distinct frames of `pairs` pairs in S_KLT_PYR -> b->t.lv (the levels' bases) and the levels' pitches.  A chain
+// (consecutive pairs of one sequence) or a key frame followed by its current frames is one run of frames: one halving per level; two unrelated
+// sets take two
+int klt_pyramid_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, KltTrackBatchParams* b) {
+    KltLevels* lv = &b->t.lv;
+    const SadFrames::Sets sets = f.sets(pairs);
+    const bool key_run = !sets.chain && !sets.prev_many && sets.cur_many && f.cur_base == f.prev_base + f.cur_pitch;      // frames 0, 1 .. pairs of one sequence
+    const long long total = sets.nprev + sets.ncur;
+    size_t off[kKltMaxLevels] = {}, bytes = 0;
+    lv->prev[0] = f.prev_base; lv->cur[0] = f.cur_base; lv->W[0] = f.W; lv->H[0] = f.H; lv->stride[0] = f.stride;
+    b->prev_pitch[0] = f.prev_pitch; b->cur_pitch[0] = f.cur_pitch;
+    for (int l = 1; l < kKltMaxLevels; ++l) {
+        lv->prev[l] = lv->cur[l] = nullptr;
+        lv->W[l] = lv->H[l] = lv->stride[l] = 0;
+        b->prev_pitch[l] = b->cur_pitch[l] = 0;
+        if (l >= levels) continue;
+        lv->W[l] = lv->W[l - 1] >> 1; lv->H[l] = lv->H[l - 1] >> 1;
+        lv->stride[l] = (lv->W[l] + 63) & ~63;
+        off[l] = bytes; bytes += (size_t)total * lv->stride[l] * lv->H[l];
+    }
+    if (levels == 1) return OFPS_HIP_OK;
+    auto* pyr = static_cast<uint8_t*>(scratch(ctx, S_KLT_PYR, bytes));
+    if (!pyr) return OFPS_HIP_ENOMEM;
+    for (int l = 1; l < levels; ++l) {
+        const size_t pitch = (size_t)lv->stride[l] * lv->H[l];
+        uint8_t* dp = pyr + off[l];
+        uint8_t* dc = dp + (size_t)sets.cur_first() * pitch;
+        const int Wp = lv->W[l - 1], Hp = lv->H[l - 1], sp = lv->stride[l - 1];
+        int rc;
+        if (sets.chain) rc = sad_down2_frames_device(ctx, lv->prev[l - 1], b->prev_pitch[l - 1], Wp, Hp, sp, dp, pitch, lv->stride[l], sets.nprev);
+        else if (key_run) rc = sad_down2_frames_device(ctx, lv->prev[l - 1], b->cur_pitch[l - 1], Wp, Hp, sp, dp, pitch, lv->stride[l], total);
+        else {
+            rc = sad_down2_frames_device(ctx, lv->prev[l - 1], b->prev_pitch[l - 1], Wp, Hp, sp, dp, pitch, lv->stride[l], sets.nprev);
+            if (rc == OFPS_HIP_OK) rc = sad_down2_frames_device(ctx, lv->cur[l - 1], b->cur_pitch[l - 1], Wp, Hp, sp, dc, pitch, lv->stride[l], sets.ncur);
+        }
+        if (rc != OFPS_HIP_OK) return rc;
+        lv->prev[l] = dp; lv->cur[l] = dc;
+        b->prev_pitch[l] = sets.prev_many ? pitch : 0; b->cur_pitch[l] = sets.cur_many ? pitch : 0;
+    }
+    return OFPS_HIP_OK;
+}
+
+int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
+    if (b.t.n <= 0) return OFPS_HIP_OK;
+    hipLaunchKernelGGL(klt_track_batch_kernel, dim3((unsigned)((b.t.n + kKltTrackWaves - 1) / kKltTrackWaves)), dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+int klt_check_sequence(ofps_hip_ctx* ctx, int n_frames, int H, int stride, size_t frame_pitch, int ref_mode, const char* who) {
+    OFPS_REQUIRE(ctx, n_frames >= 2 && n_frames <= 65536, "%s: n_frames %d outside [2, 65536]", who, n_frames);
+    OFPS_REQUIRE(ctx, ref_mode == 0 || ref_mode == 1, "%s: ref_mode %d is not 0|1", who, ref_mode);
+    OFPS_REQUIRE(ctx, frame_pitch >= (size_t)stride * H, "%s: frame_pitch %zu is below stride * H = %zu", who, frame_pitch, (size_t)stride * H);
+    return OFPS_HIP_OK;
+}
+
 }  // namespace
 
 namespace ofps {
@@ -375,6 +484,41 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
     rc = klt_track_launch(ctx, p);
     if (rc != OFPS_HIP_OK) return rc;
     return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_count) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_count);
+}
+
+// N3b.  S_KLT_WORK: [triples of the distinct prev frames][raw records, pairs x slots][keep flags, pairs x slots].  Both scratch slots are
+// written and read on ctx->stream alone and are dead behind the compaction, so two tickets of the batched stream share them; scratch() waits
+// for that stream before it frees a slot it has to grow, which is all the order they need
+int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
+                          int* d_slots) {
+    const KltSettings s = klt_settings(ctx);
+    const size_t ns = klt_slots(f.W, f.H, s.cell);
+    OFPS_REQUIRE(ctx, pairs >= 1 && (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)",
+                 pairs, ns);
+    const size_t total = (size_t)pairs * ns;
+    const int scored = f.prev_pitch ? pairs : 1;              // the distinct prev frames
+    const size_t o_raw = pad16((size_t)scored * ns * 3 * sizeof(int)), o_flag = o_raw + total * sizeof(float4);
+    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_flag + pad16(total)));
+    if (!work) return OFPS_HIP_ENOMEM;
+    auto* d_feat = reinterpret_cast<int*>(work);
+    auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
+    auto* d_flag = reinterpret_cast<uint8_t*>(work + o_flag);
+    int rc = klt_features_batch_device(ctx, f.prev_base, f.prev_pitch, scored, f.W, f.H, f.stride, s, d_feat);
+    if (rc != OFPS_HIP_OK) return rc;
+    KltTrackBatchParams b{};
+    rc = klt_pyramid_batch_device(ctx, f, pairs, levels, &b);
+    if (rc != OFPS_HIP_OK) return rc;
+    KltTrackParams& p = b.t;
+    p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
+    p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)total;
+    p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
+    b.slots_per_item = (int)ns; b.shared_features = f.prev_pitch ? 0 : 1;
+    rc = klt_track_batch_launch(ctx, b);
+    if (rc != OFPS_HIP_OK) return rc;
+    // one workgroup per item is right for a batch; ONE pair through it would scan a 4K frame's 129,600 slots on one compute unit (measured:
+    // 5 % of the pair's time), so a batch of one pair keeps the one-pair form's compactions, as SadFilter::finish does (sad_gate.hip)
+    if (pairs == 1) return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_counts) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_counts);
+    return compact_items_device(ctx, d_raw, d_flag, ns, pairs, d_out, d_counts);
 }
 
 }  // namespace ofps
@@ -515,6 +659,76 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (count > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "klt_flow: the device counted %u records in %zu slots", count, ns);
     if (count) OFPS_HIP_TRY(ctx, hipMemcpy(out_entries, d_io, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost));
     *n_out = count;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                int levels, int radius, int iters, void* d_out_entries, void* d_out_counts, void* d_out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_frames && d_out_entries && d_out_counts, "klt_flow_batch: null device pointer");
+    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
+    if (rc == OFPS_HIP_OK) rc = klt_check_sequence(ctx, n_frames, H, stride, frame_pitch, ref_mode, "klt_flow_batch");
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ofps::SadFrames f = ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride);
+    return ofps::klt_flow_batch_device(ctx, f, n_frames - 1, levels, radius, iters, static_cast<float4*>(d_out_entries),
+                                       static_cast<uint32_t*>(d_out_counts), static_cast<int*>(d_out_slots));
+}
+
+int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                            int levels, int radius, int iters, float* out_entries, uint32_t* out_counts, int32_t* out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, frames && out_entries && out_counts, "klt_flow_batch: null host pointer");
+    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
+    if (rc == OFPS_HIP_OK) rc = klt_check_sequence(ctx, n_frames, H, stride, frame_pitch, ref_mode, "klt_flow_batch");
+    if (rc != OFPS_HIP_OK) return rc;
+    const int pairs = n_frames - 1;
+    const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
+    OFPS_REQUIRE(ctx, (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)", pairs, ns);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int ss = (W + 63) & ~63;
+    const size_t fb = (size_t)ss * H, total = (size_t)pairs * ns;
+    const size_t o_count = total * sizeof(float4), o_slots = o_count + pad16((size_t)pairs * sizeof(uint32_t));
+    auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)n_frames * fb));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_slots + total * 6 * sizeof(int)));
+    if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
+    for (int k = 0; k < n_frames; ++k)
+        OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + (size_t)k * fb, ss, frames + (size_t)k * frame_pitch, stride, W, H, ctx->stream));
+    rc = ofps::klt_flow_batch_device(ctx, ofps::SadFrames::sequence(d_fr, fb, ref_mode, W, H, ss), pairs, levels, radius, iters,
+                                     reinterpret_cast<float4*>(d_io), reinterpret_cast<uint32_t*>(d_io + o_count),
+                                     out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, d_io + o_count, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_io + o_slots, total * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < pairs; ++k) {                         // an item's kept records alone: what lies behind them in its slot is unspecified
+        if (out_counts[k] > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "klt_flow_batch: the device counted %u records in %zu slots", out_counts[k], ns);
+        if (out_counts[k])
+            OFPS_HIP_TRY(ctx, hipMemcpy(out_entries + (size_t)k * ns * 4, d_io + (size_t)k * ns * sizeof(float4), (size_t)out_counts[k] * sizeof(float4),
+                                        hipMemcpyDeviceToHost));
+    }
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_set_batch_decoder(ofps_hip_ctx* ctx, int decoder, int levels, int radius, int iters) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, decoder == OFPS_HIP_BATCH_DECODER_SAD || decoder == OFPS_HIP_BATCH_DECODER_KLT, "set_batch_decoder: decoder %d is not 0|1", decoder);
+    if (decoder == OFPS_HIP_BATCH_DECODER_KLT) {
+        OFPS_REQUIRE(ctx, levels >= 1 && levels <= kKltMaxLevels, "set_batch_decoder: levels %d outside [1, %d]", levels, kKltMaxLevels);
+        OFPS_REQUIRE(ctx, radius >= 1 && radius <= kKltMaxRadius, "set_batch_decoder: radius %d outside [1, %d]", radius, kKltMaxRadius);
+        OFPS_REQUIRE(ctx, iters >= 1 && iters <= kKltMaxIters, "set_batch_decoder: iters %d outside [1, %d]", iters, kKltMaxIters);
+        ctx->opt.klt_levels = levels; ctx->opt.klt_radius = radius; ctx->opt.klt_iters = iters;
+    }
+    ctx->opt.batch_decoder = decoder;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_batch_decoder(ofps_hip_ctx* ctx, int32_t* decoder, int32_t* levels, int32_t* radius, int32_t* iters) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    if (decoder) *decoder = ctx->opt.batch_decoder;
+    if (levels) *levels = ctx->opt.klt_levels;
+    if (radius) *radius = ctx->opt.klt_radius;
+    if (iters) *iters = ctx->opt.klt_iters;
     return OFPS_HIP_OK;
 }
 

@@ -326,12 +326,22 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     }
     const int dstride = (W + 63) & ~63;
     const size_t pitch = (size_t)dstride * H;
-    const size_t nblk = ofps_hip_sad_block_count(W, H, prm->block);
     const int tix = (int)(tno % kTickets);
+    const auto& o = ctx->opt;
+    // the batch decoder switch (include/ofps_hip.h N3b): hip_klt in place of the search.  Its settings are the context's at this push; a frame
+    // the decoder refuses is refused here, before anything is uploaded.  The slot count takes the block count's place in every size below, the
+    // kept counts travel where the batch filter's do.  With the switch at 0 `klt` is false and nothing below differs from what it was
+    const bool klt = o.batch_decoder == OFPS_HIP_BATCH_DECODER_KLT;
+    if (klt) {
+        rc = klt_check_call(ctx, W, H, dstride, o.klt_levels, o.klt_radius, o.klt_iters, "push_frames_async");
+        if (rc != OFPS_HIP_OK) return rc;
+        OFPS_REQUIRE(ctx, (unsigned long long)n * ofps_hip_klt_slot_count(W, H, o.klt_cell) < (1ull << 31), "push_frames_async: %d frames of %zu slots", n,
+                     ofps_hip_klt_slot_count(W, H, o.klt_cell));
+    }
+    const size_t nblk = klt ? ofps_hip_klt_slot_count(W, H, o.klt_cell) : ofps_hip_sad_block_count(W, H, prm->block);
     // the batch filter switch (include/ofps_hip.h N1b) with a criterion on: the filtered batched search and the tail's per-item device counts;
     // the ticket follows the settings the context has now.  Else everything below is what it is without the switch
-    const auto& o = ctx->opt;
-    const bool filtered = o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0 || o.sad_intra > 0);
+    const bool filtered = !klt && o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0 || o.sad_intra > 0);
     if (filtered) {                                              // refused before anything is uploaded
         SadFilter chk{{nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, o.sad_intra, o.sad_cut, /*want_triples=*/false};
         rc = chk.plan(ctx, "push_frames_async");
@@ -339,7 +349,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     }
     // capacity: both buffers and the per-ticket outputs are sized for the largest batch seen (grow-only; growing waits
     // for work in flight)
-    const size_t out_bytes = sizeof(TailRecord) + (filtered ? sizeof(uint32_t) : 0);      // per frame; filtered: the n kept counts behind the n quaternions
+    const size_t out_bytes = sizeof(TailRecord) + (filtered || klt ? sizeof(uint32_t) : 0);      // per frame; filtered, hip_klt: the n kept counts behind the n quaternions
     const size_t cap_frames = (size_t)n + 1;
     auto& fs = ctx->scratch[ofps::S_BATCH_FRAMES];
     size_t per_buf = fs.cap / kTickets / (pitch ? pitch : 1);
@@ -405,16 +415,17 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     const int first = has_prev ? 0 : 1;                           // the stream's very first frame has no pair
     const int pairs = n - first;
     t.n = n; t.first_has_prev = has_prev ? 1 : 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.n_vectors = nblk;
-    t.filtered = filtered && pairs > 0;
+    t.filtered = (filtered || klt) && pairs > 0;
     if (halo_mode) t.isl.K = 0;                                  // the multi-device workers list no islands (include/ofps_hip.h A5i)
     else islands_ticket_arm(ctx, &t.isl, prm, n);
     if (pairs > 0) {
         float4* ent0 = d_ent + (size_t)first * nblk;
         // filtered: item j's kept records lead its slot of the record buffer, its count is word j behind the quaternions.  Searches, flags
         // and the compaction run on the compute stream, in front of the tail that reads the counts there
-        uint32_t* d_cnt = filtered ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
+        uint32_t* d_cnt = filtered || klt ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
         const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
-        if (filtered)
+        if (klt) rc = klt_flow_batch_device(ctx, fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr);
+        else if (filtered)
             rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
                                           "push_frames_async", tix, kTickets, o.sad_intra, o.sad_cut);
         else rc = sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0, nullptr);
@@ -432,7 +443,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         rc = frame_tail_device(ctx, ent0, nblk, pairs, d_cnt, filtered ? 3 : 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode,
                                d_res[first], d_quat + first, d_field, nullptr, nullptr, &t.isl);
         if (rc != OFPS_HIP_OK) return rc;
-        if (filtered || prm->run_detector || prm->run_estimator) {         // (the kept counts travel in this read-back)
+        if (filtered || klt || prm->run_detector || prm->run_estimator) {         // (the kept counts travel in this read-back)
             rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * out_bytes, s);
             if (rc != OFPS_HIP_OK) return rc;
         }

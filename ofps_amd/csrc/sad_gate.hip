@@ -165,6 +165,15 @@ static int sad_gate_check(ofps_hip_ctx* ctx, int block, int min_pixels, const ch
     return OFPS_HIP_OK;
 }
 
+// compact_items_kernel for a caller outside this file (klt.hip's batch form): records alone, no triples
+int compact_items_device(ofps_hip_ctx* ctx, const float4* d_in, const uint8_t* d_flags, size_t n, int items, float4* d_out, uint32_t* d_counts) {
+    OFPS_REQUIRE(ctx, items >= 1 && n < (1ull << 32), "compact_items: %d items of %zu records", items, n);
+    hipLaunchKernelGGL(compact_items_kernel, dim3((unsigned)items), dim3(1024), 0, ctx->stream, d_in, nullptr, d_flags, (uint32_t)n, d_out, nullptr,
+                       d_counts);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
 // ---- SadFilter (common.hpp): the steps of the filtered search
 int SadFilter::plan(ofps_hip_ctx* ctx, const char* who) {
     int rc = limit > 0 ? sad_consistency_check(ctx, block, limit, who) : OFPS_HIP_OK;

@@ -440,6 +440,11 @@ int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int sr
     return down2_device(ctx, src, 0, W, H, src_stride, dst, 0, dst_stride, 1);
 }
 
+int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
+                            int dst_stride, long long frames) {
+    return down2_device(ctx, src, src_pitch, W, H, src_stride, dst, dst_pitch, dst_stride, frames);
+}
+
 int sad_hier_reach(int range, int levels) {
     if (range < 0 || range > 64 || levels < 1 || levels > 3) return -1;
     int r = range;

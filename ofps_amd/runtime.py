@@ -4,6 +4,7 @@ device-pointer call wrappers.  All compute happens in libofps_hip.so; nothing he
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -663,6 +664,50 @@ class HipContext:
         self._check(self._lib.ofps_hip_klt_flow_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, levels, radius, iters,
                                                     C.c_void_p(d_out_entries), C.c_void_p(d_out_count), C.c_void_p(d_out_slots or 0)))
 
+    # ---- N3b: hip_klt on a batch of pairs, and as the batched stream forms' decoder
+    BATCH_DECODER_SAD, BATCH_DECODER_KLT = 0, 1
+
+    def klt_flow_batch(self, frames: np.ndarray, levels: int, radius: int, iters: int, ref_mode: int = 0, want_slots=False):
+        """frames uint8 [n_frames, H, W] (a view with padded rows and frames further apart is passed as it is); item k = the pair (k, k + 1),
+        or (0, k + 1) with ref_mode 1 -> (entries float32 [pairs, slots, 4], counts uint32 [pairs][, slots int32 [pairs, slots, 6]]).  Item k's
+        kept records are entries[k, :counts[k]]; the rows behind them are not written."""
+        assert frames.dtype == np.uint8 and frames.ndim == 3
+        n, H, W = frames.shape
+        pitch, stride, unit = frames.strides
+        assert unit == 1 and stride >= W, "frames: rows must be byte-contiguous"
+        pairs, ns = max(n - 1, 0), self.klt_slot_count(W, H)
+        ent = np.zeros((max(pairs, 1), max(ns, 1), 4), np.float32)
+        counts = np.zeros(max(pairs, 1), np.uint32)
+        slots = np.zeros((max(pairs, 1), max(ns, 1), 6), np.int32) if want_slots else None
+        self._check(self._lib.ofps_hip_klt_flow_batch(self._h, C.cast(C.c_void_p(frames.ctypes.data), C.POINTER(C.c_uint8)), n, W, H, stride,
+                                                      pitch if n > 1 else stride * H, ref_mode, levels, radius, iters, _fp(ent),
+                                                      counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      slots.ctypes.data_as(C.POINTER(C.c_int32)) if want_slots else None))
+        return (ent[:pairs], counts[:pairs], slots[:pairs]) if want_slots else (ent[:pairs], counts[:pairs])
+
+    def klt_flow_batch_dev(self, d_frames: int, n_frames: int, W: int, H: int, stride: int, frame_pitch: int, ref_mode: int, levels: int,
+                           radius: int, iters: int, d_out_entries: int, d_out_counts: int, d_out_slots: int | None = None):
+        """Enqueue only: d_out_entries holds pairs x klt_slot_count records, d_out_counts pairs uint32, d_out_slots (optional) 6 int32 per slot."""
+        self._check(self._lib.ofps_hip_klt_flow_batch_dev(self._h, C.c_void_p(d_frames), n_frames, W, H, stride, frame_pitch, ref_mode, levels,
+                                                          radius, iters, C.c_void_p(d_out_entries), C.c_void_p(d_out_counts),
+                                                          C.c_void_p(d_out_slots or 0)))
+
+    def set_batch_decoder(self, decoder: int = 0, levels: int = 4, radius: int = 7, iters: int = 10):
+        """What push_frames_async searches with: BATCH_DECODER_SAD (default), or BATCH_DECODER_KLT with these levels, window radius and
+        iterations and the set_klt values (include/ofps_hip.h N3b)."""
+        self._check(self._lib.ofps_hip_set_batch_decoder(self._h, decoder, levels, radius, iters))
+
+    def get_batch_decoder(self) -> dict:
+        v = [C.c_int32(0) for _ in range(4)]
+        self._check(self._lib.ofps_hip_get_batch_decoder(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("decoder", "levels", "radius", "iters"), (int(x.value) for x in v)))
+
+    def batch_record_capacity(self, W: int, H: int, block: int = 16) -> int:
+        """records per frame of push_frames_async's out_entries: the slot count with the batch decoder at KLT, else the block count"""
+        if self.get_batch_decoder()["decoder"] == self.BATCH_DECODER_KLT:
+            return self.klt_slot_count(W, H)
+        return int(self._lib.ofps_hip_sad_block_count(W, H, block))
+
     LK_CONTRAST_MASK, LK_FULLRES_RECORDS, FLOW_FARNEBACK, FLOW_USE_PREVIOUS, LK_REDUCED = 1, 2, 4, 8, 16
     FLOW_SPARSE = 32            # hip_klt (include/ofps_hip.h N3) in place of flow, mask and output stage; levels / radius / iters = L / w / K
     FMT_LUMA, FMT_BGR, FMT_RGBA, FMT_BGRA = 0, 1, 2, 3
@@ -1096,9 +1141,11 @@ class HipContext:
                           target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16, use_ransac=False,
                           num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, out_entries: np.ndarray | None = None) -> int:
         """Batched form (ofps_hip_push_frames_async): frames uint8 [n, H, W] contiguous -> ticket; keep `frames` and
-        `out_entries` ([n, nblk, 4] float32) alive until frames_wait(ticket)."""
+        `out_entries` ([n, nblk, 4] float32; with the batch decoder at KLT [n, slots, 4]: batch_record_capacity) alive until frames_wait(ticket)."""
         assert frames.dtype == np.uint8 and frames.ndim == 3 and frames.flags["C_CONTIGUOUS"]
         n, H, W = frames.shape
+        if out_entries is not None and self.get_batch_decoder()["decoder"] == self.BATCH_DECODER_KLT:
+            assert out_entries.size >= n * self.klt_slot_count(W, H) * 4, "out_entries: n * slots records with the batch decoder at KLT"
         prm = self._frame_params(block, search_range, detector, min_size, subdivide, target_motion, estimator, aspect, fov_y_deg,
                                  use_ransac, num_iters, inlier_deg, num_samples, seed)
         t = C.c_int(0)
@@ -1208,6 +1255,16 @@ class MultiDevice:
         _lib.load().ofps_hip_multi_stream_plan(batch, n_workers, C.byref(w), C.byref(h), C.byref(t))
         return int(w.value), int(h.value), int(t.value)
 
+    @staticmethod
+    def batch_record_capacity(W: int, H: int, block: int = 16) -> int:
+        """records per frame of push_frames_async's out_entries.  The workers' contexts take the batch decoder from the environment at their
+        init (OFPS_HIP_BATCH_DECODER, OFPS_HIP_KLT_CELL): the slot count with KLT, else the block count"""
+        lib = _lib.load()
+        if os.environ.get("OFPS_HIP_BATCH_DECODER") == "1":
+            cell = os.environ.get("OFPS_HIP_KLT_CELL", "16")
+            return int(lib.ofps_hip_klt_slot_count(W, H, int(cell) if cell in ("8", "16", "32") else 16))
+        return int(lib.ofps_hip_sad_block_count(W, H, block))
+
     def push_frames_async(self, frames: np.ndarray, block=16, search_range=16, detector=True, min_size=0.05, subdivide=3,
                           target_motion=0.003, estimator=True, aspect=16 / 9, fov_y_deg=39.6 * 9 / 16, use_ransac=False,
                           num_iters=200, inlier_deg=0.05, num_samples=1000, seed=0, out_entries: np.ndarray | None = None) -> int:
@@ -1218,6 +1275,8 @@ class MultiDevice:
         n, H, W = frames.shape
         pitch, stride, unit = frames.strides
         assert unit == 1 and stride >= W and (n == 1 or pitch >= stride * H), "frames: rows must be byte-contiguous"
+        if out_entries is not None:
+            assert out_entries.size >= n * self.batch_record_capacity(W, H, block) * 4, "out_entries: n * batch_record_capacity records"
         prm = _lib.FrameParams(block, search_range, int(detector), min_size, subdivide, target_motion, int(estimator),
                                aspect, fov_y_deg, int(use_ransac), num_iters, inlier_deg, num_samples, seed)
         t = C.c_int(0)

@@ -12,7 +12,15 @@ integer jumps; synth.camera_warp_pair: a smooth sub-pixel camera motion), on fra
   lk       ofps_hip_lk_flow_dev with the bench's parameters (3 levels, radius 4, 3 steps), records out
 Protocol: time per call of a saturated queue -- `--calls` (50) calls between two HIP events on the context's stream --, the median of
 `--reps` (7) such windows behind `--warm` (2) windows that are not counted.  Beside the times: the slot count, the kept count and the
-status histogram of the flow (0 kept, 1 no feature, 2 flat, 3 left the frame, 4 residual)."""
+status histogram of the flow (0 kept, 1 no feature, 2 flat, 3 left the frame, 4 residual).
+
+--batch N: the batch form (N3b) in place of the table above.  Per geometry and content a chain of N + 1 frames resident in device memory
+(luma_sequence: N + 1 frames of the sequence; camera_warp_pair: the pair's two frames in turn, so the pairs are the warp and its inverse), and
+  batch       one ofps_hip_klt_flow_batch_dev call over the N pairs
+  one_by_one  N ofps_hip_klt_flow_dev calls over the same pairs
+both in microseconds per PAIR, a window holding about `--calls` pairs.  The batch form's split into score, pyramid, track and compaction is not
+taken here: it is the kernel times of a `rocprofv3 --kernel-trace --stats` run of this mode (klt_score_batch_kernel, sad_down2_kernel,
+klt_track_batch_kernel, compact_items_kernel), in a run of its own."""
 import argparse
 import json
 import os
@@ -91,8 +99,46 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
             "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
+def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm):
+    n_frames, H, W = frames.shape
+    N = n_frames - 1
+    ctx.set_klt(cell, 2, 1, 1, max_residual)
+    ns = ctx.klt_slot_count(W, H)
+    d_fr = ctx.malloc(n_frames * W * H)
+    ctx.memcpy_h2d(d_fr, frames)
+    d_rec, d_cnt = ctx.malloc(16 * ns * N), ctx.malloc(max(4 * N, 16))
+    d_rec1, d_cnt1 = ctx.malloc(16 * ns * N), ctx.malloc(max(4 * N, 16))
+    windows = max(1, (calls + N - 1) // N)
+
+    def batch():
+        ctx.klt_flow_batch_dev(d_fr, n_frames, W, H, W, W * H, 0, levels, radius, iters, d_rec, d_cnt)
+
+    def one_by_one():
+        for k in range(N):
+            ctx.klt_flow_dev(d_fr + k * W * H, d_fr + (k + 1) * W * H, W, H, W, levels, radius, iters, d_rec1 + 16 * ns * k, d_cnt1 + 4 * k)
+
+    t = {"batch": window_ms(ctx, batch, windows, reps, warm), "one_by_one": window_ms(ctx, one_by_one, windows, reps, warm)}
+    for v in t.values():                                      # per call of N pairs -> per pair
+        for key in v:
+            v[key] = round(v[key] / N, 2)
+    batch(); one_by_one(); ctx.sync()
+    cnt, cnt1 = np.zeros(max(N, 4), np.uint32), np.zeros(max(N, 4), np.uint32)
+    ctx.memcpy_d2h(cnt, d_cnt); ctx.memcpy_d2h(cnt1, d_cnt1)
+    rec, rec1 = np.zeros((N, ns, 4), np.float32), np.zeros((N, ns, 4), np.float32)
+    ctx.memcpy_d2h(rec, d_rec); ctx.memcpy_d2h(rec1, d_rec1)
+    same = bool((cnt[:N] == cnt1[:N]).all() and all(rec[k, :cnt[k]].tobytes() == rec1[k, :cnt[k]].tobytes() for k in range(N)))
+    for p in (d_fr, d_rec, d_cnt, d_rec1, d_cnt1):
+        ctx.free(p)
+    return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
+            "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
+            "us_per_pair": t}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=0, help="N > 0: time the batch form over N pairs against N one-pair calls")
+    ap.add_argument("--no-1080p", action="store_true")
+    ap.add_argument("--content", choices=["both", "luma_sequence", "camera_warp_pair"], default="both", help="--batch: one content alone (a kernel trace per content)")
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warm", type=int, default=2)
@@ -104,9 +150,17 @@ def main():
     a = ap.parse_args()
     ctx = HipContext(0)
     rows = []
-    for W, H, cell in [(1920, 1080, 16)] + ([] if a.no_4k else [(3840, 2160, 8)]):
-        lum = synth.luma_sequence(2, W, H, max_step=6, seed=5)
+    for W, H, cell in ([] if a.no_1080p else [(1920, 1080, 16)]) + ([] if a.no_4k else [(3840, 2160, 8)]):
+        lum = synth.luma_sequence(max(a.batch + 1, 2), W, H, max_step=6, seed=5)
         warp = synth.camera_warp_pair(W, H, shift=(3.3 * W / 1920, -2.6 * H / 1080))
+        if a.batch > 0:
+            chain = np.stack([warp[k & 1] for k in range(a.batch + 1)])
+            for name, fr in (("luma_sequence", lum), ("camera_warp_pair", chain)):
+                if a.content not in ("both", name):
+                    continue
+                rows.append(one_batch(ctx, name, np.ascontiguousarray(fr), cell, a.levels, a.radius, a.iters, a.max_residual, a.calls, a.reps, a.warm))
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            continue
         for name, (p, c) in (("luma_sequence", (lum[0], lum[1])), ("camera_warp_pair", (warp[0], warp[1]))):
             rows.append(one(ctx, name, np.ascontiguousarray(p), np.ascontiguousarray(c), cell, a.levels, a.radius, a.iters, a.max_residual,
                             a.calls, a.reps, a.warm))
