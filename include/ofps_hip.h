@@ -726,6 +726,34 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
 int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
                           void* d_out_entries, void* d_out_count /* one uint32 */, void* d_out_slots /* or NULL */);
 
+/* ---- N3m: hip_klt with mean removal: tracking that ignores a brightness offset between the frames (csrc/klt.hip) ----
+ * Build-defined, off by default.  N3's step solves A u = -sum (J - I) grad I on raw grey levels: an offset o between the frames adds
+ * o * sum grad I to the right-hand side and o per pixel to the residual.  A setting of the context, mean_removal in {0, 1}
+ * (ofps_hip_set_klt_mean_removal; option and environment variable OFPS_HIP_KLT_MEAN_REMOVAL).  With 0 every entry point enqueues the
+ * kernels it enqueues without this row.  With 1 tracking a feature differs from N3 in three places, and in nothing else; N = n * n:
+ *   per level, after the template: sx = sum Ix, sy = sum Iy over the n x n interior; A11 = N * sum Ix*Ix - sx * sx,
+ *     A12 = N * sum Ix*Iy - sx * sy, A22 = N * sum Iy*Iy - sy * sy; T = e * N * N * 262144; the flat test, det, X, Y and Z as in N3 on
+ *     these values;
+ *   per iteration: d = J - I on the window, sd = sum d; b1 = N * sum d*Ix - sd * sx, b2 = N * sum d*Iy - sd * sy; the f64 lines of N3
+ *     (num_x, u_x = (-512.0 * num_x) / det, ..., rint, clamp) unchanged and in the same order.  This is the normal equation of the model
+ *     "shift plus one unknown offset" with the offset eliminated; the common factor N cancels;
+ *   residual, at the final dq: sd = sum d; m = floor((2 sd + N) / (2 N)), floor towards minus infinity; res = sum |d - m|; the loss test
+ *     res > 16 R N is unchanged.
+ * Number range: all integers are signed 64-bit.  With |Ix| <= 130,560, |d| <= 65,280 and N <= 225 every quantity stays below 9e14, so
+ * the conversions to f64 are exact.
+ * Consequences.  If no pixel of cur + o clips, on level 0 and on the pyramid's levels, S gives exactly J + 256 o, d shifts by 256 o and
+ * b1, b2 and res do not change: the slots of (prev, cur + o) equal those of (prev, cur) bit for bit.  A window whose gradient is constant
+ * (a ramp) has centred A = 0 and is status 2: shift and offset cannot be told apart there, so small windows on smooth content are flat
+ * with mean removal where they are not without.
+ * Every entry point that tracks follows the setting, with no new argument: ofps_hip_klt_track[_dev], _flow[_dev], _flow_batch[_dev],
+ * OFPS_HIP_FLOW_SPARSE in the dense decoders' stream and fused forms, ofps_hip_push_frames_async and the multi-device workers' pushes
+ * with the batch decoder at KLT (the workers' contexts read the environment variable at ofps_hip_init, as they read N3b's).
+ * ofps_hip_klt_features[_dev] does not change: the score is built from gradients.  Bit-exact against the restatement
+ * tests/indep_klt_zm.py.  A value other than 0 | 1 is OFPS_HIP_EINVAL and the setting stays as it was.  Additive: OFPS_HIP_API_VERSION
+ * stays. */
+int ofps_hip_set_klt_mean_removal(ofps_hip_ctx* ctx, int on);
+int ofps_hip_get_klt_mean_removal(ofps_hip_ctx* ctx);        /* 0 | 1; OFPS_HIP_EINVAL for a NULL context */
+
 /* ---- N3b: hip_klt on a batch of pairs, and in the batched stream forms (csrc/klt.hip, csrc/pipeline.hip) ----
  * Nothing about the arithmetic is new.  Item k of a sequence of n_frames >= 2 frames, frame_pitch >= stride * H bytes apart, is the pair
  * (k, k + 1) with ref_mode 0 and (0, k + 1) with ref_mode 1; pairs = n_frames - 1.  Per item the kept records (kept slots first, in slot

@@ -232,6 +232,8 @@ struct ofps_hip_ctx {
         // ofps_hip_set_klt: hip_klt's lattice cell (8 | 16 | 32), score window radius [1, 3], smallest score of a feature, smallest eigenvalue of
         // a template's structure tensor per pixel [1, 65535], residual limit in sixteenths of a grey level per pixel (0 = off) (klt.hip, N3)
         int klt_cell = 16, klt_score_radius = 2, klt_min_score = 1, klt_min_eig = 1, klt_max_residual = 0;
+        // ofps_hip_set_klt_mean_removal: 1 = hip_klt tracks under the model "shift plus one brightness offset" (include/ofps_hip.h N3m)
+        int klt_mean_removal = 0;
         // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
         // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
         int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;

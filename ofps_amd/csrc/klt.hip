@@ -9,6 +9,10 @@
 // klt_track_kernel: one wave = one slot, the lanes over the n * n <= 225 window pixels (four per lane), the (n + 2)^2 template samples
 //   of a level in LDS, the template's gradients in registers; A11, A12, A22, b1, b2 and the residual are 64-bit integer sums reduced
 //   across the wave by a butterfly, so every lane holds them and takes the same branches.  All levels in one launch.
+// klt_track_zm_kernel: the same body with mean removal (N3m): per level sx = sum Ix and sy = sum Iy are reduced beside the three products
+//   (both in one 64-bit butterfly, a word each) and every lane's gradients become the centred N Ix - sx, N Iy - sy (below 6e7: int32), so
+//   the iteration's two sums are N3m's b1 and b2 as they are -- one more reduction per level, none per iteration --, and the residual takes a
+//   32-bit one more for the mean of d.
 #include "common.hpp"
 
 #include <cmath>
@@ -63,6 +67,11 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 
 __device__ __forceinline__ long long wave_sum_i64(long long v) {
     for (int m = 1; m < 64; m <<= 1) v += (long long)shfl_xor_u64((unsigned long long)v, m);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
 
@@ -194,8 +203,9 @@ __device__ __forceinline__ void klt_store(const KltTrackParams& p, long long slo
 }
 
 // one wave's slot.  BATCH: the slot's item picks the frames (b: the launch's pitches) and, with shared features, its triple; the outputs are
-// indexed by the slot either way.  Everything behind the pointers is one text for both kernels
-template <bool BATCH>
+// indexed by the slot either way.  Everything behind the pointers is one text for both kernels.  ZM: mean removal (N3m); the lines it adds
+// are compiled into its own two kernels alone
+template <bool BATCH, bool ZM>
 __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
@@ -248,7 +258,21 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
             }
         }
         a11 = wave_sum_i64(a11); a12 = wave_sum_i64(a12); a22 = wave_sum_i64(a22);
-        const long long T = (long long)p.min_eig * n2 * 262144ll;
+        const long long T = (long long)p.min_eig * n2 * 262144ll * (ZM ? n2 : 1);
+        if constexpr (ZM) {
+            // N3m: A of the model "shift plus one offset", the offset eliminated; every term stays below 9e14.  From here on ix, iy hold the
+            // centred gradients, whose products with d sum to N3m's b1, b2
+            // sx and sy stay below 3e7 in magnitude, so both go through ONE 64-bit reduction, sx in the upper word: the sum's lower word is sy
+            long long sxy = 0;
+            for (int k = 0; k < 4; ++k) sxy += (long long)ix[k] * 4294967296ll + iy[k];      // (0 where the lane has no pixel)
+            sxy = wave_sum_i64(sxy);
+            const int sy = (int)(unsigned)(unsigned long long)sxy;
+            const int sx = (int)((sxy - sy) / 4294967296ll);
+            a11 = n2 * a11 - (long long)sx * sx; a12 = n2 * a12 - (long long)sx * sy; a22 = n2 * a22 - (long long)sy * sy;
+            for (int k = 0; k < 4; ++k) {
+                if (lane + 64 * k < n2) { ix[k] = n2 * ix[k] - sx; iy[k] = n2 * iy[k] - sy; }
+            }
+        }
         const double X = (double)(a11 - T), Y = (double)(a22 - T), Z = (double)a12;
         const double xy = X * Y, zz = Z * Z;
         if (!(xy >= zz && X + Y >= 0.0)) { status = KLT_FLAT; break; }
@@ -285,10 +309,28 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
     if (status == KLT_KEPT) {
         const uint8_t* __restrict__ cur0 = BATCH ? p.lv.cur[0] + item * b->cur_pitch[0] : p.lv.cur[0];
         long long sum = 0;
-        for (int k = 0; k < 4; ++k) {
-            if (lane + 64 * k < n2) {
-                const int d = klt_sample(cur0, W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
-                sum += d < 0 ? -d : d;
+        if constexpr (ZM) {
+            // N3m: the residual around the window's mean difference m = floor((2 sd + N) / (2 N)), |m| <= 65,280
+            int d[4], sd = 0;                                     // |sd| <= 225 * 65,280: a 32-bit reduction
+            for (int k = 0; k < 4; ++k) {
+                d[k] = 0;
+                if (lane + 64 * k < n2) {
+                    d[k] = klt_sample(cur0, W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
+                    sd += d[k];
+                }
+            }
+            sd = wave_sum_i32(sd);
+            const int num = 2 * sd + n2, den = 2 * n2;
+            const int mean = num / den - (num % den < 0 ? 1 : 0);
+            for (int k = 0; k < 4; ++k) {
+                if (lane + 64 * k < n2) { const int e = d[k] - mean; sum += e < 0 ? -e : e; }
+            }
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                if (lane + 64 * k < n2) {
+                    const int d = klt_sample(cur0, W0, H0, p.lv.stride[0], cqx + dqx + 256 * (pi[k] - w), cqy + dqy + 256 * (pj[k] - w)) - ic[k];
+                    sum += d < 0 ? -d : d;
+                }
             }
         }
         res = wave_sum_i64(sum);
@@ -299,12 +341,23 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
 
 __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const KltTrackParams p) {
     __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
-    klt_track_body<false>(p, nullptr, tmpl);
+    klt_track_body<false, false>(p, nullptr, tmpl);
 }
 
 __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_kernel(const KltTrackBatchParams p) {
     __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
-    klt_track_body<true>(p.t, &p, tmpl);
+    klt_track_body<true, false>(p.t, &p, tmpl);
+}
+
+// N3m: the two kernels of a context whose mean_removal is 1
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_zm_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, true>(p, nullptr, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_zm_kernel(const KltTrackBatchParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, true>(p.t, &p, tmpl);
 }
 
 struct KltSettings { int cell, r, min_score, min_eig, max_residual; };
@@ -378,7 +431,9 @@ int klt_pyramid_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* 
 
 int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p) {
     if (p.n <= 0) return OFPS_HIP_OK;
-    hipLaunchKernelGGL(klt_track_kernel, dim3((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves)), dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    const dim3 grid((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves));
+    if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(klt_track_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
@@ -440,7 +495,9 @@ int klt_pyramid_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, i
 
 int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
     if (b.t.n <= 0) return OFPS_HIP_OK;
-    hipLaunchKernelGGL(klt_track_batch_kernel, dim3((unsigned)((b.t.n + kKltTrackWaves - 1) / kKltTrackWaves)), dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
+    const dim3 grid((unsigned)((b.t.n + kKltTrackWaves - 1) / kKltTrackWaves));
+    if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
+    else hipLaunchKernelGGL(klt_track_batch_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
@@ -543,6 +600,15 @@ int ofps_hip_get_klt(ofps_hip_ctx* ctx, int32_t* cell, int32_t* score_radius, in
     if (max_residual) *max_residual = ctx->opt.klt_max_residual;
     return OFPS_HIP_OK;
 }
+
+int ofps_hip_set_klt_mean_removal(ofps_hip_ctx* ctx, int on) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, on == 0 || on == 1, "set_klt_mean_removal: %d is not 0|1", on);
+    ctx->opt.klt_mean_removal = on;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_klt_mean_removal(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_mean_removal : OFPS_HIP_EINVAL; }
 
 size_t ofps_hip_klt_slot_count(int W, int H, int cell) {
     if (W < 1 || H < 1 || (cell != 8 && cell != 16 && cell != 32)) return 0;

@@ -209,6 +209,7 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
     if (klt_) {                                                       // hip_klt: the settings a ticket follows, and one record slot per lattice cell
         ctx_.check(ofps_hip_set_klt(ctx_.get(), (int)klt_->cell, (int)klt_->score_radius, (int)klt_->min_score, (int)klt_->min_eig,
                                     (int)klt_->max_residual));
+        ctx_.check(ofps_hip_set_klt_mean_removal(ctx_.get(), klt_->mean_removal ? 1 : 0));
         out_.resize(klt_record_floats(w_, h_, max_w_, max_h_, process_fullres_, klt_->cell));
     } else {
         out_.resize(records_fullres ? 4 * w_ * h_ : 4 * std::min(max_w_, w_) * std::min(max_h_, h_));
@@ -269,7 +270,8 @@ std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage&
             {"Cell size", PropertyMut::usize(&s.cell, 8, 32)}, {"Score radius", PropertyMut::usize(&s.score_radius, 1, 3)},
             {"Min score", PropertyMut::usize(&s.min_score, 1, kKltMaxScore)}, {"Min eigenvalue", PropertyMut::usize(&s.min_eig, 1, kKltMaxEig)},
             {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)}, {"Levels", PropertyMut::usize(at.levels, 1, 6)},
-            {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)}};
+            {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)},
+            {"Mean removal", PropertyMut::boolean(&s.mean_removal)}};
 }
 
 // ------------------------------------------------------------------ .mvec

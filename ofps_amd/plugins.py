@@ -278,12 +278,16 @@ class HipKltDecoder(HipLkDecoder):
     _PROPS = (("Width", "usize", "max_w", 1, 2000), ("Height", "usize", "max_h", 1, 2000), ("Process Fullres", "bool", "process_fullres", None, None),
               ("Cell size", "usize", "cell", 8, 32), ("Score radius", "usize", "score_radius", 1, 3), ("Min score", "usize", "min_score", 1, 2 ** 31 - 1),
               ("Min eigenvalue", "usize", "min_eig", 1, 65535), ("Max residual", "usize", "max_residual", 0, 4080),
-              ("Levels", "usize", "levels", 1, 6), ("Window radius", "usize", "radius", 1, 7), ("Iterations", "usize", "iters", 1, 30))
+              ("Levels", "usize", "levels", 1, 6), ("Window radius", "usize", "radius", 1, 7), ("Iterations", "usize", "iters", 1, 30),
+              # build-defined: the tracker solves for the shift and one brightness offset per window, for streams whose brightness changes
+              # between frames (include/ofps_hip.h N3m); hip_sad's property of the same name is its counterpart
+              ("Mean removal", "bool", "mean_removal", None, None))
 
     def __init__(self, frames, framerate=None, device: int = 0, frame_format: int = HipContext.FMT_LUMA):
         super().__init__(frames, framerate, device, frame_format)
         self.levels, self.radius, self.iters = 4, 7, 10
         self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual = 16, 2, 1, 1, 0
+        self.mean_removal = False
         self.contrast_mask = False
 
     def process_frame(self, field: list, out_frame=None, skip_frames: int = 0) -> bool:
@@ -299,6 +303,7 @@ class HipKltDecoder(HipLkDecoder):
             self._on_device = None
             return False
         self.ctx.set_klt(self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual)
+        self.ctx.set_klt_mean_removal(1 if self.mean_removal else 0)
         return self._decode(field, dict(reduced=not self.process_fullres, fmt=self.frame_format, sparse=True))
 
 

@@ -596,6 +596,14 @@ class HipContext:
         self._check(self._lib.ofps_hip_get_klt(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("cell", "score_radius", "min_score", "min_eig", "max_residual"), (int(x.value) for x in v)))
 
+    def set_klt_mean_removal(self, on: int):
+        """1: every hip_klt form of this context tracks under the model "shift plus one brightness offset" and measures the residual around
+        the window's mean difference (include/ofps_hip.h N3m); 0 (default): N3 as it is."""
+        self._check(self._lib.ofps_hip_set_klt_mean_removal(self._h, int(on)))
+
+    def get_klt_mean_removal(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_mean_removal(self._h))
+
     def klt_slot_count(self, W: int, H: int, cell: int | None = None) -> int:
         return int(self._lib.ofps_hip_klt_slot_count(W, H, self.get_klt()["cell"] if cell is None else cell))
 

@@ -20,7 +20,10 @@ status histogram of the flow (0 kept, 1 no feature, 2 flat, 3 left the frame, 4 
   one_by_one  N ofps_hip_klt_flow_dev calls over the same pairs
 both in microseconds per PAIR, a window holding about `--calls` pairs.  The batch form's split into score, pyramid, track and compaction is not
 taken here: it is the kernel times of a `rocprofv3 --kernel-trace --stats` run of this mode (klt_score_batch_kernel, sad_down2_kernel,
-klt_track_batch_kernel, compact_items_kernel), in a run of its own."""
+klt_track_batch_kernel, compact_items_kernel), in a run of its own.
+
+--mean-removal: the same table, or the same batch mode, with ofps_hip_set_klt_mean_removal(1) (N3m): every hip_klt row then runs
+klt_track_zm_kernel / klt_track_batch_zm_kernel; the rows say so ("mean_removal": 1).  --klt-only leaves the hip_sad and hip_lk rows out."""
 import argparse
 import json
 import os
@@ -45,7 +48,7 @@ def window_ms(ctx, fn, calls, reps, warm):
     return {"median_us": round(float(np.median(out)) * 1e3, 2), "min_us": round(min(out) * 1e3, 2), "max_us": round(max(out) * 1e3, 2)}
 
 
-def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, reps, warm):
+def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, reps, warm, klt_only=False):
     H, W = prev.shape
     ctx.set_klt(cell, 2, 1, 1, max_residual)
     ns = ctx.klt_slot_count(W, H)
@@ -82,9 +85,10 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
         "pyramid": window_ms(ctx, pyramid, calls, reps, warm),
         "track": window_ms(ctx, lambda: ctx.klt_track_dev(d_prev, d_cur, W, H, W, d_pts, len(pts), levels, radius, iters, d_quad), calls, reps, warm),
         "flow": window_ms(ctx, lambda: ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots), calls, reps, warm),
-        "sad_16x16_pm16": window_ms(ctx, lambda: ctx.sad_flow_dev(d_fr, 2, W, H, W, W * H, 0, 16, 16, d_sad, None), calls, reps, warm),
-        "lk_3_4_3": window_ms(ctx, lambda: ctx.lk_flow_dev(d_prev, d_cur, W, H, W, 3, 4, 3, None, d_lk), calls, reps, warm),
     }
+    if not klt_only:
+        t["sad_16x16_pm16"] = window_ms(ctx, lambda: ctx.sad_flow_dev(d_fr, 2, W, H, W, W * H, 0, 16, 16, d_sad, None), calls, reps, warm)
+        t["lk_3_4_3"] = window_ms(ctx, lambda: ctx.lk_flow_dev(d_prev, d_cur, W, H, W, 3, 4, 3, None, d_lk), calls, reps, warm)
     t["track_alone_derived_us"] = round(t["track"]["median_us"] - t["pyramid"]["median_us"], 2)
     ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots)
     ctx.sync()
@@ -96,7 +100,7 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     for p in [d_fr, d_tri, d_quad, d_rec, d_cnt, d_slots, d_pts, d_sad, d_lk] + [b for lv in pyr for b in lv[3:]]:
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
+            "mean_removal": ctx.get_klt_mean_removal(), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
 def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm):
@@ -130,7 +134,7 @@ def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, call
     for p in (d_fr, d_rec, d_cnt, d_rec1, d_cnt1):
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
+            "mean_removal": ctx.get_klt_mean_removal(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
             "us_per_pair": t}
 
 
@@ -147,8 +151,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--max-residual", type=int, default=0)
     ap.add_argument("--no-4k", action="store_true")
+    ap.add_argument("--mean-removal", action="store_true", help="hip_klt with mean removal (include/ofps_hip.h N3m)")
+    ap.add_argument("--klt-only", action="store_true", help="no hip_sad and hip_lk rows beside hip_klt's")
     a = ap.parse_args()
     ctx = HipContext(0)
+    ctx.set_klt_mean_removal(1 if a.mean_removal else 0)
     rows = []
     for W, H, cell in ([] if a.no_1080p else [(1920, 1080, 16)]) + ([] if a.no_4k else [(3840, 2160, 8)]):
         lum = synth.luma_sequence(max(a.batch + 1, 2), W, H, max_step=6, seed=5)
@@ -163,7 +170,7 @@ def main():
             continue
         for name, (p, c) in (("luma_sequence", (lum[0], lum[1])), ("camera_warp_pair", (warp[0], warp[1]))):
             rows.append(one(ctx, name, np.ascontiguousarray(p), np.ascontiguousarray(c), cell, a.levels, a.radius, a.iters, a.max_residual,
-                            a.calls, a.reps, a.warm))
+                            a.calls, a.reps, a.warm, a.klt_only))
             print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
     ctx.close()
     print(json.dumps({"calls_per_window": a.calls, "windows": a.reps, "warm_windows": a.warm, "rows": rows}))
