@@ -754,6 +754,40 @@ int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_c
 int ofps_hip_set_klt_mean_removal(ofps_hip_ctx* ctx, int on);
 int ofps_hip_get_klt_mean_removal(ofps_hip_ctx* ctx);        /* 0 | 1; OFPS_HIP_EINVAL for a NULL context */
 
+/* ---- N3f: hip_klt's forward-backward check: a track that does not return to its feature is dropped (csrc/klt.hip) ----
+ * Build-defined, off by default; hip_klt's counterpart of hip_sad's consistency check (N1c).  N3's only test of a finished track is the
+ * optional residual limit: a track that converged on content that was repainted or uncovered between the frames, that lies beyond the
+ * pyramid's reach or across a motion boundary is kept with full weight.  A setting of the context, fb_limit F in [0, 4096], in units of
+ * 1/256 pixel (ofps_hip_set_klt_fb; option and environment variable OFPS_HIP_KLT_FB).  With F = 0 every entry point enqueues the kernels,
+ * streams and bytes it enqueues without this row.  With F > 0 a slot whose forward track ends with status 0 and displacement dq runs a
+ * backward pass:
+ *   it starts at P = (256 x + dqx, 256 y + dqy), which the forward pass's final frame test has put inside the frame;
+ *   it is N3's tracking with prev and cur exchanged, started at P: the template is sampled from cur_l; the level's centre is
+ *     cq = ((P + 128) >> l) - 128 per axis, arithmetic shift (for P = 256 x this is N3's (((2x + 1) * 128) >> l) - 128); the frame test is on
+ *     P + bq * 2^l against [0, 256 (W - 1)] and [0, 256 (H - 1)]; everything else is N3's text with the same L, w, K, min_eig and
+ *     max_residual, and with N3m on the same mean-removal lines.  It yields (bqx, bqy, bres, bstatus);
+ *   the round-trip distance is e = max(|dqx + bqx|, |dqy + bqy|), N1c's measure;
+ *   the slot is kept iff bstatus == 0 and e < F; otherwise its status is 5, "did not return", which reports the forward dq and res, as
+ *     status 4 does, and yields no record.  F = 1 is an exact round trip.
+ * Statuses 1 to 4 are the forward pass's and are unchanged; kept records are, bit for bit, the records of the same slots without the
+ * check.  On the device the backward pass runs inside the track launch, in the wave that finished the forward pass: no second launch, no
+ * intermediate array, no launch count that depends on the number of pairs.
+ * Every entry point that tracks follows the setting, with no new argument: ofps_hip_klt_track[_dev], _flow[_dev], _flow_batch[_dev] in
+ * chain and key mode, OFPS_HIP_FLOW_SPARSE in the dense decoders' stream and fused forms, ofps_hip_push_frames_async and the multi-device
+ * workers' pushes with the batch decoder at KLT (the workers' contexts read the environment variable at ofps_hip_init).
+ * ofps_hip_klt_features[_dev] does not change.  A negative value or one above 4096 is OFPS_HIP_EINVAL and the setting stays as it was.
+ * ofps_hip_klt_track_q[_dev]: the stage the check is built from.  ofps_hip_klt_track[_dev]'s signature with points as int32 (Px, Py) in
+ * 1/256 pixel; one direction, from prev into cur as given, started at P as above, with the context's min_eig, max_residual and mean
+ * removal; it never applies the check.  A point outside [0, 256 (W - 1)] x [0, 256 (H - 1)] is OFPS_HIP_EINVAL in the host form and
+ * status 3 in the _dev form, with no access out of bounds.  At P = 256 (x, y) it answers what ofps_hip_klt_track answers at (x, y) with
+ * the check off.  Bit-exact against the restatement tests/indep_klt_fb.py.  Additive: OFPS_HIP_API_VERSION stays. */
+int ofps_hip_set_klt_fb(ofps_hip_ctx* ctx, int limit);
+int ofps_hip_get_klt_fb(ofps_hip_ctx* ctx);                  /* [0, 4096]; OFPS_HIP_EINVAL for a NULL context */
+int ofps_hip_klt_track_q(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points /* 2 * n */,
+                         size_t n, int levels, int radius, int iters, int32_t* out_quads /* 4 * n */);
+int ofps_hip_klt_track_q_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                             int levels, int radius, int iters, void* d_out_quads);
+
 /* ---- N3b: hip_klt on a batch of pairs, and in the batched stream forms (csrc/klt.hip, csrc/pipeline.hip) ----
  * Nothing about the arithmetic is new.  Item k of a sequence of n_frames >= 2 frames, frame_pitch >= stride * H bytes apart, is the pair
  * (k, k + 1) with ref_mode 0 and (0, k + 1) with ref_mode 1; pairs = n_frames - 1.  Per item the kept records (kept slots first, in slot

@@ -234,6 +234,8 @@ struct ofps_hip_ctx {
         int klt_cell = 16, klt_score_radius = 2, klt_min_score = 1, klt_min_eig = 1, klt_max_residual = 0;
         // ofps_hip_set_klt_mean_removal: 1 = hip_klt tracks under the model "shift plus one brightness offset" (include/ofps_hip.h N3m)
         int klt_mean_removal = 0;
+        // ofps_hip_set_klt_fb: hip_klt's forward-backward check, the round-trip limit F in 1/256 pixel, 0 = off (include/ofps_hip.h N3f)
+        int klt_fb = 0;
         // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
         // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
         int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;
@@ -381,7 +383,7 @@ int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pi
 // klt.hip (include/ofps_hip.h N3): hip_klt on one pair of device frames with the context's settings -- the kept records first, in slot order, and
 // their count in device memory; d_out holds ofps_hip_klt_slot_count records, d_slots (optional) 6 int32 per slot.  Enqueues on ctx->stream only
 // the decoder's limits on one call: levels, radius, iters, a frame of 8 .. 32768 pixels a side whose top level is at least 8 x 8, stride >= W
-constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3, kKltMaxMinEig = 65535, kKltMaxResidual = 4080;
+constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3, kKltMaxMinEig = 65535, kKltMaxResidual = 4080, kKltMaxFb = 4096;
 int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who);
 int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
                     float4* d_out, uint32_t* d_count, int* d_slots);

@@ -13,6 +13,10 @@
 //   (both in one 64-bit butterfly, a word each) and every lane's gradients become the centred N Ix - sx, N Iy - sy (below 6e7: int32), so
 //   the iteration's two sums are N3m's b1 and b2 as they are -- one more reduction per level, none per iteration --, and the residual takes a
 //   32-bit one more for the mean of d.
+// klt_track_*fb_kernel: the same body with the forward-backward check (N3f): the wave whose forward pass ends with status 0 runs the pass
+//   once more right behind it, from P = 256 (x, y) + dq and with the two frames' pointers exchanged, on the same LDS template rows and in the
+//   same registers, and keeps the slot iff that pass is kept too and comes back to within F / 256 pixel; status 5 otherwise.
+// klt_track_q_kernel, klt_track_q_zm_kernel: one direction from points given in 1/256 pixel, the stage the check is built from.
 #include "common.hpp"
 
 #include <cmath>
@@ -25,7 +29,10 @@ constexpr int kKltTemplate = (2 * kKltMaxRadius + 3) * (2 * kKltMaxRadius + 3); 
 constexpr int kKltTemplatePitch = (kKltTemplate + 3) & ~3;
 constexpr int kKltTrackWaves = 4;
 
-enum { KLT_KEPT = 0, KLT_NONE = 1, KLT_FLAT = 2, KLT_LEFT = 3, KLT_RESIDUAL = 4 };
+enum { KLT_KEPT = 0, KLT_NONE = 1, KLT_FLAT = 2, KLT_LEFT = 3, KLT_RESIDUAL = 4, KLT_NO_RETURN = 5 };
+
+// how klt_track_body starts and ends: N3 from a pixel; N3 and N3f's backward pass behind it; one pass from a 1/256-pixel position (the stage form)
+enum { KLT_MODE_PIXEL = 0, KLT_MODE_FB = 1, KLT_MODE_Q = 2 };
 
 struct KltLevels {
     const uint8_t* prev[kKltMaxLevels];
@@ -38,6 +45,7 @@ struct KltTrackParams {
     int L, w, K, min_eig, max_residual;
     const int* pts;                      // n points, pt_stride ints apart: (x, y[, score])
     int pt_stride, from_features, n;     // from_features: the points are the score kernel's triples, x < 0 = no feature (status 1)
+    int fb_limit;                        // N3f: F in 1/256 pixel, read by the FB kernels alone (it lies where the struct had padding)
     int* out_quad;                       // 4 per slot or null
     int* out_slots;                      // 6 per slot or null
     float4* out_rec;                     // the slot's record (zeros unless kept) or null
@@ -181,9 +189,10 @@ __device__ __forceinline__ int klt_sample(const uint8_t* __restrict__ img, int W
     return (s + 128) >> 8;
 }
 
-// what one lane stores for a slot: statuses 1, 2 and 3 report dq = (0, 0) and res = 0
+// what one lane stores for a slot: statuses 1, 2 and 3 report dq = (0, 0) and res = 0; status 5 (FB alone) the forward pass's, as status 4
+template <bool FB = false>
 __device__ __forceinline__ void klt_store(const KltTrackParams& p, long long slot, int x, int y, int score, int dqx, int dqy, long long res, int status) {
-    if (status != KLT_KEPT && status != KLT_RESIDUAL) { dqx = 0; dqy = 0; res = 0; }
+    if (status != KLT_KEPT && status != KLT_RESIDUAL && !(FB && status == KLT_NO_RETURN)) { dqx = 0; dqy = 0; res = 0; }
     if (p.out_quad) {
         int* o = p.out_quad + 4 * (size_t)slot;
         o[0] = dqx; o[1] = dqy; o[2] = (int)res; o[3] = status;
@@ -202,11 +211,30 @@ __device__ __forceinline__ void klt_store(const KltTrackParams& p, long long slo
     }
 }
 
+// N3f's kernels alone (where FB is true): a value, or a test, that is the same in every lane, told to the compiler, so that the branch on it is
+// a scalar one and needs no saved exec mask -- with the second pass around the first the scalar registers run out otherwise.  Elsewhere the
+// value as it is: the constant condition is folded before any instruction is chosen, so the plain kernels keep theirs
+#define KLT_UNIFORM(v) (FB ? __builtin_amdgcn_readfirstlane(v) : (v))
+#define KLT_UNIFORM_TEST(c) (FB ? __builtin_amdgcn_readfirstlane((int)(c)) != 0 : (c))
+
+// level l of the slot's frame: the previous frame's, or with `second` the current frame's
+template <bool BATCH>
+__device__ __forceinline__ const uint8_t* klt_level(const KltTrackParams& p, const KltTrackBatchParams* b, size_t item, int l, bool second) {
+    // the arrays are chosen, not the loaded values: where `second` is not a constant (N3f's kernels) one pointer and one pitch are loaded
+    const uint8_t* const* base = second ? p.lv.cur : p.lv.prev;
+    if constexpr (BATCH) return base[l] + item * (second ? b->cur_pitch : b->prev_pitch)[l];
+    else return base[l];
+}
+
 // one wave's slot.  BATCH: the slot's item picks the frames (b: the launch's pitches) and, with shared features, its triple; the outputs are
 // indexed by the slot either way.  Everything behind the pointers is one text for both kernels.  ZM: mean removal (N3m); the lines it adds
-// are compiled into its own two kernels alone
-template <bool BATCH, bool ZM>
+// are compiled into its own kernels alone.  MODE: KLT_MODE_PIXEL is N3 as it was, from the pixel (x, y), and compiles to the instructions it
+// had.  The other two start a pass at a position P in 1/256 pixel -- the level's centre ((P + 128) >> l) - 128 and the frame test on
+// P + dq * 2^l, which for P = 256 (x, y) are N3's values --: KLT_MODE_Q reads P from the points and runs one pass; KLT_MODE_FB (N3f) runs N3's
+// pass from 256 (x, y) and, where it ends with status 0, a second pass from P = 256 (x, y) + dq with prev and cur exchanged
+template <bool BATCH, bool ZM, int MODE = KLT_MODE_PIXEL>
 __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl) {
+    constexpr bool FB = MODE == KLT_MODE_FB, AT_Q = MODE != KLT_MODE_PIXEL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
     if (slot >= p.n) return;                                  // the whole wave
@@ -218,15 +246,15 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
         if (b->shared_features) pt_slot = slot - (long long)item * b->slots_per_item;
     }
     const int* pt = p.pts + (size_t)pt_slot * p.pt_stride;
-    const int x = pt[0], y = pt[1], score = p.from_features ? pt[2] : 0;
+    const int x = KLT_UNIFORM(pt[0]), y = KLT_UNIFORM(pt[1]), score = KLT_UNIFORM(p.from_features ? pt[2] : 0);      // KLT_MODE_Q: (Px, Py) in 1/256 pixel
     const int W0 = p.lv.W[0], H0 = p.lv.H[0];
     const int w = p.w, n = 2 * w + 1, n2 = n * n, m = n + 2;
     int status = KLT_KEPT, dqx = 0, dqy = 0;
     long long res = 0;
     if (p.from_features && x < 0) status = KLT_NONE;
-    else if (x < 0 || x >= W0 || y < 0 || y >= H0) status = KLT_LEFT;
+    else if (MODE == KLT_MODE_Q ? (x < 0 || x > 256 * (W0 - 1) || y < 0 || y > 256 * (H0 - 1)) : (x < 0 || x >= W0 || y < 0 || y >= H0)) status = KLT_LEFT;
     if (status != KLT_KEPT) {                                 // no feature, or a point outside the frame: the wave leaves at once
-        if (lane == 0) klt_store(p, slot, x, y, score, 0, 0, 0, status);
+        if (lane == 0) klt_store<FB>(p, slot, x, y, score, 0, 0, 0, status);
         return;
     }
     // the lane's window pixels lane + 64 k: their offsets from the window centre, and the template's value and gradients there
@@ -236,13 +264,26 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
         pj[k] = q / n; pi[k] = q - pj[k] * n;
         ix[k] = iy[k] = ic[k] = 0;
     }
+    int px = MODE == KLT_MODE_Q ? x : 256 * x, py = MODE == KLT_MODE_Q ? y : 256 * y;      // the pass's start (read with AT_Q alone)
+    int fdqx = 0, fdqy = 0;                                   // FB: the forward pass's answer while the backward pass runs
+    long long fres = 0;
+    // one pass from (x, y) or, with AT_Q, from (px, py).  FB comes here a second time, with `back`: the two frames change places.  (A jump and
+    // not a loop around the pass: a loop of one round changes the instructions the plain kernels are compiled to.)
+    bool back = false;                                        // wave-uniform
+another_pass: __attribute__((unused));
+    {
     int cqx = 0, cqy = 0;
-    for (int l = p.L - 1; l >= 0 && status == KLT_KEPT; --l) {
-        const uint8_t* __restrict__ prev = BATCH ? p.lv.prev[l] + item * b->prev_pitch[l] : p.lv.prev[l];
-        const uint8_t* __restrict__ cur = BATCH ? p.lv.cur[l] + item * b->cur_pitch[l] : p.lv.cur[l];
+    for (int l = p.L - 1; l >= 0 && KLT_UNIFORM(status) == KLT_KEPT; --l) {
+        const uint8_t* __restrict__ prev = klt_level<BATCH>(p, b, item, l, back);
+        const uint8_t* __restrict__ cur = klt_level<BATCH>(p, b, item, l, !back);
         const int Wl = p.lv.W[l], Hl = p.lv.H[l], sl = p.lv.stride[l];
-        cqx = (((2 * x + 1) * 128) >> l) - 128;
-        cqy = (((2 * y + 1) * 128) >> l) - 128;
+        if constexpr (AT_Q) {
+            cqx = ((px + 128) >> l) - 128;
+            cqy = ((py + 128) >> l) - 128;
+        } else {
+            cqx = (((2 * x + 1) * 128) >> l) - 128;
+            cqy = (((2 * y + 1) * 128) >> l) - 128;
+        }
         wave_sync();                                          // the previous level's template has been read
         for (int idx = lane; idx < m * m; idx += 64) {
             const int j = idx / m, i = idx - j * m;
@@ -275,14 +316,14 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
         }
         const double X = (double)(a11 - T), Y = (double)(a22 - T), Z = (double)a12;
         const double xy = X * Y, zz = Z * Z;
-        if (!(xy >= zz && X + Y >= 0.0)) { status = KLT_FLAT; break; }
+        if (KLT_UNIFORM_TEST(!(xy >= zz && X + Y >= 0.0))) { status = KLT_FLAT; break; }
         const double A11 = (double)a11, A22 = (double)a22;
         const double det = A11 * A22 - zz;
-        if (det <= 0.0) { status = KLT_FLAT; break; }
+        if (KLT_UNIFORM_TEST(det <= 0.0)) { status = KLT_FLAT; break; }
         const double lim = 256.0 * w;
         for (int it = 0; it < p.K; ++it) {
-            const long long fx = 256ll * x + (long long)dqx * (1ll << l), fy = 256ll * y + (long long)dqy * (1ll << l);
-            if (fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1)) { status = KLT_LEFT; break; }
+            const long long fx = (AT_Q ? (long long)px : 256ll * x) + (long long)dqx * (1ll << l), fy = (AT_Q ? (long long)py : 256ll * y) + (long long)dqy * (1ll << l);
+            if (KLT_UNIFORM_TEST(fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1))) { status = KLT_LEFT; break; }
             long long b1 = 0, b2 = 0;
             for (int k = 0; k < 4; ++k) {
                 if (lane + 64 * k < n2) {
@@ -297,17 +338,17 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
             const double ux = (-512.0 * num_x) / det, uy = (-512.0 * num_y) / det;
             const int uqx = (int)rint(fmin(fmax(ux, -lim), lim)), uqy = (int)rint(fmin(fmax(uy, -lim), lim));
             dqx += uqx; dqy += uqy;
-            if (uqx == 0 && uqy == 0) break;
+            if (KLT_UNIFORM(uqx) == 0 && KLT_UNIFORM(uqy) == 0) break;
         }
-        if (status != KLT_KEPT) break;
+        if (KLT_UNIFORM(status) != KLT_KEPT) break;
         if (l > 0) { dqx *= 2; dqy *= 2; }
     }
-    if (status == KLT_KEPT) {
-        const long long fx = 256ll * x + dqx, fy = 256ll * y + dqy;
+    if (KLT_UNIFORM(status) == KLT_KEPT) {
+        const long long fx = (AT_Q ? (long long)px : 256ll * x) + dqx, fy = (AT_Q ? (long long)py : 256ll * y) + dqy;
         if (fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1)) status = KLT_LEFT;
     }
-    if (status == KLT_KEPT) {
-        const uint8_t* __restrict__ cur0 = BATCH ? p.lv.cur[0] + item * b->cur_pitch[0] : p.lv.cur[0];
+    if (KLT_UNIFORM(status) == KLT_KEPT) {
+        const uint8_t* __restrict__ cur0 = klt_level<BATCH>(p, b, item, 0, !back);
         long long sum = 0;
         if constexpr (ZM) {
             // N3m: the residual around the window's mean difference m = floor((2 sd + N) / (2 N)), |m| <= 65,280
@@ -336,8 +377,32 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
         res = wave_sum_i64(sum);
         if (p.max_residual > 0 && res > 16ll * p.max_residual * n2) status = KLT_RESIDUAL;
     }
-    if (lane == 0) klt_store(p, slot, x, y, score, dqx, dqy, res, status);
+    }
+    if constexpr (FB) {
+        // N3f: the kernel holds the pass's text once.  Every value here is the same in all lanes: the wave takes one way.  The forward pass's
+        // final frame test has put P inside the frame, and a kept |dq| is below 256 * 32768, so everything fits an int
+        if (!back) {
+            // a forward pass that fails leaves as it does without the check.  The test and the new start are scalars, so that `back`, what it
+            // selects and the levels' centres stay in scalar registers: 92 / 94 vector registers, five waves per SIMD as the plain kernels
+            if (__builtin_amdgcn_readfirstlane(status) == KLT_KEPT) {
+                fdqx = dqx; fdqy = dqy; fres = res;
+                px = __builtin_amdgcn_readfirstlane(px + dqx); py = __builtin_amdgcn_readfirstlane(py + dqy);
+                dqx = 0; dqy = 0; res = 0;
+                back = true;
+                goto another_pass;
+            }
+        } else {
+            const int ex = fdqx + dqx, ey = fdqy + dqy;
+            const int ax = ex < 0 ? -ex : ex, ay = ey < 0 ? -ey : ey;
+            status = (status == KLT_KEPT && (ax > ay ? ax : ay) < p.fb_limit) ? KLT_KEPT : KLT_NO_RETURN;
+            dqx = fdqx; dqy = fdqy; res = fres;
+        }
+    }
+    if (lane == 0) klt_store<FB>(p, slot, x, y, score, dqx, dqy, res, status);
 }
+
+#undef KLT_UNIFORM
+#undef KLT_UNIFORM_TEST
 
 __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_kernel(const KltTrackParams p) {
     __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
@@ -358,6 +423,37 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_zm_kernel(const
 __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_zm_kernel(const KltTrackBatchParams p) {
     __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
     klt_track_body<true, true>(p.t, &p, tmpl);
+}
+
+// N3f: the four kernels of a context whose fb_limit is above 0, and the two of the stage form ofps_hip_klt_track_q
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_fb_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, false, KLT_MODE_FB>(p, nullptr, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_fb_kernel(const KltTrackBatchParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, false, KLT_MODE_FB>(p.t, &p, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_zm_fb_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, true, KLT_MODE_FB>(p, nullptr, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_zm_fb_kernel(const KltTrackBatchParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, true, KLT_MODE_FB>(p.t, &p, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_q_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, false, KLT_MODE_Q>(p, nullptr, tmpl);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_q_zm_kernel(const KltTrackParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, true, KLT_MODE_Q>(p, nullptr, tmpl);
 }
 
 struct KltSettings { int cell, r, min_score, min_eig, max_residual; };
@@ -429,10 +525,19 @@ int klt_pyramid_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* 
     return OFPS_HIP_OK;
 }
 
-int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p) {
+// at_q: the stage form ofps_hip_klt_track_q -- points in 1/256 pixel, one direction, never the check
+int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p, bool at_q = false) {
     if (p.n <= 0) return OFPS_HIP_OK;
     const dim3 grid((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves));
-    if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    if (at_q) {
+        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_q_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+        else hipLaunchKernelGGL(klt_track_q_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    } else if (ctx->opt.klt_fb > 0) {                         // N3f: the same launch, the backward pass inside it
+        KltTrackParams f = p;
+        f.fb_limit = ctx->opt.klt_fb;
+        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        else hipLaunchKernelGGL(klt_track_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
     else hipLaunchKernelGGL(klt_track_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
@@ -496,7 +601,12 @@ int klt_pyramid_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, i
 int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
     if (b.t.n <= 0) return OFPS_HIP_OK;
     const dim3 grid((unsigned)((b.t.n + kKltTrackWaves - 1) / kKltTrackWaves));
-    if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
+    if (ctx->opt.klt_fb > 0) {                                // N3f
+        KltTrackBatchParams f = b;
+        f.t.fb_limit = ctx->opt.klt_fb;
+        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        else hipLaunchKernelGGL(klt_track_batch_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
     else hipLaunchKernelGGL(klt_track_batch_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
@@ -610,6 +720,15 @@ int ofps_hip_set_klt_mean_removal(ofps_hip_ctx* ctx, int on) {
 
 int ofps_hip_get_klt_mean_removal(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_mean_removal : OFPS_HIP_EINVAL; }
 
+int ofps_hip_set_klt_fb(ofps_hip_ctx* ctx, int limit) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, limit >= 0 && limit <= kKltMaxFb, "set_klt_fb: limit %d outside [0, %d]", limit, kKltMaxFb);
+    ctx->opt.klt_fb = limit;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_klt_fb(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_fb : OFPS_HIP_EINVAL; }
+
 size_t ofps_hip_klt_slot_count(int W, int H, int cell) {
     if (W < 1 || H < 1 || (cell != 8 && cell != 16 && cell != 32)) return 0;
     return klt_slots(W, H, cell);
@@ -644,8 +763,9 @@ int ofps_hip_klt_features(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, 
     return OFPS_HIP_OK;
 }
 
-int ofps_hip_klt_track_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
-                           int levels, int radius, int iters, void* d_out_quads) {
+// ofps_hip_klt_track_dev and, with at_q, ofps_hip_klt_track_q_dev (N3f's stage form: the points are positions in 1/256 pixel)
+static int klt_track_dev_impl(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                              int levels, int radius, int iters, void* d_out_quads, bool at_q) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && (n == 0 || (d_points && d_out_quads)), "klt_track: null device pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
@@ -659,18 +779,19 @@ int ofps_hip_klt_track_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_
     p.L = levels; p.w = radius; p.K = iters; p.min_eig = ctx->opt.klt_min_eig; p.max_residual = ctx->opt.klt_max_residual;
     p.pts = static_cast<const int*>(d_points); p.pt_stride = 2; p.from_features = 0; p.n = (int)n;
     p.out_quad = static_cast<int*>(d_out_quads);
-    return klt_track_launch(ctx, p);
+    return klt_track_launch(ctx, p, at_q);
 }
 
-int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
-                       int levels, int radius, int iters, int32_t* out_quads) {
+static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
+                               int levels, int radius, int iters, int32_t* out_quads, bool at_q) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && (n == 0 || (points && out_quads)), "klt_track: null host pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
     int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_track");
     if (rc != OFPS_HIP_OK) return rc;
+    const int xmax = at_q ? 256 * (W - 1) : W - 1, ymax = at_q ? 256 * (H - 1) : H - 1;
     for (size_t k = 0; k < n; ++k)
-        OFPS_REQUIRE(ctx, points[2 * k] >= 0 && points[2 * k] < W && points[2 * k + 1] >= 0 && points[2 * k + 1] < H,
+        OFPS_REQUIRE(ctx, points[2 * k] >= 0 && points[2 * k] <= xmax && points[2 * k + 1] >= 0 && points[2 * k + 1] <= ymax,
                      "klt_track: point %zu = (%d, %d) lies outside the %d x %d frame", k, points[2 * k], points[2 * k + 1], W, H);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return OFPS_HIP_OK;
@@ -682,11 +803,31 @@ int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cu
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io, points, n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    rc = ofps_hip_klt_track_dev(ctx, d_fr, d_fr + fb, W, H, ss, d_io, n, levels, radius, iters, d_io + o_quad);
+    rc = klt_track_dev_impl(ctx, d_fr, d_fr + fb, W, H, ss, d_io, n, levels, radius, iters, d_io + o_quad, at_q);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_quads, d_io + o_quad, n * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_track_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                           int levels, int radius, int iters, void* d_out_quads) {
+    return klt_track_dev_impl(ctx, d_prev, d_cur, W, H, stride, d_points, n, levels, radius, iters, d_out_quads, false);
+}
+
+int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
+                       int levels, int radius, int iters, int32_t* out_quads) {
+    return klt_track_host_impl(ctx, prev, cur, W, H, stride, points, n, levels, radius, iters, out_quads, false);
+}
+
+int ofps_hip_klt_track_q_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
+                             int levels, int radius, int iters, void* d_out_quads) {
+    return klt_track_dev_impl(ctx, d_prev, d_cur, W, H, stride, d_points, n, levels, radius, iters, d_out_quads, true);
+}
+
+int ofps_hip_klt_track_q(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
+                         int levels, int radius, int iters, int32_t* out_quads) {
+    return klt_track_host_impl(ctx, prev, cur, W, H, stride, points, n, levels, radius, iters, out_quads, true);
 }
 
 int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,

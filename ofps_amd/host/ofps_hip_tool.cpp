@@ -7,12 +7,13 @@
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
-//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal]]
+//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N]]
 //                                                       PCIe-inclusive per-frame time of the hip_sad process_frame shape; `multi`:
 //                                                       the stream over several workers (ofps_hip_multi_push_frames_async), with
 //                                                       detector + estimator per frame; `--klt` (batch, multi): hip_klt as the
 //                                                       batched stream's decoder (ofps_hip_set_batch_decoder / OFPS_HIP_BATCH_DECODER);
-//                                                       `--klt-mean-removal`: with its mean removal on (include/ofps_hip.h N3m)
+//                                                       `--klt-mean-removal`: with its mean removal on (include/ofps_hip.h N3m);
+//                                                       `--klt-fb N`: with its forward-backward check at N / 256 pixel (N3f)
 //   track   <decoder> <arg> [aspect fov_y] [lsq|ransac] tracking loop, ofps-suite/src/app/tracking/worker.rs:305-412
 //   mvec-copy <in.mvec> <out.mvec>                      CPU-only .mvec round trip (reader + writer)
 //   multi-extract <raw.y> <w> <h> <out.mvec> [dev ...]  the whole clip over several GPUs (ofps_hip_multi_*): same bytes as `extract hip_sad`
@@ -213,6 +214,7 @@ int main(int argc, char** argv) {
             // `--probe` (batch mode): also print the bare H2D rate of one batch buffer, the CPU this thread runs on and the NUMA
             // node the page-locked buffers landed on (the batched form is bimodal from process to process: profiles/r05/batched_bimodal.txt)
             int sb_block = 16, sb_range = 16;
+            int sb_klt_fb = 0;                                 // `--klt-fb N` beside `--klt`: ofps_hip_set_klt_fb(N) / OFPS_HIP_KLT_FB=N
             bool sb_klt_zm = false;                            // `--klt-mean-removal` beside `--klt`: ofps_hip_set_klt_mean_removal(1) / OFPS_HIP_KLT_MEAN_REMOVAL=1
             bool sb_probe = false, sb_klt = false;             // `--klt` (batch and multi modes): hip_klt as the batched stream's decoder (N3b), levels 4, radius 7, 10 iterations
             {
@@ -221,12 +223,14 @@ int main(int argc, char** argv) {
                     if (std::string(argv[a]) == "--probe") { sb_probe = true; continue; }
                     if (std::string(argv[a]) == "--klt") { sb_klt = true; continue; }
                     if (std::string(argv[a]) == "--klt-mean-removal") { sb_klt_zm = true; continue; }
+                    if (a + 1 < argc && std::string(argv[a]) == "--klt-fb") { sb_klt_fb = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--block") { sb_block = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--range") { sb_range = std::atoi(argv[++a]); continue; }
                     argv[keep++] = argv[a];
                 }
                 argc = keep;
                 if (sb_klt_zm && !sb_klt) throw Error("stream-bench: --klt-mean-removal needs --klt");
+                if (sb_klt_fb && !sb_klt) throw Error("stream-bench: --klt-fb needs --klt");
             }
             // the Decoder::process_frame shape without Python in the loop: frames are already in page-locked buffers (a
             // decoder that writes there), one H2D + search + 16 B/vector D2H per frame
@@ -245,6 +249,7 @@ int main(int argc, char** argv) {
                 // the workers' contexts take the decoder from the environment at their init alone
                 if (sb_klt) setenv("OFPS_HIP_BATCH_DECODER", "1", 1);
                 if (sb_klt_zm) setenv("OFPS_HIP_KLT_MEAN_REMOVAL", "1", 1);
+                if (sb_klt_fb) setenv("OFPS_HIP_KLT_FB", std::to_string(sb_klt_fb).c_str(), 1);
                 if (ofps_hip_multi_init(devices.data(), (int)devices.size(), &m) != OFPS_HIP_OK) throw Error(ofps_hip_multi_last_error(nullptr));
                 const int nw = (int)devices.size(), slots = 2 * nw;
                 HipContext alloc;                                           // page-locked memory comes from any context
@@ -279,9 +284,9 @@ int main(int argc, char** argv) {
                 run(nb);
                 const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / ((double)nb * mb);
                 std::printf("{\"mode\": \"multi_read_ahead_batched\", \"workers\": %d, \"batch\": %d, \"frames\": %d, \"block\": %d, \"range\": %d, "
-                            "\"ms_per_frame\": %.4f, \"Mvectors_per_s\": %.2f, \"decoder\": \"%s\", \"mean_removal\": %d, \"capacity\": %zu, \"last_n_vectors\": %zu, "
+                            "\"ms_per_frame\": %.4f, \"Mvectors_per_s\": %.2f, \"decoder\": \"%s\", \"mean_removal\": %d, \"fb_limit\": %d, \"capacity\": %zu, \"last_n_vectors\": %zu, "
                             "\"per_frame\": \"vectors + block-motion island + almeida LSQ quaternion\"}\n",
-                            nw, mb, nb * mb, sb_block, sb_range, ms, (double)nblk / ms / 1e3, sb_klt ? "hip_klt" : "hip_sad", sb_klt_zm ? 1 : 0,
+                            nw, mb, nb * mb, sb_block, sb_range, ms, (double)nblk / ms / 1e3, sb_klt ? "hip_klt" : "hip_sad", sb_klt_zm ? 1 : 0, sb_klt_fb,
                             nblk, (size_t)res[(size_t)mb - 1].n_vectors);
                 for (auto p : pin) ofps_hip_host_free(alloc.get(), p);
                 for (auto p : ent) ofps_hip_host_free(alloc.get(), p);
@@ -295,6 +300,7 @@ int main(int argc, char** argv) {
                 if (sb_klt) {
                     ctx.check(ofps_hip_set_batch_decoder(ctx.get(), OFPS_HIP_BATCH_DECODER_KLT, 4, 7, 10));
                     if (sb_klt_zm) ctx.check(ofps_hip_set_klt_mean_removal(ctx.get(), 1));
+                    if (sb_klt_fb) ctx.check(ofps_hip_set_klt_fb(ctx.get(), sb_klt_fb));
                     ctx.check(ofps_hip_get_klt(ctx.get(), &klt_cell, nullptr, nullptr, nullptr, nullptr));
                 }
                 const size_t nblk = sb_klt ? ofps_hip_klt_slot_count(W, H, klt_cell) : ofps_hip_sad_block_count(W, H, 16);
@@ -342,8 +348,8 @@ int main(int argc, char** argv) {
                                 "\"bare_h2d_GBs\": [%.1f, %.1f], \"buffer_numa_node\": [%d, %d], \"cpu\": %d}\n", batch, nb * batch, ms,
                                 (double)nblk / ms / 1e3, probe_gbs[0], probe_gbs[1], probe_node[0], probe_node[1], probe_cpu);
                 else if (sb_klt)
-                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
-                                "\"capacity\": %zu, \"last_n_vectors\": %zu}\n", ofps_hip_get_klt_mean_removal(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
+                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"fb_limit\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
+                                "\"capacity\": %zu, \"last_n_vectors\": %zu}\n", ofps_hip_get_klt_mean_removal(ctx.get()), ofps_hip_get_klt_fb(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
                 else
                 std::printf("{\"mode\": \"read_ahead_batched\", \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, \"Mvectors_per_s\": %.2f}\n", batch,
                             nb * batch, ms, (double)nblk / ms / 1e3);

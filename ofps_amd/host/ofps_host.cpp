@@ -210,6 +210,7 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
         ctx_.check(ofps_hip_set_klt(ctx_.get(), (int)klt_->cell, (int)klt_->score_radius, (int)klt_->min_score, (int)klt_->min_eig,
                                     (int)klt_->max_residual));
         ctx_.check(ofps_hip_set_klt_mean_removal(ctx_.get(), klt_->mean_removal ? 1 : 0));
+        ctx_.check(ofps_hip_set_klt_fb(ctx_.get(), (int)klt_->fb_limit));
         out_.resize(klt_record_floats(w_, h_, max_w_, max_h_, process_fullres_, klt_->cell));
     } else {
         out_.resize(records_fullres ? 4 * w_ * h_ : 4 * std::min(max_w_, w_) * std::min(max_h_, h_));
@@ -271,7 +272,7 @@ std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage&
             {"Min score", PropertyMut::usize(&s.min_score, 1, kKltMaxScore)}, {"Min eigenvalue", PropertyMut::usize(&s.min_eig, 1, kKltMaxEig)},
             {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)}, {"Levels", PropertyMut::usize(at.levels, 1, 6)},
             {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)},
-            {"Mean removal", PropertyMut::boolean(&s.mean_removal)}};
+            {"Mean removal", PropertyMut::boolean(&s.mean_removal)}, {"Consistency check", PropertyMut::usize(&s.fb_limit, 0, kKltMaxFb)}};
 }
 
 // ------------------------------------------------------------------ .mvec

@@ -162,10 +162,11 @@ private:
 };
 
 // "hip_klt" (include/ofps_hip.h N3): what the decoder below keeps for it, its property table, and the size of its record buffer
-constexpr size_t kKltMaxResidual = 4080, kKltMaxEig = 65535, kKltMaxScore = 2147483647;
+constexpr size_t kKltMaxResidual = 4080, kKltMaxEig = 65535, kKltMaxScore = 2147483647, kKltMaxFb = 4096;
 struct KltSettings {
     size_t cell = 16, score_radius = 2, min_score = 1, min_eig = 1, max_residual = 0;
     bool mean_removal = false;             // "Mean removal" (N3m): ofps_hip_set_klt_mean_removal before every push
+    size_t fb_limit = 0;                   // "Consistency check" (N3f): ofps_hip_set_klt_fb before every push, 1/256 pixel, 0 = off
 };
 // the storage behind hip_klt's properties; klt_props is the one table of their names and bounds (the decoder's props_mut returns it)
 struct KltPropStorage { size_t *max_w, *max_h; bool* process_fullres; KltSettings* settings; size_t *levels, *radius, *iters; };

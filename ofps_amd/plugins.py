@@ -281,13 +281,17 @@ class HipKltDecoder(HipLkDecoder):
               ("Levels", "usize", "levels", 1, 6), ("Window radius", "usize", "radius", 1, 7), ("Iterations", "usize", "iters", 1, 30),
               # build-defined: the tracker solves for the shift and one brightness offset per window, for streams whose brightness changes
               # between frames (include/ofps_hip.h N3m); hip_sad's property of the same name is its counterpart
-              ("Mean removal", "bool", "mean_removal", None, None))
+              ("Mean removal", "bool", "mean_removal", None, None),
+              # build-defined: the forward-backward check (include/ofps_hip.h N3f), the round-trip limit in 1/256 pixel, 0 = off; hip_sad's
+              # property of the same name is its counterpart
+              ("Consistency check", "usize", "fb_limit", 0, 4096))
 
     def __init__(self, frames, framerate=None, device: int = 0, frame_format: int = HipContext.FMT_LUMA):
         super().__init__(frames, framerate, device, frame_format)
         self.levels, self.radius, self.iters = 4, 7, 10
         self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual = 16, 2, 1, 1, 0
         self.mean_removal = False
+        self.fb_limit = 0
         self.contrast_mask = False
 
     def process_frame(self, field: list, out_frame=None, skip_frames: int = 0) -> bool:
@@ -304,6 +308,7 @@ class HipKltDecoder(HipLkDecoder):
             return False
         self.ctx.set_klt(self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual)
         self.ctx.set_klt_mean_removal(1 if self.mean_removal else 0)
+        self.ctx.set_klt_fb(self.fb_limit)
         return self._decode(field, dict(reduced=not self.process_fullres, fmt=self.frame_format, sparse=True))
 
 

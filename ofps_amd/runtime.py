@@ -604,6 +604,14 @@ class HipContext:
     def get_klt_mean_removal(self) -> int:
         return int(self._lib.ofps_hip_get_klt_mean_removal(self._h))
 
+    def set_klt_fb(self, limit: int):
+        """hip_klt's forward-backward check (include/ofps_hip.h N3f): limit F in [0, 4096] in 1/256 pixel; a kept track is followed back from
+        where it ended and dropped (status 5) unless that pass is kept too and returns to within F of the feature.  0 (default): off."""
+        self._check(self._lib.ofps_hip_set_klt_fb(self._h, int(limit)))
+
+    def get_klt_fb(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_fb(self._h))
+
     def klt_slot_count(self, W: int, H: int, cell: int | None = None) -> int:
         return int(self._lib.ofps_hip_klt_slot_count(W, H, self.get_klt()["cell"] if cell is None else cell))
 
@@ -643,6 +651,28 @@ class HipContext:
                                                  stride, pts.ctypes.data_as(i32) if len(pts) else None, len(pts), levels, radius, iters,
                                                  out.ctypes.data_as(i32)))
         return out[:len(pts)]
+
+    def klt_track_q(self, prev: np.ndarray, cur: np.ndarray, points: np.ndarray, levels: int, radius: int, iters: int,
+                    stride: int | None = None) -> np.ndarray:
+        """N3f's stage form: points int [n, 2] (Px, Py) in 1/256 pixel inside the frame -> int32 [n, 4]: (dqx, dqy, res, status); one direction,
+        from prev into cur, never checked"""
+        p, stride = self._luma_view(prev, stride)
+        c, stride_c = self._luma_view(cur, stride)
+        assert p.shape == c.shape and stride == stride_c
+        H, W = p.shape
+        pts = np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+        out = np.zeros((max(len(pts), 1), 4), np.int32)
+        u8, i32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_track_q(self._h, C.cast(C.c_void_p(p.ctypes.data), u8), C.cast(C.c_void_p(c.ctypes.data), u8), W, H,
+                                                   stride, pts.ctypes.data_as(i32) if len(pts) else None, len(pts), levels, radius, iters,
+                                                   out.ctypes.data_as(i32)))
+        return out[:len(pts)]
+
+    def klt_track_q_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, d_points: int, n: int, levels: int, radius: int, iters: int,
+                        d_out_quads: int):
+        """Enqueue only; a position outside the frame comes back with status 3."""
+        self._check(self._lib.ofps_hip_klt_track_q_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, C.c_void_p(d_points), n,
+                                                       levels, radius, iters, C.c_void_p(d_out_quads)))
 
     def klt_track_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, d_points: int, n: int, levels: int, radius: int, iters: int,
                       d_out_quads: int):

@@ -27,7 +27,8 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               with --klt also hip_klt: the sparse decoder (include/ofps_hip.h N3) with its defaults -- cell 16, levels 4, window radius 7, 10
               iterations, no residual limit; --klt-cell C [C ...] and --klt-residual R [R ...] add hip_klt_c<C>r<R> for every other pair of
               "Cell size" and "Max residual"; --klt-mean-removal adds the same columns once more with "Mean removal" on (include/ofps_hip.h
-              N3m) as hip_klt_m and hip_klt_c<C>r<R>_m; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
+              N3m) as hip_klt_m and hip_klt_c<C>r<R>_m; --klt-fb N [N ...] adds every hip_klt column once more per N with "Consistency check" = N
+              (include/ofps_hip.h N3f, the round-trip limit in 1/256 pixel) as hip_klt_f<N>, and with --klt-mean-removal as hip_klt_f<N>_m; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
   cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
               cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
@@ -173,7 +174,7 @@ CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
         fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
         cut_clip=False, sad_split=(), klt=False, klt_cells=(16,), klt_residuals=(0,), skip=(),
-        klt_mean_removal=False):
+        klt_mean_removal=False, klt_fb=()):
     from ofps_amd.plugins import HipFlowDecoder, HipKltDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -239,6 +240,12 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
                 if klt_mean_removal:        # ... and the same once more with "Mean removal" on (include/ofps_hip.h N3m)
                     props_km = dict(props_k, **{"Mean removal": True})
                     combos += [(tag + "_m", HipKltDecoder, False, props_km), (tag + "_m", HipKltDecoder, True, props_km)]
+                for fb in klt_fb:           # ... and once more per limit of the forward-backward check (include/ofps_hip.h N3f)
+                    props_kf = dict(props_k, **{"Consistency check": fb})
+                    combos += [(f"{tag}_f{fb}", HipKltDecoder, False, props_kf), (f"{tag}_f{fb}", HipKltDecoder, True, props_kf)]
+                    if klt_mean_removal:
+                        props_kfm = dict(props_kf, **{"Mean removal": True})
+                        combos += [(f"{tag}_f{fb}_m", HipKltDecoder, False, props_kfm), (f"{tag}_f{fb}_m", HipKltDecoder, True, props_kfm)]
     combos = [c for c in combos if c[0] not in skip]
     res = {}
     clips = []
@@ -396,6 +403,7 @@ def main():
     ap.add_argument("--klt-cell", nargs="*", type=int, default=[16], metavar="C", help="with --klt: \"Cell size\" values; hip_klt_c<C>r<R> beside hip_klt")
     ap.add_argument("--klt-residual", nargs="*", type=int, default=[0], metavar="R", help="with --klt: \"Max residual\" values (sixteenths of a grey level)")
     ap.add_argument("--klt-mean-removal", action="store_true", help="with --klt: every hip_klt column once more with \"Mean removal\" on, as <column>_m")
+    ap.add_argument("--klt-fb", nargs="*", type=int, default=[], metavar="N", help="with --klt: \"Consistency check\" values in 1/256 pixel; hip_klt_f<N> beside hip_klt")
     ap.add_argument("--skip", nargs="*", default=[], metavar="NAME", help="decoder columns to leave out, e.g. hip_lk5 hip_flow")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
@@ -403,7 +411,7 @@ def main():
               sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
               sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split),
               klt=args.klt, klt_cells=tuple(args.klt_cell), klt_residuals=tuple(args.klt_residual), skip=tuple(args.skip),
-              klt_mean_removal=args.klt_mean_removal)
+              klt_mean_removal=args.klt_mean_removal, klt_fb=tuple(args.klt_fb))
     txt = table(res)
     print(txt)
     if args.out:

@@ -67,9 +67,16 @@ int main() {
         if (name == "Window radius") listed += u && u->val == 7 && u->min == 1 && u->max == 7;
         if (name == "Iterations") listed += u && u->val == 10 && u->min == 1 && u->max == 30;
         if (name == "Mean removal") listed += std::holds_alternative<bool>(v) && !std::get<bool>(v);      // N3m: a boolean, off by default
+        if (name == "Consistency check") listed += u && u->val == 0 && u->min == 0 && u->max == 4096;     // N3f: 1/256 pixel, 0 = off
     }
-    CHECK(listed == 9);
-    CHECK(p.props().back().first == "Mean removal");                                 // behind "Iterations"
+    CHECK(listed == 10);
+    {
+        const auto all = p.props();                                                  // "Iterations", "Mean removal", "Consistency check" last
+        CHECK(all.size() >= 3 && all[all.size() - 3].first == "Iterations" && all[all.size() - 2].first == "Mean removal");
+        CHECK(all.back().first == "Consistency check");
+    }
+    CHECK(p.set_prop("Consistency check", Property{BoundedProp<size_t>{64, 0, kKltMaxFb}}) && p.set.fb_limit == 64);
+    CHECK(p.set_prop("Consistency check", Property{true}) && p.set.fb_limit == 64);           // a mismatched kind is ignored
     CHECK(p.set_prop("Mean removal", Property{true}) && p.set.mean_removal);
     CHECK(p.set_prop("Mean removal", Property{BoundedProp<size_t>{0, 0, 1}}) && p.set.mean_removal);    // a mismatched kind is ignored
     CHECK(p.set_prop("Max residual", Property{BoundedProp<size_t>{160, 0, kKltMaxResidual}}) && p.set.max_residual == 160);
@@ -79,7 +86,8 @@ int main() {
         "detector": [{"selected_plugin": "hip_block_motion", "arg": "", "extra": null}, true],
         "settings": {"worker": {"decoder_properties": {"Cell size": {"Usize": {"val": 8, "min": 8, "max": 32}},
         "Max residual": {"Usize": {"val": 64, "min": 0, "max": 4080}}, "Levels": {"Usize": {"val": 3, "min": 1, "max": 6}},
-        "Process Fullres": {"Bool": false}, "Mean removal": {"Bool": true}, "Not a property of this plugin": {"Bool": true}}, "realtime_processing": false,
+        "Process Fullres": {"Bool": false}, "Mean removal": {"Bool": true}, "Consistency check": {"Usize": {"val": 16, "min": 0, "max": 4096}},
+        "Not a property of this plugin": {"Bool": true}}, "realtime_processing": false,
         "detector_properties": {}}, "overlay_mf": false, "max_frame_gap": 2, "min_frames": 2,
         "draw_perf_stats": {"summary_window": false, "graph_window": false}}})";
     try {
@@ -88,6 +96,7 @@ int main() {
         transfer_props(c.decoder_properties, q);
         CHECK(q.set.cell == 8 && q.set.max_residual == 64 && q.levels == 3 && !q.process_fullres && q.radius == 7 && q.set.min_eig == 1);
         CHECK(q.set.mean_removal && !KltProps().set.mean_removal);
+        CHECK(q.set.fb_limit == 16 && KltProps().set.fb_limit == 0);
         CHECK(klt_record_floats(64, 48, q.max_w, q.max_h, true, q.set.cell) == 4 * 8 * 6);
         size_t seen = 0;
         for (const auto& [name, v] : q.props())
@@ -96,6 +105,10 @@ int main() {
         for (const auto& [name, v] : q.props())
             if (name == "Mean removal") zm = std::get<bool>(v);
         CHECK(zm);
+        size_t fb = 0;
+        for (const auto& [name, v] : q.props())
+            if (name == "Consistency check") fb = std::get<BoundedProp<size_t>>(v).val;
+        CHECK(fb == 16);
         CHECK(seen == 8);                                                            // and out again, as a saved configuration would store it
     } catch (const Error& e) {
         std::fprintf(stderr, "configuration: %s\n", e.what());

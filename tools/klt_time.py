@@ -23,7 +23,9 @@ taken here: it is the kernel times of a `rocprofv3 --kernel-trace --stats` run o
 klt_track_batch_kernel, compact_items_kernel), in a run of its own.
 
 --mean-removal: the same table, or the same batch mode, with ofps_hip_set_klt_mean_removal(1) (N3m): every hip_klt row then runs
-klt_track_zm_kernel / klt_track_batch_zm_kernel; the rows say so ("mean_removal": 1).  --klt-only leaves the hip_sad and hip_lk rows out."""
+klt_track_zm_kernel / klt_track_batch_zm_kernel; the rows say so ("mean_removal": 1).  --klt-only leaves the hip_sad and hip_lk rows out.
+--fb N: with ofps_hip_set_klt_fb(N) (N3f): every hip_klt row then runs the FB kernels, the backward pass inside the track launch for the slots
+the forward pass kept; the rows say so ("fb_limit": N) and their "kept" and status histogram (5 = did not return) are the checked ones."""
 import argparse
 import json
 import os
@@ -100,7 +102,7 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     for p in [d_fr, d_tri, d_quad, d_rec, d_cnt, d_slots, d_pts, d_sad, d_lk] + [b for lv in pyr for b in lv[3:]]:
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "mean_removal": ctx.get_klt_mean_removal(), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
+            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
 def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm):
@@ -134,7 +136,7 @@ def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, call
     for p in (d_fr, d_rec, d_cnt, d_rec1, d_cnt1):
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "mean_removal": ctx.get_klt_mean_removal(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
+            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
             "us_per_pair": t}
 
 
@@ -152,10 +154,12 @@ def main():
     ap.add_argument("--max-residual", type=int, default=0)
     ap.add_argument("--no-4k", action="store_true")
     ap.add_argument("--mean-removal", action="store_true", help="hip_klt with mean removal (include/ofps_hip.h N3m)")
+    ap.add_argument("--fb", type=int, default=0, metavar="N", help="hip_klt with the forward-backward check at N / 256 pixel (include/ofps_hip.h N3f)")
     ap.add_argument("--klt-only", action="store_true", help="no hip_sad and hip_lk rows beside hip_klt's")
     a = ap.parse_args()
     ctx = HipContext(0)
     ctx.set_klt_mean_removal(1 if a.mean_removal else 0)
+    ctx.set_klt_fb(a.fb)
     rows = []
     for W, H, cell in ([] if a.no_1080p else [(1920, 1080, 16)]) + ([] if a.no_4k else [(3840, 2160, 8)]):
         lum = synth.luma_sequence(max(a.batch + 1, 2), W, H, max_step=6, seed=5)
