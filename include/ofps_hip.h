@@ -788,6 +788,59 @@ int ofps_hip_klt_track_q(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* 
 int ofps_hip_klt_track_q_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
                              int levels, int radius, int iters, void* d_out_quads);
 
+/* ---- N3p: hip_klt with motion prediction: a track starts from the previous pair's flow (csrc/klt.hip, csrc/dense_decoder.hip) ----
+ * Build-defined, off by default; hip_klt's counterpart of hip_sad's neighbour predictors (N1p) and of OFPS_HIP_FLOW_USE_PREVIOUS.  N3 starts
+ * every track at dq = (0, 0), so the pyramid has to reach the whole motion of the pair; started from the previous pair's flow it has to
+ * reach the CHANGE of motion between two pairs.
+ * Guess.  A track may start from a guess g = (gx, gy), int32, in 1/256 pixel at level 0:
+ *   N3's line "dq = (0, 0)" becomes dq = (gx >> (L - 1), gy >> (L - 1)), arithmetic shift (-1 >> 1 = -1; L = 1 is no shift);
+ *   the guess is replaced by (0, 0) if |gx| or |gy| exceeds 2^23 (8,388,608);
+ *   it is replaced by (0, 0) too if the start fails N3's frame test: 256 x + dqx * 2^(L - 1) outside [0, 256 (W - 1)] or
+ *     256 y + dqy * 2^(L - 1) outside [0, 256 (H - 1)] (in a pass that starts at a position P, N3f's backward pass: P + ...);
+ *   everything after that line is N3's text, N3m's where mean removal is on.  The reported dq is the whole displacement, guess included;
+ *   statuses 1, 2 and 3 report zeros as before.  A guess of (0, 0) gives N3's answer bit for bit.
+ * With N3f on, the backward pass starts at P = 256 (x, y) + dq as before, with the guess (-gx, -gy): the negation first, then the three
+ *   rules above.  (Not the forward result: that would start the backward pass on the feature and weaken the check.)
+ * Predictor.  The guess of lattice slot (cx, cy) is made from the raw slots of the previous pair on the same lattice, int32
+ *   (x, y, score, dqx, dqy, status) per slot as ofps_hip_klt_flow writes them.  The candidates are the slot itself and its left, right,
+ *   upper and lower lattice neighbours, those that lie inside the lattice and have status 0; slots of status 1 to 5 are not used.  With
+ *   none the guess is (0, 0); with k of them it is, per component, the element of index (k - 1) / 2 (integer division) of the k values
+ *   sorted ascending: the median, the lower middle for an even k.  All-integer.
+ * Setting of the context, prediction in {0, 1} (ofps_hip_set_klt_prediction; option and environment variable OFPS_HIP_KLT_PREDICTION).
+ *   Any other value is OFPS_HIP_EINVAL and the setting stays as it was.  With 0 every entry point enqueues the launches and bytes it
+ *   enqueues without this row.  Only the stream forms below read it.
+ * ofps_hip_klt_predict[_dev]: the previous pair's slots (6 * slots int32) and W, H, cell -> int32 (gx, gy) per slot: the predictor alone.
+ * ofps_hip_klt_track_from[_dev]: ofps_hip_klt_track[_dev] with one guess per point, `guesses` (2 * n int32).  It follows the context's
+ *   min_eig, max_residual, mean removal and fb_limit and does not read the prediction setting.  A guess beyond +-2^23 is OFPS_HIP_EINVAL
+ *   in the host form and (0, 0) in the _dev form.
+ * ofps_hip_klt_flow_from[_dev]: ofps_hip_klt_flow[_dev] with `prev_slots` (6 * slots int32, or NULL).  With NULL it is ofps_hip_klt_flow,
+ *   bit for bit and launch for launch; otherwise every feature starts from its slot's predicted guess (the predictor runs inside the track
+ *   launch).  The caller passes one call's out_slots to the next.  It does not read the setting either.  In the _dev form d_prev_slots
+ *   and d_out_slots must not overlap (the track reads neighbours' previous slots while it writes its own: two buffers, alternating);
+ *   overlapping arrays are OFPS_HIP_EINVAL.  The host form copies prev_slots first: there the two may be one array.
+ * OFPS_HIP_FLOW_SPARSE in the dense decoders' stream and fused forms (ofps_hip_lk_push_frame*, ofps_hip_lk_push_frame_fused[_async], full
+ *   resolution and reduced, every frame format): with the setting on the stream keeps the last pair's raw slots on the device (two buffers
+ *   per stream that alternate by pair) and the track of pair k reads the slots of pair k - 1: records, counts, island and quaternion are
+ *   those of a chain of ofps_hip_klt_flow_from calls on the frames the tracker reads.  The slots are forgotten on ofps_hip_lk_reset and
+ *   ofps_hip_lk_rewind, on the stream's first pair, and on any change of geometry, format, mode, cell or flags.  A pair pushed with the
+ *   setting off writes no slots, so its successor starts from zero: the setting may be switched in mid-stream.
+ * The batch form ofps_hip_klt_flow_batch[_dev], ofps_hip_push_frames_async and the multi-device workers IGNORE the setting and return the
+ *   bytes they return without it: item k's guess would depend on item k - 1's result, which would serialise the one track launch N3b
+ *   exists for.  ofps_hip_klt_track[_dev], _track_q[_dev], _flow[_dev] and ofps_hip_lk_decode start from (0, 0) as before.
+ * Bit-exact against the restatement tests/indep_klt_pred.py.  Additive: OFPS_HIP_API_VERSION stays. */
+int ofps_hip_set_klt_prediction(ofps_hip_ctx* ctx, int on);
+int ofps_hip_get_klt_prediction(ofps_hip_ctx* ctx);          /* 0 | 1; OFPS_HIP_EINVAL for a NULL context */
+int ofps_hip_klt_predict(ofps_hip_ctx* ctx, const int32_t* prev_slots /* 6 * slots */, int W, int H, int cell, int32_t* out_guesses /* 2 * slots */);
+int ofps_hip_klt_predict_dev(ofps_hip_ctx* ctx, const void* d_prev_slots, int W, int H, int cell, void* d_out_guesses);
+int ofps_hip_klt_track_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points /* 2 * n */,
+                            const int32_t* guesses /* 2 * n */, size_t n, int levels, int radius, int iters, int32_t* out_quads /* 4 * n */);
+int ofps_hip_klt_track_from_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points,
+                                const void* d_guesses, size_t n, int levels, int radius, int iters, void* d_out_quads);
+int ofps_hip_klt_flow_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
+                           const int32_t* prev_slots /* 6 * slots, or NULL */, float* out_entries, uint32_t* n_out, int32_t* out_slots /* or NULL */);
+int ofps_hip_klt_flow_from_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                               const void* d_prev_slots, void* d_out_entries, void* d_out_count, void* d_out_slots);
+
 /* ---- N3b: hip_klt on a batch of pairs, and in the batched stream forms (csrc/klt.hip, csrc/pipeline.hip) ----
  * Nothing about the arithmetic is new.  Item k of a sequence of n_frames >= 2 frames, frame_pitch >= stride * H bytes apart, is the pair
  * (k, k + 1) with ref_mode 0 and (0, k + 1) with ref_mode 1; pairs = n_frames - 1.  Per item the kept records (kept slots first, in slot

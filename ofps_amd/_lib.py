@@ -128,6 +128,14 @@ PROTOTYPES = {
     "ofps_hip_get_klt_fb": (C.c_int, [_ctx]),
     "ofps_hip_klt_track_q": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _i32p, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p]),
     "ofps_hip_klt_track_q_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
+    "ofps_hip_set_klt_prediction": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_klt_prediction": (C.c_int, [_ctx]),
+    "ofps_hip_klt_predict": (C.c_int, [_ctx, _i32p, C.c_int, C.c_int, C.c_int, _i32p]),
+    "ofps_hip_klt_predict_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "ofps_hip_klt_track_from": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p]),
+    "ofps_hip_klt_track_from_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
+    "ofps_hip_klt_flow_from": (C.c_int, [_ctx, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f32p, _u32p, _i32p]),
+    "ofps_hip_klt_flow_from_dev": (C.c_int, [_ctx, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "ofps_hip_klt_slot_count": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ofps_hip_klt_features": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, _i32p]),
     "ofps_hip_klt_features_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, _vp]),

@@ -167,6 +167,9 @@ struct DenseStream {
     bool fb_params_valid = false; int fb_levels = 0, fb_radius = 0;     // the hip_flow stream's last Farneback parameters (a change with a ticket in flight is refused)
     uint64_t frame_serial = 0;           // frames of the stream carry ids (FarnebackState::cache); the id of the frame in each slot
     uint64_t slot_id[kSlots] = {0, 0, 0};
+    // N3p (OFPS_HIP_FLOW_SPARSE with klt_prediction 1): the last pair's raw slots lie in half `pair & 1` of S_KLT_PRED; the pair that follows
+    // reads them if nothing of what they were made under has changed
+    struct KltPred { bool valid = false; long pair = 0; int fw = 0, fh = 0, cell = 0; unsigned flags = 0; uint64_t gen = 0; } klt_pred;
     hipStream_t copy_stream = nullptr;
     struct Ticket {
         bool pending = false;
@@ -236,6 +239,8 @@ struct ofps_hip_ctx {
         int klt_mean_removal = 0;
         // ofps_hip_set_klt_fb: hip_klt's forward-backward check, the round-trip limit F in 1/256 pixel, 0 = off (include/ofps_hip.h N3f)
         int klt_fb = 0;
+        // ofps_hip_set_klt_prediction: 1 = the sparse stream forms start a pair's tracks from the previous pair's flow (include/ofps_hip.h N3p)
+        int klt_prediction = 0;
         // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
         // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
         int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;
@@ -310,9 +315,10 @@ enum ScratchSlot {
     S_SPLIT,                // hip_sad's split step (sad_split.hip, N1s): [raw slots, 4 records per block][sub triples, 12 i32 per block][slot flags, 4 u8 per block][split flags, u8 per block].  Compute stream only, written anew by every search
     S_KLT_PYR,              // hip_klt (klt.hip, N3): both frames' pyramid levels above 0.  Compute stream only, written anew by every call
     S_KLT_WORK,             // ... [features, 3 i32 per slot][raw records per slot][keep flags, u8 per slot], in front of the compaction
-    S_KLT_HOST              // ... the host-pointer forms' device-side inputs and outputs
+    S_KLT_HOST,             // ... the host-pointer forms' device-side inputs and outputs
+    S_KLT_PRED              // N3p: the sparse stream's raw slots of the last two pairs, 6 i32 per slot each.  Compute stream only
 };
-static_assert(S_KLT_HOST < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_KLT_PRED < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -386,7 +392,7 @@ int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pi
 constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3, kKltMaxMinEig = 65535, kKltMaxResidual = 4080, kKltMaxFb = 4096;
 int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who);
 int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
-                    float4* d_out, uint32_t* d_count, int* d_slots);
+                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots = nullptr);      // d_prev_slots: N3p, the previous pair's raw slots
 // N3b: item k of `pairs` pairs of `f` = klt_flow_device on that pair, bit for bit, in a number of launches that does not depend on `pairs`:
 // one score launch over the distinct prev frames, one halving per level over the distinct frames, one track launch of pairs x slots waves, the
 // segmented compaction.  d_out: pairs slots of the slot count, item k's kept records lead slot k; d_counts: pairs counts; d_slots (optional):

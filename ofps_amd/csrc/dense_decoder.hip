@@ -126,12 +126,13 @@ __global__ __launch_bounds__(256) void dense_copy_records_kernel(const float4* _
 int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int levels, int radius, int iters,
                      const DenseGrid& g, float4* rec_dst, uint32_t* cnt_dst, uint64_t prev_id = 0,
                      uint64_t cur_id = 0, const uint8_t* d_mask_ready = nullptr, const float4** tail_rec = nullptr,
-                     const uint32_t** tail_cnt = nullptr) {
+                     const uint32_t** tail_cnt = nullptr, int* klt_slots = nullptr, const int* klt_prev_slots = nullptr) {
     // tail_rec / tail_cnt (fused form): where a tail finds the records and their count in DEVICE memory -- rec_dst / cnt_dst, which the
     // caller then points at device scratch, or the compaction's own output, which is then not copied to rec_dst at all
     if (tail_rec) { *tail_rec = rec_dst; *tail_cnt = cnt_dst; }
     // hip_klt: features, pyramid, track, flags, the ordered compaction and the count, straight to rec_dst / cnt_dst
-    if (g.sparse) return ofps::klt_flow_device(ctx, d_prev, d_cur, W, H, W, levels, radius, iters, rec_dst, cnt_dst, nullptr);
+    // (N3p, the stream forms with klt_prediction 1: the pair's raw slots are kept in klt_slots, its tracks start from klt_prev_slots' flow)
+    if (g.sparse) return ofps::klt_flow_device(ctx, d_prev, d_cur, W, H, W, levels, radius, iters, rec_dst, cnt_dst, klt_slots, klt_prev_slots);
     const size_t px = (size_t)W * H, cells = g.per_pixel ? 1 : (size_t)g.gw * g.gh;
     auto* d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_ENTRIES, px * sizeof(float4)));
     auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_FIELD, cells * sizeof(float2)));
@@ -222,6 +223,7 @@ int dense_stream_drain(ofps_hip_ctx* ctx) {
     OFPS_HIP_TRY(ctx, ctx->dense.ring.drain());
     OFPS_HIP_TRY(ctx, ctx->dense.sync_side_streams());
     ctx->dense.frames = 0;
+    ctx->dense.klt_pred.valid = false;
     return OFPS_HIP_OK;
 }
 
@@ -367,10 +369,28 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
         }
         const float4* d_rec = nullptr;                       // fused form: the records and their count in device memory
         const uint32_t* d_cnt = nullptr;
+        // N3p: with the setting on the stream keeps each pair's raw slots, two buffers that alternate by pair (per stream, not per ticket: the
+        // track launches of two tickets in flight run on the one compute stream, in order).  Pair k reads pair k - 1's if that pair wrote them
+        // on this lattice under these flags; a pair pushed with the setting off writes none, so its successor starts from zero
+        ofps::DenseStream::KltPred& kp = ds.klt_pred;
+        int* klt_slots = nullptr;
+        const int* klt_prev_slots = nullptr;
+        const bool predict = g.sparse && ctx->opt.klt_prediction;
+        if (predict) {
+            const size_t half = (g.max_records * 6 * sizeof(int) + 255) & ~(size_t)255;
+            auto* d_pred = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_PRED, 2 * half));
+            if (!d_pred) return OFPS_HIP_ENOMEM;
+            const uint64_t gen = ctx->scratch[ofps::S_KLT_PRED].gen;
+            if (kp.valid && kp.pair == frames_after - 1 && kp.fw == g.fw && kp.fh == g.fh && kp.cell == ctx->opt.klt_cell && kp.flags == flags && kp.gen == gen)
+                klt_prev_slots = reinterpret_cast<const int*>(d_pred + (size_t)(kp.pair & 1) * half);
+            klt_slots = reinterpret_cast<int*>(d_pred + (size_t)(frames_after & 1) * half);
+        }
+        kp.valid = false;                                    // (until this pair has enqueued everything)
         rc = dense_enqueue_frame(ctx, d_frames + (size_t)prev_slot * px, d_frames + (size_t)slot * px, g.fw, g.fh, levels, radius, iters, g,
                                  rec_dst, cnt_dst, ds.slot_id[prev_slot], ds.slot_id[slot], d_mask_ready, tail ? &d_rec : nullptr,
-                                 tail ? &d_cnt : nullptr);
+                                 tail ? &d_cnt : nullptr, klt_slots, klt_prev_slots);
         if (rc != OFPS_HIP_OK) return rc;
+        if (predict) kp = {true, frames_after, g.fw, g.fh, ctx->opt.klt_cell, flags, ctx->scratch[ofps::S_KLT_PRED].gen};
         if (tail) {
             const unsigned copy_blocks = (unsigned)((g.max_records + 255) / 256 < 1024 ? (g.max_records + 255) / 256 : 1024);
             hipLaunchKernelGGL(dense_copy_records_kernel, dim3(copy_blocks ? copy_blocks : 1), dim3(256), 0, s, d_rec,

@@ -17,6 +17,9 @@
 //   once more right behind it, from P = 256 (x, y) + dq and with the two frames' pointers exchanged, on the same LDS template rows and in the
 //   same registers, and keeps the slot iff that pass is kept too and comes back to within F / 256 pixel; status 5 otherwise.
 // klt_track_q_kernel, klt_track_q_zm_kernel: one direction from points given in 1/256 pixel, the stage the check is built from.
+// klt_track_pred*_kernel: the one-pair kernels with motion prediction (N3p): a pass starts from the slot's guess -- given by the caller, or made
+//   by klt_predict_slot from the previous pair's raw slots in front of the wave's first level -- in place of dq = (0, 0), N3f's backward pass
+//   from its negation.  klt_predict_kernel: the predictor alone, a lane per slot.
 #include "common.hpp"
 
 #include <cmath>
@@ -59,6 +62,18 @@ struct KltTrackBatchParams {
     size_t prev_pitch[kKltMaxLevels], cur_pitch[kKltMaxLevels];
     int slots_per_item, shared_features;
 };
+
+// N3p's track launch: where slot s starts from.  `guesses`: 2 ints per slot, the stage form; else `prev_slots`: the previous pair's raw slots
+// on the nx x ny lattice whose slot s this is, the guess made from them by klt_predict_slot.  (A wrapper, as the batch form's: KltTrackParams
+// keeps its size, so no kernel argument of the other kernels moves.)
+struct KltTrackPredParams {
+    KltTrackParams t;
+    const int* guesses;
+    const int* prev_slots;
+    int nx, ny;
+};
+
+constexpr int kKltMaxGuess = 1 << 23;                        // N3p: a guess beyond it, per component, is (0, 0)
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -226,14 +241,42 @@ __device__ __forceinline__ const uint8_t* klt_level(const KltTrackParams& p, con
     else return base[l];
 }
 
+__device__ __forceinline__ void klt_cmpx(int& a, int& b) { const int lo = a < b ? a : b, hi = a < b ? b : a; a = lo; b = hi; }
+
+// N3p's predictor: the guess of lattice slot (cx, cy) from the previous pair's raw slots, 6 ints each -- the slot and its left, right, upper and
+// lower neighbours, those inside the lattice with status 0; per component the element (k - 1) / 2 of the k values in ascending order, (0, 0)
+// with none.  The missing candidates sort behind the others as INT_MAX (a value that is INT_MAX itself answers the same either way)
+__device__ __forceinline__ void klt_predict_slot(const int* __restrict__ prev_slots, int nx, int ny, int cx, int cy, int& gx, int& gy) {
+    const int ox[5] = {0, -1, 1, 0, 0}, oy[5] = {0, 0, 0, -1, 1};
+    int vx[5], vy[5], k = 0;
+    for (int c = 0; c < 5; ++c) {
+        const int x = cx + ox[c], y = cy + oy[c];
+        vx[c] = vy[c] = 0x7fffffff;
+        if (x >= 0 && x < nx && y >= 0 && y < ny) {
+            const int* s = prev_slots + 6 * ((size_t)y * nx + x);
+            if (s[5] == KLT_KEPT) { vx[c] = s[3]; vy[c] = s[4]; ++k; }
+        }
+    }
+    // five values in ascending order by nine compare-exchanges
+    klt_cmpx(vx[0], vx[1]); klt_cmpx(vx[3], vx[4]); klt_cmpx(vx[2], vx[4]); klt_cmpx(vx[2], vx[3]); klt_cmpx(vx[0], vx[3]);
+    klt_cmpx(vx[0], vx[2]); klt_cmpx(vx[1], vx[4]); klt_cmpx(vx[1], vx[3]); klt_cmpx(vx[1], vx[2]);
+    klt_cmpx(vy[0], vy[1]); klt_cmpx(vy[3], vy[4]); klt_cmpx(vy[2], vy[4]); klt_cmpx(vy[2], vy[3]); klt_cmpx(vy[0], vy[3]);
+    klt_cmpx(vy[0], vy[2]); klt_cmpx(vy[1], vy[4]); klt_cmpx(vy[1], vy[3]); klt_cmpx(vy[1], vy[2]);
+    const int mid = (k - 1) >> 1;
+    gx = k == 0 ? 0 : (mid == 0 ? vx[0] : (mid == 1 ? vx[1] : vx[2]));
+    gy = k == 0 ? 0 : (mid == 0 ? vy[0] : (mid == 1 ? vy[1] : vy[2]));
+}
+
 // one wave's slot.  BATCH: the slot's item picks the frames (b: the launch's pitches) and, with shared features, its triple; the outputs are
 // indexed by the slot either way.  Everything behind the pointers is one text for both kernels.  ZM: mean removal (N3m); the lines it adds
 // are compiled into its own kernels alone.  MODE: KLT_MODE_PIXEL is N3 as it was, from the pixel (x, y), and compiles to the instructions it
 // had.  The other two start a pass at a position P in 1/256 pixel -- the level's centre ((P + 128) >> l) - 128 and the frame test on
 // P + dq * 2^l, which for P = 256 (x, y) are N3's values --: KLT_MODE_Q reads P from the points and runs one pass; KLT_MODE_FB (N3f) runs N3's
-// pass from 256 (x, y) and, where it ends with status 0, a second pass from P = 256 (x, y) + dq with prev and cur exchanged
-template <bool BATCH, bool ZM, int MODE = KLT_MODE_PIXEL>
-__device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl) {
+// pass from 256 (x, y) and, where it ends with status 0, a second pass from P = 256 (x, y) + dq with prev and cur exchanged.  PRED (N3p): a
+// pass starts from the slot's guess g (the backward pass from -g) in place of dq = (0, 0); g is one value per wave, read or predicted once
+// and held in scalar registers.  Its lines are compiled into its own kernels alone
+template <bool BATCH, bool ZM, int MODE = KLT_MODE_PIXEL, bool PRED = false>
+__device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl, const KltTrackPredParams* g = nullptr) {
     constexpr bool FB = MODE == KLT_MODE_FB, AT_Q = MODE != KLT_MODE_PIXEL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
@@ -265,6 +308,14 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
         ix[k] = iy[k] = ic[k] = 0;
     }
     int px = MODE == KLT_MODE_Q ? x : 256 * x, py = MODE == KLT_MODE_Q ? y : 256 * y;      // the pass's start (read with AT_Q alone)
+    int gx = 0, gy = 0;                                       // PRED: the slot's guess, 1/256 pixel at level 0
+    if constexpr (PRED) {
+        const int s = __builtin_amdgcn_readfirstlane((int)slot);      // the wave's slot as a scalar: what is read below is read once per wave
+        if (g->guesses) { gx = g->guesses[2 * (size_t)s]; gy = g->guesses[2 * (size_t)s + 1]; }
+        else klt_predict_slot(g->prev_slots, g->nx, g->ny, s % g->nx, s / g->nx, gx, gy);
+        gx = __builtin_amdgcn_readfirstlane(gx); gy = __builtin_amdgcn_readfirstlane(gy);
+        if (gx < -kKltMaxGuess || gx > kKltMaxGuess || gy < -kKltMaxGuess || gy > kKltMaxGuess) { gx = 0; gy = 0; }
+    }
     int fdqx = 0, fdqy = 0;                                   // FB: the forward pass's answer while the backward pass runs
     long long fres = 0;
     // one pass from (x, y) or, with AT_Q, from (px, py).  FB comes here a second time, with `back`: the two frames change places.  (A jump and
@@ -273,6 +324,15 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
 another_pass: __attribute__((unused));
     {
     int cqx = 0, cqy = 0;
+    if constexpr (PRED) {
+        // dq = g >> (L - 1) (the backward pass: -g), unless N3's frame test fails on the start: then (0, 0).  |g| <= 2^23 and a start inside the
+        // frame: every dq of the pass stays an int as it does without a guess
+        const int sh = p.L - 1;
+        const int sx = (back ? -gx : gx) >> sh, sy = (back ? -gy : gy) >> sh;
+        const long long fx = (AT_Q ? (long long)px : 256ll * x) + (long long)sx * (1ll << sh), fy = (AT_Q ? (long long)py : 256ll * y) + (long long)sy * (1ll << sh);
+        const bool out = __builtin_amdgcn_readfirstlane((int)(fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1))) != 0;
+        dqx = out ? 0 : sx; dqy = out ? 0 : sy;
+    }
     for (int l = p.L - 1; l >= 0 && KLT_UNIFORM(status) == KLT_KEPT; --l) {
         const uint8_t* __restrict__ prev = klt_level<BATCH>(p, b, item, l, back);
         const uint8_t* __restrict__ cur = klt_level<BATCH>(p, b, item, l, !back);
@@ -456,6 +516,35 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_q_zm_kernel(con
     klt_track_body<false, true, KLT_MODE_Q>(p, nullptr, tmpl);
 }
 
+// N3p: the four one-pair kernels whose tracks start from a guess, and the predictor's stage form (a lane per slot)
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_pred_kernel(const KltTrackPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, false, KLT_MODE_PIXEL, true>(p.t, nullptr, tmpl, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_pred_zm_kernel(const KltTrackPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, true, KLT_MODE_PIXEL, true>(p.t, nullptr, tmpl, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_pred_fb_kernel(const KltTrackPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, false, KLT_MODE_FB, true>(p.t, nullptr, tmpl, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_pred_zm_fb_kernel(const KltTrackPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<false, true, KLT_MODE_FB, true>(p.t, nullptr, tmpl, &p);
+}
+
+__global__ __launch_bounds__(256) void klt_predict_kernel(const int* __restrict__ prev_slots, int nx, int ny, int* __restrict__ out) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= (long long)nx * ny) return;
+    int gx, gy;
+    klt_predict_slot(prev_slots, nx, ny, (int)(s % nx), (int)(s / nx), gx, gy);
+    out[2 * s] = gx; out[2 * s + 1] = gy;
+}
+
 struct KltSettings { int cell, r, min_score, min_eig, max_residual; };
 
 KltSettings klt_settings(const ofps_hip_ctx* ctx) {
@@ -539,6 +628,29 @@ int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p, bool at_q = fal
         else hipLaunchKernelGGL(klt_track_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
     } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
     else hipLaunchKernelGGL(klt_track_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+// N3p: the track launch whose slots start from caller-given guesses or from the guesses predicted from prev_slots (one of the two is set)
+int klt_track_pred_launch(ofps_hip_ctx* ctx, const KltTrackParams& p, const int* d_guesses, const int* d_prev_slots, int nx, int ny) {
+    if (p.n <= 0) return OFPS_HIP_OK;
+    const dim3 grid((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves));
+    KltTrackPredParams f{p, d_guesses, d_prev_slots, nx, ny};
+    f.t.fb_limit = ctx->opt.klt_fb;
+    if (ctx->opt.klt_fb > 0) {
+        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_pred_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        else hipLaunchKernelGGL(klt_track_pred_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_pred_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+    else hipLaunchKernelGGL(klt_track_pred_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+    OFPS_HIP_TRY(ctx, hipGetLastError());
+    return OFPS_HIP_OK;
+}
+
+int klt_predict_device(ofps_hip_ctx* ctx, const int* d_prev_slots, int W, int H, int cell, int* d_out) {
+    const int nx = (W + cell - 1) / cell, ny = (H + cell - 1) / cell;
+    const size_t ns = (size_t)nx * ny;
+    hipLaunchKernelGGL(klt_predict_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, d_prev_slots, nx, ny, d_out);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
@@ -629,9 +741,10 @@ int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int 
 }
 
 // features of prev -> pyramid of both frames -> track -> status flags -> the ordered compaction -> count on the device.  Enqueues on
-// ctx->stream, synchronises nothing.  d_out: capacity = the slot count; d_slots (optional): 6 int32 per slot
+// ctx->stream, synchronises nothing.  d_out: capacity = the slot count; d_slots (optional): 6 int32 per slot.  d_prev_slots (N3p, optional):
+// the previous pair's raw slots on the same lattice, every feature starts from its slot's predicted guess; null: the launches without N3p
 int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
-                    float4* d_out, uint32_t* d_count, int* d_slots) {
+                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots) {
     const KltSettings s = klt_settings(ctx);
     const size_t ns = klt_slots(W, H, s.cell);
     const size_t o_raw = pad16(ns * 3 * sizeof(int)), o_flag = o_raw + ns * sizeof(float4);
@@ -648,7 +761,9 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
     p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
     p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)ns;
     p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
-    rc = klt_track_launch(ctx, p);
+    // the predictor runs inside the track kernel, in front of the wave's first level: no launch and no array of guesses between the two
+    if (d_prev_slots) rc = klt_track_pred_launch(ctx, p, nullptr, d_prev_slots, (W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell);
+    else rc = klt_track_launch(ctx, p);
     if (rc != OFPS_HIP_OK) return rc;
     return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_count) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_count);
 }
@@ -729,6 +844,15 @@ int ofps_hip_set_klt_fb(ofps_hip_ctx* ctx, int limit) {
 
 int ofps_hip_get_klt_fb(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_fb : OFPS_HIP_EINVAL; }
 
+int ofps_hip_set_klt_prediction(ofps_hip_ctx* ctx, int on) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, on == 0 || on == 1, "set_klt_prediction: %d is not 0|1", on);
+    ctx->opt.klt_prediction = on;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_klt_prediction(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_prediction : OFPS_HIP_EINVAL; }
+
 size_t ofps_hip_klt_slot_count(int W, int H, int cell) {
     if (W < 1 || H < 1 || (cell != 8 && cell != 16 && cell != 32)) return 0;
     return klt_slots(W, H, cell);
@@ -765,7 +889,7 @@ int ofps_hip_klt_features(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, 
 
 // ofps_hip_klt_track_dev and, with at_q, ofps_hip_klt_track_q_dev (N3f's stage form: the points are positions in 1/256 pixel)
 static int klt_track_dev_impl(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
-                              int levels, int radius, int iters, void* d_out_quads, bool at_q) {
+                              int levels, int radius, int iters, void* d_out_quads, bool at_q, const void* d_guesses = nullptr) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && (n == 0 || (d_points && d_out_quads)), "klt_track: null device pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
@@ -779,11 +903,12 @@ static int klt_track_dev_impl(ofps_hip_ctx* ctx, const void* d_prev, const void*
     p.L = levels; p.w = radius; p.K = iters; p.min_eig = ctx->opt.klt_min_eig; p.max_residual = ctx->opt.klt_max_residual;
     p.pts = static_cast<const int*>(d_points); p.pt_stride = 2; p.from_features = 0; p.n = (int)n;
     p.out_quad = static_cast<int*>(d_out_quads);
+    if (d_guesses) return klt_track_pred_launch(ctx, p, static_cast<const int*>(d_guesses), nullptr, 0, 0);
     return klt_track_launch(ctx, p, at_q);
 }
 
 static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
-                               int levels, int radius, int iters, int32_t* out_quads, bool at_q) {
+                               int levels, int radius, int iters, int32_t* out_quads, bool at_q, const int32_t* guesses = nullptr) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && (n == 0 || (points && out_quads)), "klt_track: null host pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
@@ -793,17 +918,21 @@ static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uin
     for (size_t k = 0; k < n; ++k)
         OFPS_REQUIRE(ctx, points[2 * k] >= 0 && points[2 * k] <= xmax && points[2 * k + 1] >= 0 && points[2 * k + 1] <= ymax,
                      "klt_track: point %zu = (%d, %d) lies outside the %d x %d frame", k, points[2 * k], points[2 * k + 1], W, H);
+    for (size_t k = 0; guesses && k < n; ++k)
+        OFPS_REQUIRE(ctx, guesses[2 * k] >= -kKltMaxGuess && guesses[2 * k] <= kKltMaxGuess && guesses[2 * k + 1] >= -kKltMaxGuess && guesses[2 * k + 1] <= kKltMaxGuess,
+                     "klt_track_from: guess %zu = (%d, %d) lies beyond +-2^23", k, guesses[2 * k], guesses[2 * k + 1]);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return OFPS_HIP_OK;
     const int ss = (W + 63) & ~63;
-    const size_t fb = (size_t)ss * H, o_quad = pad16(n * 2 * sizeof(int));
+    const size_t fb = (size_t)ss * H, o_quad = pad16(n * 2 * sizeof(int)), o_guess = o_quad + n * 4 * sizeof(int);
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
-    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_quad + n * 4 * sizeof(int)));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_guess + (guesses ? n * 2 * sizeof(int) : 0)));
     if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io, points, n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    rc = klt_track_dev_impl(ctx, d_fr, d_fr + fb, W, H, ss, d_io, n, levels, radius, iters, d_io + o_quad, at_q);
+    if (guesses) OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io + o_guess, guesses, n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    rc = klt_track_dev_impl(ctx, d_fr, d_fr + fb, W, H, ss, d_io, n, levels, radius, iters, d_io + o_quad, at_q, guesses ? d_io + o_guess : nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_quads, d_io + o_quad, n * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -820,6 +949,44 @@ int ofps_hip_klt_track(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cu
     return klt_track_host_impl(ctx, prev, cur, W, H, stride, points, n, levels, radius, iters, out_quads, false);
 }
 
+int ofps_hip_klt_track_from_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points,
+                                const void* d_guesses, size_t n, int levels, int radius, int iters, void* d_out_quads) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, n == 0 || d_guesses, "klt_track_from: null device pointer");
+    return klt_track_dev_impl(ctx, d_prev, d_cur, W, H, stride, d_points, n, levels, radius, iters, d_out_quads, false, d_guesses);
+}
+
+int ofps_hip_klt_track_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points,
+                            const int32_t* guesses, size_t n, int levels, int radius, int iters, int32_t* out_quads) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, n == 0 || guesses, "klt_track_from: null host pointer");
+    return klt_track_host_impl(ctx, prev, cur, W, H, stride, points, n, levels, radius, iters, out_quads, false, guesses);
+}
+
+int ofps_hip_klt_predict_dev(ofps_hip_ctx* ctx, const void* d_prev_slots, int W, int H, int cell, void* d_out_guesses) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, d_prev_slots && d_out_guesses, "klt_predict: null device pointer");
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && W <= 32768 && H <= 32768 && (cell == 8 || cell == 16 || cell == 32), "klt_predict: bad lattice W=%d H=%d cell=%d", W, H, cell);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return klt_predict_device(ctx, static_cast<const int*>(d_prev_slots), W, H, cell, static_cast<int*>(d_out_guesses));
+}
+
+int ofps_hip_klt_predict(ofps_hip_ctx* ctx, const int32_t* prev_slots, int W, int H, int cell, int32_t* out_guesses) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, prev_slots && out_guesses, "klt_predict: null host pointer");
+    OFPS_REQUIRE(ctx, W >= 1 && H >= 1 && W <= 32768 && H <= 32768 && (cell == 8 || cell == 16 || cell == 32), "klt_predict: bad lattice W=%d H=%d cell=%d", W, H, cell);
+    OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ns = klt_slots(W, H, cell), o_out = pad16(ns * 6 * sizeof(int));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_out + ns * 2 * sizeof(int)));
+    if (!d_io) return OFPS_HIP_ENOMEM;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io, prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = klt_predict_device(ctx, reinterpret_cast<const int*>(d_io), W, H, cell, reinterpret_cast<int*>(d_io + o_out));
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_guesses, d_io + o_out, ns * 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OFPS_HIP_OK;
+}
+
 int ofps_hip_klt_track_q_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, const void* d_points, size_t n,
                              int levels, int radius, int iters, void* d_out_quads) {
     return klt_track_dev_impl(ctx, d_prev, d_cur, W, H, stride, d_points, n, levels, radius, iters, d_out_quads, true);
@@ -830,19 +997,32 @@ int ofps_hip_klt_track_q(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* 
     return klt_track_host_impl(ctx, prev, cur, W, H, stride, points, n, levels, radius, iters, out_quads, true);
 }
 
-int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
-                          void* d_out_entries, void* d_out_count, void* d_out_slots) {
+int ofps_hip_klt_flow_from_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                               const void* d_prev_slots, void* d_out_entries, void* d_out_count, void* d_out_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "klt_flow: null device pointer");
     const int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
     if (rc != OFPS_HIP_OK) return rc;
+    if (d_prev_slots && d_out_slots) {
+        // a wave reads its neighbours' previous slots while other waves write theirs: the two arrays must not share a byte
+        const size_t bytes = klt_slots(W, H, ctx->opt.klt_cell) * 6 * sizeof(int);
+        const char* a = static_cast<const char*>(d_prev_slots);
+        const char* b = static_cast<const char*>(d_out_slots);
+        OFPS_REQUIRE(ctx, a + bytes <= b || b + bytes <= a, "klt_flow_from: d_prev_slots and d_out_slots overlap");
+    }
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return ofps::klt_flow_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, levels, radius, iters,
-                                 static_cast<float4*>(d_out_entries), static_cast<uint32_t*>(d_out_count), static_cast<int*>(d_out_slots));
+                                 static_cast<float4*>(d_out_entries), static_cast<uint32_t*>(d_out_count), static_cast<int*>(d_out_slots),
+                                 static_cast<const int*>(d_prev_slots));
 }
 
-int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
-                      float* out_entries, uint32_t* n_out, int32_t* out_slots) {
+int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                          void* d_out_entries, void* d_out_count, void* d_out_slots) {
+    return ofps_hip_klt_flow_from_dev(ctx, d_prev, d_cur, W, H, stride, levels, radius, iters, nullptr, d_out_entries, d_out_count, d_out_slots);
+}
+
+int ofps_hip_klt_flow_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
+                           const int32_t* prev_slots, float* out_entries, uint32_t* n_out, int32_t* out_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "klt_flow: null host pointer");
     int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
@@ -850,14 +1030,16 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
     const int ss = (W + 63) & ~63;
-    const size_t fb = (size_t)ss * H, o_count = ns * sizeof(float4), o_slots = o_count + 16;
+    const size_t fb = (size_t)ss * H, o_count = ns * sizeof(float4), o_slots = o_count + 16, o_prev = o_slots + ns * 6 * sizeof(int);
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
-    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_slots + ns * 6 * sizeof(int)));
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_prev + (prev_slots ? ns * 6 * sizeof(int) : 0)));
     if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
+    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io + o_prev, prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
     rc = ofps::klt_flow_device(ctx, d_fr, d_fr + fb, W, H, ss, levels, radius, iters, reinterpret_cast<float4*>(d_io),
-                               reinterpret_cast<uint32_t*>(d_io + o_count), out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr);
+                               reinterpret_cast<uint32_t*>(d_io + o_count), out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr,
+                               prev_slots ? reinterpret_cast<const int*>(d_io + o_prev) : nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     uint32_t count = 0;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(&count, d_io + o_count, sizeof(count), hipMemcpyDeviceToHost, ctx->stream));
@@ -867,6 +1049,11 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (count) OFPS_HIP_TRY(ctx, hipMemcpy(out_entries, d_io, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost));
     *n_out = count;
     return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
+                      float* out_entries, uint32_t* n_out, int32_t* out_slots) {
+    return ofps_hip_klt_flow_from(ctx, prev, cur, W, H, stride, levels, radius, iters, nullptr, out_entries, n_out, out_slots);
 }
 
 int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,

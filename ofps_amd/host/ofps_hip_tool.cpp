@@ -7,13 +7,15 @@
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
-//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N]]
+//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N] [--klt-predict]]
 //                                                       PCIe-inclusive per-frame time of the hip_sad process_frame shape; `multi`:
 //                                                       the stream over several workers (ofps_hip_multi_push_frames_async), with
 //                                                       detector + estimator per frame; `--klt` (batch, multi): hip_klt as the
 //                                                       batched stream's decoder (ofps_hip_set_batch_decoder / OFPS_HIP_BATCH_DECODER);
 //                                                       `--klt-mean-removal`: with its mean removal on (include/ofps_hip.h N3m);
-//                                                       `--klt-fb N`: with its forward-backward check at N / 256 pixel (N3f)
+//                                                       `--klt-fb N`: with its forward-backward check at N / 256 pixel (N3f);
+//                                                       `--klt-predict`: with the prediction setting on (N3p), which the batched and
+//                                                       multi-device forms ignore: the figures are those without it
 //   track   <decoder> <arg> [aspect fov_y] [lsq|ransac] tracking loop, ofps-suite/src/app/tracking/worker.rs:305-412
 //   mvec-copy <in.mvec> <out.mvec>                      CPU-only .mvec round trip (reader + writer)
 //   multi-extract <raw.y> <w> <h> <out.mvec> [dev ...]  the whole clip over several GPUs (ofps_hip_multi_*): same bytes as `extract hip_sad`
@@ -40,6 +42,19 @@ static double mean(const std::vector<double>& v) {
     double s = 0;
     for (double x : v) s += x;
     return v.empty() ? 0.0 : s / (double)v.size();
+}
+
+// "name": value, ... of a plugin's properties, as the members of a JSON object
+static void print_props(const std::vector<std::pair<std::string, Property>>& props) {
+    bool first = true;
+    for (auto& [n, p] : props) {
+        std::printf("%s\"%s\": ", first ? "" : ", ", n.c_str());
+        if (auto fl = std::get_if<BoundedProp<float>>(&p)) std::printf("%.9g", (double)fl->val);
+        else if (auto u = std::get_if<BoundedProp<size_t>>(&p)) std::printf("%zu", u->val);
+        else if (auto b = std::get_if<bool>(&p)) std::printf("%s", *b ? "true" : "false");
+        else std::printf("\"%s\"", std::get<std::string>(p).c_str());
+        first = false;
+    }
 }
 
 int main(int argc, char** argv) {
@@ -164,17 +179,11 @@ int main(int argc, char** argv) {
                 export_perf_csv(perf_dir, cfg.decoder.selected_plugin, {{"decoder", &run.decoder_ms}, {cfg.detector.selected_plugin, &run.detector_ms}});
             std::printf("{\"frames\": %zu, \"decoder_ms_mean\": %.4f, \"detector_ms_mean\": %.4f, \"max_frame_gap\": %zu, \"min_frames\": %zu, "
                         "\"detector_properties\": {", run.frames, mean(run.decoder_ms), mean(run.detector_ms), cfg.max_frame_gap, cfg.min_frames);
-            bool first = true;
-            for (auto& [n, p] : det->props()) {
-                std::printf("%s\"%s\": ", first ? "" : ", ", n.c_str());
-                if (auto fl = std::get_if<BoundedProp<float>>(&p)) std::printf("%.9g", (double)fl->val);
-                else if (auto u = std::get_if<BoundedProp<size_t>>(&p)) std::printf("%zu", u->val);
-                else if (auto b = std::get_if<bool>(&p)) std::printf("%s", *b ? "true" : "false");
-                else std::printf("\"%s\"", std::get<std::string>(p).c_str());
-                first = false;
-            }
+            print_props(det->props());
+            std::printf("}, \"decoder_properties\": {");       // what the decoder ran with: the saved configuration's values behind transfer_props
+            print_props(dec->props());
             std::printf("}, \"motion_ranges\": [");
-            first = true;
+            bool first = true;
             for (auto [s, e] : run.filtered(cfg.max_frame_gap, cfg.min_frames)) {
                 std::printf("%s[%zu, %zu]", first ? "" : ", ", s, e);
                 first = false;
@@ -215,6 +224,7 @@ int main(int argc, char** argv) {
             // node the page-locked buffers landed on (the batched form is bimodal from process to process: profiles/r05/batched_bimodal.txt)
             int sb_block = 16, sb_range = 16;
             int sb_klt_fb = 0;                                 // `--klt-fb N` beside `--klt`: ofps_hip_set_klt_fb(N) / OFPS_HIP_KLT_FB=N
+            bool sb_klt_pred = false;                          // `--klt-predict` beside `--klt`: ofps_hip_set_klt_prediction(1) / OFPS_HIP_KLT_PREDICTION=1
             bool sb_klt_zm = false;                            // `--klt-mean-removal` beside `--klt`: ofps_hip_set_klt_mean_removal(1) / OFPS_HIP_KLT_MEAN_REMOVAL=1
             bool sb_probe = false, sb_klt = false;             // `--klt` (batch and multi modes): hip_klt as the batched stream's decoder (N3b), levels 4, radius 7, 10 iterations
             {
@@ -223,6 +233,7 @@ int main(int argc, char** argv) {
                     if (std::string(argv[a]) == "--probe") { sb_probe = true; continue; }
                     if (std::string(argv[a]) == "--klt") { sb_klt = true; continue; }
                     if (std::string(argv[a]) == "--klt-mean-removal") { sb_klt_zm = true; continue; }
+                    if (std::string(argv[a]) == "--klt-predict") { sb_klt_pred = true; continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--klt-fb") { sb_klt_fb = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--block") { sb_block = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--range") { sb_range = std::atoi(argv[++a]); continue; }
@@ -231,6 +242,7 @@ int main(int argc, char** argv) {
                 argc = keep;
                 if (sb_klt_zm && !sb_klt) throw Error("stream-bench: --klt-mean-removal needs --klt");
                 if (sb_klt_fb && !sb_klt) throw Error("stream-bench: --klt-fb needs --klt");
+                if (sb_klt_pred && !sb_klt) throw Error("stream-bench: --klt-predict needs --klt");
             }
             // the Decoder::process_frame shape without Python in the loop: frames are already in page-locked buffers (a
             // decoder that writes there), one H2D + search + 16 B/vector D2H per frame
@@ -250,6 +262,7 @@ int main(int argc, char** argv) {
                 if (sb_klt) setenv("OFPS_HIP_BATCH_DECODER", "1", 1);
                 if (sb_klt_zm) setenv("OFPS_HIP_KLT_MEAN_REMOVAL", "1", 1);
                 if (sb_klt_fb) setenv("OFPS_HIP_KLT_FB", std::to_string(sb_klt_fb).c_str(), 1);
+                if (sb_klt_pred) setenv("OFPS_HIP_KLT_PREDICTION", "1", 1);
                 if (ofps_hip_multi_init(devices.data(), (int)devices.size(), &m) != OFPS_HIP_OK) throw Error(ofps_hip_multi_last_error(nullptr));
                 const int nw = (int)devices.size(), slots = 2 * nw;
                 HipContext alloc;                                           // page-locked memory comes from any context
@@ -301,6 +314,7 @@ int main(int argc, char** argv) {
                     ctx.check(ofps_hip_set_batch_decoder(ctx.get(), OFPS_HIP_BATCH_DECODER_KLT, 4, 7, 10));
                     if (sb_klt_zm) ctx.check(ofps_hip_set_klt_mean_removal(ctx.get(), 1));
                     if (sb_klt_fb) ctx.check(ofps_hip_set_klt_fb(ctx.get(), sb_klt_fb));
+                    if (sb_klt_pred) ctx.check(ofps_hip_set_klt_prediction(ctx.get(), 1));
                     ctx.check(ofps_hip_get_klt(ctx.get(), &klt_cell, nullptr, nullptr, nullptr, nullptr));
                 }
                 const size_t nblk = sb_klt ? ofps_hip_klt_slot_count(W, H, klt_cell) : ofps_hip_sad_block_count(W, H, 16);
@@ -348,8 +362,9 @@ int main(int argc, char** argv) {
                                 "\"bare_h2d_GBs\": [%.1f, %.1f], \"buffer_numa_node\": [%d, %d], \"cpu\": %d}\n", batch, nb * batch, ms,
                                 (double)nblk / ms / 1e3, probe_gbs[0], probe_gbs[1], probe_node[0], probe_node[1], probe_cpu);
                 else if (sb_klt)
-                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"fb_limit\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
-                                "\"capacity\": %zu, \"last_n_vectors\": %zu}\n", ofps_hip_get_klt_mean_removal(ctx.get()), ofps_hip_get_klt_fb(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
+                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"fb_limit\": %d, \"prediction\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
+                                "\"capacity\": %zu, \"last_n_vectors\": %zu}\n", ofps_hip_get_klt_mean_removal(ctx.get()), ofps_hip_get_klt_fb(ctx.get()),
+                                ofps_hip_get_klt_prediction(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
                 else
                 std::printf("{\"mode\": \"read_ahead_batched\", \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, \"Mvectors_per_s\": %.2f}\n", batch,
                             nb * batch, ms, (double)nblk / ms / 1e3);

@@ -211,6 +211,7 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
                                     (int)klt_->max_residual));
         ctx_.check(ofps_hip_set_klt_mean_removal(ctx_.get(), klt_->mean_removal ? 1 : 0));
         ctx_.check(ofps_hip_set_klt_fb(ctx_.get(), (int)klt_->fb_limit));
+        ctx_.check(ofps_hip_set_klt_prediction(ctx_.get(), klt_->prediction ? 1 : 0));
         out_.resize(klt_record_floats(w_, h_, max_w_, max_h_, process_fullres_, klt_->cell));
     } else {
         out_.resize(records_fullres ? 4 * w_ * h_ : 4 * std::min(max_w_, w_) * std::min(max_h_, h_));
@@ -245,7 +246,7 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
 }
 
 std::vector<std::pair<std::string, PropertyMut>> HipLkDecoder::props_mut() {   // cv-decoder/src/lib.rs:35-52 + the flow's knobs
-    if (klt_) return klt_props({&max_w_, &max_h_, &process_fullres_, &*klt_, &levels_, &radius_, &iters_});
+    if (klt_) return klt_decoder_props({&max_w_, &max_h_, &process_fullres_, &*klt_, &levels_, &radius_, &iters_});
     return {{"Width", PropertyMut::usize(&max_w_, 1, 2000)}, {"Height", PropertyMut::usize(&max_h_, 1, 2000)},
             {"Pyramid levels", PropertyMut::usize(&levels_, 1, 8)}, {"Window radius", PropertyMut::usize(&radius_, 1, farneback_ ? 7 : 15)},
             {"Iterations", PropertyMut::usize(&iters_, 1, 64)}, {"Contrast mask", PropertyMut::boolean(&contrast_mask_)},
@@ -273,6 +274,12 @@ std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage&
             {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)}, {"Levels", PropertyMut::usize(at.levels, 1, 6)},
             {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)},
             {"Mean removal", PropertyMut::boolean(&s.mean_removal)}, {"Consistency check", PropertyMut::usize(&s.fb_limit, 0, kKltMaxFb)}};
+}
+
+std::vector<std::pair<std::string, PropertyMut>> klt_decoder_props(const KltPropStorage& at) {
+    auto props = klt_props(at);
+    props.emplace_back("Prediction", PropertyMut::boolean(&at.settings->prediction));      // N3p: an extension, behind the table
+    return props;
 }
 
 // ------------------------------------------------------------------ .mvec

@@ -167,10 +167,14 @@ struct KltSettings {
     size_t cell = 16, score_radius = 2, min_score = 1, min_eig = 1, max_residual = 0;
     bool mean_removal = false;             // "Mean removal" (N3m): ofps_hip_set_klt_mean_removal before every push
     size_t fb_limit = 0;                   // "Consistency check" (N3f): ofps_hip_set_klt_fb before every push, 1/256 pixel, 0 = off
+    bool prediction = false;               // "Prediction" (N3p): ofps_hip_set_klt_prediction before every push; an extension property, which the
+                                           // decoder's props_mut appends behind klt_props' table
 };
 // the storage behind hip_klt's properties; klt_props is the one table of their names and bounds (the decoder's props_mut returns it)
 struct KltPropStorage { size_t *max_w, *max_h; bool* process_fullres; KltSettings* settings; size_t *levels, *radius, *iters; };
 std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage& at);
+// the decoder's full list (what HipKltDecoder's props_mut returns): klt_props' table and, behind it, the extension property "Prediction" (N3p)
+std::vector<std::pair<std::string, PropertyMut>> klt_decoder_props(const KltPropStorage& at);
 // the floats of hip_klt's record buffer: four per slot of the cell lattice over the frames the tracker reads (the capped grid's frames
 // with "Process Fullres" = false); throws Error for a cell size the library does not know or a lattice without a slot
 size_t klt_record_floats(size_t w, size_t h, size_t max_w, size_t max_h, bool process_fullres, size_t cell);

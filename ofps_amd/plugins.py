@@ -286,13 +286,27 @@ class HipKltDecoder(HipLkDecoder):
               # property of the same name is its counterpart
               ("Consistency check", "usize", "fb_limit", 0, 4096))
 
+    # build-defined (include/ofps_hip.h N3p): every pair's tracks start from the previous pair's flow.  props() keeps its list; the
+    # extension is listed by ext_props() and set through the same set_prop
+    _EXT_PROPS = (("Prediction", "bool", "prediction", None, None),)
+
     def __init__(self, frames, framerate=None, device: int = 0, frame_format: int = HipContext.FMT_LUMA):
         super().__init__(frames, framerate, device, frame_format)
         self.levels, self.radius, self.iters = 4, 7, 10
         self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual = 16, 2, 1, 1, 0
         self.mean_removal = False
         self.fb_limit = 0
+        self.prediction = False
         self.contrast_mask = False
+
+    def ext_props(self):
+        return [(name, kind, getattr(self, attr), lo, hi) for name, kind, attr, lo, hi in self._EXT_PROPS]
+
+    def set_prop(self, name: str, value) -> bool:
+        if name == "Prediction":
+            self.prediction = bool(value)
+            return True
+        return super().set_prop(name, value)
 
     def process_frame(self, field: list, out_frame=None, skip_frames: int = 0) -> bool:
         for _ in range(skip_frames + 1):
@@ -309,6 +323,7 @@ class HipKltDecoder(HipLkDecoder):
         self.ctx.set_klt(self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual)
         self.ctx.set_klt_mean_removal(1 if self.mean_removal else 0)
         self.ctx.set_klt_fb(self.fb_limit)
+        self.ctx.set_klt_prediction(1 if self.prediction else 0)
         return self._decode(field, dict(reduced=not self.process_fullres, fmt=self.frame_format, sparse=True))
 
 

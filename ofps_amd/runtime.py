@@ -702,6 +702,84 @@ class HipContext:
         self._check(self._lib.ofps_hip_klt_flow_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, levels, radius, iters,
                                                     C.c_void_p(d_out_entries), C.c_void_p(d_out_count), C.c_void_p(d_out_slots or 0)))
 
+    # ---- N3p: hip_klt with motion prediction
+    def set_klt_prediction(self, on: int):
+        """1: the sparse stream forms (OFPS_HIP_FLOW_SPARSE) start every pair's tracks from the previous pair's flow (include/ofps_hip.h N3p);
+        0 (default): every track starts from zero.  The batch forms and the stage forms do not read it."""
+        self._check(self._lib.ofps_hip_set_klt_prediction(self._h, int(on)))
+
+    def get_klt_prediction(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_prediction(self._h))
+
+    def klt_predict(self, prev_slots: np.ndarray, W: int, H: int, cell: int | None = None) -> np.ndarray:
+        """The predictor alone: the previous pair's raw slots int32 [slots, 6] on the W x H lattice -> int32 [slots, 2], the guess (gx, gy) of
+        every slot in 1/256 pixel"""
+        cell = self.get_klt()["cell"] if cell is None else cell
+        ns = self.klt_slot_count(W, H, cell)
+        ps = np.ascontiguousarray(prev_slots, np.int32).reshape(-1, 6)
+        assert len(ps) == ns
+        out = np.zeros((max(ns, 1), 2), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_predict(self._h, ps.ctypes.data_as(i32), W, H, cell, out.ctypes.data_as(i32)))
+        return out[:ns]
+
+    def klt_predict_dev(self, d_prev_slots: int, W: int, H: int, cell: int, d_out_guesses: int):
+        self._check(self._lib.ofps_hip_klt_predict_dev(self._h, C.c_void_p(d_prev_slots), W, H, cell, C.c_void_p(d_out_guesses)))
+
+    def klt_track_from(self, prev: np.ndarray, cur: np.ndarray, points: np.ndarray, guesses: np.ndarray, levels: int, radius: int, iters: int,
+                       stride: int | None = None) -> np.ndarray:
+        """klt_track with one guess per point: guesses int [n, 2] (gx, gy) in 1/256 pixel, within +-2^23 -> int32 [n, 4]: (dqx, dqy, res,
+        status), dq the whole displacement"""
+        p, stride = self._luma_view(prev, stride)
+        c, stride_c = self._luma_view(cur, stride)
+        assert p.shape == c.shape and stride == stride_c
+        H, W = p.shape
+        pts = np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+        gs = np.ascontiguousarray(guesses, np.int32).reshape(-1, 2)
+        assert len(gs) == len(pts)
+        out = np.zeros((max(len(pts), 1), 4), np.int32)
+        u8, i32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_track_from(self._h, C.cast(C.c_void_p(p.ctypes.data), u8), C.cast(C.c_void_p(c.ctypes.data), u8), W, H,
+                                                      stride, pts.ctypes.data_as(i32) if len(pts) else None,
+                                                      gs.ctypes.data_as(i32) if len(pts) else None, len(pts), levels, radius, iters,
+                                                      out.ctypes.data_as(i32)))
+        return out[:len(pts)]
+
+    def klt_track_from_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, d_points: int, d_guesses: int, n: int, levels: int,
+                           radius: int, iters: int, d_out_quads: int):
+        """Enqueue only; a point outside the frame comes back with status 3, a guess beyond +-2^23 counts as (0, 0)."""
+        self._check(self._lib.ofps_hip_klt_track_from_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, C.c_void_p(d_points),
+                                                          C.c_void_p(d_guesses), n, levels, radius, iters, C.c_void_p(d_out_quads)))
+
+    def klt_flow_from(self, prev: np.ndarray, cur: np.ndarray, levels: int, radius: int, iters: int, prev_slots: np.ndarray | None = None,
+                      want_slots=True, stride: int | None = None):
+        """klt_flow whose features start from the guesses predicted from prev_slots (the previous call's slots; None: from zero).
+        -> entries float32 [count, 4] [, slots int32 [slots, 6]]"""
+        p, stride = self._luma_view(prev, stride)
+        c, stride_c = self._luma_view(cur, stride)
+        assert p.shape == c.shape and stride == stride_c
+        H, W = p.shape
+        ns = self.klt_slot_count(W, H)
+        ent = np.zeros((max(ns, 1), 4), np.float32)
+        slots = np.zeros((max(ns, 1), 6), np.int32) if want_slots else None
+        ps = None
+        if prev_slots is not None:
+            ps = np.ascontiguousarray(prev_slots, np.int32).reshape(-1, 6)
+            assert len(ps) == ns
+        n = C.c_uint32(0)
+        u8, i32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_flow_from(self._h, C.cast(C.c_void_p(p.ctypes.data), u8), C.cast(C.c_void_p(c.ctypes.data), u8), W, H,
+                                                     stride, levels, radius, iters, ps.ctypes.data_as(i32) if ps is not None else None,
+                                                     _fp(ent), C.byref(n), slots.ctypes.data_as(i32) if want_slots else None))
+        return (ent[:n.value], slots[:ns]) if want_slots else ent[:n.value]
+
+    def klt_flow_from_dev(self, d_prev: int, d_cur: int, W: int, H: int, stride: int, levels: int, radius: int, iters: int,
+                          d_prev_slots: int | None, d_out_entries: int, d_out_count: int, d_out_slots: int | None = None):
+        """Enqueue only: klt_flow_dev with the previous pair's slots in device memory (None: klt_flow_dev itself)."""
+        self._check(self._lib.ofps_hip_klt_flow_from_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_cur), W, H, stride, levels, radius, iters,
+                                                         C.c_void_p(d_prev_slots or 0), C.c_void_p(d_out_entries), C.c_void_p(d_out_count),
+                                                         C.c_void_p(d_out_slots or 0)))
+
     # ---- N3b: hip_klt on a batch of pairs, and as the batched stream forms' decoder
     BATCH_DECODER_SAD, BATCH_DECODER_KLT = 0, 1
 

@@ -28,7 +28,7 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               iterations, no residual limit; --klt-cell C [C ...] and --klt-residual R [R ...] add hip_klt_c<C>r<R> for every other pair of
               "Cell size" and "Max residual"; --klt-mean-removal adds the same columns once more with "Mean removal" on (include/ofps_hip.h
               N3m) as hip_klt_m and hip_klt_c<C>r<R>_m; --klt-fb N [N ...] adds every hip_klt column once more per N with "Consistency check" = N
-              (include/ofps_hip.h N3f, the round-trip limit in 1/256 pixel) as hip_klt_f<N>, and with --klt-mean-removal as hip_klt_f<N>_m; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
+              (include/ofps_hip.h N3f, the round-trip limit in 1/256 pixel) as hip_klt_f<N>, and with --klt-mean-removal as hip_klt_f<N>_m; --klt-predict adds every hip_klt column once more with "Prediction" on (N3p) as <column>_p, --klt-levels L runs them all at L pyramid levels; --ramp-clips adds pans whose rate grows linearly from 0 to 1.5 and to 3 degrees per frame and swings back; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
   cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
               cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
@@ -61,7 +61,7 @@ def triangle(rate, n, period):
     return np.where(((k + period) // (2 * period)) % 2 == 0, rate, -rate).astype(np.float64)
 
 
-def clip_table(quick=False, fast_clips=False):
+def clip_table(quick=False, fast_clips=False, ramp_clips=False):
     """name -> (W, H, fov_y_deg, per-frame eulers [n, 3] (roll = tilt, pitch = image roll, yaw = pan), distractor)"""
     n = 24 if quick else 60
     W, H = 1920, 1080
@@ -82,6 +82,12 @@ def clip_table(quick=False, fast_clips=False):
     if fast_clips:      # beyond the plain search's reach at 1080p (16.32 px per degree at the centre); the accumulated pan stays within +-9 degrees
         t["fast_pan_1.5"] = (W, H, 60.0, np.stack([z, z, triangle(1.5, n, 4)], 1), None)
         t["fast_pan_3.0"] = (W, H, 60.0, np.stack([z, z, triangle(3.0, n, 3)], 1), None)
+    if ramp_clips:      # pans whose rate grows linearly from 0 to the fast clips' rates over m frames, falls back through 0 to the same rate the
+        def ramp(rate, m):      # other way, and so on: smooth motion that starts at rest; the accumulated pan stays within 0 .. rate * m = 9 degrees
+            ph = (k % (4 * m)) / float(m)
+            return rate * np.where(ph <= 1, ph, np.where(ph <= 3, 2 - ph, ph - 4))
+        t["ramp_pan_1.5"] = (W, H, 60.0, np.stack([z, z, ramp(1.5, 6)], 1), None)      # the rate changes by 0.25 degrees (4 px) per pair
+        t["ramp_pan_3.0"] = (W, H, 60.0, np.stack([z, z, ramp(3.0, 3)], 1), None)      # ... by 1 degree (16 px) per pair
     return t
 
 
@@ -174,7 +180,7 @@ CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
         fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
         cut_clip=False, sad_split=(), klt=False, klt_cells=(16,), klt_residuals=(0,), skip=(),
-        klt_mean_removal=False, klt_fb=()):
+        klt_mean_removal=False, klt_fb=(), klt_predict=False, ramp_clips=False, klt_levels=0):
     from ofps_amd.plugins import HipFlowDecoder, HipKltDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -246,10 +252,14 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
                     if klt_mean_removal:
                         props_kfm = dict(props_kf, **{"Mean removal": True})
                         combos += [(f"{tag}_f{fb}_m", HipKltDecoder, False, props_kfm), (f"{tag}_f{fb}_m", HipKltDecoder, True, props_kfm)]
+    if klt and klt_predict:     # every hip_klt column once more with "Prediction" on (include/ofps_hip.h N3p), as <column>_p
+        combos += [(c[0] + "_p", c[1], c[2], dict(c[3], **{"Prediction": True})) for c in combos if c[1] is HipKltDecoder]
+    if klt and klt_levels:      # ... and all of them at another number of pyramid levels
+        combos = [(c[0], c[1], c[2], dict(c[3], **{"Levels": klt_levels})) if c[1] is HipKltDecoder else c for c in combos]
     combos = [c for c in combos if c[0] not in skip]
     res = {}
     clips = []
-    for name, geom in clip_table(quick, fast_clips).items():
+    for name, geom in clip_table(quick, fast_clips, ramp_clips).items():
         if only and name not in only:
             continue
         clip_seed = 21 + len({c[2] for c in clips})                # the n-th clip that runs renders with seed 21 + n
@@ -404,6 +414,9 @@ def main():
     ap.add_argument("--klt-residual", nargs="*", type=int, default=[0], metavar="R", help="with --klt: \"Max residual\" values (sixteenths of a grey level)")
     ap.add_argument("--klt-mean-removal", action="store_true", help="with --klt: every hip_klt column once more with \"Mean removal\" on, as <column>_m")
     ap.add_argument("--klt-fb", nargs="*", type=int, default=[], metavar="N", help="with --klt: \"Consistency check\" values in 1/256 pixel; hip_klt_f<N> beside hip_klt")
+    ap.add_argument("--klt-predict", action="store_true", help="with --klt: every hip_klt column once more with \"Prediction\" on, as <column>_p")
+    ap.add_argument("--klt-levels", type=int, default=0, metavar="L", help="with --klt: \"Levels\" of every hip_klt column (0 = the decoder's 4)")
+    ap.add_argument("--ramp-clips", action="store_true", help="add 1080p pans whose rate grows linearly from 0 to 1.5 and to 3 degrees per frame and falls back")
     ap.add_argument("--skip", nargs="*", default=[], metavar="NAME", help="decoder columns to leave out, e.g. hip_lk5 hip_flow")
     args = ap.parse_args()
     res = run(args.quick, args.oracle_lk_pairs, not args.no_oracle, args.only, log=lambda s: print(s, file=sys.stderr, flush=True), quarter_pel=args.quarter_pel,
@@ -411,7 +424,8 @@ def main():
               sad_only=args.sad_only, sad_predictors=args.sad_predictors, lighting=tuple(args.lighting), sad_prefilter=tuple(args.sad_prefilter),
               sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split),
               klt=args.klt, klt_cells=tuple(args.klt_cell), klt_residuals=tuple(args.klt_residual), skip=tuple(args.skip),
-              klt_mean_removal=args.klt_mean_removal, klt_fb=tuple(args.klt_fb))
+              klt_mean_removal=args.klt_mean_removal, klt_fb=tuple(args.klt_fb), klt_predict=args.klt_predict, ramp_clips=args.ramp_clips,
+              klt_levels=args.klt_levels)
     txt = table(res)
     print(txt)
     if args.out:

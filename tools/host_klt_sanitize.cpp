@@ -1,6 +1,6 @@
 // host_klt_sanitize.cpp -- stand-alone check of the host layer's additions for hip_klt (include/ofps_hip.h N3) under AddressSanitizer +
 // UndefinedBehaviorSanitizer: the record-buffer sizing from ofps_hip_klt_slot_count (ofps::klt_record_floats) and the decoder's properties'
-// way -- through ofps::klt_props, the table HipKltDecoder::props_mut itself returns -- from a saved configuration's JSON through
+// way -- through ofps::klt_decoder_props, the list HipKltDecoder::props_mut itself returns -- from a saved configuration's JSON through
 // transfer_props into a plugin object and back out through props().  No GPU, no context: of the library only its two pure functions
 // (ofps_hip_klt_slot_count, ofps_hip_cv_grid) are called.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/host_klt_sanitize.cpp ofps_amd/host/ofps_host.cpp \
@@ -20,13 +20,13 @@ namespace {
 int failures = 0;
 #define CHECK(cond) do { if (!(cond)) { std::fprintf(stderr, "FAILED line %d: %s\n", __LINE__, #cond); ++failures; } } while (0)
 
-// the decoder's own property table (ofps::klt_props, what HipKltDecoder::props_mut returns) over storage that needs no context
+// the decoder's own property list (ofps::klt_decoder_props, what HipKltDecoder::props_mut returns) over storage that needs no context
 struct KltProps : Properties {
     size_t max_w = 150, max_h = 150, levels = 4, radius = 7, iters = 10;
     bool process_fullres = true;
     KltSettings set;
     std::vector<std::pair<std::string, PropertyMut>> props_mut() override {
-        return klt_props({&max_w, &max_h, &process_fullres, &set, &levels, &radius, &iters});
+        return klt_decoder_props({&max_w, &max_h, &process_fullres, &set, &levels, &radius, &iters});
     }
 };
 
@@ -68,13 +68,18 @@ int main() {
         if (name == "Iterations") listed += u && u->val == 10 && u->min == 1 && u->max == 30;
         if (name == "Mean removal") listed += std::holds_alternative<bool>(v) && !std::get<bool>(v);      // N3m: a boolean, off by default
         if (name == "Consistency check") listed += u && u->val == 0 && u->min == 0 && u->max == 4096;     // N3f: 1/256 pixel, 0 = off
+        if (name == "Prediction") listed += std::holds_alternative<bool>(v) && !std::get<bool>(v);         // N3p: a boolean, off by default
     }
-    CHECK(listed == 10);
+    CHECK(listed == 11);
     {
-        const auto all = p.props();                                                  // "Iterations", "Mean removal", "Consistency check" last
-        CHECK(all.size() >= 3 && all[all.size() - 3].first == "Iterations" && all[all.size() - 2].first == "Mean removal");
-        CHECK(all.back().first == "Consistency check");
+        const auto all = p.props();                          // "Iterations", "Mean removal", "Consistency check", and the extension "Prediction" last
+        CHECK(all.size() >= 4 && all[all.size() - 4].first == "Iterations" && all[all.size() - 3].first == "Mean removal");
+        CHECK(all[all.size() - 2].first == "Consistency check" && all.back().first == "Prediction");
+        CHECK(klt_props({&p.max_w, &p.max_h, &p.process_fullres, &p.set, &p.levels, &p.radius, &p.iters}).back().first == "Consistency check");
     }
+    CHECK(p.set_prop("Prediction", Property{true}) && p.set.prediction);
+    CHECK(p.set_prop("Prediction", Property{BoundedProp<size_t>{0, 0, 1}}) && p.set.prediction);       // a mismatched kind is ignored
+    CHECK(!p.set_prop("Predictions", Property{true}));
     CHECK(p.set_prop("Consistency check", Property{BoundedProp<size_t>{64, 0, kKltMaxFb}}) && p.set.fb_limit == 64);
     CHECK(p.set_prop("Consistency check", Property{true}) && p.set.fb_limit == 64);           // a mismatched kind is ignored
     CHECK(p.set_prop("Mean removal", Property{true}) && p.set.mean_removal);
@@ -87,6 +92,7 @@ int main() {
         "settings": {"worker": {"decoder_properties": {"Cell size": {"Usize": {"val": 8, "min": 8, "max": 32}},
         "Max residual": {"Usize": {"val": 64, "min": 0, "max": 4080}}, "Levels": {"Usize": {"val": 3, "min": 1, "max": 6}},
         "Process Fullres": {"Bool": false}, "Mean removal": {"Bool": true}, "Consistency check": {"Usize": {"val": 16, "min": 0, "max": 4096}},
+        "Prediction": {"Bool": true},
         "Not a property of this plugin": {"Bool": true}}, "realtime_processing": false,
         "detector_properties": {}}, "overlay_mf": false, "max_frame_gap": 2, "min_frames": 2,
         "draw_perf_stats": {"summary_window": false, "graph_window": false}}})";
@@ -97,6 +103,7 @@ int main() {
         CHECK(q.set.cell == 8 && q.set.max_residual == 64 && q.levels == 3 && !q.process_fullres && q.radius == 7 && q.set.min_eig == 1);
         CHECK(q.set.mean_removal && !KltProps().set.mean_removal);
         CHECK(q.set.fb_limit == 16 && KltProps().set.fb_limit == 0);
+        CHECK(q.set.prediction && !KltProps().set.prediction);
         CHECK(klt_record_floats(64, 48, q.max_w, q.max_h, true, q.set.cell) == 4 * 8 * 6);
         size_t seen = 0;
         for (const auto& [name, v] : q.props())

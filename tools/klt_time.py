@@ -25,7 +25,9 @@ klt_track_batch_kernel, compact_items_kernel), in a run of its own.
 --mean-removal: the same table, or the same batch mode, with ofps_hip_set_klt_mean_removal(1) (N3m): every hip_klt row then runs
 klt_track_zm_kernel / klt_track_batch_zm_kernel; the rows say so ("mean_removal": 1).  --klt-only leaves the hip_sad and hip_lk rows out.
 --fb N: with ofps_hip_set_klt_fb(N) (N3f): every hip_klt row then runs the FB kernels, the backward pass inside the track launch for the slots
-the forward pass kept; the rows say so ("fb_limit": N) and their "kept" and status histogram (5 = did not return) are the checked ones."""
+the forward pass kept; the rows say so ("fb_limit": N) and their "kept" and status histogram (5 = did not return) are the checked ones.
+--predict: the one-pair rows also time the predictor alone ("predict") and ofps_hip_klt_flow_from_dev started from the pair's own slots
+("flow_from", N3p: a steady pair, every track starts from its answer and runs the klt_track_pred kernels); the rows say so ("predict": 1)."""
 import argparse
 import json
 import os
@@ -50,7 +52,7 @@ def window_ms(ctx, fn, calls, reps, warm):
     return {"median_us": round(float(np.median(out)) * 1e3, 2), "min_us": round(min(out) * 1e3, 2), "max_us": round(max(out) * 1e3, 2)}
 
 
-def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, reps, warm, klt_only=False):
+def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, reps, warm, klt_only=False, predict=False):
     H, W = prev.shape
     ctx.set_klt(cell, 2, 1, 1, max_residual)
     ns = ctx.klt_slot_count(W, H)
@@ -94,6 +96,16 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     t["track_alone_derived_us"] = round(t["track"]["median_us"] - t["pyramid"]["median_us"], 2)
     ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots)
     ctx.sync()
+    if predict:         # N3p on a steady pair: the pair's own slots as the previous pair's, so every track starts from its answer
+        d_slots0, d_guess = ctx.malloc(24 * ns), ctx.malloc(8 * ns)
+        keep = np.zeros((ns, 6), np.int32)
+        ctx.memcpy_d2h(keep, d_slots)
+        ctx.memcpy_h2d(d_slots0, keep)
+        t["predict"] = window_ms(ctx, lambda: ctx.klt_predict_dev(d_slots0, W, H, cell, d_guess), calls, reps, warm)
+        t["flow_from"] = window_ms(ctx, lambda: ctx.klt_flow_from_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_slots0, d_rec, d_cnt, d_slots), calls, reps, warm)
+        ctx.klt_flow_from_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_slots0, d_rec, d_cnt, d_slots)
+        ctx.sync()
+        ctx.free(d_slots0); ctx.free(d_guess)
     slots = np.zeros((ns, 6), np.int32)
     cnt = np.zeros(4, np.uint32)
     ctx.memcpy_d2h(slots, d_slots)
@@ -102,7 +114,7 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     for p in [d_fr, d_tri, d_quad, d_rec, d_cnt, d_slots, d_pts, d_sad, d_lk] + [b for lv in pyr for b in lv[3:]]:
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
+            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "predict": int(predict), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
 def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm):
@@ -156,6 +168,8 @@ def main():
     ap.add_argument("--mean-removal", action="store_true", help="hip_klt with mean removal (include/ofps_hip.h N3m)")
     ap.add_argument("--fb", type=int, default=0, metavar="N", help="hip_klt with the forward-backward check at N / 256 pixel (include/ofps_hip.h N3f)")
     ap.add_argument("--klt-only", action="store_true", help="no hip_sad and hip_lk rows beside hip_klt's")
+    ap.add_argument("--predict", action="store_true", help="one-pair rows: also the predictor alone and ofps_hip_klt_flow_from_dev started from the pair's own slots "
+                                                           "(include/ofps_hip.h N3p); kept and the status histogram are then that call's")
     a = ap.parse_args()
     ctx = HipContext(0)
     ctx.set_klt_mean_removal(1 if a.mean_removal else 0)
@@ -174,7 +188,7 @@ def main():
             continue
         for name, (p, c) in (("luma_sequence", (lum[0], lum[1])), ("camera_warp_pair", (warp[0], warp[1]))):
             rows.append(one(ctx, name, np.ascontiguousarray(p), np.ascontiguousarray(c), cell, a.levels, a.radius, a.iters, a.max_residual,
-                            a.calls, a.reps, a.warm, a.klt_only))
+                            a.calls, a.reps, a.warm, a.klt_only, a.predict))
             print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
     ctx.close()
     print(json.dumps({"calls_per_window": a.calls, "windows": a.reps, "warm_windows": a.warm, "rows": rows}))

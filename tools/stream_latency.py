@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--ransac", action="store_true")
     ap.add_argument("--split", type=int, default=0, metavar="T")
     ap.add_argument("--klt", action="store_true")
+    ap.add_argument("--klt-predict", action="store_true", help="with --klt: the prediction setting on (include/ofps_hip.h N3p)")
+    ap.add_argument("--klt-levels", type=int, default=4, help="with --klt: pyramid levels")
     ap.add_argument("--lib", default=None)
     args = ap.parse_args()
     W, H = args.width, args.height
@@ -72,6 +74,8 @@ def main():
     ctx = HipContext(0)
     if args.split:
         ctx.set_sad_split(args.split)
+    if args.klt_predict:
+        ctx.set_klt_prediction(1)
     # the receive buffer IS the page-locked staging buffer (recv_into writes the frame where the DMA engine reads it):
     # no host copy, no pageable-memory staging inside hipMemcpy
     pinned = ctx.pinned_frame(H, W)
@@ -85,7 +89,7 @@ def main():
         t_arr = time.perf_counter()
         frame = pinned
         if args.klt:
-            r = ctx.lk_push_frame_fused(frame, 4, 7, 10, sparse=True, use_ransac=args.ransac, seed=k, want_entries=False, want_field=False)
+            r = ctx.lk_push_frame_fused(frame, args.klt_levels, 7, 10, sparse=True, use_ransac=args.ransac, seed=k, want_entries=False, want_field=False)
         else:
             r = ctx.push_frame(frame, block=16, search_range=16, use_ransac=args.ransac, seed=k)
         t_done = time.perf_counter()
@@ -93,7 +97,7 @@ def main():
             lat.append((t_done - t_arr) * 1e3)
         islands += r["motion"] is not None
     lat = np.array(lat)
-    print(json.dumps({"config": f"{W}x{H}@{args.fps:g} TCP loop-back, {'hip_klt (cell 16, 4 levels, radius 7, 10 iterations)' if args.klt else '16x16 +-16 SAD'} + block-motion + almeida "
+    print(json.dumps({"config": f"{W}x{H}@{args.fps:g} TCP loop-back, {f'hip_klt (cell 16, {args.klt_levels} levels, radius 7, 10 iterations, prediction {int(args.klt_predict)})' if args.klt else '16x16 +-16 SAD'} + block-motion + almeida "
                                 f"({'RANSAC' if args.ransac else 'LSQ'}) per frame", "frames": args.frames,
                       "latency_ms": {"p50": round(float(np.percentile(lat, 50)), 3), "p90": round(float(np.percentile(lat, 90)), 3),
                                      "p99": round(float(np.percentile(lat, 99)), 3), "max": round(float(lat.max()), 3)},
