@@ -824,9 +824,10 @@ int ofps_hip_klt_track_q_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* 
  *   those of a chain of ofps_hip_klt_flow_from calls on the frames the tracker reads.  The slots are forgotten on ofps_hip_lk_reset and
  *   ofps_hip_lk_rewind, on the stream's first pair, and on any change of geometry, format, mode, cell or flags.  A pair pushed with the
  *   setting off writes no slots, so its successor starts from zero: the setting may be switched in mid-stream.
- * The batch form ofps_hip_klt_flow_batch[_dev], ofps_hip_push_frames_async and the multi-device workers IGNORE the setting and return the
- *   bytes they return without it: item k's guess would depend on item k - 1's result, which would serialise the one track launch N3b
- *   exists for.  ofps_hip_klt_track[_dev], _track_q[_dev], _flow[_dev] and ofps_hip_lk_decode start from (0, 0) as before.
+ * The batch form ofps_hip_klt_flow_batch[_dev] and ofps_hip_push_frames_async IGNORE the setting while N3pb's switch (below) is 0, its
+ *   default, and return the bytes they return without it: item k's guess depends on item k - 1's result, which serialises the one track
+ *   launch N3b exists for, so that is asked for separately.  The multi-device workers IGNORE the setting and N3pb's switch always.
+ *   ofps_hip_klt_track[_dev], _track_q[_dev], _flow[_dev] and ofps_hip_lk_decode start from (0, 0) as before.
  * Bit-exact against the restatement tests/indep_klt_pred.py.  Additive: OFPS_HIP_API_VERSION stays. */
 int ofps_hip_set_klt_prediction(ofps_hip_ctx* ctx, int on);
 int ofps_hip_get_klt_prediction(ofps_hip_ctx* ctx);          /* 0 | 1; OFPS_HIP_EINVAL for a NULL context */
@@ -875,6 +876,45 @@ int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_f
 enum { OFPS_HIP_BATCH_DECODER_SAD = 0, OFPS_HIP_BATCH_DECODER_KLT = 1 };
 int ofps_hip_set_batch_decoder(ofps_hip_ctx* ctx, int decoder, int levels, int radius, int iters);   /* levels, radius, iters: read only for KLT */
 int ofps_hip_get_batch_decoder(ofps_hip_ctx* ctx, int32_t* decoder, int32_t* levels, int32_t* radius, int32_t* iters);   /* any may be NULL */
+
+/* ---- N3pb: motion prediction in the batch form and the batched stream: a chained batch (csrc/klt.hip, csrc/pipeline.hip) ----
+ * Build-defined, off by default.  Nothing about the arithmetic of N3, N3m, N3f or N3p changes.  A CHAINED batch: item k starts every track
+ * from the guess that N3p's predictor makes from item k - 1's raw slots; item 0 starts from the guesses made from `prev_slots`, from (0, 0)
+ * where there are none.  This holds in both ref_modes; with ref_mode 1 (pairs (0, k + 1)) the features, and so the lattice's slots, are the
+ * same for all items, so every item only has to reach the increment of a displacement that grows with k.  With N3f on, the backward pass
+ * starts from the negated guess, as in N3p.  Per item, records, count and raw slots equal a chain of ofps_hip_klt_flow_from calls on the
+ * item's pair, each given the slots of the call before, bit for bit.
+ * On the device only the track step serialises: the score launch, the one halving per level and the segmented compaction stay one launch
+ * each for the whole batch; the track step is `pairs` launches on the context's stream, one item each, launch k reading the slots launch
+ * k - 1 wrote (in the caller's slot array, or in scratch when the caller takes no slots).  Stream order is the only dependency between
+ * items, and no launch reads the array it writes.
+ * ofps_hip_klt_flow_batch_from[_dev]: ofps_hip_klt_flow_batch[_dev] with one more trailing argument, `prev_slots` (6 * slots int32, or
+ *   NULL).  Always chained; it reads neither prediction setting, as ofps_hip_klt_flow_from does not.  It refuses what _flow_batch refuses.
+ *   In the _dev form d_prev_slots must not share a byte with d_out_slots (pairs * 6 * slots int32): OFPS_HIP_EINVAL.  The host form copies
+ *   prev_slots first: there it may lie inside out_slots.
+ * Switch of the context, batch_prediction in {0, 1} (ofps_hip_set_klt_batch_prediction; option and environment variable
+ *   OFPS_HIP_KLT_BATCH_PREDICTION).  Any other value is OFPS_HIP_EINVAL and the setting stays as it was.  With the switch AND N3p's
+ *   prediction setting both 1, ofps_hip_klt_flow_batch[_dev] is ofps_hip_klt_flow_batch_from[_dev] with NULL, and
+ *   ofps_hip_push_frames_async with the batch decoder at KLT chains within a ticket and ACROSS tickets: the stream keeps the raw slots of
+ *   its newest pair on the device (two buffers that alternate by ticket, so a ticket of one frame never reads what it writes; written and
+ *   read on the compute stream alone), and the next ticket's first item starts from them.  Frame j's records, kept count, island and
+ *   quaternion then do not depend on how the frames were cut into tickets, and equal those of the sparse one-pair stream with N3p's
+ *   setting on (records and counts bit for bit, the rest within N3b's bounds).  The slots are forgotten on the stream's first frame, on a
+ *   change of geometry or cell, on ofps_hip_reset_frames, and by any ticket pushed with either setting at 0 or with the search as decoder:
+ *   such a ticket enqueues exactly what it enqueues without this row and leaves no slots, so its successor starts from zero.  The
+ *   settings may be switched in mid-stream.  With either at 0 every batched form enqueues the launches and bytes it enqueues without this
+ *   row.
+ * The multi-device workers (ofps_hip_multi_push_frames_async) ignore both settings: a worker sees every n-th batch, so its first item has
+ *   no predecessor on its device, and an answer must not depend on the number of devices.
+ * Bit-exact against the restatement tests/indep_klt_batch_pred.py.  Additive: OFPS_HIP_API_VERSION stays. */
+int ofps_hip_set_klt_batch_prediction(ofps_hip_ctx* ctx, int on);
+int ofps_hip_get_klt_batch_prediction(ofps_hip_ctx* ctx);    /* 0 | 1; OFPS_HIP_EINVAL for a NULL context */
+int ofps_hip_klt_flow_batch_from(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                 int levels, int radius, int iters, float* out_entries /* pairs * 4 * slots */, uint32_t* out_counts /* pairs */,
+                                 int32_t* out_slots /* pairs * 6 * slots, or NULL */, const int32_t* prev_slots /* 6 * slots, or NULL */);
+int ofps_hip_klt_flow_batch_from_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch,
+                                     int ref_mode, int levels, int radius, int iters, void* d_out_entries, void* d_out_counts,
+                                     void* d_out_slots /* or NULL */, const void* d_prev_slots /* or NULL */);
 
 /* ---- A1-A4: MotionFieldDensifier ---- */
 int ofps_hip_densify(ofps_hip_ctx* ctx, const float* entries, size_t n, int w, int h,

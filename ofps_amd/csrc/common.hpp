@@ -142,6 +142,10 @@ struct BatchStream {
     static constexpr int kTickets = 2;
     int w = 0, h = 0;
     void* last_frame = nullptr;          // device address of the newest frame of the batched stream
+    // N3pb (both prediction settings 1, the KLT decoder): the raw slots of the newest frame's pair lie in half `half` of S_KLT_BATCH_PRED; the
+    // next ticket's first item starts from them if it is chained too, on the same lattice and the same allocation.  The halves alternate by
+    // ticket: a ticket of one frame reads one and writes the other.  Written and read on the compute stream alone
+    struct KltPred { bool valid = false; int half = 0, w = 0, h = 0, cell = 0; uint64_t gen = 0; } klt_pred;
     struct Ticket {
         bool pending = false;
         hipEvent_t done = nullptr, uploaded = nullptr, prev_copied = nullptr;
@@ -241,6 +245,9 @@ struct ofps_hip_ctx {
         int klt_fb = 0;
         // ofps_hip_set_klt_prediction: 1 = the sparse stream forms start a pair's tracks from the previous pair's flow (include/ofps_hip.h N3p)
         int klt_prediction = 0;
+        // OFPS_HIP_KLT_BATCH_PREDICTION / ofps_hip_set_klt_batch_prediction: 1 = with klt_prediction 1 as well, the batch form and the batched stream
+        // (not the ofps_hip_multi_* workers) chain their items: each starts from the item before (include/ofps_hip.h N3pb)
+        int klt_batch_prediction = 0;
         // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
         // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
         int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;
@@ -316,9 +323,10 @@ enum ScratchSlot {
     S_KLT_PYR,              // hip_klt (klt.hip, N3): both frames' pyramid levels above 0.  Compute stream only, written anew by every call
     S_KLT_WORK,             // ... [features, 3 i32 per slot][raw records per slot][keep flags, u8 per slot], in front of the compaction
     S_KLT_HOST,             // ... the host-pointer forms' device-side inputs and outputs
-    S_KLT_PRED              // N3p: the sparse stream's raw slots of the last two pairs, 6 i32 per slot each.  Compute stream only
+    S_KLT_PRED,             // N3p: the sparse stream's raw slots of the last two pairs, 6 i32 per slot each.  Compute stream only
+    S_KLT_BATCH_PRED        // N3pb: the batched stream's raw slots of the last item of the last two chained tickets, 6 i32 per slot each.  Compute stream only
 };
-static_assert(S_KLT_PRED < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_KLT_BATCH_PRED < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -397,8 +405,11 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
 // one score launch over the distinct prev frames, one halving per level over the distinct frames, one track launch of pairs x slots waves, the
 // segmented compaction.  d_out: pairs slots of the slot count, item k's kept records lead slot k; d_counts: pairs counts; d_slots (optional):
 // 6 int32 per slot, item-major.  Works in S_KLT_PYR and S_KLT_WORK (compute stream only, consumed in front of the compaction: tickets share them)
+// chained (N3pb): the track step becomes `pairs` launches, one item each, in order on ctx->stream; item k's tracks start from the guesses made from
+// item k - 1's raw slots, item 0's from d_prev_slots (null: from zero).  d_last_slots (optional): the last item's raw slots go there and not
+// into d_slots; neither it nor d_prev_slots may share a byte with d_slots or with each other
 int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
-                          int* d_slots);
+                          int* d_slots, bool chained = false, const int* d_prev_slots = nullptr, int* d_last_slots = nullptr);
 // sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
 constexpr int kSadPrefilterMax = 16;
 int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,

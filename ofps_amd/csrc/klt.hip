@@ -20,6 +20,9 @@
 // klt_track_pred*_kernel: the one-pair kernels with motion prediction (N3p): a pass starts from the slot's guess -- given by the caller, or made
 //   by klt_predict_slot from the previous pair's raw slots in front of the wave's first level -- in place of dq = (0, 0), N3f's backward pass
 //   from its negation.  klt_predict_kernel: the predictor alone, a lane per slot.
+// klt_track_batch_pred*_kernel: the batch kernels with motion prediction (N3pb): ONE item of a batch per launch, its slots' guesses predicted from
+//   the raw slots the launch of the item before has written.  The launches follow one another on the context's stream, which is all that orders
+//   them: no wave waits for another.
 #include "common.hpp"
 
 #include <cmath>
@@ -71,6 +74,14 @@ struct KltTrackPredParams {
     const int* guesses;
     const int* prev_slots;
     int nx, ny;
+};
+
+// N3pb's track launch: the slots first_slot .. t.n - 1 of the batch, ONE item's.  Where they start from: the guesses klt_predict_slot makes from
+// `prev_slots`, the raw slots of the item before on the item's nx x ny lattice (null: every guess is (0, 0)).  Never the array the launch writes
+struct KltTrackBatchPredParams {
+    KltTrackBatchParams b;
+    const int* prev_slots;
+    int first_slot, nx, ny;
 };
 
 constexpr int kKltMaxGuess = 1 << 23;                        // N3p: a guess beyond it, per component, is (0, 0)
@@ -274,12 +285,14 @@ __device__ __forceinline__ void klt_predict_slot(const int* __restrict__ prev_sl
 // P + dq * 2^l, which for P = 256 (x, y) are N3's values --: KLT_MODE_Q reads P from the points and runs one pass; KLT_MODE_FB (N3f) runs N3's
 // pass from 256 (x, y) and, where it ends with status 0, a second pass from P = 256 (x, y) + dq with prev and cur exchanged.  PRED (N3p): a
 // pass starts from the slot's guess g (the backward pass from -g) in place of dq = (0, 0); g is one value per wave, read or predicted once
-// and held in scalar registers.  Its lines are compiled into its own kernels alone
+// and held in scalar registers.  Its lines are compiled into its own kernels alone.  BATCH and PRED (N3pb): the launch's first wave is slot
+// c->first_slot of the batch, and the guess is predicted from c->prev_slots at the slot's place within its item
 template <bool BATCH, bool ZM, int MODE = KLT_MODE_PIXEL, bool PRED = false>
-__device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl, const KltTrackPredParams* g = nullptr) {
+__device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const KltTrackBatchParams* b, int* tmpl, const KltTrackPredParams* g = nullptr,
+                                               const KltTrackBatchPredParams* c = nullptr) {
     constexpr bool FB = MODE == KLT_MODE_FB, AT_Q = MODE != KLT_MODE_PIXEL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave;
+    const long long slot = (long long)blockIdx.x * kKltTrackWaves + wave + (BATCH && PRED ? c->first_slot : 0);
     if (slot >= p.n) return;                                  // the whole wave
     int* I = tmpl + wave * kKltTemplatePitch;
     size_t item = 0;
@@ -309,7 +322,17 @@ __device__ __forceinline__ void klt_track_body(const KltTrackParams& p, const Kl
     }
     int px = MODE == KLT_MODE_Q ? x : 256 * x, py = MODE == KLT_MODE_Q ? y : 256 * y;      // the pass's start (read with AT_Q alone)
     int gx = 0, gy = 0;                                       // PRED: the slot's guess, 1/256 pixel at level 0
-    if constexpr (PRED) {
+    if constexpr (PRED && BATCH) {
+        // the wave's lattice cell, the slot's place within its item, as a scalar
+        const int s = __builtin_amdgcn_readfirstlane((int)slot - (int)item * b->slots_per_item);
+        if (c->prev_slots) klt_predict_slot(c->prev_slots, c->nx, c->ny, s % c->nx, s / c->nx, gx, gy);
+        gx = __builtin_amdgcn_readfirstlane(gx); gy = __builtin_amdgcn_readfirstlane(gy);
+        if (gx < -kKltMaxGuess || gx > kKltMaxGuess || gy < -kKltMaxGuess || gy > kKltMaxGuess) { gx = 0; gy = 0; }
+        // with the second pass around the first, and the item's pitches beside it, two scalars that live through both passes are two more than
+        // the scalar registers hold: the guess waits in the wave's template row, behind the 17 x 17 samples, and each pass reads it back
+        // (every lane stores the same two words: a test on the lane here would be kept, as a mask in two scalar registers, for the store at the end)
+        if constexpr (FB) { I[kKltTemplate] = gx; I[kKltTemplate + 1] = gy; }
+    } else if constexpr (PRED) {
         const int s = __builtin_amdgcn_readfirstlane((int)slot);      // the wave's slot as a scalar: what is read below is read once per wave
         if (g->guesses) { gx = g->guesses[2 * (size_t)s]; gy = g->guesses[2 * (size_t)s + 1]; }
         else klt_predict_slot(g->prev_slots, g->nx, g->ny, s % g->nx, s / g->nx, gx, gy);
@@ -328,6 +351,10 @@ another_pass: __attribute__((unused));
         // dq = g >> (L - 1) (the backward pass: -g), unless N3's frame test fails on the start: then (0, 0).  |g| <= 2^23 and a start inside the
         // frame: every dq of the pass stays an int as it does without a guess
         const int sh = p.L - 1;
+        if constexpr (BATCH && FB) {
+            wave_sync();
+            gx = __builtin_amdgcn_readfirstlane(I[kKltTemplate]); gy = __builtin_amdgcn_readfirstlane(I[kKltTemplate + 1]);
+        }
         const int sx = (back ? -gx : gx) >> sh, sy = (back ? -gy : gy) >> sh;
         const long long fx = (AT_Q ? (long long)px : 256ll * x) + (long long)sx * (1ll << sh), fy = (AT_Q ? (long long)py : 256ll * y) + (long long)sy * (1ll << sh);
         const bool out = __builtin_amdgcn_readfirstlane((int)(fx < 0 || fx > 256ll * (W0 - 1) || fy < 0 || fy > 256ll * (H0 - 1))) != 0;
@@ -537,6 +564,27 @@ __global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_pred_zm_fb_kern
     klt_track_body<false, true, KLT_MODE_FB, true>(p.t, nullptr, tmpl, &p);
 }
 
+// N3pb: the four batch kernels whose launch is one item, started from the item before
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_pred_kernel(const KltTrackBatchPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, false, KLT_MODE_PIXEL, true>(p.b.t, &p.b, tmpl, nullptr, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_pred_zm_kernel(const KltTrackBatchPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, true, KLT_MODE_PIXEL, true>(p.b.t, &p.b, tmpl, nullptr, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_pred_fb_kernel(const KltTrackBatchPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, false, KLT_MODE_FB, true>(p.b.t, &p.b, tmpl, nullptr, &p);
+}
+
+__global__ __launch_bounds__(64 * kKltTrackWaves) void klt_track_batch_pred_zm_fb_kernel(const KltTrackBatchPredParams p) {
+    __shared__ int tmpl[kKltTrackWaves * kKltTemplatePitch];
+    klt_track_body<true, true, KLT_MODE_FB, true>(p.b.t, &p.b, tmpl, nullptr, &p);
+}
+
 __global__ __launch_bounds__(256) void klt_predict_kernel(const int* __restrict__ prev_slots, int nx, int ny, int* __restrict__ out) {
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
     if (s >= (long long)nx * ny) return;
@@ -724,6 +772,37 @@ int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
     return OFPS_HIP_OK;
 }
 
+// N3pb: `pairs` launches, one item each, in item order on ctx->stream.  Item k writes its raw slots where the caller wants them (b.t.out_slots,
+// item-major: the caller's array, or S_KLT_WORK's), the last item into d_last_slots if that is given; item k + 1 reads them there.  Item 0 reads
+// d_prev_slots (null: zero guesses).  No launch reads the array it writes: the items' slots are ns apart, and the callers keep d_prev_slots
+// and d_last_slots apart from each other and from the rest
+int klt_track_batch_pred_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b, int pairs, int nx, int ny, const int* d_prev_slots, int* d_last_slots) {
+    const int ns = b.slots_per_item;
+    if (ns <= 0 || pairs <= 0) return OFPS_HIP_OK;
+    const dim3 grid((unsigned)((ns + kKltTrackWaves - 1) / kKltTrackWaves));
+    int* const all = b.t.out_slots;                           // 6 ints per slot of the batch
+    const int* prev = d_prev_slots;
+    for (int k = 0; k < pairs; ++k) {
+        KltTrackBatchPredParams f{b, prev, k * ns, nx, ny};
+        f.b.t.n = (k + 1) * ns;
+        f.b.t.fb_limit = ctx->opt.klt_fb;
+        int* mine = all + 6 * (size_t)k * ns;
+        if (k == pairs - 1 && d_last_slots) {
+            // the kernel stores at 6 * slot behind out_slots, slot counted from the batch's first: this item's slots land in d_last_slots
+            mine = d_last_slots;
+            f.b.t.out_slots = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(d_last_slots) - 6 * (size_t)k * ns * sizeof(int));
+        }
+        if (ctx->opt.klt_fb > 0) {
+            if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_pred_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+            else hipLaunchKernelGGL(klt_track_batch_pred_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_pred_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        else hipLaunchKernelGGL(klt_track_batch_pred_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
+        OFPS_HIP_TRY(ctx, hipGetLastError());
+        prev = mine;
+    }
+    return OFPS_HIP_OK;
+}
+
 int klt_check_sequence(ofps_hip_ctx* ctx, int n_frames, int H, int stride, size_t frame_pitch, int ref_mode, const char* who) {
     OFPS_REQUIRE(ctx, n_frames >= 2 && n_frames <= 65536, "%s: n_frames %d outside [2, 65536]", who, n_frames);
     OFPS_REQUIRE(ctx, ref_mode == 0 || ref_mode == 1, "%s: ref_mode %d is not 0|1", who, ref_mode);
@@ -770,9 +849,12 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
 
 // N3b.  S_KLT_WORK: [triples of the distinct prev frames][raw records, pairs x slots][keep flags, pairs x slots].  Both scratch slots are
 // written and read on ctx->stream alone and are dead behind the compaction, so two tickets of the batched stream share them; scratch() waits
-// for that stream before it frees a slot it has to grow, which is all the order they need
+// for that stream before it frees a slot it has to grow, which is all the order they need.
+// chained (N3pb): the track step is one launch per item, item k started from item k - 1's raw slots, item 0 from d_prev_slots (null: from zero);
+// a caller that wants no slots has them in S_KLT_WORK, behind the flags ([raw slots, 6 i32 per slot of the batch]), where they are dead behind
+// the last track launch.  d_last_slots (optional): where the last item's raw slots go instead, for the call that follows
 int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
-                          int* d_slots) {
+                          int* d_slots, bool chained, const int* d_prev_slots, int* d_last_slots) {
     const KltSettings s = klt_settings(ctx);
     const size_t ns = klt_slots(f.W, f.H, s.cell);
     OFPS_REQUIRE(ctx, pairs >= 1 && (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)",
@@ -780,11 +862,13 @@ int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
     const size_t total = (size_t)pairs * ns;
     const int scored = f.prev_pitch ? pairs : 1;              // the distinct prev frames
     const size_t o_raw = pad16((size_t)scored * ns * 3 * sizeof(int)), o_flag = o_raw + total * sizeof(float4);
-    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_flag + pad16(total)));
+    const size_t o_wslots = o_flag + pad16(total);            // chained, and the caller takes no slots: they lie here
+    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)));
     if (!work) return OFPS_HIP_ENOMEM;
     auto* d_feat = reinterpret_cast<int*>(work);
     auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
     auto* d_flag = reinterpret_cast<uint8_t*>(work + o_flag);
+    if (chained && !d_slots) d_slots = reinterpret_cast<int*>(work + o_wslots);
     int rc = klt_features_batch_device(ctx, f.prev_base, f.prev_pitch, scored, f.W, f.H, f.stride, s, d_feat);
     if (rc != OFPS_HIP_OK) return rc;
     KltTrackBatchParams b{};
@@ -795,7 +879,8 @@ int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
     p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)total;
     p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
     b.slots_per_item = (int)ns; b.shared_features = f.prev_pitch ? 0 : 1;
-    rc = klt_track_batch_launch(ctx, b);
+    if (chained) rc = klt_track_batch_pred_launch(ctx, b, pairs, (f.W + s.cell - 1) / s.cell, (f.H + s.cell - 1) / s.cell, d_prev_slots, d_last_slots);
+    else rc = klt_track_batch_launch(ctx, b);
     if (rc != OFPS_HIP_OK) return rc;
     // one workgroup per item is right for a batch; ONE pair through it would scan a 4K frame's 129,600 slots on one compute unit (measured:
     // 5 % of the pair's time), so a batch of one pair keeps the one-pair form's compactions, as SadFilter::finish does (sad_gate.hip)
@@ -852,6 +937,15 @@ int ofps_hip_set_klt_prediction(ofps_hip_ctx* ctx, int on) {
 }
 
 int ofps_hip_get_klt_prediction(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_prediction : OFPS_HIP_EINVAL; }
+
+int ofps_hip_set_klt_batch_prediction(ofps_hip_ctx* ctx, int on) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    OFPS_REQUIRE(ctx, on == 0 || on == 1, "set_klt_batch_prediction: %d is not 0|1", on);
+    ctx->opt.klt_batch_prediction = on;
+    return OFPS_HIP_OK;
+}
+
+int ofps_hip_get_klt_batch_prediction(ofps_hip_ctx* ctx) { return ctx ? ctx->opt.klt_batch_prediction : OFPS_HIP_EINVAL; }
 
 size_t ofps_hip_klt_slot_count(int W, int H, int cell) {
     if (W < 1 || H < 1 || (cell != 8 && cell != 16 && cell != 32)) return 0;
@@ -1056,21 +1150,51 @@ int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     return ofps_hip_klt_flow_from(ctx, prev, cur, W, H, stride, levels, radius, iters, nullptr, out_entries, n_out, out_slots);
 }
 
-int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
-                                int levels, int radius, int iters, void* d_out_entries, void* d_out_counts, void* d_out_slots) {
+// ofps_hip_klt_flow_batch_dev and, with `chained`, ofps_hip_klt_flow_batch_from_dev (N3pb)
+static int klt_flow_batch_dev_impl(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                   int levels, int radius, int iters, void* d_out_entries, void* d_out_counts, void* d_out_slots, bool chained,
+                                   const void* d_prev_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_frames && d_out_entries && d_out_counts, "klt_flow_batch: null device pointer");
     int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
     if (rc == OFPS_HIP_OK) rc = klt_check_sequence(ctx, n_frames, H, stride, frame_pitch, ref_mode, "klt_flow_batch");
     if (rc != OFPS_HIP_OK) return rc;
+    if (d_prev_slots && d_out_slots) {
+        // item 0's waves read the previous slots while they, and later the other items, write the batch's: the two arrays must not share a byte
+        const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
+        const char* a = static_cast<const char*>(d_prev_slots);
+        const char* b = static_cast<const char*>(d_out_slots);
+        OFPS_REQUIRE(ctx, a + ns * 6 * sizeof(int) <= b || b + (size_t)(n_frames - 1) * ns * 6 * sizeof(int) <= a,
+                     "klt_flow_batch_from: d_prev_slots and d_out_slots overlap");
+    }
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ofps::SadFrames f = ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride);
     return ofps::klt_flow_batch_device(ctx, f, n_frames - 1, levels, radius, iters, static_cast<float4*>(d_out_entries),
-                                       static_cast<uint32_t*>(d_out_counts), static_cast<int*>(d_out_slots));
+                                       static_cast<uint32_t*>(d_out_counts), static_cast<int*>(d_out_slots), chained,
+                                       static_cast<const int*>(d_prev_slots));
 }
 
-int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
-                            int levels, int radius, int iters, float* out_entries, uint32_t* out_counts, int32_t* out_slots) {
+// N3pb's switch: the plain batch entry points chain iff the context has both prediction settings on
+static bool klt_batch_chained(const ofps_hip_ctx* ctx) { return ctx->opt.klt_prediction && ctx->opt.klt_batch_prediction; }
+
+int ofps_hip_klt_flow_batch_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                int levels, int radius, int iters, void* d_out_entries, void* d_out_counts, void* d_out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    return klt_flow_batch_dev_impl(ctx, d_frames, n_frames, W, H, stride, frame_pitch, ref_mode, levels, radius, iters, d_out_entries, d_out_counts,
+                                   d_out_slots, klt_batch_chained(ctx), nullptr);
+}
+
+int ofps_hip_klt_flow_batch_from_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                     int levels, int radius, int iters, void* d_out_entries, void* d_out_counts, void* d_out_slots,
+                                     const void* d_prev_slots) {
+    return klt_flow_batch_dev_impl(ctx, d_frames, n_frames, W, H, stride, frame_pitch, ref_mode, levels, radius, iters, d_out_entries, d_out_counts,
+                                   d_out_slots, true, d_prev_slots);
+}
+
+// ofps_hip_klt_flow_batch and, with `chained`, ofps_hip_klt_flow_batch_from (N3pb): prev_slots is copied to the device first, so it may be out_slots
+static int klt_flow_batch_host_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                    int levels, int radius, int iters, float* out_entries, uint32_t* out_counts, int32_t* out_slots, bool chained,
+                                    const int32_t* prev_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, frames && out_entries && out_counts, "klt_flow_batch: null host pointer");
     int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
@@ -1084,13 +1208,16 @@ int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_fram
     const size_t fb = (size_t)ss * H, total = (size_t)pairs * ns;
     const size_t o_count = total * sizeof(float4), o_slots = o_count + pad16((size_t)pairs * sizeof(uint32_t));
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)n_frames * fb));
-    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_slots + total * 6 * sizeof(int)));
+    const size_t o_prev = o_slots + total * 6 * sizeof(int);
+    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_prev + (prev_slots ? ns * 6 * sizeof(int) : 0)));
     if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
+    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io + o_prev, prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     for (int k = 0; k < n_frames; ++k)
         OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + (size_t)k * fb, ss, frames + (size_t)k * frame_pitch, stride, W, H, ctx->stream));
     rc = ofps::klt_flow_batch_device(ctx, ofps::SadFrames::sequence(d_fr, fb, ref_mode, W, H, ss), pairs, levels, radius, iters,
                                      reinterpret_cast<float4*>(d_io), reinterpret_cast<uint32_t*>(d_io + o_count),
-                                     out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr);
+                                     out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr, chained,
+                                     prev_slots ? reinterpret_cast<const int*>(d_io + o_prev) : nullptr);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, d_io + o_count, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_io + o_slots, total * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1102,6 +1229,20 @@ int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_fram
                                         hipMemcpyDeviceToHost));
     }
     return OFPS_HIP_OK;
+}
+
+int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                            int levels, int radius, int iters, float* out_entries, uint32_t* out_counts, int32_t* out_slots) {
+    if (!ctx) return OFPS_HIP_EINVAL;
+    return klt_flow_batch_host_impl(ctx, frames, n_frames, W, H, stride, frame_pitch, ref_mode, levels, radius, iters, out_entries, out_counts, out_slots,
+                                    klt_batch_chained(ctx), nullptr);
+}
+
+int ofps_hip_klt_flow_batch_from(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,
+                                 int levels, int radius, int iters, float* out_entries, uint32_t* out_counts, int32_t* out_slots,
+                                 const int32_t* prev_slots) {
+    return klt_flow_batch_host_impl(ctx, frames, n_frames, W, H, stride, frame_pitch, ref_mode, levels, radius, iters, out_entries, out_counts, out_slots,
+                                    true, prev_slots);
 }
 
 int ofps_hip_set_batch_decoder(ofps_hip_ctx* ctx, int decoder, int levels, int radius, int iters) {

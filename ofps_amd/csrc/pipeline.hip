@@ -215,6 +215,7 @@ int ofps_hip_reset_frames(ofps_hip_ctx* ctx) {
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     OFPS_HIP_TRY(ctx, ctx->batch.ring.drain());
     ctx->batch.last_frame = nullptr;
+    ctx->batch.klt_pred.valid = false;
     return pipe_drain(ctx);
 }
 
@@ -323,6 +324,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     if (W != ctx->batch.w || H != ctx->batch.h) {              // geometry change restarts the stream
         OFPS_HIP_TRY(ctx, ctx->batch.ring.drain());
         ctx->batch.w = W; ctx->batch.h = H; ctx->batch.last_frame = nullptr;
+        ctx->batch.klt_pred.valid = false;
     }
     const int dstride = (W + 63) & ~63;
     const size_t pitch = (size_t)dstride * H;
@@ -339,6 +341,24 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
                      ofps_hip_klt_slot_count(W, H, o.klt_cell));
     }
     const size_t nblk = klt ? ofps_hip_klt_slot_count(W, H, o.klt_cell) : ofps_hip_sad_block_count(W, H, prm->block);
+    // N3pb: with both prediction settings on the ticket's items are chained, item 0 behind the last item of the ticket before.  That item's raw
+    // slots wait in one half of S_KLT_BATCH_PRED, this ticket's last item writes the other half.  Any other ticket -- a setting off, the search,
+    // a multi-device worker's (halo_mode 1: a worker sees every n-th batch, its first item has no predecessor there) -- enqueues what it
+    // enqueued without the switch and leaves no slots behind: its successor starts from zero
+    BatchStream::KltPred& kp = ctx->batch.klt_pred;
+    const bool chained = klt && !halo_mode && o.klt_prediction && o.klt_batch_prediction;
+    const int* d_pred_in = nullptr;
+    int* d_pred_out = nullptr;
+    if (chained) {
+        const size_t half = (nblk * 6 * sizeof(int) + 255) & ~(size_t)255;
+        auto* d_pred = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_BATCH_PRED, 2 * half));
+        if (!d_pred) return OFPS_HIP_ENOMEM;
+        if (kp.valid && ctx->batch.last_frame && kp.w == W && kp.h == H && kp.cell == o.klt_cell && kp.gen == ctx->scratch[ofps::S_KLT_BATCH_PRED].gen)
+            d_pred_in = reinterpret_cast<const int*>(d_pred + (size_t)kp.half * half);
+        else kp.half = 0;
+        d_pred_out = reinterpret_cast<int*>(d_pred + (size_t)(kp.half ^ 1) * half);
+    }
+    const int pred_half = kp.half ^ 1;
     // the batch filter switch (include/ofps_hip.h N1b) with a criterion on: the filtered batched search and the tail's per-item device counts;
     // the ticket follows the settings the context has now.  Else everything below is what it is without the switch
     const bool filtered = !klt && o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0 || o.sad_intra > 0);
@@ -414,6 +434,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     // ---- compute stream: pairs (slot j, slot j + 1), j = first .. n - 1
     const int first = has_prev ? 0 : 1;                           // the stream's very first frame has no pair
     const int pairs = n - first;
+    kp.valid = false;                                            // (until this ticket's last item has been enqueued, and only if it is chained)
     t.n = n; t.first_has_prev = has_prev ? 1 : 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.n_vectors = nblk;
     t.filtered = (filtered || klt) && pairs > 0;
     if (halo_mode) t.isl.K = 0;                                  // the multi-device workers list no islands (include/ofps_hip.h A5i)
@@ -424,8 +445,10 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         // and the compaction run on the compute stream, in front of the tail that reads the counts there
         uint32_t* d_cnt = filtered || klt ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
         const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
-        if (klt) rc = klt_flow_batch_device(ctx, fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr);
-        else if (filtered)
+        if (klt) {
+            rc = klt_flow_batch_device(ctx, fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr, chained, d_pred_in, d_pred_out);
+            if (rc == OFPS_HIP_OK && chained) kp = {true, pred_half, W, H, o.klt_cell, ctx->scratch[ofps::S_KLT_BATCH_PRED].gen};
+        } else if (filtered)
             rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
                                           "push_frames_async", tix, kTickets, o.sad_intra, o.sad_cut);
         else rc = sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0, nullptr);

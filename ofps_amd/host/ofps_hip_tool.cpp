@@ -7,7 +7,7 @@
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
-//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N] [--klt-predict]]
+//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N] [--klt-predict [--klt-batch-predict]]]
 //                                                       PCIe-inclusive per-frame time of the hip_sad process_frame shape; `multi`:
 //                                                       the stream over several workers (ofps_hip_multi_push_frames_async), with
 //                                                       detector + estimator per frame; `--klt` (batch, multi): hip_klt as the
@@ -15,7 +15,9 @@
 //                                                       `--klt-mean-removal`: with its mean removal on (include/ofps_hip.h N3m);
 //                                                       `--klt-fb N`: with its forward-backward check at N / 256 pixel (N3f);
 //                                                       `--klt-predict`: with the prediction setting on (N3p), which the batched and
-//                                                       multi-device forms ignore: the figures are those without it
+//                                                       multi-device forms ignore: the figures are those without it;
+//                                                       `--klt-batch-predict` beside it (batch mode): the batched stream's switch
+//                                                       (N3pb) as well, the tickets' items chained; alone it changes nothing
 //   track   <decoder> <arg> [aspect fov_y] [lsq|ransac] tracking loop, ofps-suite/src/app/tracking/worker.rs:305-412
 //   mvec-copy <in.mvec> <out.mvec>                      CPU-only .mvec round trip (reader + writer)
 //   multi-extract <raw.y> <w> <h> <out.mvec> [dev ...]  the whole clip over several GPUs (ofps_hip_multi_*): same bytes as `extract hip_sad`
@@ -225,6 +227,7 @@ int main(int argc, char** argv) {
             int sb_block = 16, sb_range = 16;
             int sb_klt_fb = 0;                                 // `--klt-fb N` beside `--klt`: ofps_hip_set_klt_fb(N) / OFPS_HIP_KLT_FB=N
             bool sb_klt_pred = false;                          // `--klt-predict` beside `--klt`: ofps_hip_set_klt_prediction(1) / OFPS_HIP_KLT_PREDICTION=1
+            bool sb_klt_bpred = false;                         // `--klt-batch-predict` beside `--klt`: ofps_hip_set_klt_batch_prediction(1), batch mode alone (the multi-device workers ignore it)
             bool sb_klt_zm = false;                            // `--klt-mean-removal` beside `--klt`: ofps_hip_set_klt_mean_removal(1) / OFPS_HIP_KLT_MEAN_REMOVAL=1
             bool sb_probe = false, sb_klt = false;             // `--klt` (batch and multi modes): hip_klt as the batched stream's decoder (N3b), levels 4, radius 7, 10 iterations
             {
@@ -234,6 +237,7 @@ int main(int argc, char** argv) {
                     if (std::string(argv[a]) == "--klt") { sb_klt = true; continue; }
                     if (std::string(argv[a]) == "--klt-mean-removal") { sb_klt_zm = true; continue; }
                     if (std::string(argv[a]) == "--klt-predict") { sb_klt_pred = true; continue; }
+                    if (std::string(argv[a]) == "--klt-batch-predict") { sb_klt_bpred = true; continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--klt-fb") { sb_klt_fb = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--block") { sb_block = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--range") { sb_range = std::atoi(argv[++a]); continue; }
@@ -243,6 +247,7 @@ int main(int argc, char** argv) {
                 if (sb_klt_zm && !sb_klt) throw Error("stream-bench: --klt-mean-removal needs --klt");
                 if (sb_klt_fb && !sb_klt) throw Error("stream-bench: --klt-fb needs --klt");
                 if (sb_klt_pred && !sb_klt) throw Error("stream-bench: --klt-predict needs --klt");
+                if (sb_klt_bpred && !sb_klt) throw Error("stream-bench: --klt-batch-predict needs --klt");
             }
             // the Decoder::process_frame shape without Python in the loop: frames are already in page-locked buffers (a
             // decoder that writes there), one H2D + search + 16 B/vector D2H per frame
@@ -315,6 +320,7 @@ int main(int argc, char** argv) {
                     if (sb_klt_zm) ctx.check(ofps_hip_set_klt_mean_removal(ctx.get(), 1));
                     if (sb_klt_fb) ctx.check(ofps_hip_set_klt_fb(ctx.get(), sb_klt_fb));
                     if (sb_klt_pred) ctx.check(ofps_hip_set_klt_prediction(ctx.get(), 1));
+                    if (sb_klt_bpred) ctx.check(ofps_hip_set_klt_batch_prediction(ctx.get(), 1));
                     ctx.check(ofps_hip_get_klt(ctx.get(), &klt_cell, nullptr, nullptr, nullptr, nullptr));
                 }
                 const size_t nblk = sb_klt ? ofps_hip_klt_slot_count(W, H, klt_cell) : ofps_hip_sad_block_count(W, H, 16);
@@ -362,9 +368,9 @@ int main(int argc, char** argv) {
                                 "\"bare_h2d_GBs\": [%.1f, %.1f], \"buffer_numa_node\": [%d, %d], \"cpu\": %d}\n", batch, nb * batch, ms,
                                 (double)nblk / ms / 1e3, probe_gbs[0], probe_gbs[1], probe_node[0], probe_node[1], probe_cpu);
                 else if (sb_klt)
-                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"fb_limit\": %d, \"prediction\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
+                    std::printf("{\"mode\": \"read_ahead_batched\", \"decoder\": \"hip_klt\", \"mean_removal\": %d, \"fb_limit\": %d, \"prediction\": %d, \"batch_prediction\": %d, \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, "
                                 "\"capacity\": %zu, \"last_n_vectors\": %zu}\n", ofps_hip_get_klt_mean_removal(ctx.get()), ofps_hip_get_klt_fb(ctx.get()),
-                                ofps_hip_get_klt_prediction(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
+                                ofps_hip_get_klt_prediction(ctx.get()), ofps_hip_get_klt_batch_prediction(ctx.get()), batch, nb * batch, ms, nblk, (size_t)res[(size_t)batch - 1].n_vectors);
                 else
                 std::printf("{\"mode\": \"read_ahead_batched\", \"batch\": %d, \"frames\": %d, \"ms_per_frame\": %.4f, \"Mvectors_per_s\": %.2f}\n", batch,
                             nb * batch, ms, (double)nblk / ms / 1e3);

@@ -808,6 +808,48 @@ class HipContext:
                                                           radius, iters, C.c_void_p(d_out_entries), C.c_void_p(d_out_counts),
                                                           C.c_void_p(d_out_slots or 0)))
 
+    # ---- N3pb: motion prediction in the batch form and the batched stream
+    def set_klt_batch_prediction(self, on: int):
+        """1, with set_klt_prediction(1) as well: klt_flow_batch[_dev] and push_frames_async with the batch decoder at KLT chain their items,
+        each started from the item before, across tickets too (include/ofps_hip.h N3pb); 0 (default): they ignore the prediction setting."""
+        self._check(self._lib.ofps_hip_set_klt_batch_prediction(self._h, int(on)))
+
+    def get_klt_batch_prediction(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_batch_prediction(self._h))
+
+    def klt_flow_batch_from(self, frames: np.ndarray, levels: int, radius: int, iters: int, ref_mode: int = 0, prev_slots: np.ndarray | None = None,
+                            want_slots=True):
+        """klt_flow_batch, chained: item k starts from the guesses predicted from item k - 1's slots, item 0 from prev_slots' (int32
+        [slots, 6]; None: from zero).  Reads neither prediction setting.  -> (entries, counts[, slots]) as klt_flow_batch"""
+        assert frames.dtype == np.uint8 and frames.ndim == 3
+        n, H, W = frames.shape
+        pitch, stride, unit = frames.strides
+        assert unit == 1 and stride >= W, "frames: rows must be byte-contiguous"
+        pairs, ns = max(n - 1, 0), self.klt_slot_count(W, H)
+        ent = np.zeros((max(pairs, 1), max(ns, 1), 4), np.float32)
+        counts = np.zeros(max(pairs, 1), np.uint32)
+        slots = np.zeros((max(pairs, 1), max(ns, 1), 6), np.int32) if want_slots else None
+        ps = None
+        if prev_slots is not None:
+            ps = np.ascontiguousarray(prev_slots, np.int32).reshape(-1, 6)
+            assert len(ps) == ns
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_klt_flow_batch_from(self._h, C.cast(C.c_void_p(frames.ctypes.data), C.POINTER(C.c_uint8)), n, W, H, stride,
+                                                           pitch if n > 1 else stride * H, ref_mode, levels, radius, iters, _fp(ent),
+                                                           counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                           slots.ctypes.data_as(i32) if want_slots else None,
+                                                           ps.ctypes.data_as(i32) if ps is not None else None))
+        return (ent[:pairs], counts[:pairs], slots[:pairs]) if want_slots else (ent[:pairs], counts[:pairs])
+
+    def klt_flow_batch_from_dev(self, d_frames: int, n_frames: int, W: int, H: int, stride: int, frame_pitch: int, ref_mode: int, levels: int,
+                                radius: int, iters: int, d_out_entries: int, d_out_counts: int, d_out_slots: int | None = None,
+                                d_prev_slots: int | None = None):
+        """Enqueue only: klt_flow_batch_dev, chained, with the slots item 0 starts from in device memory (None: from zero); they must not overlap
+        d_out_slots."""
+        self._check(self._lib.ofps_hip_klt_flow_batch_from_dev(self._h, C.c_void_p(d_frames), n_frames, W, H, stride, frame_pitch, ref_mode, levels,
+                                                               radius, iters, C.c_void_p(d_out_entries), C.c_void_p(d_out_counts),
+                                                               C.c_void_p(d_out_slots or 0), C.c_void_p(d_prev_slots or 0)))
+
     def set_batch_decoder(self, decoder: int = 0, levels: int = 4, radius: int = 7, iters: int = 10):
         """What push_frames_async searches with: BATCH_DECODER_SAD (default), or BATCH_DECODER_KLT with these levels, window radius and
         iterations and the set_klt values (include/ofps_hip.h N3b)."""

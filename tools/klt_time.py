@@ -27,7 +27,12 @@ klt_track_zm_kernel / klt_track_batch_zm_kernel; the rows say so ("mean_removal"
 --fb N: with ofps_hip_set_klt_fb(N) (N3f): every hip_klt row then runs the FB kernels, the backward pass inside the track launch for the slots
 the forward pass kept; the rows say so ("fb_limit": N) and their "kept" and status histogram (5 = did not return) are the checked ones.
 --predict: the one-pair rows also time the predictor alone ("predict") and ofps_hip_klt_flow_from_dev started from the pair's own slots
-("flow_from", N3p: a steady pair, every track starts from its answer and runs the klt_track_pred kernels); the rows say so ("predict": 1)."""
+("flow_from", N3p: a steady pair, every track starts from its answer and runs the klt_track_pred kernels); the rows say so ("predict": 1).
+--batch-predict (with --batch N): two more columns, the chained batch (N3pb) and what it replaces, both per pair:
+  chained          one ofps_hip_klt_flow_batch_from_dev call over the N pairs, from zero: one score launch, one halving per level, N track launches
+                   (klt_track_batch_pred kernels), one compaction
+  one_by_one_from  N ofps_hip_klt_flow_from_dev calls over the same pairs, each given the slots of the one before
+and "chained_equals_one_by_one_from" says whether the two agree in counts and records."""
 import argparse
 import json
 import os
@@ -117,7 +122,7 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
             "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "predict": int(predict), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
-def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm):
+def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm, batch_predict=False):
     n_frames, H, W = frames.shape
     N = n_frames - 1
     ctx.set_klt(cell, 2, 1, 1, max_residual)
@@ -136,6 +141,29 @@ def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, call
             ctx.klt_flow_dev(d_fr + k * W * H, d_fr + (k + 1) * W * H, W, H, W, levels, radius, iters, d_rec1 + 16 * ns * k, d_cnt1 + 4 * k)
 
     t = {"batch": window_ms(ctx, batch, windows, reps, warm), "one_by_one": window_ms(ctx, one_by_one, windows, reps, warm)}
+    chained_same = None
+    if batch_predict:                                         # N3pb: the chained batch against the chain of one-pair calls it equals
+        d_rec2, d_cnt2, d_sl = ctx.malloc(16 * ns * N), ctx.malloc(max(4 * N, 16)), [ctx.malloc(24 * ns), ctx.malloc(24 * ns)]
+
+        def chained():
+            ctx.klt_flow_batch_from_dev(d_fr, n_frames, W, H, W, W * H, 0, levels, radius, iters, d_rec, d_cnt, None, None)
+
+        def one_by_one_from():
+            for k in range(N):
+                ctx.klt_flow_from_dev(d_fr + k * W * H, d_fr + (k + 1) * W * H, W, H, W, levels, radius, iters, d_sl[(k + 1) & 1] if k else None,
+                                      d_rec2 + 16 * ns * k, d_cnt2 + 4 * k, d_sl[k & 1])
+
+        t["chained"] = window_ms(ctx, chained, windows, reps, warm)
+        t["one_by_one_from"] = window_ms(ctx, one_by_one_from, windows, reps, warm)
+        chained(); one_by_one_from(); ctx.sync()
+        c0, c2 = np.zeros(max(N, 4), np.uint32), np.zeros(max(N, 4), np.uint32)
+        ctx.memcpy_d2h(c0, d_cnt); ctx.memcpy_d2h(c2, d_cnt2)
+        r0, r2 = np.zeros((N, ns, 4), np.float32), np.zeros((N, ns, 4), np.float32)
+        ctx.memcpy_d2h(r0, d_rec); ctx.memcpy_d2h(r2, d_rec2)
+        chained_same = bool((c0[:N] == c2[:N]).all() and all(r0[k, :c0[k]].tobytes() == r2[k, :c0[k]].tobytes() for k in range(N)))
+        chained_kept = [int(c) for c in c0[:N]]
+        for p in [d_rec2, d_cnt2] + d_sl:
+            ctx.free(p)
     for v in t.values():                                      # per call of N pairs -> per pair
         for key in v:
             v[key] = round(v[key] / N, 2)
@@ -147,9 +175,12 @@ def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, call
     same = bool((cnt[:N] == cnt1[:N]).all() and all(rec[k, :cnt[k]].tobytes() == rec1[k, :cnt[k]].tobytes() for k in range(N)))
     for p in (d_fr, d_rec, d_cnt, d_rec1, d_cnt1):
         ctx.free(p)
-    return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
-            "us_per_pair": t}
+    row = {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
+           "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
+           "us_per_pair": t}
+    if batch_predict:
+        row.update({"chained_kept": chained_kept, "chained_equals_one_by_one_from": chained_same})
+    return row
 
 
 def main():
@@ -170,6 +201,8 @@ def main():
     ap.add_argument("--klt-only", action="store_true", help="no hip_sad and hip_lk rows beside hip_klt's")
     ap.add_argument("--predict", action="store_true", help="one-pair rows: also the predictor alone and ofps_hip_klt_flow_from_dev started from the pair's own slots "
                                                            "(include/ofps_hip.h N3p); kept and the status histogram are then that call's")
+    ap.add_argument("--batch-predict", action="store_true", help="--batch: also the chained batch (include/ofps_hip.h N3pb) and the chain of "
+                                                                 "ofps_hip_klt_flow_from_dev calls it equals")
     a = ap.parse_args()
     ctx = HipContext(0)
     ctx.set_klt_mean_removal(1 if a.mean_removal else 0)
@@ -183,7 +216,7 @@ def main():
             for name, fr in (("luma_sequence", lum), ("camera_warp_pair", chain)):
                 if a.content not in ("both", name):
                     continue
-                rows.append(one_batch(ctx, name, np.ascontiguousarray(fr), cell, a.levels, a.radius, a.iters, a.max_residual, a.calls, a.reps, a.warm))
+                rows.append(one_batch(ctx, name, np.ascontiguousarray(fr), cell, a.levels, a.radius, a.iters, a.max_residual, a.calls, a.reps, a.warm, a.batch_predict))
                 print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
             continue
         for name, (p, c) in (("luma_sequence", (lum[0], lum[1])), ("camera_warp_pair", (warp[0], warp[1]))):
