@@ -274,6 +274,10 @@ struct StripCfg {
     static constexpr int MAXCOL = (NB - 1) * BW + (NG - 1) + BW;  // highest dword a lane touches
     static constexpr int SW = ((MAXCOL + 1 > TILE_WG * GDW ? MAXCOL + 1 : TILE_WG * GDW) + 3) / 4 * 4;  // 16-B rows
     static_assert((NB - 1) * BW + EDGE_COL + BW <= SW, "edge column must lie inside a window row");
+    // the window's LDS image is lane-linear when a window row is exactly its 16-byte granules: staging lane l = (row sr, granule
+    // sc) then writes bytes 16 l .. 16 l + 15 of the step's rows, which is the shape of a 16-byte direct global -> LDS load
+    // (wave-uniform LDS base + 16 x lane).  16x16 +-16 and +-32, 8x8 +-16 and +-32; every other entry stages through registers.
+    static constexpr bool LANE_LINEAR = GRAN == 16 && SW == TILE_WG * GDW;
     // the dx = +R pass gives lane chunk g the window rows g*KE .. g*KE + B + KE - 2: the last chunks run past the window (those dy are
     // masked); the tile is allocated that much taller so the walk needs no row clamp (uninitialised LDS, never used in a result)
     static constexpr int TILE_ROWS = TILE_H > NG * KE + B - 1 ? TILE_H : NG * KE + B - 1;
@@ -288,7 +292,10 @@ struct StripCfg {
     static constexpr int NP = (NCAND + SPLIT - 1) / SPLIT;
     // (8x8 +-8 is the one entry that fits 64 VGPRs, 8 waves per SIMD: say so, or the dx = +R pass's second read of its block rows
     // costs it the eighth wave for one register)
-    static constexpr int MIN_WAVES = (B == 8 && R == 8) ? 8 : ((2 * NP + B * BW + 40 <= 168) ? 3 : 2);
+    // (8x8 +-16 and +-12 fit 5 and 6 waves by a few registers; with the current block read through a buffer descriptor hipcc
+    // schedules them a dozen registers wider unless told: 104 and 92 VGPRs instead of 95 and 80)
+    static constexpr int MIN_WAVES = (B == 8 && R == 8) ? 8 : (B == 8 && R == 16) ? 5 : (B == 8 && R == 12) ? 6
+                                     : ((2 * NP + B * BW + 40 <= 168) ? 3 : 2);
     // small ranges: (d2 << 6 | dy index) fits the low 16 bits of the lane key, so the key alone identifies the
     // candidate and the scan needs no separate index tracking
     static constexpr bool COMPACT_KEY = ((2 * R * R) << 6) + NCAND < 65536 && NCAND <= 64;
@@ -360,6 +367,33 @@ __device__ __forceinline__ void strip_rows(unsigned long long (&acc)[N], const u
 constexpr int kSadColKeys = OFPS_SAD_COLKEYS;
 constexpr int kColSlotDwords = kSadColKeys == 2 ? 4 * 64 : 0;       // LDS per wave for the column minima
 
+// Timing-only builds that price the parts of a strip that are not SADs (HISTORY 41; OFPS_HIP_EXTRA_FLAGS=-DOFPS_SAD_PRICE=<bits>).
+// Each bit takes one part out of strip_body and leaves every SAD instruction and its operands in place; the RESULTS ARE WRONG by
+// design, such a library is for the clock only and is never shipped.  1: the key builds and ds_min_u32 of the main walk;
+// 2: the dx = +R pass except its v_sad_u8; 4: column finalisation, decode, butterfly and records (one dummy store stays);
+// 8: window staging and the current-block loads (the walk reads whatever LDS and the registers hold); 15: the SAD floor.
+#ifndef OFPS_SAD_PRICE
+#define OFPS_SAD_PRICE 0
+#endif
+constexpr int kSadPrice = OFPS_SAD_PRICE;
+// -DOFPS_SAD_DIRECT_STAGE=0: register staging everywhere (A/B builds of the direct memory -> LDS window staging);
+// -DOFPS_SAD_BUFFER_LOADS=0: the current block through per-lane 64-bit pointers (A/B builds of the scalar-descriptor loads)
+#ifndef OFPS_SAD_DIRECT_STAGE
+#define OFPS_SAD_DIRECT_STAGE 1
+#endif
+#ifndef OFPS_SAD_BUFFER_LOADS
+#define OFPS_SAD_BUFFER_LOADS 1
+#endif
+// Frame rows through a buffer descriptor: address = scalar base + scalar row offset + 32-bit lane offset, all three operands of
+// the load itself.  Written with pointers, hipcc makes every row's address a 64-bit per-lane value (v_lshl_add_u64 /
+// v_mad_i64_i32, several issue slots each), whichever way the sum is spelled (HISTORY 28, piece 3).  No range check is asked of
+// the descriptor (raw, 2 GiB from its base): lanes and rows outside the frame are predicated off as with pointers.
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const uint8_t* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, 0x7FFFFFFF, 0x00020000);
+}
+
 template <int B, int R, int I0, int N = StripCfg<B, R>::NP>
 __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const uint32_t* lds, uint32_t tile_off,
                                            const uint32_t (&colk)[4], const uint32_t (&colk_pos)[4], int y0, int H, uint32_t& bkey, int& bi,
@@ -372,6 +406,7 @@ __device__ __forceinline__ void strip_pass(const uint32_t (&c)[B][B / 4], const 
     strip_rows<B, R, I0, N>(acc, c, lds, tile_off, std::make_integer_sequence<int, ROWS>{});
 #pragma unroll
     for (int ii = 0; ii < N; ++ii) asm volatile("" : "+v"(acc[ii]));
+    if constexpr ((kSadPrice & 1) != 0) return;                          // timing-only: the sums stay (pinned), the keys go
     if constexpr (kSadColKeys != 0 && (C::RANK_KEY || C::COMPACT_KEY)) {
         // per-column keys: SAD << 16 | low, low = dy^2 << 1 | (dy > 0) (RANK_KEY) or dy^2 << 6 | dy index (COMPACT_KEY): the order
         // (SAD, dy^2, dy) inside a column.  A dy clipped by the frame (uniform over the strip) takes the all-ones constant, which
@@ -500,7 +535,31 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
 
     // ---- this lane's block of the current frame -> VGPRs (lanes of one block read the same lines)
     uint32_t c[B][C::BW];
-    {
+    if constexpr ((kSadPrice & 8) != 0) {
+#pragma unroll
+        for (int y = 0; y < B; ++y)
+#pragma unroll
+            for (int q = 0; q < C::BW; ++q) asm volatile("" : "=v"(c[y][q]));       // timing-only: whatever the registers hold
+    } else if constexpr (OFPS_SAD_BUFFER_LOADS != 0) {
+        const __amdgpu_buffer_rsrc_t crs = frame_rsrc(cur + (size_t)y0 * p.stride);
+        const uint32_t coff = (uint32_t)((blk_on ? bx : p.nbx - 1) * B);
+#pragma unroll
+        for (int y = 0; y < B; ++y) {
+            if constexpr (C::BW % 4 == 0) {
+#pragma unroll
+                for (int q4 = 0; q4 < C::BW; q4 += 4) {
+                    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(crs, coff + 4 * q4, y * p.stride, 0);
+                    c[y][q4 + 0] = v.x; c[y][q4 + 1] = v.y; c[y][q4 + 2] = v.z; c[y][q4 + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int q2 = 0; q2 < C::BW; q2 += 2) {
+                    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(crs, coff + 4 * q2, y * p.stride, 0);
+                    c[y][q2 + 0] = v.x; c[y][q2 + 1] = v.y;
+                }
+            }
+        }
+    } else {
         const int bxc = blk_on ? bx : p.nbx - 1;
         const uint8_t* cp = cur + (size_t)y0 * p.stride + bxc * B;
 #pragma unroll
@@ -525,25 +584,46 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
     // the rows LR at a time: its source pointer advances by a row pitch, its LDS destination is base + immediate -- no
     // per-granule division, no per-granule address arithmetic (the flat index / TILE_WG form cost ~20 VALU operations per
     // step, 140-160 per strip: 2 % of a strip that is otherwise packed SADs; profiles/r05/sad_colkeys.txt)
-    {
+    if constexpr ((kSadPrice & 8) == 0) {
         constexpr int LR = 64 / C::TILE_WG;                            // window rows per step (TILE_WG <= 64 lanes)
         constexpr int STEPS = (C::TILE_H + LR - 1) / LR;
         const int tx0 = bx0 * B - R, ty0 = y0 - R;
         const int sr = lane / C::TILE_WG, sc = lane - sr * C::TILE_WG;
         const int gx = tx0 + C::GRAN * sc;
         const bool lane_on = sr < LR && gx >= 0 && gx < p.W;
-        const uint8_t* src = prev + (ptrdiff_t)(ty0 + sr) * p.stride + gx;       // dereferenced only for rows inside the frame
-        uint32_t* dst = tile + sr * C::SW + C::GDW * sc;
+        if constexpr (C::LANE_LINEAR && OFPS_SAD_DIRECT_STAGE != 0) {
+            // Lane-linear window (StripCfg): the granules go from memory straight into LDS, no VGPRs and no ds_write between.  The
+            // loads of all steps are in flight together and are waited for once, where the walk has to wait for its window anyway
+            // (and for the current block, issued before them); register staging waited for each step's data before its ds_write.
+            // The LDS destination is wave-uniform (the step's first row) + 16 x lane, added by the hardware; a lane outside the
+            // frame is off in exec and writes nothing, so the cells it would have written stay unwritten as with register staging.
+            // Source: the window's origin in the descriptor (it may lie before the frame; no lane that is on reads there), the
+            // step's rows as the scalar offset, the lane's (row, granule) as its 32-bit offset.
+            using lptr_t = __attribute__((address_space(3))) void*;
+            const __amdgpu_buffer_rsrc_t wrs = frame_rsrc(prev + (ptrdiff_t)ty0 * p.stride + tx0);
+            const uint32_t loff = (uint32_t)(sr * p.stride + C::GRAN * sc);
 #pragma unroll
-        for (int it = 0; it < STEPS; ++it) {
-            const int row = sr + it * LR;
-            const bool row_in_tile = (it + 1) * LR <= C::TILE_H || row < C::TILE_H;
-            if (lane_on && row_in_tile && (unsigned)(ty0 + row) < (unsigned)p.H) {
-                const uint8_t* sp = src + (ptrdiff_t)(it * LR) * p.stride;
-                uint32_t* dp = dst + it * LR * C::SW;
-                if constexpr (C::GRAN == 16) *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
-                else if constexpr (C::GRAN == 8) *reinterpret_cast<uint2*>(dp) = *reinterpret_cast<const uint2*>(sp);
-                else *dp = *reinterpret_cast<const uint32_t*>(sp);
+            for (int it = 0; it < STEPS; ++it) {
+                const int row = sr + it * LR;
+                const bool row_in_tile = (it + 1) * LR <= C::TILE_H || row < C::TILE_H;
+                if (lane_on && row_in_tile && (unsigned)(ty0 + row) < (unsigned)p.H)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lptr_t)(tile + it * LR * C::SW), 16, loff, it * LR * p.stride, 0, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+            const uint8_t* src = prev + (ptrdiff_t)(ty0 + sr) * p.stride + gx;       // dereferenced only for rows inside the frame
+            uint32_t* dst = tile + sr * C::SW + C::GDW * sc;
+#pragma unroll
+            for (int it = 0; it < STEPS; ++it) {
+                const int row = sr + it * LR;
+                const bool row_in_tile = (it + 1) * LR <= C::TILE_H || row < C::TILE_H;
+                if (lane_on && row_in_tile && (unsigned)(ty0 + row) < (unsigned)p.H) {
+                    const uint8_t* sp = src + (ptrdiff_t)(it * LR) * p.stride;
+                    uint32_t* dp = dst + it * LR * C::SW;
+                    if constexpr (C::GRAN == 16) *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+                    else if constexpr (C::GRAN == 8) *reinterpret_cast<uint2*>(dp) = *reinterpret_cast<const uint2*>(sp);
+                    else *dp = *reinterpret_cast<const uint32_t*>(sp);
+                }
             }
         }
     }
@@ -585,7 +665,7 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
     else
         strip_clipped<B, R>(c, tiles, lane_off, colk, colk_pos, y0, p.H, ilo, ihi, bkey, bi, colmin, amin,
                             std::make_integer_sequence<int, StripClip<B, R>::NCH>{});
-    if constexpr (kSadColKeys != 0 && (C::RANK_KEY || C::COMPACT_KEY)) {
+    if constexpr ((kSadPrice & 4) == 0 && kSadColKeys != 0 && (C::RANK_KEY || C::COMPACT_KEY)) {
         // column minima -> the lane key of the product layout (SAD << 16 | d2 << KSHIFT | code / dy index), once per strip
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -606,7 +686,7 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
     }
     // decode (d2, dy) -> dx; build the cross-lane key (SAD, d2, dy, dx)
     unsigned long long best = ~0ull;
-    if (bkey != 0xFFFFFFFFu) {
+    if ((kSadPrice & 4) == 0 && bkey != 0xFFFFFFFFu) {
         const uint32_t d2 = (bkey & 0xFFFFu) >> C::KSHIFT;
         int dx = dx0, dy;
         if constexpr (C::RANK_KEY) {
@@ -640,7 +720,33 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
         // (lane-dependent) rows are read again -- ERL short loads that hit the cache the block was just read through
         const int yl = g * C::ERL;
         uint32_t cl[C::ERL][C::BW];
-        {
+        if constexpr ((kSadPrice & 2) != 0) {
+#pragma unroll
+            for (int r = 0; r < C::ERL; ++r)
+#pragma unroll
+                for (int q = 0; q < C::BW; ++q) cl[r][q] = c[r][q];           // timing-only: no second read of the block rows
+        } else if constexpr (OFPS_SAD_BUFFER_LOADS != 0) {
+            const __amdgpu_buffer_rsrc_t crs = frame_rsrc(cur + (size_t)y0 * p.stride);
+            const uint32_t coff = (uint32_t)((blk_on ? bx : p.nbx - 1) * B);
+#pragma unroll
+            for (int r = 0; r < C::ERL; ++r) {
+                const int y = (C::NG * C::ERL > B && yl + r > B - 1) ? B - 1 : yl + r;     // idle lanes re-read the last row
+                const uint32_t roff = coff + (uint32_t)(y * p.stride);
+                if constexpr (C::BW % 4 == 0) {
+#pragma unroll
+                    for (int q4 = 0; q4 < C::BW; q4 += 4) {
+                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(crs, roff + 4 * q4, 0, 0);
+                        cl[r][q4 + 0] = v.x; cl[r][q4 + 1] = v.y; cl[r][q4 + 2] = v.z; cl[r][q4 + 3] = v.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int q2 = 0; q2 < C::BW; q2 += 2) {
+                        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(crs, roff + 4 * q2, 0, 0);
+                        cl[r][q2 + 0] = v.x; cl[r][q2 + 1] = v.y;
+                    }
+                }
+            }
+        } else {
             const int bxc = blk_on ? bx : p.nbx - 1;
             const uint8_t* cp = cur + (size_t)y0 * p.stride + bxc * B;
 #pragma unroll
@@ -700,15 +806,19 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
 #pragma unroll
             for (int q = 0; q < C::BW; ++q) elast = __builtin_amdgcn_sad_u8(ecol[(2 * R + y) * C::SW + q], cl[r][q], elast);
         }
-        if constexpr (C::NG * C::ERL > B) elast = yl < B ? elast : 0u;
+        if constexpr ((kSadPrice & 2) != 0) {
+            asm volatile("" : "+v"(elast));                                   // timing-only: the sums stay, the rest of the pass goes
+        } else {
+            if constexpr (C::NG * C::ERL > B) elast = yl < B ? elast : 0u;
 #pragma unroll
-        for (int m = 1; m < C::NG; m <<= 1) elast += (uint32_t)__shfl_xor((int)elast, m, 64);
+            for (int m = 1; m < C::NG; m <<= 1) elast += (uint32_t)__shfl_xor((int)elast, m, 64);
+        }
     }
 
     // ---- candidates of the dx = +R pass: a 32-bit key (SAD << 16 | d2) and the dy index over the lane's chunk in ascending dy with a
     // strict <, then dy = +R (the same key in every lane of the block: a minimum does not mind), one 64-bit key at the end.
     // Equal (SAD, d2) inside the column means dy = -+|dy|, and the walk keeps the first: the spec's order.
-    {
+    if constexpr ((kSadPrice & 2) == 0) {
         const bool xok = blk_on && bx * B + R + B <= p.W;
         const int chi = ihi < 2 * R - 1 ? ihi : 2 * R - 1;                  // the chunks stop below dy = +R
         uint32_t ek = 0xFFFFFFFFu;
@@ -730,6 +840,12 @@ __device__ __forceinline__ void strip_body(const SadParams& p, int strips_per_ro
         }
         const unsigned long long k64 = ((unsigned long long)ek << 32) | (unsigned long long)(uint32_t)((ei << 8) | (2 * R));
         best = (xok && ek != 0xFFFFFFFFu && k64 < best) ? k64 : best;
+    }
+    if constexpr ((kSadPrice & 4) != 0) {
+        // timing-only: one store that depends on everything kept above, so that nothing before it is dead code
+        if (lane == 0)
+            p.out_entries[((size_t)pair * p.nby + by) * p.nbx + bx].x = __uint_as_float((uint32_t)best ^ (uint32_t)(best >> 32) ^ bkey ^ elast);
+        return;
     }
     // ---- min over the NG lanes of each block (aligned power-of-two segments: xor butterfly)
 #pragma unroll

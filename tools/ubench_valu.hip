@@ -4,6 +4,8 @@
 //   pk:    v_pk_fma_f32, eight independent accumulator pairs (two FMAs per lane and instruction)
 //   fmix:  v_fma_mix_f32 (f16 / f32 sources mixed, f32 result), alone and as 5 of the 7 instructions of the LK tap
 //   mix:   the LK tap (sub, fmac, sub, fmac, sub, fmac, fmac through one tmp), two taps interleaved on two tmps
+//   int:   the 32-bit integer forms an argmin key build can take (HISTORY 41: shift/mask-and-or, bit-field insert, 24-bit mad, SDWA move
+//          into a preserved half) beside v_add_u32 / v_min_u32 / v_perm_b32, and the 64-bit address forms (v_lshl_add_u64, v_mad_i64_i32)
 // at 1..8 waves per SIMD.  build: hipcc --offload-arch=gfx950 -O3 tools/ubench_valu.hip -o tools/ubench_valu ; run on the GPU box.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -45,6 +47,37 @@ __global__ __launch_bounds__(256) void k(float* out, float seed) {
             asm volatile(TAPM("%0", "%1", "%2") TAPM("%3", "%4", "%5") TAPM("%0", "%2", "%1") TAPM("%3", "%5", "%4") TAPM("%0", "%1", "%2")
                          TAPM("%3", "%4", "%5") TAPM("%0", "%2", "%1") TAPM("%3", "%5", "%4") TAPM("%0", "%1", "%2")
                          : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(t0), "+v"(t1) : "v"(b), "v"(c));
+        } else if constexpr (MODE >= 10 && MODE < 30) {   // 64 = 8 x 8 independent integer operations, one form per mode
+#define I8(OP) R8(OP("%0") OP("%1") OP("%2") OP("%3") OP("%4") OP("%5") OP("%6") OP("%7"))
+#define IOPS : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b), "v"(c)
+#define OP_ADD(D) "v_add_u32 " D ", " D ", %8\n\t"
+#define OP_MIN(D) "v_min_u32 " D ", " D ", %8\n\t"
+#define OP_PERM(D) "v_perm_b32 " D ", " D ", %8, %9\n\t"
+#define OP_LSHL_OR(D) "v_lshl_or_b32 " D ", " D ", 16, %8\n\t"
+#define OP_AND_OR(D) "v_and_or_b32 " D ", " D ", %8, %9\n\t"
+#define OP_LSHL_ADD(D) "v_lshl_add_u32 " D ", " D ", 16, %8\n\t"
+#define OP_BFI(D) "v_bfi_b32 " D ", %8, " D ", %9\n\t"
+#define OP_MAD24(D) "v_mad_u32_u24 " D ", " D ", %8, %9\n\t"
+#define OP_SDWA(D) "v_mov_b32_sdwa " D ", %8 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0\n\t"
+#define OP_OR_SDWA(D) "v_or_b32_sdwa " D ", %8, %9 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_0\n\t"
+            if constexpr (MODE == 10) asm volatile(I8(OP_ADD) IOPS);
+            else if constexpr (MODE == 11) asm volatile(I8(OP_MIN) IOPS);
+            else if constexpr (MODE == 12) asm volatile(I8(OP_PERM) IOPS);
+            else if constexpr (MODE == 13) asm volatile(I8(OP_LSHL_OR) IOPS);
+            else if constexpr (MODE == 14) asm volatile(I8(OP_AND_OR) IOPS);
+            else if constexpr (MODE == 15) asm volatile(I8(OP_LSHL_ADD) IOPS);
+            else if constexpr (MODE == 16) asm volatile(I8(OP_BFI) IOPS);
+            else if constexpr (MODE == 17) asm volatile(I8(OP_MAD24) IOPS);
+            else if constexpr (MODE == 18) asm volatile(I8(OP_SDWA) IOPS);
+            else if constexpr (MODE == 19) asm volatile(I8(OP_OR_SDWA) IOPS);
+            else if constexpr (MODE == 20)       // 64-bit shift-add, 4 independent pairs
+                asm volatile(R8(R8("v_lshl_add_u64 v[100:101], v[100:101], 1, v[108:109]\n\tv_lshl_add_u64 v[102:103], v[102:103], 1, v[108:109]\n\t"
+                                   "v_lshl_add_u64 v[104:105], v[104:105], 1, v[108:109]\n\tv_lshl_add_u64 v[106:107], v[106:107], 1, v[108:109]\n\t"))
+                             ::: "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109");
+            else                                 // 32 x 32 -> 64-bit multiply-add, 4 independent pairs
+                asm volatile(R8(R8("v_mad_i64_i32 v[100:101], vcc, v108, v109, v[100:101]\n\tv_mad_i64_i32 v[102:103], vcc, v108, v109, v[102:103]\n\t"
+                                   "v_mad_i64_i32 v[104:105], vcc, v108, v109, v[104:105]\n\tv_mad_i64_i32 v[106:107], vcc, v108, v109, v[106:107]\n\t"))
+                             ::: "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "vcc");
         } else if constexpr (MODE == 4) {    // the LK tap, 9 taps through one tmp: 63 instructions
 #define TAP(L0, L1, T) "v_sub_f32 %8, " L1 ", " L0 "\n\tv_fmac_f32 " L0 ", %10, %8\n\tv_sub_f32 %8, " L0 ", " T "\n\tv_fmac_f32 " T ", %11, %8\n\t" \
                        "v_sub_f32 %8, %10, " T "\n\tv_fmac_f32 %6, %11, %8\n\tv_fmac_f32 %7, %10, %8\n\t"
@@ -94,5 +127,17 @@ int main() {
     run<5>("LK tap, two pixels interleaved, two tmps", 56, d, p.multiProcessorCount);
     run<6>("v_fma_mix_f32, 8 independent accumulators", 64, d, p.multiProcessorCount);
     run<7>("LK tap x 9 with 5 of 7 as v_fma_mix_f32", 63, d, p.multiProcessorCount);
+    run<10>("v_add_u32, 8 independent", 64, d, p.multiProcessorCount);
+    run<11>("v_min_u32, 8 independent", 64, d, p.multiProcessorCount);
+    run<12>("v_perm_b32, 8 independent", 64, d, p.multiProcessorCount);
+    run<13>("v_lshl_or_b32, 8 independent", 64, d, p.multiProcessorCount);
+    run<14>("v_and_or_b32, 8 independent", 64, d, p.multiProcessorCount);
+    run<15>("v_lshl_add_u32, 8 independent", 64, d, p.multiProcessorCount);
+    run<16>("v_bfi_b32, 8 independent", 64, d, p.multiProcessorCount);
+    run<17>("v_mad_u32_u24, 8 independent", 64, d, p.multiProcessorCount);
+    run<18>("v_mov_b32_sdwa into a preserved high half", 64, d, p.multiProcessorCount);
+    run<19>("v_or_b32_sdwa into a preserved high half", 64, d, p.multiProcessorCount);
+    run<20>("v_lshl_add_u64, 4 independent pairs", 256, d, p.multiProcessorCount);
+    run<21>("v_mad_i64_i32, 4 independent pairs", 256, d, p.multiProcessorCount);
     return 0;
 }
