@@ -709,7 +709,8 @@ int ofps_hip_flow_cache_hits(ofps_hip_ctx* ctx, uint64_t* count);
  *   max_residual are the context's.  A point outside the frame: OFPS_HIP_EINVAL in the host form, status 3 in the _dev form (no access
  *   out of bounds).
  * ofps_hip_klt_flow[_dev]: the pair -> records (capacity: the slot count), their count (_dev: one uint32 in device memory) and, unless
- *   NULL, the raw slots: int32 (x, y, score, dqx, dqy, status) per slot, (-1, -1, 0, 0, 0, 1) for a cell without a feature.
+ *   NULL, the raw slots: int32 (x, y, score, dqx, dqy, status) per slot, (-1, -1, 0, 0, 0, 1) for a cell without a feature.  Statuses: 0 kept,
+ *   1 no feature, 2 flat, 3 left the frame, 4 residual loss, 5 did not return (N3f), 6 intra and 7 cut (N3i); 4 to 7 report their dq.
  * The _dev forms enqueue on the context's stream and synchronise nothing.  OFPS_HIP_FLOW_SPARSE (above) runs the same chain inside the
  * dense decoders' stream and fused forms. */
 int ofps_hip_set_klt(ofps_hip_ctx* ctx, int cell, int score_radius, int min_score, int min_eig, int max_residual);
@@ -915,6 +916,57 @@ int ofps_hip_klt_flow_batch_from(ofps_hip_ctx* ctx, const uint8_t* frames, int n
 int ofps_hip_klt_flow_batch_from_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_frames, int W, int H, int stride, size_t frame_pitch,
                                      int ref_mode, int levels, int radius, int iters, void* d_out_entries, void* d_out_counts,
                                      void* d_out_slots /* or NULL */, const void* d_prev_slots /* or NULL */);
+
+/* ---- N3i: hip_klt's intra test and scene-cut rule: a track that found nothing that belongs to it is dropped (csrc/klt_intra.hip) ----
+ * Build-defined, off by default; hip_klt's counterpart of hip_sad's intra test (N1i).  A pyramidal tracker started on content that has no
+ * counterpart in the other frame -- across a scene cut, on uncovered background, on an object that appears, beyond the pyramid's reach --
+ * still converges somewhere inside its reach and is reported with status 0 and full weight; N3's only guard is max_residual, an absolute
+ * grey-level limit that has to be tuned to the texture.  This test compares the residual the track reports with the window's own activity.
+ * All arithmetic is integer.  It applies to a pair tracked with the context's KLT settings and the call's L, w, K; n = 2w + 1, N = n * n.
+ * Activity A(k) of a slot with feature (x, y): the n x n window of the RAW level-0 previous frame centred on (x, y), pixel indices clamped
+ *   into the frame as N3's sampling clamps them; S = sum p, m = (S + N / 2) / N (integer division), A = sum |p - m|: a uint32, at most
+ *   225 * 255.  A is 1/256 of sum |Ic - 256 m| over the level-0 template's interior, so 256 A is in res's unit.  The key-frame form
+ *   (ref_mode 1) takes the window from the key frame.
+ * Residual res(k): the forward pass's residual exactly as the slot reports it: with N3m on the residual around the window's mean difference,
+ *   with N3f on the forward pass's.
+ * Candidates: cand(k) iff the slot's final status is 0, 4 or 5, the statuses that report a residual.
+ * Intra: ratio q in [1, 255], in sixteenths; intra(k) iff cand(k) and 16 * res(k) >= q * 256 * A(k), compared in signed 64-bit arithmetic;
+ *   equality is intra, so A = 0 with res = 0 is intra.
+ * Status 6, "intra": a slot with status 0 that is intra gets status 6; it reports its dq, as status 4 does, and yields no record.  Statuses 4
+ *   and 5 stay as they are (earlier tests win).  Kept records are, bit for bit, the records of the same slots with the test off.
+ * Scene cut: P in [0, 100] percent; n_cand and n_intra are counted over the pair, the candidates of status 4 and 5 included.  With P > 0 the
+ *   pair is a CUT iff 100 * n_intra >= P * n_cand (so n_cand = 0 is a cut): it yields zero records and every status 0 that is left becomes
+ *   status 7, "cut".  P has no effect while q = 0; setting it then is accepted.
+ * Prediction (N3p, N3pb) needs no new rule: the predictor reads status 0 only, and statuses 6 and 7 stand in the raw slots before the next
+ *   pair's or item's track launch reads them: after a cut every guess is (0, 0).  In a chained batch item k's verdict and cut are enqueued
+ *   behind item k's track launch and in front of item k + 1's.
+ * Settings of the context: intra q in [0, 255], 0 = off (ofps_hip_set_klt_intra; option and environment variable OFPS_HIP_KLT_INTRA) and cut P
+ *   in [0, 100], 0 = off (ofps_hip_set_klt_cut; OFPS_HIP_KLT_CUT).  A value outside its range is OFPS_HIP_EINVAL and the setting stays as it
+ *   was.  With q = 0 every entry point enqueues the launches, scratch and bytes it enqueues without this row.  With q > 0 the test runs in
+ *   launches of its own between the track launch and the compaction: one verdict launch (a chained batch: one per item) and, with P > 0, one
+ *   cut launch behind it; the track kernels are the ones that run without it.  No host synchronisation is added.
+ * Every form that runs the decoder follows the two settings, with no new argument: ofps_hip_klt_flow[_dev] and _flow_from[_dev],
+ *   _flow_batch[_dev] and _flow_batch_from[_dev] in both ref_modes, OFPS_HIP_FLOW_SPARSE in the dense decoders' stream and fused forms (a cut
+ *   frame has n_vectors 0: the estimator answers the identity and the detector no motion, as for any frame without records),
+ *   ofps_hip_push_frames_async with the batch decoder at KLT, and the multi-device workers, whose contexts read the two variables at
+ *   ofps_hip_init.  ofps_hip_klt_track*[_dev] are stages and never apply the test.
+ * ofps_hip_klt_activity[_dev]: one frame, n points as int32 (x, y), radius w in [1, 7] -> uint32 A per point.  A point outside the frame is
+ *   OFPS_HIP_EINVAL in the host form and A = 0 in the _dev form, with no access out of bounds.
+ * ofps_hip_klt_intra[_dev]: verdict and cut on caller-held data: n quads (dqx, dqy, res, status) as ofps_hip_klt_track writes them, n
+ *   activities, ratio in [1, 255], cut in [0, 100] -> int32 statuses (6 and 7 as above) and, unless NULL, [n_cand, n_intra] as uint32.
+ * Bit-exact against the restatement tests/indep_klt_intra.py.  Additive: OFPS_HIP_API_VERSION stays. */
+int ofps_hip_set_klt_intra(ofps_hip_ctx* ctx, int ratio);
+int ofps_hip_get_klt_intra(ofps_hip_ctx* ctx);               /* [0, 255]; OFPS_HIP_EINVAL for a NULL context */
+int ofps_hip_set_klt_cut(ofps_hip_ctx* ctx, int percent);
+int ofps_hip_get_klt_cut(ofps_hip_ctx* ctx);                 /* [0, 100]; OFPS_HIP_EINVAL for a NULL context */
+int ofps_hip_klt_activity(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride, const int32_t* points /* 2 * n */, size_t n, int radius,
+                          uint32_t* out_activity /* n */);
+int ofps_hip_klt_activity_dev(ofps_hip_ctx* ctx, const void* d_luma, int W, int H, int stride, const void* d_points, size_t n, int radius,
+                              void* d_out_activity);
+int ofps_hip_klt_intra(ofps_hip_ctx* ctx, const int32_t* quads /* 4 * n */, const uint32_t* activity /* n */, size_t n, int ratio, int cut,
+                       int32_t* out_status /* n */, uint32_t* out_counts /* 2, or NULL */);
+int ofps_hip_klt_intra_dev(ofps_hip_ctx* ctx, const void* d_quads, const void* d_activity, size_t n, int ratio, int cut, void* d_out_status,
+                           void* d_out_counts /* or NULL */);
 
 /* ---- A1-A4: MotionFieldDensifier ---- */
 int ofps_hip_densify(ofps_hip_ctx* ctx, const float* entries, size_t n, int w, int h,

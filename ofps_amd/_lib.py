@@ -153,6 +153,14 @@ PROTOTYPES = {
                                                _u32p, _i32p, _i32p]),
     "ofps_hip_klt_flow_batch_from_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
                                                    _vp, _vp, _vp]),
+    "ofps_hip_set_klt_intra": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_klt_intra": (C.c_int, [_ctx]),
+    "ofps_hip_set_klt_cut": (C.c_int, [_ctx, C.c_int]),
+    "ofps_hip_get_klt_cut": (C.c_int, [_ctx]),
+    "ofps_hip_klt_activity": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, _i32p, C.c_size_t, C.c_int, _u32p]),
+    "ofps_hip_klt_activity_dev": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int, _vp]),
+    "ofps_hip_klt_intra": (C.c_int, [_ctx, _i32p, _u32p, C.c_size_t, C.c_int, C.c_int, _i32p, _u32p]),
+    "ofps_hip_klt_intra_dev": (C.c_int, [_ctx, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp]),
     "ofps_hip_set_batch_decoder": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ofps_hip_get_batch_decoder": (C.c_int, [_ctx, _i32p, _i32p, _i32p, _i32p]),
     "ofps_hip_densify": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_int, C.c_int, _f32p, _u32p]),

@@ -248,6 +248,12 @@ struct ofps_hip_ctx {
         // OFPS_HIP_KLT_BATCH_PREDICTION / ofps_hip_set_klt_batch_prediction: 1 = with klt_prediction 1 as well, the batch form and the batched stream
         // (not the ofps_hip_multi_* workers) chain their items: each starts from the item before (include/ofps_hip.h N3pb)
         int klt_batch_prediction = 0;
+        // OFPS_HIP_KLT_INTRA / ofps_hip_set_klt_intra: 0 off, q in [1, 255] (sixteenths) a kept track whose residual reaches q/16 of its window's
+        // activity in the raw previous frame becomes status 6 and yields no record (klt_intra.hip, N3i)
+        int klt_intra = 0;
+        // OFPS_HIP_KLT_CUT / ofps_hip_set_klt_cut: 0 off, P in [1, 100] a pair with at least P percent of its candidates intra yields no record
+        // (status 7); no effect while klt_intra is 0 (klt_intra.hip, N3i)
+        int klt_cut = 0;
         // OFPS_HIP_BATCH_DECODER / ofps_hip_set_batch_decoder: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers'
         // pushes) search with hip_sad, 1 they run hip_klt with these levels, window radius and iterations (include/ofps_hip.h N3b)
         int batch_decoder = 0, klt_levels = 4, klt_radius = 7, klt_iters = 10;
@@ -410,6 +416,23 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
 // into d_slots; neither it nor d_prev_slots may share a byte with d_slots or with each other
 int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
                           int* d_slots, bool chained = false, const int* d_prev_slots = nullptr, int* d_last_slots = nullptr);
+// klt_intra.hip (include/ofps_hip.h N3i): hip_klt's intra test and scene-cut rule, between the track launch and the compaction.  What the two
+// call sites hand over: the level-0 previous frames (pitch 0: one key frame for every item), the feature triples (pitch 0: one set), the
+// tracks' quads, the keep flags the track launch wrote and the items' counters [candidates, intra], all but the frames and triples item-major,
+// `ns` entries per item
+constexpr int kKltIntraMax = 255, kKltCutMax = 100;
+struct KltIntraCall {
+    const uint8_t* frames; size_t frame_pitch;
+    int W, H, stride, w, ns;
+    const int* feat; size_t feat_pitch;          // 3 ints per slot; feat_pitch in ints
+    const int* quads;                            // 4 ints per slot
+    uint8_t* flags;
+    uint32_t* counts;                            // 2 per item, zero before the first verdict launch
+    int ratio, cut;
+};
+// verdict, and with c.cut > 0 the cut, for the items item0 .. item0 + items - 1, enqueued on ctx->stream.  d_slots (optional): the raw slots,
+// 6 ints per slot, indexed as the flags are; statuses 6 and 7 are written there
+int klt_intra_device(ofps_hip_ctx* ctx, const KltIntraCall& c, int item0, int items, int* d_slots);
 // sad_prefilter.hip (include/ofps_hip.h N1m): F = clamp(v - box mean + 128), radius in [1, kSadPrefilterMax]
 constexpr int kSadPrefilterMax = 16;
 int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,

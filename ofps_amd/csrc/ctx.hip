@@ -163,6 +163,12 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_KLT_BATCH_PREDICTION")) {
         if (!unset && strcmp(value, "0") && strcmp(value, "1")) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' is not 0|1", name, value);
         o.klt_batch_prediction = unset ? dflt.klt_batch_prediction : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_INTRA")) {
+        if (!unset && (strspn(value, "0123456789") != strlen(value) || strlen(value) > 3 || iv > kKltIntraMax)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' outside [0, %d]", name, value, kKltIntraMax);
+        o.klt_intra = unset ? dflt.klt_intra : iv;
+    } else if (!strcmp(name, "OFPS_HIP_KLT_CUT")) {
+        if (!unset && (strspn(value, "0123456789") != strlen(value) || strlen(value) > 3 || iv > kKltCutMax)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: '%s' outside [0, %d]", name, value, kKltCutMax);
+        o.klt_cut = unset ? dflt.klt_cut : iv;
     } else if (!strcmp(name, "OFPS_HIP_MULTI_RCCL")) {
         o.multi_rccl = unset ? 0 : (iv != 0);
     } else if (!strcmp(name, "OFPS_HIP_ALMEIDA_TEST_FAULT") || !strcmp(name, "OFPS_HIP_LK_TEST_FALL") ||
@@ -191,7 +197,7 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS", "OFPS_HIP_SAD_SPLIT",
     "OFPS_HIP_KLT_CELL", "OFPS_HIP_KLT_SCORE_RADIUS", "OFPS_HIP_KLT_MIN_SCORE", "OFPS_HIP_KLT_MIN_EIG", "OFPS_HIP_KLT_MAX_RESIDUAL",
     "OFPS_HIP_BATCH_DECODER", "OFPS_HIP_KLT_LEVELS", "OFPS_HIP_KLT_RADIUS", "OFPS_HIP_KLT_ITERS", "OFPS_HIP_KLT_MEAN_REMOVAL",
-    "OFPS_HIP_KLT_FB", "OFPS_HIP_KLT_PREDICTION", "OFPS_HIP_KLT_BATCH_PREDICTION"};
+    "OFPS_HIP_KLT_FB", "OFPS_HIP_KLT_PREDICTION", "OFPS_HIP_KLT_BATCH_PREDICTION", "OFPS_HIP_KLT_INTRA", "OFPS_HIP_KLT_CUT"};
 
 }  // namespace ofps
 

@@ -776,7 +776,9 @@ int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
 // item-major: the caller's array, or S_KLT_WORK's), the last item into d_last_slots if that is given; item k + 1 reads them there.  Item 0 reads
 // d_prev_slots (null: zero guesses).  No launch reads the array it writes: the items' slots are ns apart, and the callers keep d_prev_slots
 // and d_last_slots apart from each other and from the rest
-int klt_track_batch_pred_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b, int pairs, int nx, int ny, const int* d_prev_slots, int* d_last_slots) {
+// intra (N3i, optional): item k's verdict and cut are enqueued behind its track launch
+int klt_track_batch_pred_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b, int pairs, int nx, int ny, const int* d_prev_slots, int* d_last_slots,
+                                const KltIntraCall* intra = nullptr) {
     const int ns = b.slots_per_item;
     if (ns <= 0 || pairs <= 0) return OFPS_HIP_OK;
     const dim3 grid((unsigned)((ns + kKltTrackWaves - 1) / kKltTrackWaves));
@@ -798,6 +800,10 @@ int klt_track_batch_pred_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b,
         } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_pred_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
         else hipLaunchKernelGGL(klt_track_batch_pred_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
         OFPS_HIP_TRY(ctx, hipGetLastError());
+        if (intra) {                                          // N3i: statuses 6 and 7 stand in `mine` before the next launch's predictor reads it
+            const int rc = klt_intra_device(ctx, *intra, k, 1, f.b.t.out_slots);
+            if (rc != OFPS_HIP_OK) return rc;
+        }
         prev = mine;
     }
     return OFPS_HIP_OK;
@@ -827,7 +833,10 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
     const KltSettings s = klt_settings(ctx);
     const size_t ns = klt_slots(W, H, s.cell);
     const size_t o_raw = pad16(ns * 3 * sizeof(int)), o_flag = o_raw + ns * sizeof(float4);
-    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_flag + pad16(ns)));
+    // N3i (intra ratio above 0): [the tracks' quads, 4 i32 per slot][candidate and intra counters, 2 x u32] behind the flags
+    const int intra = ctx->opt.klt_intra;
+    const size_t o_quad = o_flag + pad16(ns), o_cnt = o_quad + ns * 4 * sizeof(int);
+    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, intra > 0 ? o_cnt + 16 : o_quad));
     if (!work) return OFPS_HIP_ENOMEM;
     auto* d_feat = reinterpret_cast<int*>(work);
     auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
@@ -839,11 +848,20 @@ int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_c
     if (rc != OFPS_HIP_OK) return rc;
     p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
     p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)ns;
-    p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
+    p.out_quad = intra > 0 ? reinterpret_cast<int*>(work + o_quad) : nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
     // the predictor runs inside the track kernel, in front of the wave's first level: no launch and no array of guesses between the two
     if (d_prev_slots) rc = klt_track_pred_launch(ctx, p, nullptr, d_prev_slots, (W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell);
     else rc = klt_track_launch(ctx, p);
     if (rc != OFPS_HIP_OK) return rc;
+    if (intra > 0) {
+        // N3i: the verdict, and the cut, rewrite flags and statuses in front of the compaction -- and of the next pair's track launch, which
+        // reads d_slots on this stream
+        auto* d_cnt = reinterpret_cast<uint32_t*>(work + o_cnt);
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
+        const KltIntraCall c{d_prev, 0, W, H, stride, radius, (int)ns, d_feat, 0, p.out_quad, d_flag, d_cnt, intra, ctx->opt.klt_cut};
+        rc = klt_intra_device(ctx, c, 0, 1, d_slots);
+        if (rc != OFPS_HIP_OK) return rc;
+    }
     return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_count) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_count);
 }
 
@@ -863,7 +881,11 @@ int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
     const int scored = f.prev_pitch ? pairs : 1;              // the distinct prev frames
     const size_t o_raw = pad16((size_t)scored * ns * 3 * sizeof(int)), o_flag = o_raw + total * sizeof(float4);
     const size_t o_wslots = o_flag + pad16(total);            // chained, and the caller takes no slots: they lie here
-    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)));
+    // N3i (intra ratio above 0): [the tracks' quads, 4 i32 per slot of the batch][candidate and intra counters, 2 x u32 per item] behind them
+    const int intra = ctx->opt.klt_intra;
+    const size_t o_quad = pad16(o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)), o_cnt = o_quad + total * 4 * sizeof(int);
+    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, intra > 0 ? o_cnt + pad16((size_t)pairs * 2 * sizeof(uint32_t))
+                                                                        : o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)));
     if (!work) return OFPS_HIP_ENOMEM;
     auto* d_feat = reinterpret_cast<int*>(work);
     auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
@@ -877,10 +899,22 @@ int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
     KltTrackParams& p = b.t;
     p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
     p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)total;
-    p.out_quad = nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
+    p.out_quad = intra > 0 ? reinterpret_cast<int*>(work + o_quad) : nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
     b.slots_per_item = (int)ns; b.shared_features = f.prev_pitch ? 0 : 1;
-    if (chained) rc = klt_track_batch_pred_launch(ctx, b, pairs, (f.W + s.cell - 1) / s.cell, (f.H + s.cell - 1) / s.cell, d_prev_slots, d_last_slots);
-    else rc = klt_track_batch_launch(ctx, b);
+    KltIntraCall ic{};
+    if (intra > 0) {
+        auto* d_cnt = reinterpret_cast<uint32_t*>(work + o_cnt);
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)pairs * 2 * sizeof(uint32_t), ctx->stream));
+        ic = KltIntraCall{f.prev_base, f.prev_pitch, f.W, f.H, f.stride, radius, (int)ns, d_feat, f.prev_pitch ? ns * 3 : 0, p.out_quad, d_flag, d_cnt,
+                          intra, ctx->opt.klt_cut};
+    }
+    // N3i in a chained batch: item k's verdict and cut go behind item k's track launch and in front of item k + 1's, which reads the statuses
+    if (chained) rc = klt_track_batch_pred_launch(ctx, b, pairs, (f.W + s.cell - 1) / s.cell, (f.H + s.cell - 1) / s.cell, d_prev_slots, d_last_slots,
+                                                  intra > 0 ? &ic : nullptr);
+    else {
+        rc = klt_track_batch_launch(ctx, b);
+        if (rc == OFPS_HIP_OK && intra > 0) rc = klt_intra_device(ctx, ic, 0, pairs, d_slots);
+    }
     if (rc != OFPS_HIP_OK) return rc;
     // one workgroup per item is right for a batch; ONE pair through it would scan a 4K frame's 129,600 slots on one compute unit (measured:
     // 5 % of the pair's time), so a batch of one pair keeps the one-pair form's compactions, as SadFilter::finish does (sad_gate.hip)

@@ -7,13 +7,15 @@
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
-//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N] [--klt-predict [--klt-batch-predict]]]
+//   stream-bench <w> <h> <frames> [sync|ahead|batch <n>|multi <n> [dev ...]] [--block B --range R  (multi; default 16 16)] [--klt [--klt-mean-removal] [--klt-fb N] [--klt-predict [--klt-batch-predict]] [--klt-intra Q [--klt-cut P]]]
 //                                                       PCIe-inclusive per-frame time of the hip_sad process_frame shape; `multi`:
 //                                                       the stream over several workers (ofps_hip_multi_push_frames_async), with
 //                                                       detector + estimator per frame; `--klt` (batch, multi): hip_klt as the
 //                                                       batched stream's decoder (ofps_hip_set_batch_decoder / OFPS_HIP_BATCH_DECODER);
 //                                                       `--klt-mean-removal`: with its mean removal on (include/ofps_hip.h N3m);
 //                                                       `--klt-fb N`: with its forward-backward check at N / 256 pixel (N3f);
+//                                                       `--klt-intra Q`, `--klt-cut P`: with its intra test at Q sixteenths and its
+//                                                       scene-cut rule at P percent (N3i);
 //                                                       `--klt-predict`: with the prediction setting on (N3p), which the batched and
 //                                                       multi-device forms ignore: the figures are those without it;
 //                                                       `--klt-batch-predict` beside it (batch mode): the batched stream's switch
@@ -226,6 +228,7 @@ int main(int argc, char** argv) {
             // node the page-locked buffers landed on (the batched form is bimodal from process to process: profiles/r05/batched_bimodal.txt)
             int sb_block = 16, sb_range = 16;
             int sb_klt_fb = 0;                                 // `--klt-fb N` beside `--klt`: ofps_hip_set_klt_fb(N) / OFPS_HIP_KLT_FB=N
+            int sb_klt_intra = 0, sb_klt_cut = 0;              // `--klt-intra Q`, `--klt-cut P` beside `--klt`: ofps_hip_set_klt_intra(Q) / _cut(P), OFPS_HIP_KLT_INTRA=Q / OFPS_HIP_KLT_CUT=P
             bool sb_klt_pred = false;                          // `--klt-predict` beside `--klt`: ofps_hip_set_klt_prediction(1) / OFPS_HIP_KLT_PREDICTION=1
             bool sb_klt_bpred = false;                         // `--klt-batch-predict` beside `--klt`: ofps_hip_set_klt_batch_prediction(1), batch mode alone (the multi-device workers ignore it)
             bool sb_klt_zm = false;                            // `--klt-mean-removal` beside `--klt`: ofps_hip_set_klt_mean_removal(1) / OFPS_HIP_KLT_MEAN_REMOVAL=1
@@ -239,6 +242,8 @@ int main(int argc, char** argv) {
                     if (std::string(argv[a]) == "--klt-predict") { sb_klt_pred = true; continue; }
                     if (std::string(argv[a]) == "--klt-batch-predict") { sb_klt_bpred = true; continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--klt-fb") { sb_klt_fb = std::atoi(argv[++a]); continue; }
+                    if (a + 1 < argc && std::string(argv[a]) == "--klt-intra") { sb_klt_intra = std::atoi(argv[++a]); continue; }
+                    if (a + 1 < argc && std::string(argv[a]) == "--klt-cut") { sb_klt_cut = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--block") { sb_block = std::atoi(argv[++a]); continue; }
                     if (a + 1 < argc && std::string(argv[a]) == "--range") { sb_range = std::atoi(argv[++a]); continue; }
                     argv[keep++] = argv[a];
@@ -246,6 +251,7 @@ int main(int argc, char** argv) {
                 argc = keep;
                 if (sb_klt_zm && !sb_klt) throw Error("stream-bench: --klt-mean-removal needs --klt");
                 if (sb_klt_fb && !sb_klt) throw Error("stream-bench: --klt-fb needs --klt");
+                if ((sb_klt_intra || sb_klt_cut) && !sb_klt) throw Error("stream-bench: --klt-intra and --klt-cut need --klt");
                 if (sb_klt_pred && !sb_klt) throw Error("stream-bench: --klt-predict needs --klt");
                 if (sb_klt_bpred && !sb_klt) throw Error("stream-bench: --klt-batch-predict needs --klt");
             }
@@ -268,6 +274,8 @@ int main(int argc, char** argv) {
                 if (sb_klt_zm) setenv("OFPS_HIP_KLT_MEAN_REMOVAL", "1", 1);
                 if (sb_klt_fb) setenv("OFPS_HIP_KLT_FB", std::to_string(sb_klt_fb).c_str(), 1);
                 if (sb_klt_pred) setenv("OFPS_HIP_KLT_PREDICTION", "1", 1);
+                if (sb_klt_intra) setenv("OFPS_HIP_KLT_INTRA", std::to_string(sb_klt_intra).c_str(), 1);
+                if (sb_klt_cut) setenv("OFPS_HIP_KLT_CUT", std::to_string(sb_klt_cut).c_str(), 1);
                 if (ofps_hip_multi_init(devices.data(), (int)devices.size(), &m) != OFPS_HIP_OK) throw Error(ofps_hip_multi_last_error(nullptr));
                 const int nw = (int)devices.size(), slots = 2 * nw;
                 HipContext alloc;                                           // page-locked memory comes from any context
@@ -321,6 +329,8 @@ int main(int argc, char** argv) {
                     if (sb_klt_fb) ctx.check(ofps_hip_set_klt_fb(ctx.get(), sb_klt_fb));
                     if (sb_klt_pred) ctx.check(ofps_hip_set_klt_prediction(ctx.get(), 1));
                     if (sb_klt_bpred) ctx.check(ofps_hip_set_klt_batch_prediction(ctx.get(), 1));
+                    if (sb_klt_intra) ctx.check(ofps_hip_set_klt_intra(ctx.get(), sb_klt_intra));
+                    if (sb_klt_cut) ctx.check(ofps_hip_set_klt_cut(ctx.get(), sb_klt_cut));
                     ctx.check(ofps_hip_get_klt(ctx.get(), &klt_cell, nullptr, nullptr, nullptr, nullptr));
                 }
                 const size_t nblk = sb_klt ? ofps_hip_klt_slot_count(W, H, klt_cell) : ofps_hip_sad_block_count(W, H, 16);

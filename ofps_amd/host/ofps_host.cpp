@@ -211,6 +211,8 @@ bool HipLkDecoder::process_frame(MotionVectors& field, std::vector<RGBA>* out_fr
                                     (int)klt_->max_residual));
         ctx_.check(ofps_hip_set_klt_mean_removal(ctx_.get(), klt_->mean_removal ? 1 : 0));
         ctx_.check(ofps_hip_set_klt_fb(ctx_.get(), (int)klt_->fb_limit));
+        ctx_.check(ofps_hip_set_klt_intra(ctx_.get(), (int)klt_->intra_test));
+        ctx_.check(ofps_hip_set_klt_cut(ctx_.get(), (int)klt_->scene_cut));
         ctx_.check(ofps_hip_set_klt_prediction(ctx_.get(), klt_->prediction ? 1 : 0));
         out_.resize(klt_record_floats(w_, h_, max_w_, max_h_, process_fullres_, klt_->cell));
     } else {
@@ -271,7 +273,9 @@ std::vector<std::pair<std::string, PropertyMut>> klt_props(const KltPropStorage&
             {"Process Fullres", PropertyMut::boolean(at.process_fullres)},
             {"Cell size", PropertyMut::usize(&s.cell, 8, 32)}, {"Score radius", PropertyMut::usize(&s.score_radius, 1, 3)},
             {"Min score", PropertyMut::usize(&s.min_score, 1, kKltMaxScore)}, {"Min eigenvalue", PropertyMut::usize(&s.min_eig, 1, kKltMaxEig)},
-            {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)}, {"Levels", PropertyMut::usize(at.levels, 1, 6)},
+            {"Max residual", PropertyMut::usize(&s.max_residual, 0, kKltMaxResidual)},
+            {"Intra test", PropertyMut::usize(&s.intra_test, 0, 255)}, {"Scene cut", PropertyMut::usize(&s.scene_cut, 0, 100)},      // N3i, named as on hip_sad
+            {"Levels", PropertyMut::usize(at.levels, 1, 6)},
             {"Window radius", PropertyMut::usize(at.radius, 1, 7)}, {"Iterations", PropertyMut::usize(at.iters, 1, 30)},
             {"Mean removal", PropertyMut::boolean(&s.mean_removal)}, {"Consistency check", PropertyMut::usize(&s.fb_limit, 0, kKltMaxFb)}};
 }

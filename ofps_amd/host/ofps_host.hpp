@@ -167,6 +167,7 @@ struct KltSettings {
     size_t cell = 16, score_radius = 2, min_score = 1, min_eig = 1, max_residual = 0;
     bool mean_removal = false;             // "Mean removal" (N3m): ofps_hip_set_klt_mean_removal before every push
     size_t fb_limit = 0;                   // "Consistency check" (N3f): ofps_hip_set_klt_fb before every push, 1/256 pixel, 0 = off
+    size_t intra_test = 0, scene_cut = 0;  // "Intra test", "Scene cut" (N3i): ofps_hip_set_klt_intra / _cut before every push, sixteenths / percent, 0 = off
     bool prediction = false;               // "Prediction" (N3p): ofps_hip_set_klt_prediction before every push; an extension property, which the
                                            // decoder's props_mut appends behind klt_props' table
 };

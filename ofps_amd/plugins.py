@@ -278,6 +278,13 @@ class HipKltDecoder(HipLkDecoder):
     _PROPS = (("Width", "usize", "max_w", 1, 2000), ("Height", "usize", "max_h", 1, 2000), ("Process Fullres", "bool", "process_fullres", None, None),
               ("Cell size", "usize", "cell", 8, 32), ("Score radius", "usize", "score_radius", 1, 3), ("Min score", "usize", "min_score", 1, 2 ** 31 - 1),
               ("Min eigenvalue", "usize", "min_eig", 1, 65535), ("Max residual", "usize", "max_residual", 0, 4080),
+              # build-defined, named as on hip_sad (include/ofps_hip.h N3i): 0 = off; q = a kept track whose residual reaches q/16 of its
+              # window's activity (sum of |pixel - window mean|) in the previous frame yields no vector.  On a stream whose brightness
+              # changes between frames every track is intra unless "Mean removal" is on (measured: docs/history/42_klt_intra.md)
+              ("Intra test", "usize", "intra_test", 0, 255),
+              # build-defined: 0 = off; P = a frame with at least P percent of its tracks intra yields no vector at all.  No effect while
+              # "Intra test" is 0.  Recommended beside it (50): the intra test alone leaves accidental survivors at a cut
+              ("Scene cut", "usize", "scene_cut", 0, 100),
               ("Levels", "usize", "levels", 1, 6), ("Window radius", "usize", "radius", 1, 7), ("Iterations", "usize", "iters", 1, 30),
               # build-defined: the tracker solves for the shift and one brightness offset per window, for streams whose brightness changes
               # between frames (include/ofps_hip.h N3m); hip_sad's property of the same name is its counterpart
@@ -296,6 +303,8 @@ class HipKltDecoder(HipLkDecoder):
         self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual = 16, 2, 1, 1, 0
         self.mean_removal = False
         self.fb_limit = 0
+        self.intra_test = 0
+        self.scene_cut = 0
         self.prediction = False
         self.contrast_mask = False
 
@@ -323,6 +332,8 @@ class HipKltDecoder(HipLkDecoder):
         self.ctx.set_klt(self.cell, self.score_radius, self.min_score, self.min_eig, self.max_residual)
         self.ctx.set_klt_mean_removal(1 if self.mean_removal else 0)
         self.ctx.set_klt_fb(self.fb_limit)
+        self.ctx.set_klt_intra(self.intra_test)
+        self.ctx.set_klt_cut(self.scene_cut)
         self.ctx.set_klt_prediction(1 if self.prediction else 0)
         return self._decode(field, dict(reduced=not self.process_fullres, fmt=self.frame_format, sparse=True))
 

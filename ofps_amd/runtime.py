@@ -850,6 +850,58 @@ class HipContext:
                                                                radius, iters, C.c_void_p(d_out_entries), C.c_void_p(d_out_counts),
                                                                C.c_void_p(d_out_slots or 0), C.c_void_p(d_prev_slots or 0)))
 
+    # ---- N3i: hip_klt's intra test and scene-cut rule
+    def set_klt_intra(self, ratio: int):
+        """hip_klt's intra test (include/ofps_hip.h N3i): 0 = off (default); q in [1, 255] (sixteenths) = a kept track whose residual reaches
+        q/16 of its window's activity in the raw previous frame (16 * res >= q * 256 * A) becomes status 6 and yields no record, in every form
+        that runs the decoder."""
+        self._check(self._lib.ofps_hip_set_klt_intra(self._h, int(ratio)))
+
+    def get_klt_intra(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_intra(self._h))
+
+    def set_klt_cut(self, percent: int):
+        """hip_klt's scene-cut rule (N3i): 0 = off (default); P in [1, 100] = a pair with at least P percent of its candidates intra yields no
+        record at all, its statuses 0 become 7.  No effect while the intra ratio is 0."""
+        self._check(self._lib.ofps_hip_set_klt_cut(self._h, int(percent)))
+
+    def get_klt_cut(self) -> int:
+        return int(self._lib.ofps_hip_get_klt_cut(self._h))
+
+    def klt_activity(self, luma: np.ndarray, points: np.ndarray, radius: int, stride: int | None = None) -> np.ndarray:
+        """points int [n, 2] (x, y) inside the frame -> uint32 [n]: sum |p - rounded window mean| over each point's (2 radius + 1)^2 window,
+        pixel indices clamped into the frame"""
+        g, stride = self._luma_view(luma, stride)
+        H, W = g.shape
+        pts = np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+        out = np.zeros(max(len(pts), 1), np.uint32)
+        self._check(self._lib.ofps_hip_klt_activity(self._h, C.cast(C.c_void_p(g.ctypes.data), C.POINTER(C.c_uint8)), W, H, stride,
+                                                    pts.ctypes.data_as(C.POINTER(C.c_int32)) if len(pts) else None, len(pts), radius,
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:len(pts)]
+
+    def klt_activity_dev(self, d_luma: int, W: int, H: int, stride: int, d_points: int, n: int, radius: int, d_out_activity: int):
+        """Enqueue only; a point outside the frame comes back with A = 0."""
+        self._check(self._lib.ofps_hip_klt_activity_dev(self._h, C.c_void_p(d_luma), W, H, stride, C.c_void_p(d_points), n, radius,
+                                                        C.c_void_p(d_out_activity)))
+
+    def klt_intra(self, quads: np.ndarray, activity: np.ndarray, ratio: int, cut: int = 0, want_counts=True):
+        """Verdict and cut rule alone on [n, 4] quads (dqx, dqy, res, status) and the points' activities -> (statuses int32 [n],
+        [n_cand, n_intra] uint32 or None)."""
+        q = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+        a = np.ascontiguousarray(activity, np.uint32).reshape(-1)
+        assert len(q) == len(a)
+        st = np.zeros(max(len(q), 1), np.int32)
+        counts = np.zeros(2, np.uint32) if want_counts else None
+        i32, u32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        self._check(self._lib.ofps_hip_klt_intra(self._h, q.ctypes.data_as(i32) if len(q) else None, a.ctypes.data_as(u32) if len(q) else None, len(q),
+                                                 ratio, cut, st.ctypes.data_as(i32), counts.ctypes.data_as(u32) if want_counts else None))
+        return st[:len(q)], counts
+
+    def klt_intra_dev(self, d_quads: int, d_activity: int, n: int, ratio: int, cut: int, d_out_status: int, d_out_counts: int | None = None):
+        self._check(self._lib.ofps_hip_klt_intra_dev(self._h, C.c_void_p(d_quads), C.c_void_p(d_activity), n, ratio, cut, C.c_void_p(d_out_status),
+                                                     C.c_void_p(d_out_counts or 0)))
+
     def set_batch_decoder(self, decoder: int = 0, levels: int = 4, radius: int = 7, iters: int = 10):
         """What push_frames_async searches with: BATCH_DECODER_SAD (default), or BATCH_DECODER_KLT with these levels, window radius and
         iterations and the set_klt values (include/ofps_hip.h N3b)."""
@@ -1367,7 +1419,9 @@ def device_count() -> int:
 
 class MultiDevice:
     """In-process multi-device dispatcher (include/ofps_hip.h: ofps_hip_multi_*): one worker thread + one context per entry
-    of `devices` (entries may repeat), frame pairs split into contiguous ranges, results in pair order."""
+    of `devices` (entries may repeat), frame pairs split into contiguous ranges, results in pair order.  The workers' contexts read their
+    options from the environment when the dispatcher is made and nowhere else: with the batch decoder at KLT, OFPS_HIP_KLT_INTRA and
+    OFPS_HIP_KLT_CUT (include/ofps_hip.h N3i) among them."""
 
     def __init__(self, devices):
         self._lib = _lib.load()

@@ -28,7 +28,7 @@ Every clip runs through the tracking loop of ofps-suite/src/app/tracking/worker.
               iterations, no residual limit; --klt-cell C [C ...] and --klt-residual R [R ...] add hip_klt_c<C>r<R> for every other pair of
               "Cell size" and "Max residual"; --klt-mean-removal adds the same columns once more with "Mean removal" on (include/ofps_hip.h
               N3m) as hip_klt_m and hip_klt_c<C>r<R>_m; --klt-fb N [N ...] adds every hip_klt column once more per N with "Consistency check" = N
-              (include/ofps_hip.h N3f, the round-trip limit in 1/256 pixel) as hip_klt_f<N>, and with --klt-mean-removal as hip_klt_f<N>_m; --klt-predict adds every hip_klt column once more with "Prediction" on (N3p) as <column>_p, --klt-levels L runs them all at L pyramid levels; --ramp-clips adds pans whose rate grows linearly from 0 to 1.5 and to 3 degrees per frame and swings back; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
+              (include/ofps_hip.h N3f, the round-trip limit in 1/256 pixel) as hip_klt_f<N>, and with --klt-mean-removal as hip_klt_f<N>_m; --klt-intra Q [Q ...] adds every hip_klt column once more per Q with "Intra test" = Q (include/ofps_hip.h N3i) as <column>_i<Q>, "Scene cut" at --klt-cut P in those columns; --klt-predict adds every hip_klt column once more with "Prediction" on (N3p) as <column>_p, --klt-levels L runs them all at L pyramid levels; --ramp-clips adds pans whose rate grows linearly from 0 to 1.5 and to 3 degrees per frame and swings back; --skip NAME [NAME ...] leaves decoder columns out (e.g. hip_lk5 hip_flow: most of the run time)
   cut clip    --cut-clip adds pan_0.2_cut: pan_0.2's rotations with the second half of the frames rendered from another canvas seed: one scene
               cut, the planted rotation across it unchanged.  Its rows also report the error at the cut pair
   lighting    --lighting L [L ...] runs every clip once per L, rendered once (rows "clip@L"; none = the clip as rendered): step = the exposure
@@ -180,7 +180,7 @@ CUT_CLIP, CUT_SEEDS = "pan_0.2_cut", (61, 62)
 def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, quarter_pel=False, sad_gate=0, sad_consistency=0, sad_levels=0,
         fast_clips=False, sad_only=False, sad_predictors=0, lighting=("none",), sad_prefilter=(), sad_median=(), sad_intra=(), sad_cut=0,
         cut_clip=False, sad_split=(), klt=False, klt_cells=(16,), klt_residuals=(0,), skip=(),
-        klt_mean_removal=False, klt_fb=(), klt_predict=False, ramp_clips=False, klt_levels=0):
+        klt_mean_removal=False, klt_fb=(), klt_predict=False, ramp_clips=False, klt_levels=0, klt_intra=(), klt_cut=0):
     from ofps_amd.plugins import HipFlowDecoder, HipKltDecoder, HipLkDecoder, HipSadDecoder, StandardCamera
     combos = [("hip_sad", HipSadDecoder, False, {}), ("hip_sad", HipSadDecoder, True, {}), ("hip_lk", HipLkDecoder, False, {}),
               ("hip_lk", HipLkDecoder, True, {}),
@@ -252,6 +252,8 @@ def run(quick=False, oracle_lk_pairs=3, with_oracle=True, only=None, log=print, 
                     if klt_mean_removal:
                         props_kfm = dict(props_kf, **{"Mean removal": True})
                         combos += [(f"{tag}_f{fb}_m", HipKltDecoder, False, props_kfm), (f"{tag}_f{fb}_m", HipKltDecoder, True, props_kfm)]
+    if klt and klt_intra:       # every hip_klt column once more per ratio of the intra test (include/ofps_hip.h N3i), "Scene cut" at --klt-cut, as <column>_i<Q>
+        combos += [(f"{c[0]}_i{q}", c[1], c[2], dict(c[3], **{"Intra test": q, "Scene cut": klt_cut})) for q in klt_intra for c in combos if c[1] is HipKltDecoder]
     if klt and klt_predict:     # every hip_klt column once more with "Prediction" on (include/ofps_hip.h N3p), as <column>_p
         combos += [(c[0] + "_p", c[1], c[2], dict(c[3], **{"Prediction": True})) for c in combos if c[1] is HipKltDecoder]
     if klt and klt_levels:      # ... and all of them at another number of pyramid levels
@@ -414,6 +416,8 @@ def main():
     ap.add_argument("--klt-residual", nargs="*", type=int, default=[0], metavar="R", help="with --klt: \"Max residual\" values (sixteenths of a grey level)")
     ap.add_argument("--klt-mean-removal", action="store_true", help="with --klt: every hip_klt column once more with \"Mean removal\" on, as <column>_m")
     ap.add_argument("--klt-fb", nargs="*", type=int, default=[], metavar="N", help="with --klt: \"Consistency check\" values in 1/256 pixel; hip_klt_f<N> beside hip_klt")
+    ap.add_argument("--klt-intra", nargs="*", type=int, default=[], metavar="Q", help="with --klt: \"Intra test\" ratios in sixteenths; <column>_i<Q> beside every hip_klt column")
+    ap.add_argument("--klt-cut", type=int, default=0, metavar="P", help="\"Scene cut\" of the <column>_i<Q> columns, percent (0 = off)")
     ap.add_argument("--klt-predict", action="store_true", help="with --klt: every hip_klt column once more with \"Prediction\" on, as <column>_p")
     ap.add_argument("--klt-levels", type=int, default=0, metavar="L", help="with --klt: \"Levels\" of every hip_klt column (0 = the decoder's 4)")
     ap.add_argument("--ramp-clips", action="store_true", help="add 1080p pans whose rate grows linearly from 0 to 1.5 and to 3 degrees per frame and falls back")
@@ -425,7 +429,7 @@ def main():
               sad_median=tuple(args.sad_median), sad_intra=tuple(args.sad_intra), sad_cut=args.sad_cut, cut_clip=args.cut_clip, sad_split=tuple(args.sad_split),
               klt=args.klt, klt_cells=tuple(args.klt_cell), klt_residuals=tuple(args.klt_residual), skip=tuple(args.skip),
               klt_mean_removal=args.klt_mean_removal, klt_fb=tuple(args.klt_fb), klt_predict=args.klt_predict, ramp_clips=args.ramp_clips,
-              klt_levels=args.klt_levels)
+              klt_levels=args.klt_levels, klt_intra=tuple(args.klt_intra), klt_cut=args.klt_cut)
     txt = table(res)
     print(txt)
     if args.out:

@@ -32,7 +32,11 @@ the forward pass kept; the rows say so ("fb_limit": N) and their "kept" and stat
   chained          one ofps_hip_klt_flow_batch_from_dev call over the N pairs, from zero: one score launch, one halving per level, N track launches
                    (klt_track_batch_pred kernels), one compaction
   one_by_one_from  N ofps_hip_klt_flow_from_dev calls over the same pairs, each given the slots of the one before
-and "chained_equals_one_by_one_from" says whether the two agree in counts and records."""
+and "chained_equals_one_by_one_from" says whether the two agree in counts and records.
+--intra Q [--cut P]: with ofps_hip_set_klt_intra(Q) and ofps_hip_set_klt_cut(P) (N3i): every row that runs the decoder ("flow", "flow_from", the
+batch columns) then enqueues klt_activity_kernel<true> and, with P > 0, klt_cut_kernel between the track launch and the compaction; the stage
+rows (score, pyramid, track) do not change.  The rows say so ("intra", "cut"), their "kept" and status histogram (6 = intra, 7 = cut) are the
+filtered ones, and a one-pair row also times the activity stage alone ("activity": ofps_hip_klt_activity_dev on the frame's features)."""
 import argparse
 import json
 import os
@@ -98,6 +102,10 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     if not klt_only:
         t["sad_16x16_pm16"] = window_ms(ctx, lambda: ctx.sad_flow_dev(d_fr, 2, W, H, W, W * H, 0, 16, 16, d_sad, None), calls, reps, warm)
         t["lk_3_4_3"] = window_ms(ctx, lambda: ctx.lk_flow_dev(d_prev, d_cur, W, H, W, 3, 4, 3, None, d_lk), calls, reps, warm)
+    if ctx.get_klt_intra() > 0:
+        d_act = ctx.malloc(max(4 * len(pts), 16))
+        t["activity"] = window_ms(ctx, lambda: ctx.klt_activity_dev(d_prev, W, H, W, d_pts, len(pts), radius, d_act), calls, reps, warm)
+        ctx.free(d_act)
     t["track_alone_derived_us"] = round(t["track"]["median_us"] - t["pyramid"]["median_us"], 2)
     ctx.klt_flow_dev(d_prev, d_cur, W, H, W, levels, radius, iters, d_rec, d_cnt, d_slots)
     ctx.sync()
@@ -119,7 +127,7 @@ def one(ctx, name, prev, cur, cell, levels, radius, iters, max_residual, calls, 
     for p in [d_fr, d_tri, d_quad, d_rec, d_cnt, d_slots, d_pts, d_sad, d_lk] + [b for lv in pyr for b in lv[3:]]:
         ctx.free(p)
     return {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "predict": int(predict), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
+            "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "intra": ctx.get_klt_intra(), "cut": ctx.get_klt_cut(), "predict": int(predict), "slots": int(ns), "features": int(len(pts)), "kept": int(cnt[0]), "status_histogram": {int(a): int(b) for a, b in zip(u, c)}, "times": t}
 
 
 def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, calls, reps, warm, batch_predict=False):
@@ -176,7 +184,7 @@ def one_batch(ctx, name, frames, cell, levels, radius, iters, max_residual, call
     for p in (d_fr, d_rec, d_cnt, d_rec1, d_cnt1):
         ctx.free(p)
     row = {"case": name, "geometry": f"{W}x{H}", "cell": cell, "levels": levels, "radius": radius, "iters": iters, "max_residual": max_residual,
-           "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
+           "mean_removal": ctx.get_klt_mean_removal(), "fb_limit": ctx.get_klt_fb(), "intra": ctx.get_klt_intra(), "cut": ctx.get_klt_cut(), "batch": N, "slots": int(ns), "kept": [int(c) for c in cnt[:N]], "batch_equals_one_by_one": same, "calls_per_window": windows,
            "us_per_pair": t}
     if batch_predict:
         row.update({"chained_kept": chained_kept, "chained_equals_one_by_one_from": chained_same})
@@ -203,10 +211,14 @@ def main():
                                                            "(include/ofps_hip.h N3p); kept and the status histogram are then that call's")
     ap.add_argument("--batch-predict", action="store_true", help="--batch: also the chained batch (include/ofps_hip.h N3pb) and the chain of "
                                                                  "ofps_hip_klt_flow_from_dev calls it equals")
+    ap.add_argument("--intra", type=int, default=0, metavar="Q", help="hip_klt with the intra test at Q sixteenths (include/ofps_hip.h N3i)")
+    ap.add_argument("--cut", type=int, default=0, metavar="P", help="with --intra: the scene-cut rule at P percent")
     a = ap.parse_args()
     ctx = HipContext(0)
     ctx.set_klt_mean_removal(1 if a.mean_removal else 0)
     ctx.set_klt_fb(a.fb)
+    ctx.set_klt_intra(a.intra)
+    ctx.set_klt_cut(a.cut)
     rows = []
     for W, H, cell in ([] if a.no_1080p else [(1920, 1080, 16)]) + ([] if a.no_4k else [(3840, 2160, 8)]):
         lum = synth.luma_sequence(max(a.batch + 1, 2), W, H, max_step=6, seed=5)
