@@ -395,29 +395,37 @@ int sad_hier_reach(int range, int levels);                  // R_0, or -1
 int sad_hier_check(ofps_hip_ctx* ctx, int W, int H, int block, int range, int levels);
 int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int levels, int predictors, void* d_out_entries,
                           void* d_out_best);
-// one pyramid step of one frame (what ofps_hip_sad_down2_dev enqueues): W x H -> (W >> 1) x (H >> 1)
-int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int src_stride, uint8_t* dst, int dst_stride);
-// ... of `frames` frames src_pitch bytes apart, their halved forms dst_pitch apart, in one launch
+// one pyramid step (what ofps_hip_sad_down2_dev enqueues for one frame), W x H -> (W >> 1) x (H >> 1), of `frames` frames src_pitch bytes apart,
+// their halved forms dst_pitch apart, in one launch
 int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
                             int dst_stride, long long frames);
-// klt.hip (include/ofps_hip.h N3): hip_klt on one pair of device frames with the context's settings -- the kept records first, in slot order, and
-// their count in device memory; d_out holds ofps_hip_klt_slot_count records, d_slots (optional) 6 int32 per slot.  Enqueues on ctx->stream only
-// the decoder's limits on one call: levels, radius, iters, a frame of 8 .. 32768 pixels a side whose top level is at least 8 x 8, stride >= W
+// klt.hip (include/ofps_hip.h N3): hip_klt with the context's settings.  The decoder's limits on one call: levels, radius, iters, a frame of
+// 8 .. 32768 pixels a side whose top level is at least 8 x 8, stride >= W -- what klt_check_call refuses, for every form of the decoder
 constexpr int kKltMaxLevels = 6, kKltMaxRadius = 7, kKltMaxIters = 30, kKltMaxScoreRadius = 3, kKltMaxMinEig = 65535, kKltMaxResidual = 4080, kKltMaxFb = 4096;
 int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who);
+struct KltLattice { int nx, ny; size_t slots() const { return (size_t)nx * ny; } };      // a partial cell at the right and lower edge counts
+inline KltLattice klt_lattice(int W, int H, int cell) { return {(W + cell - 1) / cell, (H + cell - 1) / cell}; }
+// One run of the decoder over `pairs` pairs of `f`: score -> pyramid -> track -> (N3i) verdict and cut -> the ordered compaction, enqueued on
+// ctx->stream only.  d_out: pairs x slots records, item k's kept records lead slot k; d_counts: pairs counts in device memory; d_slots
+// (optional): 6 int32 per slot, item-major.  S_KLT_PYR and S_KLT_WORK are dead behind the compaction: the batched stream's tickets share them.
+// batch = false: the one-pair kernels (pairs is 1); d_prev_slots (N3p, optional): the previous pair's raw slots, every feature starts from its
+// slot's predicted guess.  batch = true (N3b): item k = the one-pair run on that pair, bit for bit, in a number of launches that does not depend
+// on `pairs`.  chained (N3pb, batch only): the track step is `pairs` launches, one item each, in stream order; item k starts from item k - 1's raw
+// slots, item 0 from d_prev_slots (null: from zero); d_last_slots (optional): the last item's raw slots go there and not into d_slots; neither
+// it nor d_prev_slots may share a byte with d_slots or with each other
+struct KltFlowCall {
+    SadFrames f;
+    int pairs, levels, radius, iters;
+    float4* d_out; uint32_t* d_counts; int* d_slots;
+    bool batch, chained;
+    const int* d_prev_slots; int* d_last_slots;
+};
+int klt_flow_device(ofps_hip_ctx* ctx, const KltFlowCall& c);
+// ... the one-pair form on two device frames: the set {d_prev, d_cur, pitches 0}
 int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
-                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots = nullptr);      // d_prev_slots: N3p, the previous pair's raw slots
-// N3b: item k of `pairs` pairs of `f` = klt_flow_device on that pair, bit for bit, in a number of launches that does not depend on `pairs`:
-// one score launch over the distinct prev frames, one halving per level over the distinct frames, one track launch of pairs x slots waves, the
-// segmented compaction.  d_out: pairs slots of the slot count, item k's kept records lead slot k; d_counts: pairs counts; d_slots (optional):
-// 6 int32 per slot, item-major.  Works in S_KLT_PYR and S_KLT_WORK (compute stream only, consumed in front of the compaction: tickets share them)
-// chained (N3pb): the track step becomes `pairs` launches, one item each, in order on ctx->stream; item k's tracks start from the guesses made from
-// item k - 1's raw slots, item 0's from d_prev_slots (null: from zero).  d_last_slots (optional): the last item's raw slots go there and not
-// into d_slots; neither it nor d_prev_slots may share a byte with d_slots or with each other
-int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
-                          int* d_slots, bool chained = false, const int* d_prev_slots = nullptr, int* d_last_slots = nullptr);
-// klt_intra.hip (include/ofps_hip.h N3i): hip_klt's intra test and scene-cut rule, between the track launch and the compaction.  What the two
-// call sites hand over: the level-0 previous frames (pitch 0: one key frame for every item), the feature triples (pitch 0: one set), the
+                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots = nullptr);
+// klt_intra.hip (include/ofps_hip.h N3i): hip_klt's intra test and scene-cut rule, between the track launch and the compaction.  What the
+// driver hands over: the level-0 previous frames (pitch 0: one key frame for every item), the feature triples (pitch 0: one set), the
 // tracks' quads, the keep flags the track launch wrote and the items' counters [candidates, intra], all but the frames and triples item-major,
 // `ns` entries per item
 constexpr int kKltIntraMax = 255, kKltCutMax = 100;

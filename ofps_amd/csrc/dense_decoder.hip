@@ -65,9 +65,9 @@ int dense_grid_of(ofps_hip_ctx* ctx, int W, int H, int stride, int max_w, int ma
         }
         const int rc_klt = ofps::klt_check_call(ctx, g->fw, g->fh, g->fw, levels, radius, iters, who);       // the frames the tracker reads, rows dense
         if (rc_klt != OFPS_HIP_OK) return rc_klt;
-        const int cell = ctx->opt.klt_cell;
-        g->gw = (g->fw + cell - 1) / cell; g->gh = (g->fh + cell - 1) / cell;
-        g->max_records = (size_t)g->gw * g->gh;
+        const ofps::KltLattice lat = ofps::klt_lattice(g->fw, g->fh, ctx->opt.klt_cell);
+        g->gw = lat.nx; g->gh = lat.ny;
+        g->max_records = lat.slots();
         g->frontend = g->reduced || g->fmt != OFPS_HIP_FMT_LUMA;
         g->raw_row = ((size_t)W * g->cn + 3) & ~(size_t)3;
         return OFPS_HIP_OK;

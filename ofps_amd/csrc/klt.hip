@@ -23,6 +23,13 @@
 // klt_track_batch_pred*_kernel: the batch kernels with motion prediction (N3pb): ONE item of a batch per launch, its slots' guesses predicted from
 //   the raw slots the launch of the item before has written.  The launches follow one another on the context's stream, which is all that orders
 //   them: no wave waits for another.
+//
+// The host side holds each step once.  klt_track_launch: THE track launch, the kernel picked from a [check][mean removal] table of the launch's
+//   parameter struct.  klt_track_settings: the part of KltTrackParams that comes from the context and the call.  klt_pyramid_device: the levels of
+//   a SadFrames' distinct frames; the one-pair forms hand it their two frames as a batch of one pair.  KltWork: S_KLT_WORK's layout.
+//   ofps::klt_flow_device(KltFlowCall): THE driver -- score, pyramid, track, (N3i) verdict and cut, compaction -- of the one-pair form, the batch
+//   form and the chained batch, which differ in the score and the track launch alone.  KltHostIo, klt_host_read: S_KLT_HOST's layout and the
+//   read-back of the host-pointer flow forms.
 #include "common.hpp"
 
 #include <cmath>
@@ -616,19 +623,21 @@ int klt_check_frame(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, con
     return OFPS_HIP_OK;
 }
 
-int klt_check_track(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who) {
-    const int rc = klt_check_frame(ctx, W, H, stride, levels, who);
-    if (rc != OFPS_HIP_OK) return rc;
-    OFPS_REQUIRE(ctx, radius >= 1 && radius <= kKltMaxRadius, "%s: radius %d outside [1, %d]", who, radius, kKltMaxRadius);
-    OFPS_REQUIRE(ctx, iters >= 1 && iters <= kKltMaxIters, "%s: iters %d outside [1, %d]", who, iters, kKltMaxIters);
+inline size_t klt_slots(int W, int H, int cell) { return klt_lattice(W, H, cell).slots(); }
+inline size_t pad16(size_t b) { return (b + 15) & ~size_t(15); }
+
+// the two arrays of raw slots of a call with prediction: a wave reads its neighbours' previous slots while other waves, and in a batch later the
+// other items, write theirs, so the two must not share a byte
+int klt_check_apart(ofps_hip_ctx* ctx, const void* d_prev_slots, size_t prev_bytes, const void* d_out_slots, size_t out_bytes, const char* who) {
+    const char* a = static_cast<const char*>(d_prev_slots);
+    const char* b = static_cast<const char*>(d_out_slots);
+    OFPS_REQUIRE(ctx, !a || !b || a + prev_bytes <= b || b + out_bytes <= a, "%s: d_prev_slots and d_out_slots overlap", who);
     return OFPS_HIP_OK;
 }
 
-inline size_t klt_slots(int W, int H, int cell) { return (size_t)((W + cell - 1) / cell) * (size_t)((H + cell - 1) / cell); }
-inline size_t pad16(size_t b) { return (b + 15) & ~size_t(15); }
-
 int klt_features_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int H, int stride, const KltSettings& s, int* d_out) {
-    const dim3 grid((W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell);
+    const KltLattice lat = klt_lattice(W, H, s.cell);
+    const dim3 grid(lat.nx, lat.ny);
     if (s.cell == 8) hipLaunchKernelGGL(klt_score_kernel<8>, grid, dim3(64), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
     else if (s.cell == 16) hipLaunchKernelGGL(klt_score_kernel<16>, grid, dim3(256), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
     else hipLaunchKernelGGL(klt_score_kernel<32>, grid, dim3(256), 0, ctx->stream, d_img, W, H, stride, s.r, s.min_score, d_out);
@@ -636,68 +645,39 @@ int klt_features_device(ofps_hip_ctx* ctx, const uint8_t* d_img, int W, int H, i
     return OFPS_HIP_OK;
 }
 
-// both frames' levels above 0 in S_KLT_PYR (ofps_hip_sad_down2's levels, as they are) -> *lv
-int klt_pyramid_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, KltLevels* lv) {
-    size_t off[kKltMaxLevels] = {}, bytes = 0;
-    lv->prev[0] = d_prev; lv->cur[0] = d_cur; lv->W[0] = W; lv->H[0] = H; lv->stride[0] = stride;
-    for (int l = 1; l < kKltMaxLevels; ++l) {
-        lv->prev[l] = lv->cur[l] = nullptr;
-        lv->W[l] = lv->H[l] = lv->stride[l] = 0;
-        if (l >= levels) continue;
-        lv->W[l] = lv->W[l - 1] >> 1; lv->H[l] = lv->H[l - 1] >> 1;
-        lv->stride[l] = (lv->W[l] + 63) & ~63;
-        off[l] = bytes; bytes += 2 * (size_t)lv->stride[l] * lv->H[l];
-    }
-    if (levels == 1) return OFPS_HIP_OK;
-    auto* pyr = static_cast<uint8_t*>(scratch(ctx, S_KLT_PYR, bytes));
-    if (!pyr) return OFPS_HIP_ENOMEM;
-    for (int l = 1; l < levels; ++l) {
-        uint8_t* dp = pyr + off[l];
-        uint8_t* dc = dp + (size_t)lv->stride[l] * lv->H[l];
-        int rc = sad_down2_device(ctx, lv->prev[l - 1], lv->W[l - 1], lv->H[l - 1], lv->stride[l - 1], dp, lv->stride[l]);
-        if (rc == OFPS_HIP_OK) rc = sad_down2_device(ctx, lv->cur[l - 1], lv->W[l - 1], lv->H[l - 1], lv->stride[l - 1], dc, lv->stride[l]);
-        if (rc != OFPS_HIP_OK) return rc;
-        lv->prev[l] = dp; lv->cur[l] = dc;
-    }
-    return OFPS_HIP_OK;
-}
+// The track kernels of one parameter struct, [N3f's check on][N3m's mean removal on], and THE track launch: `waves` slots, four to a workgroup,
+// the kernel the context's two settings pick.  The stage form ofps_hip_klt_track_q runs one direction whatever the check's setting is: its
+// table holds the same row twice
+template <class P> using KltTrackKernels = void (*const[2][2])(P);
+constexpr KltTrackKernels<KltTrackParams> kKltTrack = {{klt_track_kernel, klt_track_zm_kernel}, {klt_track_fb_kernel, klt_track_zm_fb_kernel}};
+constexpr KltTrackKernels<KltTrackParams> kKltTrackQ = {{klt_track_q_kernel, klt_track_q_zm_kernel}, {klt_track_q_kernel, klt_track_q_zm_kernel}};
+constexpr KltTrackKernels<KltTrackPredParams> kKltTrackPred = {{klt_track_pred_kernel, klt_track_pred_zm_kernel},
+                                                               {klt_track_pred_fb_kernel, klt_track_pred_zm_fb_kernel}};
+constexpr KltTrackKernels<KltTrackBatchParams> kKltTrackBatch = {{klt_track_batch_kernel, klt_track_batch_zm_kernel},
+                                                                 {klt_track_batch_fb_kernel, klt_track_batch_zm_fb_kernel}};
+constexpr KltTrackKernels<KltTrackBatchPredParams> kKltTrackBatchPred = {{klt_track_batch_pred_kernel, klt_track_batch_pred_zm_kernel},
+                                                                         {klt_track_batch_pred_fb_kernel, klt_track_batch_pred_zm_fb_kernel}};
 
-// at_q: the stage form ofps_hip_klt_track_q -- points in 1/256 pixel, one direction, never the check
-int klt_track_launch(ofps_hip_ctx* ctx, const KltTrackParams& p, bool at_q = false) {
-    if (p.n <= 0) return OFPS_HIP_OK;
-    const dim3 grid((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves));
-    if (at_q) {
-        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_q_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
-        else hipLaunchKernelGGL(klt_track_q_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
-    } else if (ctx->opt.klt_fb > 0) {                         // N3f: the same launch, the backward pass inside it
-        KltTrackParams f = p;
-        f.fb_limit = ctx->opt.klt_fb;
-        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        else hipLaunchKernelGGL(klt_track_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(klt_track_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
+template <class P>
+int klt_track_launch(ofps_hip_ctx* ctx, KltTrackKernels<P>& kernels, long long waves, const P& p) {
+    if (waves <= 0) return OFPS_HIP_OK;
+    const dim3 grid((unsigned)((waves + kKltTrackWaves - 1) / kKltTrackWaves));
+    hipLaunchKernelGGL(kernels[ctx->opt.klt_fb > 0][ctx->opt.klt_mean_removal != 0], grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, p);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
 }
 
-// N3p: the track launch whose slots start from caller-given guesses or from the guesses predicted from prev_slots (one of the two is set)
-int klt_track_pred_launch(ofps_hip_ctx* ctx, const KltTrackParams& p, const int* d_guesses, const int* d_prev_slots, int nx, int ny) {
-    if (p.n <= 0) return OFPS_HIP_OK;
-    const dim3 grid((unsigned)((p.n + kKltTrackWaves - 1) / kKltTrackWaves));
-    KltTrackPredParams f{p, d_guesses, d_prev_slots, nx, ny};
-    f.t.fb_limit = ctx->opt.klt_fb;
-    if (ctx->opt.klt_fb > 0) {
-        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_pred_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        else hipLaunchKernelGGL(klt_track_pred_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_pred_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-    else hipLaunchKernelGGL(klt_track_pred_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-    OFPS_HIP_TRY(ctx, hipGetLastError());
-    return OFPS_HIP_OK;
+// what every track launch takes from the context and the call; the callers add the levels, the points and the outputs.  fb_limit (N3f) is above 0
+// exactly when the launch picks the FB kernels, which alone read it
+void klt_track_settings(const ofps_hip_ctx* ctx, int levels, int radius, int iters, KltTrackParams* p) {
+    p->L = levels; p->w = radius; p->K = iters; p->min_eig = ctx->opt.klt_min_eig; p->max_residual = ctx->opt.klt_max_residual;
+    p->fb_limit = ctx->opt.klt_fb;
 }
 
 int klt_predict_device(ofps_hip_ctx* ctx, const int* d_prev_slots, int W, int H, int cell, int* d_out) {
-    const int nx = (W + cell - 1) / cell, ny = (H + cell - 1) / cell;
-    const size_t ns = (size_t)nx * ny;
+    const KltLattice lat = klt_lattice(W, H, cell);
+    const int nx = lat.nx, ny = lat.ny;
+    const size_t ns = lat.slots();
     hipLaunchKernelGGL(klt_predict_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, d_prev_slots, nx, ny, d_out);
     OFPS_HIP_TRY(ctx, hipGetLastError());
     return OFPS_HIP_OK;
@@ -708,7 +688,8 @@ int klt_predict_device(ofps_hip_ctx* ctx, const int* d_prev_slots, int W, int H,
 int klt_features_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_img, size_t pitch, int frames, int W, int H, int stride, const KltSettings& s,
                               int* d_out) {
     OFPS_REQUIRE(ctx, frames >= 1 && frames <= 65535, "klt_flow_batch: %d frames to score (at most 65535)", frames);
-    const dim3 grid((W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell, frames);
+    const KltLattice lat = klt_lattice(W, H, s.cell);
+    const dim3 grid(lat.nx, lat.ny, frames);
     if (s.cell == 8) hipLaunchKernelGGL(klt_score_batch_kernel<8>, grid, dim3(64), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
     else if (s.cell == 16) hipLaunchKernelGGL(klt_score_batch_kernel<16>, grid, dim3(256), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
     else hipLaunchKernelGGL(klt_score_batch_kernel<32>, grid, dim3(256), 0, ctx->stream, d_img, pitch, W, H, stride, s.r, s.min_score, d_out);
@@ -718,8 +699,9 @@ int klt_features_batch_device(ofps_hip_ctx* ctx, const uint8_t* d_img, size_t pi
 
 // the levels above 0 of the distinct frames of `pairs` pairs in S_KLT_PYR -> b->t.lv (the levels' bases) and the levels' pitches.  A chain
 // (consecutive pairs of one sequence) or a key frame followed by its current frames is one run of frames: one halving per level; two unrelated
-// sets take two
-int klt_pyramid_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, KltTrackBatchParams* b) {
+// sets take two.  One pair of two frames anywhere (both pitches 0, pairs = 1) is two sets of one frame: two halvings per level, cur's copy one
+// frame behind prev's -- the one-pair forms' pyramid, whose kernels read b->t.lv and no pitch
+int klt_pyramid_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, KltTrackBatchParams* b) {
     KltLevels* lv = &b->t.lv;
     const SadFrames::Sets sets = f.sets(pairs);
     const bool key_run = !sets.chain && !sets.prev_many && sets.cur_many && f.cur_base == f.prev_base + f.cur_pitch;      // frames 0, 1 .. pairs of one sequence
@@ -758,52 +740,29 @@ int klt_pyramid_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, i
     return OFPS_HIP_OK;
 }
 
-int klt_track_batch_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b) {
-    if (b.t.n <= 0) return OFPS_HIP_OK;
-    const dim3 grid((unsigned)((b.t.n + kKltTrackWaves - 1) / kKltTrackWaves));
-    if (ctx->opt.klt_fb > 0) {                                // N3f
-        KltTrackBatchParams f = b;
-        f.t.fb_limit = ctx->opt.klt_fb;
-        if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        else hipLaunchKernelGGL(klt_track_batch_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-    } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
-    else hipLaunchKernelGGL(klt_track_batch_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, b);
-    OFPS_HIP_TRY(ctx, hipGetLastError());
-    return OFPS_HIP_OK;
-}
-
 // N3pb: `pairs` launches, one item each, in item order on ctx->stream.  Item k writes its raw slots where the caller wants them (b.t.out_slots,
 // item-major: the caller's array, or S_KLT_WORK's), the last item into d_last_slots if that is given; item k + 1 reads them there.  Item 0 reads
 // d_prev_slots (null: zero guesses).  No launch reads the array it writes: the items' slots are ns apart, and the callers keep d_prev_slots
 // and d_last_slots apart from each other and from the rest
 // intra (N3i, optional): item k's verdict and cut are enqueued behind its track launch
-int klt_track_batch_pred_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b, int pairs, int nx, int ny, const int* d_prev_slots, int* d_last_slots,
-                                const KltIntraCall* intra = nullptr) {
+int klt_track_chained_launch(ofps_hip_ctx* ctx, const KltTrackBatchParams& b, int pairs, KltLattice lat, const int* d_prev_slots, int* d_last_slots,
+                             const KltIntraCall* intra) {
     const int ns = b.slots_per_item;
-    if (ns <= 0 || pairs <= 0) return OFPS_HIP_OK;
-    const dim3 grid((unsigned)((ns + kKltTrackWaves - 1) / kKltTrackWaves));
     int* const all = b.t.out_slots;                           // 6 ints per slot of the batch
     const int* prev = d_prev_slots;
     for (int k = 0; k < pairs; ++k) {
-        KltTrackBatchPredParams f{b, prev, k * ns, nx, ny};
+        KltTrackBatchPredParams f{b, prev, k * ns, lat.nx, lat.ny};
         f.b.t.n = (k + 1) * ns;
-        f.b.t.fb_limit = ctx->opt.klt_fb;
         int* mine = all + 6 * (size_t)k * ns;
         if (k == pairs - 1 && d_last_slots) {
             // the kernel stores at 6 * slot behind out_slots, slot counted from the batch's first: this item's slots land in d_last_slots
             mine = d_last_slots;
             f.b.t.out_slots = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(d_last_slots) - 6 * (size_t)k * ns * sizeof(int));
         }
-        if (ctx->opt.klt_fb > 0) {
-            if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_pred_zm_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-            else hipLaunchKernelGGL(klt_track_batch_pred_fb_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        } else if (ctx->opt.klt_mean_removal) hipLaunchKernelGGL(klt_track_batch_pred_zm_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        else hipLaunchKernelGGL(klt_track_batch_pred_kernel, grid, dim3(64 * kKltTrackWaves), 0, ctx->stream, f);
-        OFPS_HIP_TRY(ctx, hipGetLastError());
-        if (intra) {                                          // N3i: statuses 6 and 7 stand in `mine` before the next launch's predictor reads it
-            const int rc = klt_intra_device(ctx, *intra, k, 1, f.b.t.out_slots);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
+        int rc = klt_track_launch(ctx, kKltTrackBatchPred, ns, f);
+        // N3i: statuses 6 and 7 stand in `mine` before the next launch's predictor reads it
+        if (rc == OFPS_HIP_OK && intra) rc = klt_intra_device(ctx, *intra, k, 1, f.b.t.out_slots);
+        if (rc != OFPS_HIP_OK) return rc;
         prev = mine;
     }
     return OFPS_HIP_OK;
@@ -816,110 +775,95 @@ int klt_check_sequence(ofps_hip_ctx* ctx, int n_frames, int H, int stride, size_
     return OFPS_HIP_OK;
 }
 
+// S_KLT_WORK of one run, every part on a multiple of 16 bytes: [triples of the `scored` distinct prev frames][raw records, pairs x slots]
+// [keep flags, pairs x slots]; own_slots (a chained batch whose caller takes no slots): [raw slots, 6 i32 per slot of the batch], dead behind the
+// last track launch; intra (N3i): [the tracks' quads, 4 i32 per slot of the batch][candidate and intra counters, 2 x u32 per item]
+struct KltWork {
+    int* feat; float4* raw; uint8_t* flag;
+    int* slots; int* quad; uint32_t* cnt;                     // null where the run has none
+    bool make(ofps_hip_ctx* ctx, int pairs, int scored, size_t ns, bool own_slots, bool intra) {
+        const size_t total = (size_t)pairs * ns;
+        const size_t o_raw = pad16((size_t)scored * ns * 3 * sizeof(int)), o_flag = o_raw + total * sizeof(float4), o_slots = o_flag + pad16(total);
+        const size_t end_slots = o_slots + (own_slots ? total * 6 * sizeof(int) : 0);
+        const size_t o_quad = pad16(end_slots), o_cnt = o_quad + total * 4 * sizeof(int);
+        auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, intra ? o_cnt + pad16((size_t)pairs * 2 * sizeof(uint32_t)) : end_slots));
+        if (!work) return false;
+        feat = reinterpret_cast<int*>(work); raw = reinterpret_cast<float4*>(work + o_raw); flag = reinterpret_cast<uint8_t*>(work + o_flag);
+        slots = own_slots ? reinterpret_cast<int*>(work + o_slots) : nullptr;
+        quad = intra ? reinterpret_cast<int*>(work + o_quad) : nullptr;
+        cnt = intra ? reinterpret_cast<uint32_t*>(work + o_cnt) : nullptr;
+        return true;
+    }
+};
+
 }  // namespace
 
 namespace ofps {
 
 // what every call of the decoder refuses, the stage forms and the dense decoders' stream forms alike
 int klt_check_call(ofps_hip_ctx* ctx, int W, int H, int stride, int levels, int radius, int iters, const char* who) {
-    return klt_check_track(ctx, W, H, stride, levels, radius, iters, who);
+    const int rc = klt_check_frame(ctx, W, H, stride, levels, who);
+    if (rc != OFPS_HIP_OK) return rc;
+    OFPS_REQUIRE(ctx, radius >= 1 && radius <= kKltMaxRadius, "%s: radius %d outside [1, %d]", who, radius, kKltMaxRadius);
+    OFPS_REQUIRE(ctx, iters >= 1 && iters <= kKltMaxIters, "%s: iters %d outside [1, %d]", who, iters, kKltMaxIters);
+    return OFPS_HIP_OK;
 }
 
-// features of prev -> pyramid of both frames -> track -> status flags -> the ordered compaction -> count on the device.  Enqueues on
-// ctx->stream, synchronises nothing.  d_out: capacity = the slot count; d_slots (optional): 6 int32 per slot.  d_prev_slots (N3p, optional):
-// the previous pair's raw slots on the same lattice, every feature starts from its slot's predicted guess; null: the launches without N3p
-int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
-                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots) {
+// THE driver of every flow form (common.hpp: KltFlowCall).  Both scratch slots are written and read on ctx->stream alone and are dead behind the
+// compaction, so two tickets of the batched stream share them; scratch() waits for that stream before it frees a slot it has to grow, which is
+// all the order they need.  One pair of the one-pair form is the batch form at pairs = 1 in everything but the kernels: the two branch where
+// those differ, the score launch and the track launch, and nowhere else
+int klt_flow_device(ofps_hip_ctx* ctx, const KltFlowCall& c) {
+    const SadFrames& f = c.f;
     const KltSettings s = klt_settings(ctx);
-    const size_t ns = klt_slots(W, H, s.cell);
-    const size_t o_raw = pad16(ns * 3 * sizeof(int)), o_flag = o_raw + ns * sizeof(float4);
-    // N3i (intra ratio above 0): [the tracks' quads, 4 i32 per slot][candidate and intra counters, 2 x u32] behind the flags
-    const int intra = ctx->opt.klt_intra;
-    const size_t o_quad = o_flag + pad16(ns), o_cnt = o_quad + ns * 4 * sizeof(int);
-    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, intra > 0 ? o_cnt + 16 : o_quad));
-    if (!work) return OFPS_HIP_ENOMEM;
-    auto* d_feat = reinterpret_cast<int*>(work);
-    auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
-    auto* d_flag = reinterpret_cast<uint8_t*>(work + o_flag);
-    int rc = klt_features_device(ctx, d_prev, W, H, stride, s, d_feat);
-    if (rc != OFPS_HIP_OK) return rc;
-    KltTrackParams p{};
-    rc = klt_pyramid_device(ctx, d_prev, d_cur, W, H, stride, levels, &p.lv);
-    if (rc != OFPS_HIP_OK) return rc;
-    p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
-    p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)ns;
-    p.out_quad = intra > 0 ? reinterpret_cast<int*>(work + o_quad) : nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
-    // the predictor runs inside the track kernel, in front of the wave's first level: no launch and no array of guesses between the two
-    if (d_prev_slots) rc = klt_track_pred_launch(ctx, p, nullptr, d_prev_slots, (W + s.cell - 1) / s.cell, (H + s.cell - 1) / s.cell);
-    else rc = klt_track_launch(ctx, p);
-    if (rc != OFPS_HIP_OK) return rc;
-    if (intra > 0) {
-        // N3i: the verdict, and the cut, rewrite flags and statuses in front of the compaction -- and of the next pair's track launch, which
-        // reads d_slots on this stream
-        auto* d_cnt = reinterpret_cast<uint32_t*>(work + o_cnt);
-        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
-        const KltIntraCall c{d_prev, 0, W, H, stride, radius, (int)ns, d_feat, 0, p.out_quad, d_flag, d_cnt, intra, ctx->opt.klt_cut};
-        rc = klt_intra_device(ctx, c, 0, 1, d_slots);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_count) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_count);
-}
-
-// N3b.  S_KLT_WORK: [triples of the distinct prev frames][raw records, pairs x slots][keep flags, pairs x slots].  Both scratch slots are
-// written and read on ctx->stream alone and are dead behind the compaction, so two tickets of the batched stream share them; scratch() waits
-// for that stream before it frees a slot it has to grow, which is all the order they need.
-// chained (N3pb): the track step is one launch per item, item k started from item k - 1's raw slots, item 0 from d_prev_slots (null: from zero);
-// a caller that wants no slots has them in S_KLT_WORK, behind the flags ([raw slots, 6 i32 per slot of the batch]), where they are dead behind
-// the last track launch.  d_last_slots (optional): where the last item's raw slots go instead, for the call that follows
-int klt_flow_batch_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int levels, int radius, int iters, float4* d_out, uint32_t* d_counts,
-                          int* d_slots, bool chained, const int* d_prev_slots, int* d_last_slots) {
-    const KltSettings s = klt_settings(ctx);
-    const size_t ns = klt_slots(f.W, f.H, s.cell);
+    const KltLattice lat = klt_lattice(f.W, f.H, s.cell);
+    const size_t ns = lat.slots();
+    const int pairs = c.pairs;
     OFPS_REQUIRE(ctx, pairs >= 1 && (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)",
                  pairs, ns);
-    const size_t total = (size_t)pairs * ns;
     const int scored = f.prev_pitch ? pairs : 1;              // the distinct prev frames
-    const size_t o_raw = pad16((size_t)scored * ns * 3 * sizeof(int)), o_flag = o_raw + total * sizeof(float4);
-    const size_t o_wslots = o_flag + pad16(total);            // chained, and the caller takes no slots: they lie here
-    // N3i (intra ratio above 0): [the tracks' quads, 4 i32 per slot of the batch][candidate and intra counters, 2 x u32 per item] behind them
     const int intra = ctx->opt.klt_intra;
-    const size_t o_quad = pad16(o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)), o_cnt = o_quad + total * 4 * sizeof(int);
-    auto* work = static_cast<char*>(scratch(ctx, S_KLT_WORK, intra > 0 ? o_cnt + pad16((size_t)pairs * 2 * sizeof(uint32_t))
-                                                                        : o_wslots + (chained && !d_slots ? total * 6 * sizeof(int) : 0)));
-    if (!work) return OFPS_HIP_ENOMEM;
-    auto* d_feat = reinterpret_cast<int*>(work);
-    auto* d_raw = reinterpret_cast<float4*>(work + o_raw);
-    auto* d_flag = reinterpret_cast<uint8_t*>(work + o_flag);
-    if (chained && !d_slots) d_slots = reinterpret_cast<int*>(work + o_wslots);
-    int rc = klt_features_batch_device(ctx, f.prev_base, f.prev_pitch, scored, f.W, f.H, f.stride, s, d_feat);
+    KltWork w;
+    if (!w.make(ctx, pairs, scored, ns, c.chained && !c.d_slots, intra > 0)) return OFPS_HIP_ENOMEM;
+    int* const d_slots = w.slots ? w.slots : c.d_slots;
+    int rc = c.batch ? klt_features_batch_device(ctx, f.prev_base, f.prev_pitch, scored, f.W, f.H, f.stride, s, w.feat)
+                     : klt_features_device(ctx, f.prev_base, f.W, f.H, f.stride, s, w.feat);
     if (rc != OFPS_HIP_OK) return rc;
     KltTrackBatchParams b{};
-    rc = klt_pyramid_batch_device(ctx, f, pairs, levels, &b);
+    rc = klt_pyramid_device(ctx, f, pairs, c.levels, &b);
     if (rc != OFPS_HIP_OK) return rc;
     KltTrackParams& p = b.t;
-    p.L = levels; p.w = radius; p.K = iters; p.min_eig = s.min_eig; p.max_residual = s.max_residual;
-    p.pts = d_feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)total;
-    p.out_quad = intra > 0 ? reinterpret_cast<int*>(work + o_quad) : nullptr; p.out_slots = d_slots; p.out_rec = d_raw; p.out_flag = d_flag;
+    klt_track_settings(ctx, c.levels, c.radius, c.iters, &p);
+    p.pts = w.feat; p.pt_stride = 3; p.from_features = 1; p.n = (int)(pairs * ns);
+    p.out_quad = w.quad; p.out_slots = d_slots; p.out_rec = w.raw; p.out_flag = w.flag;
     b.slots_per_item = (int)ns; b.shared_features = f.prev_pitch ? 0 : 1;
+    // N3i: the verdict, and the cut, rewrite flags and statuses in front of the compaction -- and of the track launch that reads these raw slots
+    // next on this stream: the next pair's, or in a chained batch item k + 1's, so there item k's verdict goes right behind item k's launch
     KltIntraCall ic{};
     if (intra > 0) {
-        auto* d_cnt = reinterpret_cast<uint32_t*>(work + o_cnt);
-        OFPS_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)pairs * 2 * sizeof(uint32_t), ctx->stream));
-        ic = KltIntraCall{f.prev_base, f.prev_pitch, f.W, f.H, f.stride, radius, (int)ns, d_feat, f.prev_pitch ? ns * 3 : 0, p.out_quad, d_flag, d_cnt,
+        OFPS_HIP_TRY(ctx, hipMemsetAsync(w.cnt, 0, (size_t)pairs * 2 * sizeof(uint32_t), ctx->stream));
+        ic = KltIntraCall{f.prev_base, f.prev_pitch, f.W, f.H, f.stride, c.radius, (int)ns, w.feat, f.prev_pitch ? ns * 3 : 0, w.quad, w.flag, w.cnt,
                           intra, ctx->opt.klt_cut};
     }
-    // N3i in a chained batch: item k's verdict and cut go behind item k's track launch and in front of item k + 1's, which reads the statuses
-    if (chained) rc = klt_track_batch_pred_launch(ctx, b, pairs, (f.W + s.cell - 1) / s.cell, (f.H + s.cell - 1) / s.cell, d_prev_slots, d_last_slots,
-                                                  intra > 0 ? &ic : nullptr);
+    if (c.chained) rc = klt_track_chained_launch(ctx, b, pairs, lat, c.d_prev_slots, c.d_last_slots, intra > 0 ? &ic : nullptr);
     else {
-        rc = klt_track_batch_launch(ctx, b);
+        if (c.batch) rc = klt_track_launch(ctx, kKltTrackBatch, p.n, b);
+        // N3p: the predictor runs inside the track kernel, in front of the wave's first level: no launch and no array of guesses between the two
+        else if (c.d_prev_slots) rc = klt_track_launch(ctx, kKltTrackPred, p.n, KltTrackPredParams{p, nullptr, c.d_prev_slots, lat.nx, lat.ny});
+        else rc = klt_track_launch(ctx, kKltTrack, p.n, p);
         if (rc == OFPS_HIP_OK && intra > 0) rc = klt_intra_device(ctx, ic, 0, pairs, d_slots);
     }
     if (rc != OFPS_HIP_OK) return rc;
     // one workgroup per item is right for a batch; ONE pair through it would scan a 4K frame's 129,600 slots on one compute unit (measured:
     // 5 % of the pair's time), so a batch of one pair keeps the one-pair form's compactions, as SadFilter::finish does (sad_gate.hip)
-    if (pairs == 1) return ns <= kCompactSmallMax ? compact_small_device(ctx, d_raw, d_flag, ns, d_out, d_counts) : compact_entries_device(ctx, d_raw, d_flag, ns, d_out, d_counts);
-    return compact_items_device(ctx, d_raw, d_flag, ns, pairs, d_out, d_counts);
+    if (pairs == 1) return ns <= kCompactSmallMax ? compact_small_device(ctx, w.raw, w.flag, ns, c.d_out, c.d_counts) : compact_entries_device(ctx, w.raw, w.flag, ns, c.d_out, c.d_counts);
+    return compact_items_device(ctx, w.raw, w.flag, ns, pairs, c.d_out, c.d_counts);
+}
+
+int klt_flow_device(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int stride, int levels, int radius, int iters,
+                    float4* d_out, uint32_t* d_count, int* d_slots, const int* d_prev_slots) {
+    return klt_flow_device(ctx, KltFlowCall{SadFrames{d_prev, d_cur, 0, 0, W, H, stride}, 1, levels, radius, iters, d_out, d_count, d_slots, false, false,
+                                            d_prev_slots, nullptr});
 }
 
 }  // namespace ofps
@@ -1021,18 +965,19 @@ static int klt_track_dev_impl(ofps_hip_ctx* ctx, const void* d_prev, const void*
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && (n == 0 || (d_points && d_out_quads)), "klt_track: null device pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
-    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_track");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_track");
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return OFPS_HIP_OK;
-    KltTrackParams p{};
-    rc = klt_pyramid_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, levels, &p.lv);
+    KltTrackBatchParams b{};                                  // the two frames as a batch of one pair; the one-pair kernels take b.t
+    rc = klt_pyramid_device(ctx, ofps::SadFrames{static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, levels, &b);
     if (rc != OFPS_HIP_OK) return rc;
-    p.L = levels; p.w = radius; p.K = iters; p.min_eig = ctx->opt.klt_min_eig; p.max_residual = ctx->opt.klt_max_residual;
+    KltTrackParams& p = b.t;
+    klt_track_settings(ctx, levels, radius, iters, &p);
     p.pts = static_cast<const int*>(d_points); p.pt_stride = 2; p.from_features = 0; p.n = (int)n;
     p.out_quad = static_cast<int*>(d_out_quads);
-    if (d_guesses) return klt_track_pred_launch(ctx, p, static_cast<const int*>(d_guesses), nullptr, 0, 0);
-    return klt_track_launch(ctx, p, at_q);
+    if (d_guesses) return klt_track_launch(ctx, kKltTrackPred, p.n, KltTrackPredParams{p, static_cast<const int*>(d_guesses), nullptr, 0, 0});
+    return klt_track_launch(ctx, at_q ? kKltTrackQ : kKltTrack, p.n, p);
 }
 
 static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, const int32_t* points, size_t n,
@@ -1040,7 +985,7 @@ static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uin
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && (n == 0 || (points && out_quads)), "klt_track: null host pointer");
     OFPS_REQUIRE(ctx, n < (1ull << 28), "klt_track: too many points");
-    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_track");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_track");
     if (rc != OFPS_HIP_OK) return rc;
     const int xmax = at_q ? 256 * (W - 1) : W - 1, ymax = at_q ? 256 * (H - 1) : H - 1;
     for (size_t k = 0; k < n; ++k)
@@ -1129,15 +1074,11 @@ int ofps_hip_klt_flow_from_dev(ofps_hip_ctx* ctx, const void* d_prev, const void
                                const void* d_prev_slots, void* d_out_entries, void* d_out_count, void* d_out_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_prev && d_cur && d_out_entries && d_out_count, "klt_flow: null device pointer");
-    const int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_flow");
     if (rc != OFPS_HIP_OK) return rc;
-    if (d_prev_slots && d_out_slots) {
-        // a wave reads its neighbours' previous slots while other waves write theirs: the two arrays must not share a byte
-        const size_t bytes = klt_slots(W, H, ctx->opt.klt_cell) * 6 * sizeof(int);
-        const char* a = static_cast<const char*>(d_prev_slots);
-        const char* b = static_cast<const char*>(d_out_slots);
-        OFPS_REQUIRE(ctx, a + bytes <= b || b + bytes <= a, "klt_flow_from: d_prev_slots and d_out_slots overlap");
-    }
+    const size_t slot_bytes = klt_slots(W, H, ctx->opt.klt_cell) * 6 * sizeof(int);
+    rc = klt_check_apart(ctx, d_prev_slots, slot_bytes, d_out_slots, slot_bytes, "klt_flow_from");
+    if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return ofps::klt_flow_device(ctx, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), W, H, stride, levels, radius, iters,
                                  static_cast<float4*>(d_out_entries), static_cast<uint32_t*>(d_out_count), static_cast<int*>(d_out_slots),
@@ -1149,34 +1090,58 @@ int ofps_hip_klt_flow_dev(ofps_hip_ctx* ctx, const void* d_prev, const void* d_c
     return ofps_hip_klt_flow_from_dev(ctx, d_prev, d_cur, W, H, stride, levels, radius, iters, nullptr, d_out_entries, d_out_count, d_out_slots);
 }
 
+// S_KLT_HOST of the host-pointer flow forms: [records, pairs x slots][counts, a u32 per item][raw slots, 6 i32 per slot of the batch]; with_prev:
+// [the previous pair's raw slots, one item's].  d: null if the scratch slot could not be had
+struct KltHostIo {
+    size_t o_count, o_slots, o_prev;
+    char* d;
+    KltHostIo(ofps_hip_ctx* ctx, int pairs, size_t ns, bool with_prev)
+        : o_count((size_t)pairs * ns * sizeof(float4)), o_slots(o_count + pad16((size_t)pairs * sizeof(uint32_t))),
+          o_prev(o_slots + (size_t)pairs * ns * 6 * sizeof(int)),
+          d(static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_prev + (with_prev ? ns * 6 * sizeof(int) : 0)))) {}
+    float4* entries() const { return reinterpret_cast<float4*>(d); }
+    uint32_t* counts() const { return reinterpret_cast<uint32_t*>(d + o_count); }
+    int* slots() const { return reinterpret_cast<int*>(d + o_slots); }
+    int* prev_slots() const { return reinterpret_cast<int*>(d + o_prev); }
+};
+
+// what a finished run hands back: the counts, the raw slots (optional), then each item's kept records alone -- what lies behind them in the item's
+// slot is unspecified.  Waits for the stream
+static int klt_host_read(ofps_hip_ctx* ctx, const KltHostIo& io, int pairs, size_t ns, const char* who, float* out_entries, uint32_t* out_counts,
+                         int32_t* out_slots) {
+    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, io.counts(), (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, io.slots(), (size_t)pairs * ns * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < pairs; ++k) {
+        if (out_counts[k] > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "%s: the device counted %u records in %zu slots", who, out_counts[k], ns);
+        if (out_counts[k])
+            OFPS_HIP_TRY(ctx, hipMemcpy(out_entries + (size_t)k * ns * 4, io.entries() + (size_t)k * ns, (size_t)out_counts[k] * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    return OFPS_HIP_OK;
+}
+
 int ofps_hip_klt_flow_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
                            const int32_t* prev_slots, float* out_entries, uint32_t* n_out, int32_t* out_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, prev && cur && out_entries && n_out, "klt_flow: null host pointer");
-    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_flow");
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
     const int ss = (W + 63) & ~63;
-    const size_t fb = (size_t)ss * H, o_count = ns * sizeof(float4), o_slots = o_count + 16, o_prev = o_slots + ns * 6 * sizeof(int);
+    const size_t fb = (size_t)ss * H;
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
-    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_prev + (prev_slots ? ns * 6 * sizeof(int) : 0)));
-    if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
-    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io + o_prev, prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const KltHostIo io(ctx, 1, ns, prev_slots != nullptr);
+    if (!d_fr || !io.d) return OFPS_HIP_ENOMEM;
+    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(io.prev_slots(), prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr, ss, prev, stride, W, H, ctx->stream));
     OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + fb, ss, cur, stride, W, H, ctx->stream));
-    rc = ofps::klt_flow_device(ctx, d_fr, d_fr + fb, W, H, ss, levels, radius, iters, reinterpret_cast<float4*>(d_io),
-                               reinterpret_cast<uint32_t*>(d_io + o_count), out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr,
-                               prev_slots ? reinterpret_cast<const int*>(d_io + o_prev) : nullptr);
-    if (rc != OFPS_HIP_OK) return rc;
-    uint32_t count = 0;
-    OFPS_HIP_TRY(ctx, hipMemcpyAsync(&count, d_io + o_count, sizeof(count), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_io + o_slots, ns * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (count > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "klt_flow: the device counted %u records in %zu slots", count, ns);
-    if (count) OFPS_HIP_TRY(ctx, hipMemcpy(out_entries, d_io, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost));
-    *n_out = count;
-    return OFPS_HIP_OK;
+    rc = ofps::klt_flow_device(ctx, d_fr, d_fr + fb, W, H, ss, levels, radius, iters, io.entries(), io.counts(), out_slots ? io.slots() : nullptr,
+                               prev_slots ? io.prev_slots() : nullptr);
+    uint32_t count = 0;                                       // n_out is written on success alone
+    if (rc == OFPS_HIP_OK) rc = klt_host_read(ctx, io, 1, ns, "klt_flow", out_entries, &count, out_slots);
+    if (rc == OFPS_HIP_OK) *n_out = count;
+    return rc;
 }
 
 int ofps_hip_klt_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int W, int H, int stride, int levels, int radius, int iters,
@@ -1190,22 +1155,17 @@ static int klt_flow_batch_dev_impl(ofps_hip_ctx* ctx, const void* d_frames, int 
                                    const void* d_prev_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, d_frames && d_out_entries && d_out_counts, "klt_flow_batch: null device pointer");
-    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
     if (rc == OFPS_HIP_OK) rc = klt_check_sequence(ctx, n_frames, H, stride, frame_pitch, ref_mode, "klt_flow_batch");
     if (rc != OFPS_HIP_OK) return rc;
-    if (d_prev_slots && d_out_slots) {
-        // item 0's waves read the previous slots while they, and later the other items, write the batch's: the two arrays must not share a byte
-        const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
-        const char* a = static_cast<const char*>(d_prev_slots);
-        const char* b = static_cast<const char*>(d_out_slots);
-        OFPS_REQUIRE(ctx, a + ns * 6 * sizeof(int) <= b || b + (size_t)(n_frames - 1) * ns * 6 * sizeof(int) <= a,
-                     "klt_flow_batch_from: d_prev_slots and d_out_slots overlap");
-    }
+    const size_t slot_bytes = klt_slots(W, H, ctx->opt.klt_cell) * 6 * sizeof(int);
+    rc = klt_check_apart(ctx, d_prev_slots, slot_bytes, d_out_slots, (size_t)(n_frames - 1) * slot_bytes, "klt_flow_batch_from");
+    if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ofps::SadFrames f = ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride);
-    return ofps::klt_flow_batch_device(ctx, f, n_frames - 1, levels, radius, iters, static_cast<float4*>(d_out_entries),
-                                       static_cast<uint32_t*>(d_out_counts), static_cast<int*>(d_out_slots), chained,
-                                       static_cast<const int*>(d_prev_slots));
+    return ofps::klt_flow_device(ctx, ofps::KltFlowCall{f, n_frames - 1, levels, radius, iters, static_cast<float4*>(d_out_entries),
+                                                        static_cast<uint32_t*>(d_out_counts), static_cast<int*>(d_out_slots), true, chained,
+                                                        static_cast<const int*>(d_prev_slots), nullptr});
 }
 
 // N3pb's switch: the plain batch entry points chain iff the context has both prediction settings on
@@ -1231,7 +1191,7 @@ static int klt_flow_batch_host_impl(ofps_hip_ctx* ctx, const uint8_t* frames, in
                                     const int32_t* prev_slots) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_REQUIRE(ctx, frames && out_entries && out_counts, "klt_flow_batch: null host pointer");
-    int rc = klt_check_track(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
+    int rc = klt_check_call(ctx, W, H, stride, levels, radius, iters, "klt_flow_batch");
     if (rc == OFPS_HIP_OK) rc = klt_check_sequence(ctx, n_frames, H, stride, frame_pitch, ref_mode, "klt_flow_batch");
     if (rc != OFPS_HIP_OK) return rc;
     const int pairs = n_frames - 1;
@@ -1239,30 +1199,18 @@ static int klt_flow_batch_host_impl(ofps_hip_ctx* ctx, const uint8_t* frames, in
     OFPS_REQUIRE(ctx, (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)", pairs, ns);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int ss = (W + 63) & ~63;
-    const size_t fb = (size_t)ss * H, total = (size_t)pairs * ns;
-    const size_t o_count = total * sizeof(float4), o_slots = o_count + pad16((size_t)pairs * sizeof(uint32_t));
+    const size_t fb = (size_t)ss * H;
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)n_frames * fb));
-    const size_t o_prev = o_slots + total * 6 * sizeof(int);
-    auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_prev + (prev_slots ? ns * 6 * sizeof(int) : 0)));
-    if (!d_fr || !d_io) return OFPS_HIP_ENOMEM;
-    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(d_io + o_prev, prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const KltHostIo io(ctx, pairs, ns, prev_slots != nullptr);
+    if (!d_fr || !io.d) return OFPS_HIP_ENOMEM;
+    if (prev_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(io.prev_slots(), prev_slots, ns * 6 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     for (int k = 0; k < n_frames; ++k)
         OFPS_HIP_TRY(ctx, ofps::upload_rows(d_fr + (size_t)k * fb, ss, frames + (size_t)k * frame_pitch, stride, W, H, ctx->stream));
-    rc = ofps::klt_flow_batch_device(ctx, ofps::SadFrames::sequence(d_fr, fb, ref_mode, W, H, ss), pairs, levels, radius, iters,
-                                     reinterpret_cast<float4*>(d_io), reinterpret_cast<uint32_t*>(d_io + o_count),
-                                     out_slots ? reinterpret_cast<int*>(d_io + o_slots) : nullptr, chained,
-                                     prev_slots ? reinterpret_cast<const int*>(d_io + o_prev) : nullptr);
+    rc = ofps::klt_flow_device(ctx, ofps::KltFlowCall{ofps::SadFrames::sequence(d_fr, fb, ref_mode, W, H, ss), pairs, levels, radius, iters, io.entries(),
+                                                      io.counts(), out_slots ? io.slots() : nullptr, true, chained,
+                                                      prev_slots ? io.prev_slots() : nullptr, nullptr});
     if (rc != OFPS_HIP_OK) return rc;
-    OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_counts, d_io + o_count, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_slots) OFPS_HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_io + o_slots, total * 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < pairs; ++k) {                         // an item's kept records alone: what lies behind them in its slot is unspecified
-        if (out_counts[k] > ns) return ofps::set_error(ctx, OFPS_HIP_EDEVICE, "klt_flow_batch: the device counted %u records in %zu slots", out_counts[k], ns);
-        if (out_counts[k])
-            OFPS_HIP_TRY(ctx, hipMemcpy(out_entries + (size_t)k * ns * 4, d_io + (size_t)k * ns * sizeof(float4), (size_t)out_counts[k] * sizeof(float4),
-                                        hipMemcpyDeviceToHost));
-    }
-    return OFPS_HIP_OK;
+    return klt_host_read(ctx, io, pairs, ns, "klt_flow_batch", out_entries, out_counts, out_slots);
 }
 
 int ofps_hip_klt_flow_batch(ofps_hip_ctx* ctx, const uint8_t* frames, int n_frames, int W, int H, int stride, size_t frame_pitch, int ref_mode,

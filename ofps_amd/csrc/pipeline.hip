@@ -446,7 +446,7 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
         uint32_t* d_cnt = filtered || klt ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
         const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
         if (klt) {
-            rc = klt_flow_batch_device(ctx, fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr, chained, d_pred_in, d_pred_out);
+            rc = klt_flow_device(ctx, KltFlowCall{fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr, true, chained, d_pred_in, d_pred_out});
             if (rc == OFPS_HIP_OK && chained) kp = {true, pred_half, W, H, o.klt_cell, ctx->scratch[ofps::S_KLT_BATCH_PRED].gen};
         } else if (filtered)
             rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,

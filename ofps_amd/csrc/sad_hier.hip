@@ -435,11 +435,7 @@ int refine_check(ofps_hip_ctx* ctx, const void* prev, const void* cur, const voi
 
 namespace ofps {
 
-// one frame -> its halved form, on ctx->stream: the level hip_klt's pyramid is made of (klt.hip)
-int sad_down2_device(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int src_stride, uint8_t* dst, int dst_stride) {
-    return down2_device(ctx, src, 0, W, H, src_stride, dst, 0, dst_stride, 1);
-}
-
+// `frames` frames -> their halved forms, on ctx->stream: the levels hip_klt's pyramid is made of (klt.hip)
 int sad_down2_frames_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch, int W, int H, int src_stride, uint8_t* dst, size_t dst_pitch,
                             int dst_stride, long long frames) {
     return down2_device(ctx, src, src_pitch, W, H, src_stride, dst, dst_pitch, dst_stride, frames);
