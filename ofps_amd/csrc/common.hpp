@@ -53,12 +53,43 @@ struct TicketRing {
 
 // What a fused ticket answers per frame, as the detector's and the estimator's last kernels store it (tail.hip).  The per-frame SAD
 // ticket (pipeline.hip: PipeOut) and the dense decoders' ticket (dense_decoder.hip: behind the records) hold one; a batch ticket holds
-// n results followed by n quaternions.
+// a BatchBlock.
 struct TailRecord {
     int result[4];                       // has_motion, area, dim, 0
     float quat[4];                       // (w, i, j, k)
 };
 static_assert(sizeof(TailRecord) == 32 && offsetof(TailRecord, quat) == 16 && sizeof(TailRecord::quat) == sizeof(float4), "result record layout");
+// A batch ticket's result block of n frames: [n results][n quaternions][n kept counts, only when the ticket is `counted`: the batch filter
+// or hip_klt].  The same layout in the push's device scratch and in the ticket's page-locked memory; nobody else spells it
+constexpr size_t kBatchResult = sizeof(TailRecord::result);
+static_assert(kBatchResult + sizeof(TailRecord::quat) == sizeof(TailRecord), "batch block layout");
+struct BatchBlock {
+    size_t n; bool counted;
+    constexpr size_t quat_at() const { return n * kBatchResult; }
+    constexpr size_t kept_at() const { return n * sizeof(TailRecord); }
+    constexpr size_t bytes() const { return kept_at() + (counted ? n * sizeof(uint32_t) : 0); }
+    int* result(char* base, size_t j) const { return reinterpret_cast<int*>(base) + 4 * j; }
+    float4* quat(char* base, size_t j) const { return reinterpret_cast<float4*>(base + quat_at()) + j; }
+    uint32_t* kept(char* base) const { return counted ? reinterpret_cast<uint32_t*>(base + kept_at()) : nullptr; }      // word j: frame j's
+};
+static_assert(BatchBlock{1, false}.bytes() == 32 && BatchBlock{1, true}.bytes() == 36 && BatchBlock{5, true}.bytes() == 5 * 32 + 5 * 4, "batch block size");
+static_assert(BatchBlock{1, false}.quat_at() == 16 && BatchBlock{1, true}.quat_at() == 16 && BatchBlock{5, true}.quat_at() == 5 * 16, "batch block quaternions");
+static_assert(BatchBlock{1, false}.kept_at() == 32 && BatchBlock{1, true}.kept_at() == 32 && BatchBlock{5, true}.kept_at() == 5 * 32, "batch block counts");
+// What every fused wait answers: zeros and the identity quaternion, then what the ticket has.  n_vectors: already clamped by the caller;
+// result (int[4]) / quat (float[4]): null for a stage that did not run or a frame without vectors; they need no alignment
+inline void fill_frame_result(ofps_hip_frame_result* out, int have_vectors, size_t n_vectors, const void* result, const void* quat) {
+    memset(out, 0, sizeof(*out));
+    out->quat[0] = 1.0f;
+    out->have_vectors = have_vectors;
+    out->n_vectors = n_vectors;
+    if (result) {
+        int res[4];
+        memcpy(res, result, sizeof(res));
+        out->has_motion = res[0]; out->area = (size_t)res[1]; out->dim = res[2];
+    }
+    if (quat) memcpy(out->quat, quat, sizeof(out->quat));
+}
+inline int padded_stride(int W) { return (W + 63) & ~63; }     // the device rows of every repacked frame: 64-byte multiples, so any host stride is accepted
 constexpr int kMaxDetectDim = 160;       // the detector's field is at most 160 x 160 vectors
 constexpr size_t kMaxFieldBytes = (size_t)kMaxDetectDim * kMaxDetectDim * sizeof(float2);
 
@@ -150,9 +181,9 @@ struct BatchStream {
         bool pending = false;
         hipEvent_t done = nullptr, uploaded = nullptr, prev_copied = nullptr;
         bool prev_copied_valid = false;
-        void* pinned = nullptr; size_t pinned_cap = 0;       // [n results][n quaternions][n kept counts, filtered tickets only]
+        void* pinned = nullptr; size_t pinned_cap = 0;       // a BatchBlock of n frames
         int n = 0, first_has_prev = 0, run_detector = 0, run_estimator = 0;
-        int filtered = 0;                // pushed with the batch filter switch and a criterion on: n kept counts follow the quaternions in the page-locked block
+        int filtered = 0;                // pushed with the batch filter switch and a criterion on, or with hip_klt, and with a pair to run: the block's kept counts are n_vectors
         size_t n_vectors = 0;
         IslandsTicket isl;               // A5i
     };
@@ -555,13 +586,25 @@ int sad_split_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block
 // fused per-frame path (pipeline.hip) makes the contrast flags and the activities on its auxiliary stream, beside the search.  Every per-block array holds pairs x nblk, item-major,
 // and every step is one launch whatever `pairs`.  With gate == 0, limit == 0 and median == 0 search() is the plain search into d_out and no
 // other step reserves or enqueues anything; the same holds for intra == 0 (cut alone does nothing).
-struct SadFilter {
+// SadCriteria: the six settings of a filtered search as one value, every one 0 = off.  The context's are of(ctx->opt); an explicit-argument
+// entry point writes out the ones it takes and leaves the rest 0
+struct SadCriteria {
+    int gate = 0, limit = 0, median = 0; // the contrast gate's min_pixels, the consistency check's limit, the median test's limit
+    int intra = 0, cut = 0;              // the intra test's ratio in sixteenths; the scene-cut rule's percentage, no effect while intra == 0
+    int split = 0;                       // the split step's threshold in sixteenths (N1s); one pair only
+    static SadCriteria of(const ofps_hip_ctx::Options& o) { return {o.sad_gate, o.sad_consistency, o.sad_median, o.sad_intra, o.sad_cut, o.sad_split}; }
+    SadCriteria without_split() const { return {gate, limit, median, intra, cut, 0}; }      // the batched forms take none
+    bool criteria() const { return gate > 0 || limit > 0 || median > 0 || intra > 0; }         // something drops blocks
+    bool on() const { return criteria() || split > 0; }   // the record count is variable and lives on the device
+    bool winners() const { return limit > 0 || median > 0 || intra > 0 || split > 0; }       // all four read the forward search's INTEGER winners, whatever the motion scale
+};
+struct SadFilter : SadCriteria {
     SadFrames fr;                        // plan() and reserve() read the geometry alone: the bases may be filled in behind them (pipeline.hip)
     int pairs, block, range;
-    int gate, limit, median;             // the contrast gate's min_pixels, the consistency check's limit, the median test's limit; 0 = off
-    int intra, cut;                      // the intra test's ratio in sixteenths, 0 = off; the scene-cut rule's percentage, 0 = off and no effect while intra == 0
     bool want_triples;                   // the caller takes the kept records' (dx, dy, SAD) triples as well
-    int split = 0;                       // the split step's threshold in sixteenths (N1s), 0 = off; one pair only
+    static SadFilter make(const SadFrames& fr, int pairs, int block, int range, const SadCriteria& c, bool want_triples) {     // the one way to make one
+        return {c, fr, pairs, block, range, want_triples};
+    }
     size_t nblk = 0;                     // per pair
     float4* d_raw = nullptr;             // S_GATE_RAW: the search's one record per block, in front of the compaction
     char* d_flags = nullptr;             // S_GATE_FLAGS, this ticket's block: [counts][kept count][keep flags]
@@ -573,9 +616,6 @@ struct SadFilter {
     int* d_sub_best = nullptr;           // S_SPLIT (split > 0): the raw slots' records (d_split_raw), the sub-blocks' triples, slot flags and split flags
     float4* d_split_raw = nullptr;
     uint8_t *d_slot_flags = nullptr, *d_split = nullptr;
-    bool criteria() const { return gate > 0 || limit > 0 || median > 0 || intra > 0; }         // something drops blocks
-    bool on() const { return criteria() || split > 0; }   // the record count is variable and lives on the device
-    bool winners() const { return limit > 0 || median > 0 || intra > 0 || split > 0; }       // all four read the forward search's INTEGER winners, whatever the motion scale
     size_t total() const { return (size_t)pairs * nblk; }
     size_t capacity() const { return split > 0 ? 4 * nblk : nblk; }       // records d_out must hold, per pair
     uint32_t* kept() const { return on() ? gate_kept(d_flags, nblk, pairs) : nullptr; }
@@ -594,9 +634,8 @@ struct SadFilter {
     int finish_split(ofps_hip_ctx* ctx, const uint8_t* flags, float4* d_out, int* d_out_best, uint32_t* d_count);     // finish()'s last step with split > 0
 };
 // the five steps on ctx->stream, the launch count independent of `pairs`; `who` leads every error text, tix / tickets: SadFilter::reserve
-int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
-                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1, int intra = 0,
-                             int cut = 0, int split = 0);
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, const SadCriteria& c, float4* d_out,
+                             int* d_out_best, uint32_t* d_counts, const char* who, int tix = 0, int tickets = 1);
 
 // compensate.hip: out = (pos, motion - camera.delta(pos, to_homogeneous(inverse(quat[item])))) per record, batch items of n records; the quaternions
 // are read on the device.  d_n (optional): the record counts in device memory, one per item, n the capacity.  d_out may equal d_entries.

@@ -504,28 +504,19 @@ int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_r
     if (!t) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
-    memset(out, 0, sizeof(*out));
-    out->quat[0] = 1.0f;                                   // identity / no motion: a stream's first frame, a plain ticket, a stage that did not run
-    out->have_vectors = t->have_vectors;
+    // identity / no motion: a stream's first frame, a plain ticket, a stage that did not run
+    const char* blk = static_cast<const char*>(t->pinned);
+    const char* tail = t->have_vectors && t->fused ? blk + t->tail_off : nullptr;
+    uint32_t cnt = 0;
+    if (t->have_vectors) memcpy(&cnt, blk, sizeof(cnt));
+    if (cnt > t->max_records) cnt = (uint32_t)t->max_records;
+    ofps::fill_frame_result(out, t->have_vectors, cnt, tail && t->run_detector ? tail + kTailResult : nullptr, tail && t->run_estimator ? tail + kTailQuat : nullptr);
     if (out_w) *out_w = t->gw;
     if (out_h) *out_h = t->gh;
     const int isl_rc = ofps::islands_collect(ctx, t->isl);             // (a plain ticket: none)
     if (isl_rc != OFPS_HIP_OK) return isl_rc;
-    if (!t->have_vectors) return OFPS_HIP_OK;
-    const char* blk = static_cast<const char*>(t->pinned);
-    uint32_t cnt = 0;
-    memcpy(&cnt, blk, sizeof(cnt));
-    if (cnt > t->max_records) cnt = (uint32_t)t->max_records;
-    out->n_vectors = cnt;
     if (out_entries && cnt) memcpy(out_entries, blk + kBlockHeader, (size_t)cnt * sizeof(float4));
-    if (!t->fused) return OFPS_HIP_OK;
-    if (t->run_detector) {
-        int res[4];
-        memcpy(res, blk + t->tail_off + kTailResult, sizeof(res));
-        out->has_motion = res[0]; out->area = (size_t)res[1]; out->dim = res[2];
-        if (out_field) memcpy(out_field, blk + t->tail_off + kTailField, (size_t)t->dim * t->dim * sizeof(float2));
-    }
-    if (t->run_estimator) memcpy(out->quat, blk + t->tail_off + kTailQuat, sizeof(out->quat));
+    if (tail && t->run_detector && out_field) memcpy(out_field, tail + kTailField, (size_t)t->dim * t->dim * sizeof(float2));
     return OFPS_HIP_OK;
 }
 

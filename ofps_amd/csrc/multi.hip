@@ -323,7 +323,7 @@ int ofps_hip_multi_stage_frames(ofps_hip_multi* m, const uint8_t* frames, int n_
         return multi_error(m, OFPS_HIP_EINVAL, "multi_stage_frames: bad arguments (n_frames=%d W=%d H=%d stride=%d ref_mode=%d)", n_frames, W, H,
                            stride, ref_mode);
     const int n = (int)m->w.size();
-    m->W = W; m->H = H; m->dstride = (W + 63) & ~63; m->pitch = (size_t)m->dstride * H; m->ref_mode = ref_mode;
+    m->W = W; m->H = H; m->dstride = ofps::padded_stride(W); m->pitch = (size_t)m->dstride * H; m->ref_mode = ref_mode;
     m->total_pairs = (size_t)n_frames - 1;
     m->staged = false;
     m->stage_gen += 1;                         // whatever the workers' result buffers hold belongs to an older batch now

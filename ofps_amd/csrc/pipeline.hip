@@ -26,8 +26,6 @@ constexpr size_t kPipeField = 4096;                             // the detector'
 constexpr size_t kPipeOutBytes = kPipeField + ofps::kMaxFieldBytes;
 static_assert(offsetof(PipeOut, r) == 0 && kPipeOutPlain == sizeof(TailRecord) && sizeof(PipeOut) == 48 && sizeof(PipeOut) <= kPipeField, "PipeOut layout");
 constexpr int kSlots = PipeStream::kSlots, kTickets = PipeStream::kTickets;
-constexpr size_t kBatchResult = sizeof(TailRecord::result);     // a batch ticket's block: [n results][n quaternions]
-static_assert(kBatchResult + sizeof(TailRecord::quat) == sizeof(TailRecord), "batch block layout");
 
 #ifndef OFPS_HIP_UPLOAD_KERNEL_SINGLE
 #define OFPS_HIP_UPLOAD_KERNEL_SINGLE 0          // A/B (tools/upload_ab.sh): the single-frame form through the upload kernel as well (transfer.hip)
@@ -68,7 +66,7 @@ int pipe_upload(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, int stride
                 size_t* pitch_out, int* dstride_out) {
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    const int dstride = (W + 63) & ~63;
+    const int dstride = ofps::padded_stride(W);
     const size_t pitch = (size_t)dstride * H;
     if (W != ctx->pipe.w || H != ctx->pipe.h) {            // geometry change restarts the stream (decoder.rs:66-72)
         rc = pipe_drain(ctx);
@@ -239,8 +237,8 @@ int ofps_hip_push_frame_async(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    Push p{ctx, prm, {{nullptr, nullptr, 0, 0, W, H, (W + 63) & ~63}, 1, prm->block, prm->range, ctx->opt.sad_gate, ctx->opt.sad_consistency,
-                      ctx->opt.sad_median, ctx->opt.sad_intra, ctx->opt.sad_cut, /*want_triples=*/false, ctx->opt.sad_split}};
+    Push p{ctx, prm, ofps::SadFilter::make({nullptr, nullptr, 0, 0, W, H, ofps::padded_stride(W)}, 1, prm->block, prm->range, ofps::SadCriteria::of(ctx->opt),
+                                           /*want_triples=*/false)};
     rc = p.claim();                                     // refused before anything is uploaded
     if (rc == OFPS_HIP_OK) rc = p.upload(luma, stride);
     if (rc == OFPS_HIP_OK && p.frame_no > 0) {          // (the first frame of a stream: Ok(false), no vectors yet)
@@ -273,22 +271,14 @@ int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* ou
         }
     }
     t->pending = false;
-    memset(out, 0, sizeof(*out));
-    out->quat[0] = 1.0f;
-    out->have_vectors = t->have_vectors;
-    out->n_vectors = t->n_vectors;
-    if (t->have_vectors) {
-        const auto* host = static_cast<const PipeOut*>(t->pinned);
-        if (t->gated) out->n_vectors = host->kept[0] < t->n_vectors ? host->kept[0] : t->n_vectors;
-        if (t->run_detector) {
-            out->has_motion = host->r.result[0];
-            out->area = (size_t)host->r.result[1];
-            out->dim = host->r.result[2];
-        }
-        if (t->run_estimator) memcpy(out->quat, host->r.quat, sizeof(out->quat));
-    }
+    const auto* host = static_cast<const PipeOut*>(t->pinned);
+    const bool has = t->have_vectors != 0;
+    ofps::fill_frame_result(out, t->have_vectors, has && t->gated && host->kept[0] < t->n_vectors ? host->kept[0] : t->n_vectors,
+                            has && t->run_detector ? host->r.result : nullptr, has && t->run_estimator ? host->r.quat : nullptr);
     return ofps::islands_collect(ctx, t->isl);
 }
+
+}  // extern "C"
 
 // ---- batched read-ahead form: n consecutive frames of the stream per ticket.  What a decoder that runs n frames ahead
 // (ofps-suite/src/app/tracking/worker.rs:165-226 decodes into a buffer on its own thread) hands over in one go: ONE H2D of the
@@ -296,9 +286,204 @@ int ofps_hip_frame_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* ou
 // launch over the batch, one read-back -- a handful of HIP calls per BATCH instead of ~9 per frame, which is what kept
 // the single-frame loop 20 % under the PCIe ceiling.  Frame j of the batch is pair (previous frame of the stream, frame
 // j); the previous frame of frame 0 is the last frame of the previous batch, kept in slot 0 of the other batch buffer.
-}  // extern "C"
-
+// The push is BatchPush's steps in the order claim -> reserve -> upload -> [decode -> tail -> read_back] -> commit, as the per-frame
+// form's is Push's; the ticket's result block is a BatchBlock (common.hpp).
 namespace ofps {
+namespace {
+// One push_frames_impl call, step by step.  Every step enqueues or returns an error; none touches the ring (commit does, last), and none
+// but commit writes the ticket, with two exceptions where they always were: prev_copied_valid in front of the copy, the islands arming at
+// the end of upload(), in front of the tail that takes it.  claim() refuses before anything is uploaded.  The settings are the context's at this push:
+//   klt      -- the batch decoder switch (include/ofps_hip.h N3b): hip_klt in place of the search; the slot count takes the block count's
+//               place in every size, the kept counts travel where the batch filter's do
+//   filtered -- the batch filter switch (N1b) with a criterion on: the filtered batched search and the tail's per-item device counts
+//   chained  -- N3pb, both prediction settings on: the ticket's items are chained, item 0 behind the last item of the ticket before.  That
+//               item's raw slots wait in one half of S_KLT_BATCH_PRED (d_pred_in), this ticket's last item writes the other (d_pred_out).
+//               Any other ticket -- a setting off, the search, a multi-device worker's (halo_mode 1: a worker sees every n-th batch, its first
+//               item has no predecessor there) -- leaves no slots behind: its successor starts from zero
+// With all three off nothing differs from the plain batched search.
+struct BatchPush {
+    ofps_hip_ctx* ctx;
+    const ofps_hip_frame_params* prm;
+    const uint8_t* frames; int n, W, H, stride; size_t frame_pitch;
+    int halo_mode; const uint8_t* halo; int halo_stride;
+    static constexpr int kTickets = BatchStream::kTickets;
+    int dstride = 0; size_t pitch = 0;   // the frames on the device
+    long tno = 0; BatchStream::Ticket* t = nullptr; int tix = 0;
+    bool klt = false, filtered = false, chained = false;
+    size_t nblk = 0;                     // records per frame: blocks, or hip_klt's slots
+    SadCriteria crit;                    // filtered: what the search follows (no split: the batched forms take none)
+    BatchBlock blk{0, false};
+    const int* d_pred_in = nullptr; int* d_pred_out = nullptr; int pred_half = 0;
+    uint8_t* buf = nullptr;              // this ticket's batch buffer: [slot 0 = previous frame][n frames]
+    float4* d_ent = nullptr; char* d_out = nullptr;      // this ticket's records and its block
+    bool has_prev = false;
+    int first = 0, pairs = 0;            // pairs (slot j, slot j + 1), j = first .. n - 1: the stream's very first frame has no pair
+    float4* ent0() const { return d_ent + (size_t)first * nblk; }
+    uint32_t* d_cnt() const { return blk.counted ? blk.kept(d_out) + first : nullptr; }     // item j's count is word j behind the quaternions
+
+    int claim() {
+        tno = ctx->batch.ring.next;
+        t = &ctx->batch.ring.at(tno);
+        OFPS_REQUIRE(ctx, !t->pending, "push_frames_async: ticket %ld has not been collected (at most %d batches in flight)",
+                     tno - kTickets, kTickets);
+        if (!t->done) {
+            OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t->done, hipEventDisableTiming));
+            OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t->uploaded, hipEventDisableTiming));
+            OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t->prev_copied, hipEventDisableTiming));
+        }
+        if (W != ctx->batch.w || H != ctx->batch.h) {              // geometry change restarts the stream
+            OFPS_HIP_TRY(ctx, ctx->batch.ring.drain());
+            ctx->batch.w = W; ctx->batch.h = H; ctx->batch.last_frame = nullptr;
+            ctx->batch.klt_pred.valid = false;
+        }
+        dstride = padded_stride(W);
+        pitch = (size_t)dstride * H;
+        tix = (int)(tno % kTickets);
+        const auto& o = ctx->opt;
+        klt = o.batch_decoder == OFPS_HIP_BATCH_DECODER_KLT;
+        if (klt) {                                                   // a frame the decoder refuses is refused here
+            const int rc = klt_check_call(ctx, W, H, dstride, o.klt_levels, o.klt_radius, o.klt_iters, "push_frames_async");
+            if (rc != OFPS_HIP_OK) return rc;
+            OFPS_REQUIRE(ctx, (unsigned long long)n * ofps_hip_klt_slot_count(W, H, o.klt_cell) < (1ull << 31), "push_frames_async: %d frames of %zu slots", n,
+                         ofps_hip_klt_slot_count(W, H, o.klt_cell));
+        }
+        nblk = klt ? ofps_hip_klt_slot_count(W, H, o.klt_cell) : ofps_hip_sad_block_count(W, H, prm->block);
+        BatchStream::KltPred& kp = ctx->batch.klt_pred;
+        chained = klt && !halo_mode && o.klt_prediction && o.klt_batch_prediction;
+        if (chained) {
+            const size_t half = (nblk * 6 * sizeof(int) + 255) & ~(size_t)255;
+            auto* d_pred = static_cast<char*>(scratch(ctx, S_KLT_BATCH_PRED, 2 * half));
+            if (!d_pred) return OFPS_HIP_ENOMEM;
+            if (kp.valid && ctx->batch.last_frame && kp.w == W && kp.h == H && kp.cell == o.klt_cell && kp.gen == ctx->scratch[S_KLT_BATCH_PRED].gen)
+                d_pred_in = reinterpret_cast<const int*>(d_pred + (size_t)kp.half * half);
+            else kp.half = 0;
+            d_pred_out = reinterpret_cast<int*>(d_pred + (size_t)(kp.half ^ 1) * half);
+        }
+        pred_half = kp.half ^ 1;
+        crit = SadCriteria::of(o).without_split();
+        filtered = !klt && o.sad_batch_filter && crit.criteria();
+        blk = {(size_t)n, filtered || klt};
+        return filtered ? SadFilter::make({nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, crit, /*want_triples=*/false).plan(ctx, "push_frames_async")
+                        : OFPS_HIP_OK;
+    }
+
+    // capacity: both buffers and the per-ticket outputs are sized for the largest batch seen (grow-only; growing waits for work in flight)
+    int reserve() {
+        const size_t cap_frames = (size_t)n + 1;
+        auto& fs = ctx->scratch[S_BATCH_FRAMES];
+        size_t per_buf = fs.cap / kTickets / (pitch ? pitch : 1);
+        if (per_buf < cap_frames) {
+            OFPS_HIP_TRY(ctx, ctx->batch.ring.drain(/*forget=*/false));
+            // the newest frame of the stream lives in the old allocation: keep a copy
+            void* keep = nullptr;
+            if (ctx->batch.last_frame) {
+                OFPS_HIP_TRY(ctx, hipMalloc(&keep, pitch));
+                OFPS_HIP_TRY(ctx, hipMemcpyAsync(keep, ctx->batch.last_frame, pitch, hipMemcpyDeviceToDevice, ctx->stream));
+                OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            auto* nb = static_cast<uint8_t*>(scratch(ctx, S_BATCH_FRAMES, kTickets * cap_frames * pitch));
+            if (!nb) { if (keep) (void)hipFree(keep); return OFPS_HIP_ENOMEM; }
+            per_buf = cap_frames;
+            if (keep) {
+                // parked in the LAST slot of the buffer this ticket does not use: nothing writes there before it is consumed
+                uint8_t* park = nb + ((size_t)(tix ^ 1) * per_buf + (per_buf - 1)) * pitch;
+                OFPS_HIP_TRY(ctx, hipMemcpyAsync(park, keep, pitch, hipMemcpyDeviceToDevice, ctx->stream));
+                OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                (void)hipFree(keep);
+                ctx->batch.last_frame = park;
+            }
+        }
+        buf = static_cast<uint8_t*>(fs.p) + (size_t)tix * per_buf * pitch;
+        auto* d_ent_all = static_cast<float4*>(scratch(ctx, S_BATCH_ENTRIES, kTickets * (size_t)n * nblk * sizeof(float4)));
+        auto* d_out_all = static_cast<char*>(scratch(ctx, S_BATCH_OUT, kTickets * blk.bytes()));
+        if (!d_ent_all || !d_out_all) return OFPS_HIP_ENOMEM;
+        d_ent = d_ent_all + (size_t)tix * (ctx->scratch[S_BATCH_ENTRIES].cap / kTickets / sizeof(float4));
+        d_out = d_out_all + (size_t)tix * (ctx->scratch[S_BATCH_OUT].cap / kTickets);
+        return host_block_reserve(ctx, &t->pinned, &t->pinned_cap, blk.bytes());
+    }
+
+    // copy stream: the n frames in one transfer (the buffer's previous tenant, ticket tno - 2, has been collected: its work is done);
+    // compute stream: the previous frame into slot 0, then the wait for the transfer
+    int upload() {
+        hipStream_t s = ctx->stream, up = ctx->pipe.copy_stream;
+        // the other ticket's copy of ITS previous frame reads slot n of this buffer's previous tenant: wait for it
+        auto& other = ctx->batch.ring.at(tno + 1);
+        if (other.pending && other.prev_copied_valid) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(up, other.prev_copied, 0));
+        if (frame_pitch == (size_t)W * H && stride == W && dstride == W) {
+            const int rc = upload_dense_device(ctx, buf + pitch, frames, (size_t)n * pitch, up, true);                        // the whole batch
+            if (rc != OFPS_HIP_OK) return rc;
+        } else {
+            for (int j = 0; j < n; ++j)
+                OFPS_HIP_TRY(ctx, upload_rows(buf + (size_t)(j + 1) * pitch, dstride, frames + (size_t)j * frame_pitch, stride, W, H, up));
+        }
+        if (halo_mode && halo) OFPS_HIP_TRY(ctx, upload_rows(buf, dstride, halo, halo_stride ? halo_stride : stride, W, H, up));       // the caller's previous frame into slot 0
+        OFPS_HIP_TRY(ctx, hipEventRecord(t->uploaded, up));
+        has_prev = halo_mode ? halo != nullptr : ctx->batch.last_frame != nullptr;
+        t->prev_copied_valid = false;
+        if (has_prev && !halo_mode) {
+            // by a copy KERNEL, not hipMemcpyAsync: the runtime may hand a device-to-device copy to the SDMA engine that is busy with the
+            // NEXT batch's 33 MB upload, and then this 2 MB copy -- and the search behind it -- waits 0.1-0.6 ms for that upload (transfer.hip)
+            const int rc = copy_words_device(ctx, buf, ctx->batch.last_frame, pitch / 4, 256, s);
+            if (rc != OFPS_HIP_OK) return rc;
+            OFPS_HIP_TRY(ctx, hipEventRecord(t->prev_copied, s));
+            t->prev_copied_valid = true;
+        }
+        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, t->uploaded, 0));
+        first = has_prev ? 0 : 1;
+        pairs = n - first;
+        // what holds whether or not a pair follows: no slots to chain from until decode() says so, and the ticket's islands
+        ctx->batch.klt_pred.valid = false;
+        if (halo_mode) t->isl.K = 0;                                 // the multi-device workers list no islands (include/ofps_hip.h A5i)
+        else islands_ticket_arm(ctx, &t->isl, prm, n);
+        return OFPS_HIP_OK;
+    }
+
+    // the one choice among the three decoders, on the compute stream: item j's [kept] records lead its slot of the record buffer [, its count
+    // is d_cnt()[j]; searches, flags and the compaction run in front of the tail that reads the counts there]
+    int decode() {
+        const auto& o = ctx->opt;
+        const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
+        if (klt) {
+            const int rc = klt_flow_device(ctx, KltFlowCall{fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0(), d_cnt(), nullptr, true, chained, d_pred_in, d_pred_out});
+            if (rc == OFPS_HIP_OK && chained) ctx->batch.klt_pred = {true, pred_half, W, H, o.klt_cell, ctx->scratch[S_KLT_BATCH_PRED].gen};
+            return rc;
+        }
+        if (filtered) return sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, crit, ent0(), nullptr, d_cnt(), "push_frames_async", tix, kTickets);
+        return sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0(), nullptr);
+    }
+
+    // one estimator launch, [one compensation launch,] one detector chain over the batch, item j seeded seed + j.  The multi-device
+    // dispatcher's worker contexts (halo_mode 1) keep the raw detector whatever their detect-compensation mode.  filtered: the tail's
+    // device-count forms with one count per item; fewer than 3 kept -> identity, as in the filtered per-frame path
+    int tail() {
+        float2* d_field = nullptr;
+        if (prm->run_detector) {
+            d_field = static_cast<float2*>(scratch(ctx, S_BATCH_FIELD, (size_t)pairs * kMaxFieldBytes));   // its own slot: the densifier works in S_WORK*
+            if (!d_field) return OFPS_HIP_ENOMEM;
+        }
+        return frame_tail_device(ctx, ent0(), nblk, pairs, d_cnt(), filtered ? 3 : 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode,
+                                 blk.result(d_out, first), blk.quat(d_out, first), d_field, nullptr, nullptr, &t->isl);
+    }
+
+    int read_back(float* out_entries) {
+        hipStream_t s = ctx->stream;
+        int rc = OFPS_HIP_OK;
+        if (blk.counted || prm->run_detector || prm->run_estimator) rc = read_back_device(ctx, t->pinned, d_out, blk.bytes(), s);     // (the kept counts travel in this read-back)
+        if (rc == OFPS_HIP_OK && out_entries) rc = read_back_device(ctx, out_entries + (size_t)first * nblk * 4, ent0(), (size_t)pairs * nblk * sizeof(float4), s);
+        return rc;
+    }
+
+    int commit(int* ticket) {
+        OFPS_HIP_TRY(ctx, hipEventRecord(t->done, ctx->stream));
+        ctx->batch.last_frame = buf + (size_t)n * pitch;
+        t->n = n; t->first_has_prev = has_prev ? 1 : 0; t->run_detector = prm->run_detector; t->run_estimator = prm->run_estimator; t->n_vectors = nblk;
+        t->filtered = blk.counted && pairs > 0;
+        *ticket = ctx->batch.ring.commit();
+        return OFPS_HIP_OK;
+    }
+};
+}  // namespace
+
 // halo_mode 0: frame 0 of the batch is paired with the context's own previous frame (ofps_hip_push_frames_async).
 // halo_mode 1: the caller supplies the previous frame (`halo`, host memory, rows `halo_stride` bytes apart; 0 = `stride`) or says there is none
 // (halo == nullptr: the very first frame of a stream) -- the multi-device dispatcher's form (multi.hip): a worker sees every
@@ -311,174 +496,16 @@ int push_frames_impl(ofps_hip_ctx* ctx, const uint8_t* frames, int n, int W, int
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = pipe_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    constexpr int kTickets = BatchStream::kTickets;
-    const long tno = ctx->batch.ring.next;
-    auto& t = ctx->batch.ring.at(tno);
-    OFPS_REQUIRE(ctx, !t.pending, "push_frames_async: ticket %ld has not been collected (at most %d batches in flight)",
-                 tno - kTickets, kTickets);
-    if (!t.done) {
-        OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
-        OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming));
-        OFPS_HIP_TRY(ctx, hipEventCreateWithFlags(&t.prev_copied, hipEventDisableTiming));
+    BatchPush p{ctx, prm, frames, n, W, H, stride, frame_pitch, halo_mode, halo, halo_stride};
+    rc = p.claim();                                     // refused before anything is uploaded
+    if (rc == OFPS_HIP_OK) rc = p.reserve();
+    if (rc == OFPS_HIP_OK) rc = p.upload();
+    if (rc == OFPS_HIP_OK && p.pairs > 0) {
+        rc = p.decode();
+        if (rc == OFPS_HIP_OK) rc = p.tail();
+        if (rc == OFPS_HIP_OK) rc = p.read_back(out_entries);
     }
-    if (W != ctx->batch.w || H != ctx->batch.h) {              // geometry change restarts the stream
-        OFPS_HIP_TRY(ctx, ctx->batch.ring.drain());
-        ctx->batch.w = W; ctx->batch.h = H; ctx->batch.last_frame = nullptr;
-        ctx->batch.klt_pred.valid = false;
-    }
-    const int dstride = (W + 63) & ~63;
-    const size_t pitch = (size_t)dstride * H;
-    const int tix = (int)(tno % kTickets);
-    const auto& o = ctx->opt;
-    // the batch decoder switch (include/ofps_hip.h N3b): hip_klt in place of the search.  Its settings are the context's at this push; a frame
-    // the decoder refuses is refused here, before anything is uploaded.  The slot count takes the block count's place in every size below, the
-    // kept counts travel where the batch filter's do.  With the switch at 0 `klt` is false and nothing below differs from what it was
-    const bool klt = o.batch_decoder == OFPS_HIP_BATCH_DECODER_KLT;
-    if (klt) {
-        rc = klt_check_call(ctx, W, H, dstride, o.klt_levels, o.klt_radius, o.klt_iters, "push_frames_async");
-        if (rc != OFPS_HIP_OK) return rc;
-        OFPS_REQUIRE(ctx, (unsigned long long)n * ofps_hip_klt_slot_count(W, H, o.klt_cell) < (1ull << 31), "push_frames_async: %d frames of %zu slots", n,
-                     ofps_hip_klt_slot_count(W, H, o.klt_cell));
-    }
-    const size_t nblk = klt ? ofps_hip_klt_slot_count(W, H, o.klt_cell) : ofps_hip_sad_block_count(W, H, prm->block);
-    // N3pb: with both prediction settings on the ticket's items are chained, item 0 behind the last item of the ticket before.  That item's raw
-    // slots wait in one half of S_KLT_BATCH_PRED, this ticket's last item writes the other half.  Any other ticket -- a setting off, the search,
-    // a multi-device worker's (halo_mode 1: a worker sees every n-th batch, its first item has no predecessor there) -- enqueues what it
-    // enqueued without the switch and leaves no slots behind: its successor starts from zero
-    BatchStream::KltPred& kp = ctx->batch.klt_pred;
-    const bool chained = klt && !halo_mode && o.klt_prediction && o.klt_batch_prediction;
-    const int* d_pred_in = nullptr;
-    int* d_pred_out = nullptr;
-    if (chained) {
-        const size_t half = (nblk * 6 * sizeof(int) + 255) & ~(size_t)255;
-        auto* d_pred = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_BATCH_PRED, 2 * half));
-        if (!d_pred) return OFPS_HIP_ENOMEM;
-        if (kp.valid && ctx->batch.last_frame && kp.w == W && kp.h == H && kp.cell == o.klt_cell && kp.gen == ctx->scratch[ofps::S_KLT_BATCH_PRED].gen)
-            d_pred_in = reinterpret_cast<const int*>(d_pred + (size_t)kp.half * half);
-        else kp.half = 0;
-        d_pred_out = reinterpret_cast<int*>(d_pred + (size_t)(kp.half ^ 1) * half);
-    }
-    const int pred_half = kp.half ^ 1;
-    // the batch filter switch (include/ofps_hip.h N1b) with a criterion on: the filtered batched search and the tail's per-item device counts;
-    // the ticket follows the settings the context has now.  Else everything below is what it is without the switch
-    const bool filtered = !klt && o.sad_batch_filter && (o.sad_gate > 0 || o.sad_consistency > 0 || o.sad_median > 0 || o.sad_intra > 0);
-    if (filtered) {                                              // refused before anything is uploaded
-        SadFilter chk{{nullptr, nullptr, 0, 0, W, H, dstride}, 1, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, o.sad_intra, o.sad_cut, /*want_triples=*/false};
-        rc = chk.plan(ctx, "push_frames_async");
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    // capacity: both buffers and the per-ticket outputs are sized for the largest batch seen (grow-only; growing waits
-    // for work in flight)
-    const size_t out_bytes = sizeof(TailRecord) + (filtered || klt ? sizeof(uint32_t) : 0);      // per frame; filtered, hip_klt: the n kept counts behind the n quaternions
-    const size_t cap_frames = (size_t)n + 1;
-    auto& fs = ctx->scratch[ofps::S_BATCH_FRAMES];
-    size_t per_buf = fs.cap / kTickets / (pitch ? pitch : 1);
-    if (per_buf < cap_frames) {
-        OFPS_HIP_TRY(ctx, ctx->batch.ring.drain(/*forget=*/false));
-        // the newest frame of the stream lives in the old allocation: keep a copy
-        void* keep = nullptr;
-        if (ctx->batch.last_frame) {
-            OFPS_HIP_TRY(ctx, hipMalloc(&keep, pitch));
-            OFPS_HIP_TRY(ctx, hipMemcpyAsync(keep, ctx->batch.last_frame, pitch, hipMemcpyDeviceToDevice, ctx->stream));
-            OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        auto* nb = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_BATCH_FRAMES, kTickets * cap_frames * pitch));
-        if (!nb) { if (keep) (void)hipFree(keep); return OFPS_HIP_ENOMEM; }
-        per_buf = cap_frames;
-        if (keep) {
-            // parked in the LAST slot of the buffer this ticket does not use: nothing writes there before it is consumed
-            uint8_t* park = nb + ((size_t)(tix ^ 1) * per_buf + (per_buf - 1)) * pitch;
-            OFPS_HIP_TRY(ctx, hipMemcpyAsync(park, keep, pitch, hipMemcpyDeviceToDevice, ctx->stream));
-            OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(keep);
-            ctx->batch.last_frame = park;
-        }
-    }
-    auto* bufs = static_cast<uint8_t*>(fs.p);
-    uint8_t* buf = bufs + (size_t)tix * per_buf * pitch;        // [slot 0 = previous frame][n frames]
-    auto* d_ent_all = static_cast<float4*>(ofps::scratch(ctx, ofps::S_BATCH_ENTRIES, kTickets * (size_t)n * nblk * sizeof(float4)));
-    auto* d_out_all = static_cast<char*>(ofps::scratch(ctx, ofps::S_BATCH_OUT, kTickets * (size_t)n * out_bytes));
-    if (!d_ent_all || !d_out_all) return OFPS_HIP_ENOMEM;
-    const size_t ent_per_ticket = ctx->scratch[ofps::S_BATCH_ENTRIES].cap / kTickets / sizeof(float4);
-    const size_t out_per_ticket = ctx->scratch[ofps::S_BATCH_OUT].cap / kTickets;
-    float4* d_ent = d_ent_all + (size_t)tix * ent_per_ticket;
-    char* d_out = d_out_all + (size_t)tix * out_per_ticket;
-    rc = host_block_reserve(ctx, &t.pinned, &t.pinned_cap, (size_t)n * out_bytes);
-    if (rc != OFPS_HIP_OK) return rc;
-    hipStream_t s = ctx->stream, up = ctx->pipe.copy_stream;
-    // ---- copy stream: the n frames in one transfer (the buffer's previous tenant, ticket tno - 2, has been collected:
-    // its work is done); compute stream: the previous frame into slot 0
-    // the other ticket's copy of ITS previous frame reads slot n of this buffer's previous tenant: wait for it
-    auto& other = ctx->batch.ring.at(tno + 1);
-    if (other.pending && other.prev_copied_valid) OFPS_HIP_TRY(ctx, hipStreamWaitEvent(up, other.prev_copied, 0));
-    if (frame_pitch == (size_t)W * H && stride == W && dstride == W) {
-        rc = upload_dense_device(ctx, buf + pitch, frames, (size_t)n * pitch, up, true);                                       // the whole batch
-        if (rc != OFPS_HIP_OK) return rc;
-    } else {
-        for (int j = 0; j < n; ++j)
-            OFPS_HIP_TRY(ctx, ofps::upload_rows(buf + (size_t)(j + 1) * pitch, dstride, frames + (size_t)j * frame_pitch, stride, W, H, up));
-    }
-    if (halo_mode && halo) OFPS_HIP_TRY(ctx, ofps::upload_rows(buf, dstride, halo, halo_stride ? halo_stride : stride, W, H, up));       // the caller's previous frame into slot 0
-    OFPS_HIP_TRY(ctx, hipEventRecord(t.uploaded, up));
-    const bool has_prev = halo_mode ? halo != nullptr : ctx->batch.last_frame != nullptr;
-    t.prev_copied_valid = false;
-    if (has_prev && !halo_mode) {
-        // by a copy KERNEL, not hipMemcpyAsync: the runtime may hand a device-to-device copy to the SDMA engine that is busy with the
-        // NEXT batch's 33 MB upload, and then this 2 MB copy -- and the search behind it -- waits 0.1-0.6 ms for that upload (transfer.hip)
-        rc = copy_words_device(ctx, buf, ctx->batch.last_frame, pitch / 4, 256, s);
-        if (rc != OFPS_HIP_OK) return rc;
-        OFPS_HIP_TRY(ctx, hipEventRecord(t.prev_copied, s));
-        t.prev_copied_valid = true;
-    }
-    OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, t.uploaded, 0));
-    // ---- compute stream: pairs (slot j, slot j + 1), j = first .. n - 1
-    const int first = has_prev ? 0 : 1;                           // the stream's very first frame has no pair
-    const int pairs = n - first;
-    kp.valid = false;                                            // (until this ticket's last item has been enqueued, and only if it is chained)
-    t.n = n; t.first_has_prev = has_prev ? 1 : 0; t.run_detector = prm->run_detector; t.run_estimator = prm->run_estimator; t.n_vectors = nblk;
-    t.filtered = (filtered || klt) && pairs > 0;
-    if (halo_mode) t.isl.K = 0;                                  // the multi-device workers list no islands (include/ofps_hip.h A5i)
-    else islands_ticket_arm(ctx, &t.isl, prm, n);
-    if (pairs > 0) {
-        float4* ent0 = d_ent + (size_t)first * nblk;
-        // filtered: item j's kept records lead its slot of the record buffer, its count is word j behind the quaternions.  Searches, flags
-        // and the compaction run on the compute stream, in front of the tail that reads the counts there
-        uint32_t* d_cnt = filtered || klt ? reinterpret_cast<uint32_t*>(d_out + (size_t)n * sizeof(TailRecord)) + first : nullptr;
-        const SadFrames fr = SadFrames::sequence(buf + (size_t)first * pitch, pitch, /*ref_mode=*/0, W, H, dstride);
-        if (klt) {
-            rc = klt_flow_device(ctx, KltFlowCall{fr, pairs, o.klt_levels, o.klt_radius, o.klt_iters, ent0, d_cnt, nullptr, true, chained, d_pred_in, d_pred_out});
-            if (rc == OFPS_HIP_OK && chained) kp = {true, pred_half, W, H, o.klt_cell, ctx->scratch[ofps::S_KLT_BATCH_PRED].gen};
-        } else if (filtered)
-            rc = sad_flow_filtered_device(ctx, fr, pairs, prm->block, prm->range, o.sad_gate, o.sad_consistency, o.sad_median, ent0, nullptr, d_cnt,
-                                          "push_frames_async", tix, kTickets, o.sad_intra, o.sad_cut);
-        else rc = sad_pairs_device(ctx, fr, pairs, prm->block, prm->range, ent0, nullptr);
-        if (rc != OFPS_HIP_OK) return rc;
-        auto* d_res = reinterpret_cast<int(*)[4]>(d_out);                           // [n][4]
-        float4* d_quat = reinterpret_cast<float4*>(d_out + (size_t)n * kBatchResult); // [n]
-        float2* d_field = nullptr;
-        if (prm->run_detector) {
-            d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_BATCH_FIELD, (size_t)pairs * kMaxFieldBytes));   // its own slot: the densifier works in S_WORK*
-            if (!d_field) return OFPS_HIP_ENOMEM;
-        }
-        // one estimator launch, [one compensation launch,] one detector chain over the batch, item j seeded seed + j.  The multi-device
-        // dispatcher's worker contexts (halo_mode 1) keep the raw detector whatever their detect-compensation mode
-        // filtered: the tail's device-count forms with one count per item; fewer than 3 kept -> identity, as in the filtered per-frame path
-        rc = frame_tail_device(ctx, ent0, nblk, pairs, d_cnt, filtered ? 3 : 0, prm, prm->seed + (uint64_t)first, /*may_compensate=*/!halo_mode,
-                               d_res[first], d_quat + first, d_field, nullptr, nullptr, &t.isl);
-        if (rc != OFPS_HIP_OK) return rc;
-        if (filtered || klt || prm->run_detector || prm->run_estimator) {         // (the kept counts travel in this read-back)
-            rc = ofps::read_back_device(ctx, t.pinned, d_out, (size_t)n * out_bytes, s);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
-        if (out_entries) {
-            rc = ofps::read_back_device(ctx, out_entries + (size_t)first * nblk * 4, ent0, (size_t)pairs * nblk * sizeof(float4), s);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
-    }
-    OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
-    ctx->batch.last_frame = buf + (size_t)n * pitch;
-    *ticket = ctx->batch.ring.commit();
-    return OFPS_HIP_OK;
+    return rc == OFPS_HIP_OK ? p.commit(ticket) : rc;
 }
 }  // namespace ofps
 
@@ -497,22 +524,13 @@ int ofps_hip_frames_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_result* o
     if (!t) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
-    const auto* res = static_cast<const int(*)[4]>(t->pinned);
-    const auto* quat = reinterpret_cast<const float(*)[4]>(static_cast<const char*>(t->pinned) + (size_t)t->n * kBatchResult);
+    const ofps::BatchBlock blk{(size_t)t->n, t->filtered != 0};
+    char* base = static_cast<char*>(t->pinned);
+    const uint32_t* kept = blk.kept(base);
     for (int j = 0; j < t->n; ++j) {
-        ofps_hip_frame_result& o = out[j];
-        memset(&o, 0, sizeof(o));
-        o.quat[0] = 1.0f;
         const bool has = j > 0 || t->first_has_prev;
-        o.have_vectors = has ? 1 : 0;
-        o.n_vectors = has ? t->n_vectors : 0;
-        if (!has) continue;
-        if (t->filtered) {
-            const auto* kept = reinterpret_cast<const uint32_t*>(static_cast<const char*>(t->pinned) + (size_t)t->n * sizeof(TailRecord));
-            if (kept[j] < o.n_vectors) o.n_vectors = kept[j];
-        }
-        if (t->run_detector) { o.has_motion = res[j][0]; o.area = (size_t)res[j][1]; o.dim = res[j][2]; }
-        if (t->run_estimator) memcpy(o.quat, quat[j], sizeof(o.quat));
+        ofps::fill_frame_result(&out[j], has ? 1 : 0, !has ? 0 : kept && kept[j] < t->n_vectors ? kept[j] : t->n_vectors,
+                                has && t->run_detector ? blk.result(base, j) : nullptr, has && t->run_estimator ? blk.quat(base, j) : nullptr);
     }
     return ofps::islands_collect(ctx, t->isl);
 }

@@ -1436,12 +1436,12 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     OFPS_REQUIRE(ctx, W > 0 && H > 0 && stride >= W && block >= 1, "sad_flow: bad geometry");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // repack to a 64-byte-multiple device stride so any host stride is accepted
-    const int dstride = (W + 63) & ~63;
+    const int dstride = ofps::padded_stride(W);
     const size_t pitch = (size_t)dstride * H;
     const size_t nblk = ofps_hip_sad_block_count(W, H, block);
     auto* d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * pitch));
-    const int split = ctx->opt.sad_split;                           // N1s: up to four records per block (sad_split.hip)
-    const size_t cap = split > 0 ? 4 * nblk : nblk;
+    const ofps::SadCriteria crit = ofps::SadCriteria::of(ctx->opt);
+    const size_t cap = crit.split > 0 ? 4 * nblk : nblk;            // N1s: up to four records per block (sad_split.hip)
     auto* d_ent = static_cast<float*>(ofps::scratch(ctx, ofps::S_ENTRIES, cap * 4 * sizeof(float)));
     auto* d_best = static_cast<int32_t*>(ofps::scratch(ctx, ofps::S_BEST, nblk * 3 * sizeof(int32_t)));
     if (!d_frames || !d_ent || !d_best) return OFPS_HIP_ENOMEM;
@@ -1450,12 +1450,11 @@ int ofps_hip_sad_flow(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     // contrast gate, consistency check, median test and / or intra test (sad_gate.hip: SadFilter): the kept records first, their count from the device with them
     uint32_t kept = UINT32_MAX;
     int rc;
-    if (ctx->opt.sad_gate > 0 || ctx->opt.sad_consistency > 0 || ctx->opt.sad_median > 0 || ctx->opt.sad_intra > 0 || split > 0) {
+    if (crit.on()) {
         auto* d_kept = static_cast<uint32_t*>(ofps::scratch(ctx, ofps::S_RESULT, sizeof(uint32_t)));
         if (!d_kept) return OFPS_HIP_ENOMEM;
-        rc = ofps::sad_flow_filtered_device(ctx, {d_frames, d_frames + pitch, 0, 0, W, H, dstride}, 1, block, range, ctx->opt.sad_gate,
-                                            ctx->opt.sad_consistency, ctx->opt.sad_median, reinterpret_cast<float4*>(d_ent),
-                                            out_best ? d_best : nullptr, d_kept, "sad_flow", 0, 1, ctx->opt.sad_intra, ctx->opt.sad_cut, split);
+        rc = ofps::sad_flow_filtered_device(ctx, {d_frames, d_frames + pitch, 0, 0, W, H, dstride}, 1, block, range, crit, reinterpret_cast<float4*>(d_ent),
+                                            out_best ? d_best : nullptr, d_kept, "sad_flow");
         if (rc != OFPS_HIP_OK) return rc;
         OFPS_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
     } else {

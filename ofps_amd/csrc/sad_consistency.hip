@@ -137,7 +137,7 @@ int ofps_hip_sad_flow_checked_dev(ofps_hip_ctx* ctx, const void* d_prev, const v
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
     return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
-                                          range, min_pixels, limit, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          range, {min_pixels, limit}, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
                                           static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 

@@ -335,9 +335,9 @@ int SadFilter::finish_split(ofps_hip_ctx* ctx, const uint8_t* flags, float4* d_o
 // `pairs` pairs of `f`, everything on ctx->stream: search[es], [contrast flags and / or activities of the current frames,] [the intra test's flags,] [the check's flags,] [the median test's
 // flags,] one compaction, one count per pair.  Item k's kept records [and triples] lead its nblk-record slot of d_out [d_out_best], d_counts[k]
 // is their number
-int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, int min_pixels, int limit, int median,
-                             float4* d_out, int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets, int intra, int cut, int split) {
-    SadFilter flt{f, pairs, block, range, min_pixels, limit, median, intra, cut, d_out_best != nullptr, split};
+int sad_flow_filtered_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int block, int range, const SadCriteria& c, float4* d_out,
+                             int* d_out_best, uint32_t* d_counts, const char* who, int tix, int tickets) {
+    SadFilter flt = SadFilter::make(f, pairs, block, range, c, d_out_best != nullptr);
     int rc = flt.plan(ctx, who);
     if (rc == OFPS_HIP_OK) rc = flt.reserve(ctx, tix, tickets);
     if (rc == OFPS_HIP_OK) rc = flt.search(ctx, d_out);
@@ -365,7 +365,7 @@ int ofps_hip_sad_flow_filtered_dev(ofps_hip_ctx* ctx, const void* d_frames, int 
                  "sad_flow_filtered_dev: contrast gate, consistency limit and median limit are all 0 (the unfiltered form is ofps_hip_sad_flow_dev)");
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return ofps::sad_flow_filtered_device(ctx, ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride),
-                                          n_frames - 1, block, range, min_pixels, limit, median, static_cast<float4*>(d_out_entries),
+                                          n_frames - 1, block, range, {min_pixels, limit, median}, static_cast<float4*>(d_out_entries),
                                           static_cast<int*>(d_out_best), static_cast<uint32_t*>(d_out_counts), "sad_flow_filtered_dev");
 }
 
@@ -421,7 +421,7 @@ int ofps_hip_sad_flow_gated_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
     const int rc = ofps::sad_gate_check(ctx, block, min_pixels, "sad_flow");             // (the filter itself takes 0 for "no gate")
     if (rc != OFPS_HIP_OK) return rc;
     return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
-                                          range, min_pixels, 0, 0, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          range, {min_pixels}, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
                                           static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 

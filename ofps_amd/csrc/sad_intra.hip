@@ -335,8 +335,8 @@ int ofps_hip_sad_flow_intra_dev(ofps_hip_ctx* ctx, const void* d_frames, int n_f
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return ofps::sad_flow_filtered_device(ctx, ofps::SadFrames::sequence(static_cast<const uint8_t*>(d_frames), frame_pitch, ref_mode, W, H, stride),
-                                          n_frames - 1, block, range, min_pixels, limit, median, static_cast<float4*>(d_out_entries),
-                                          static_cast<int*>(d_out_best), static_cast<uint32_t*>(d_out_counts), "sad_flow_intra_dev", 0, 1, intra, cut);
+                                          n_frames - 1, block, range, {min_pixels, limit, median, intra, cut}, static_cast<float4*>(d_out_entries),
+                                          static_cast<int*>(d_out_best), static_cast<uint32_t*>(d_out_counts), "sad_flow_intra_dev");
 }
 
 }  // extern "C"

@@ -166,7 +166,7 @@ int ofps_hip_sad_flow_median_dev(ofps_hip_ctx* ctx, const void* d_prev, const vo
     OFPS_REQUIRE(ctx, min_pixels >= 0, "sad_flow: contrast gate %d is negative", min_pixels);
     OFPS_REQUIRE(ctx, limit >= 0, "sad_flow: consistency limit %d is negative", limit);
     return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
-                                          range, min_pixels, limit, median_limit, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
+                                          range, {min_pixels, limit, median_limit}, static_cast<float4*>(d_out_entries), static_cast<int*>(d_out_best),
                                           static_cast<uint32_t*>(d_out_count), "sad_flow");
 }
 

@@ -338,7 +338,7 @@ int ofps_hip_sad_split(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cu
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // repack to a 64-byte-multiple device stride so any host stride is accepted (as ofps_hip_sad_flow does)
-    const int dstride = (W + 63) & ~63;
+    const int dstride = ofps::padded_stride(W);
     const size_t pitch = (size_t)dstride * H, nblk = ofps_hip_sad_block_count(W, H, block);
     if (!nblk) return OFPS_HIP_OK;
     const size_t keep_bytes = (nblk + 15) & ~size_t(15);
@@ -376,8 +376,8 @@ int ofps_hip_sad_flow_split_dev(ofps_hip_ctx* ctx, const void* d_prev, const voi
                  ofps::kSadSplitMax);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return ofps::sad_flow_filtered_device(ctx, {static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_cur), 0, 0, W, H, stride}, 1, block,
-                                          range, min_pixels, limit, median, static_cast<float4*>(d_out_entries), nullptr,
-                                          static_cast<uint32_t*>(d_out_count), "sad_flow_split_dev", 0, 1, 0, 0, threshold);
+                                          range, {min_pixels, limit, median, /*intra=*/0, /*cut=*/0, threshold}, static_cast<float4*>(d_out_entries), nullptr,
+                                          static_cast<uint32_t*>(d_out_count), "sad_flow_split_dev");
 }
 
 }  // extern "C"

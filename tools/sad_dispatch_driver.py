@@ -4,14 +4,20 @@ neither.  The four 320 x 192 frames of tests/sad_gate_cases.py, block 16, range 
   push      four ofps_hip_push_frame calls with all criteria off, gate 1, limit 1, median 2, and all three with motion scale 4 + levels 2 +
             mean removal 4;
   batch     the same frames as one ofps_hip_push_frames_async ticket, batch filter switch on, all three criteria;
+  stream    the batched stream cut 1 + 2 + 1 (the buffers grow, the previous frame is parked): plain, one ticket at a time and two in flight;
+            batch filter switch on with all three criteria plus intra 8 / cut 50;
+  multi     one MultiDevice([0]) stream of two batches of two, the workers' halo mode;
+  sad_flow  ofps_hip_sad_flow on frames 1 and 2 under gate 1, limit 1, median 2, intra 8 and split 16, each alone;
   filtered  ofps_hip_sad_flow_filtered_dev with all three criteria in both ref_modes.
 Prints one line per case with the SHA-256 of everything the case returned; --out writes the lines to a file.
-  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/sad_dispatch_driver.py [--lib <libofps_hip.so>] [--out <file>]
+  rocprofv3 --kernel-trace [--memory-copy-trace] --output-format csv [json] -d <dir> -- python tools/sad_dispatch_driver.py [--lib <libofps_hip.so>] [--out <file>]
   python tools/sad_dispatch_driver.py --list <dir>      the (kernel name, grid, workgroup) of every launch under <dir> in dispatch order, the
-                                                        `_items_kernel` forms of an older build named as their one-pair kernels"""
+                                                        `_items_kernel` forms of an older build named as their one-pair kernels; then, when the
+                                                        run traced them, the runtime's copies in start order, by direction and size"""
 import csv
 import glob
 import hashlib
+import json
 import os
 import re
 import sys
@@ -30,6 +36,26 @@ def listing(directory):
         for step in ("block_contrast", "sad_consistency", "sad_median"):
             name = name.replace(step + "_items_kernel", step + "_kernel")
         print(f"{name:44s} grid {r['Grid_Size_X']:>8s} {r['Grid_Size_Y']:>5s} {r['Grid_Size_Z']:>5s}  wg {r['Workgroup_Size_X']:>4s}")
+    # --memory-copy-trace: the copies the runtime's engines made, in start order, by direction and size.  The CSV has no size column; the
+    # JSON output of the same run (--output-format csv json) has, in records that carry "bytes" beside their timestamps
+    sizes = {}
+    for f in glob.glob(os.path.join(directory, "**", "*results.json"), recursive=True):
+        def walk(node):
+            if isinstance(node, dict):
+                if "bytes" in node and "start_timestamp" in node:
+                    sizes[int(node["start_timestamp"])] = int(node["bytes"])
+                for v in node.values():
+                    walk(v)
+            elif isinstance(node, list):
+                for v in node:
+                    walk(v)
+        walk(json.load(open(f)))
+    copies = []
+    for f in glob.glob(os.path.join(directory, "**", "*memory_copy_trace.csv"), recursive=True):
+        copies += list(csv.DictReader(open(f)))
+    copies.sort(key=lambda r: int(r["Start_Timestamp"]))
+    for r in copies:
+        print(f"copy {r['Direction'].replace('MEMORY_COPY_', ''):44s} bytes {sizes.get(int(r['Start_Timestamp']), '?')}")
 
 
 def main():
@@ -84,6 +110,47 @@ def main():
     ctx.reset_frames()
     ctx.free_pinned(buf); ctx.free_pinned(ent)
     settings()
+
+    # the batched stream cut 1 + 2 + 1: the batch buffers grow at the second ticket and the stream's previous frame is parked
+    def stream(pusher, sizes, in_flight):
+        parts, pending, start = [], [], 0
+
+        def collect():
+            t, e, _ = pending.pop(0)
+            for j, r in enumerate(pusher.frames_wait(t)):
+                parts.extend(result_bytes(r, e[j]))
+        for size in sizes:
+            if len(pending) >= in_flight:
+                collect()
+            batch, e = np.ascontiguousarray(f[start:start + size]), np.zeros((size, NBLK, 4), np.float32)
+            pending.append((pusher.push_frames_async(batch, out_entries=e, **dict(prm, seed=gc.SEED + start)), e, batch))
+            start += size
+        while pending:
+            collect()
+        pusher.reset_frames()
+        return parts
+
+    done("stream 1+2+1 plain", stream(ctx, (1, 2, 1), 1))
+    done("stream 1+2+1 plain in flight", stream(ctx, (1, 2, 1), 2))
+    settings(gate=1, limit=1, median=2, batch_filter=1)
+    ctx.set_sad_intra(8); ctx.set_sad_cut(50)
+    done("stream 1+2+1 all intra8 cut50", stream(ctx, (1, 2, 1), 1))
+    ctx.set_sad_intra(0); ctx.set_sad_cut(0)
+    settings()
+    # the multi-device workers' pushes (halo mode).  ONE worker, so that the listing is deterministic: two workers' launches interleave as
+    # their threads run
+    from ofps_amd.runtime import MultiDevice
+    md = MultiDevice([0])
+    done("multi one worker 2+2", stream(md, (2, 2), 2))
+    md.close()
+
+    # ofps_hip_sad_flow with the context's criteria, one at a time, and under split
+    for case, apply in (("gate1", lambda v: ctx.set_sad_gate(v and 1)), ("limit1", lambda v: ctx.set_sad_consistency(v and 1)),
+                        ("median2", lambda v: ctx.set_sad_median(v and 2)), ("intra8", lambda v: ctx.set_sad_intra(v and 8)),
+                        ("split16", lambda v: ctx.set_sad_split(v and 16))):
+        apply(1)
+        done(f"sad_flow {case}", list(ctx.sad_flow(f[1], f[2], B, R, want_best=True)))
+        apply(0)
 
     d_frames = torch.from_numpy(f).cuda()
     for ref_mode in (0, 1):
