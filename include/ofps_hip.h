@@ -1054,6 +1054,70 @@ int ofps_hip_get_detect_islands(ofps_hip_ctx* ctx);
 int ofps_hip_frame_islands(ofps_hip_ctx* ctx, int item, int32_t out_counts[4], int32_t* out_table, int capacity /* records */,
                            void* out_labels /* uint16 x dim*dim, or NULL */);
 
+/* ---- A5t: island tracks -- follow the islands across frames (csrc/detect_tracks.hip; build-defined, off by default) ----
+ * A5i ranks the islands of one frame by area; rank is not identity.  This step gives every listed island an id that survives rank
+ * swaps and short gaps, an age, a hit count and the integer sums of its cells' motion.  Build-defined: the reference has a temporal rule
+ * for the frame as a whole only (ofps-suite/src/app/detection.rs:195-212); the definition below is this library's.  All integer.
+ * Parameters: max_tracks = T in [1, 256]; reach in [0, 4] cells (Chebyshev); max_gap = G in [0, 255] frames.
+ * Input per frame: A5i's counts, table and labels for max_islands = K (the rows are matched by rank: the table is taken and not read);
+ *   optionally cells, the densified field, 2 f32 per cell (the detector's own densify).
+ * State: ofps_hip_island_tracker_bytes(dim, T) bytes, opaque to callers, 4-byte aligned; all-zero bytes are a fresh tracker.  It holds a
+ *   step counter t, the count of ids handed out (the first id is 1; ids are never reused), per slot s < T (id, born, hits, last) with id 0
+ *   = free, and per cell an owner (a slot or none) and gone, the frames since that owner was confirmed there.  Every byte of the state
+ *   after a step is a function of the inputs: freed slots and cleared cells are written back to zero.  Layout: int32 t, handed, 0, 0; 4
+ *   int32 per slot; uint16 owner per cell (slot + 1, 0 = none), padded to 16 bytes; uint8 gone per cell, padded to 16 bytes.  Ids stay
+ *   below 2^31: a tracker that has handed out 2^31 - 1 ids is to be zeroed.
+ * One step, with n = min(n_listed, T); only ranks r < n take part:
+ *   1. t += 1.
+ *   2. Overlap: for r < n and every live slot s, O[r][s] = the number of ordered pairs (c, c') with labels[c] == r, owner[c'] == s and
+ *      max(|x - x'|, |y - y'|) <= reach, both cells inside the grid.  A pair count, nothing de-duplicated: at most 25,600 * 81.
+ *   3. Match, in rank order r = 0 .. n - 1: among the live slots not yet claimed in this step with O[r][s] >= 1 take the largest O, ties
+ *      to the smaller id; claim it, hits += 1, last = t.  If there is none: take the lowest-index free slot, id = the next id, born = t,
+ *      hits = 1, last = t, claim it.  If there is no free slot either, the island is untracked in this frame.
+ *   4. Paint: every cell of a tracked island gets owner = its slot and gone = 0.  Every other cell that has an owner -- cells of
+ *      untracked islands and of islands at rank >= n among them -- gets gone += 1, and loses its owner (gone = 0) when gone > G.
+ *   5. Expire: a live slot with t - last > G is freed (all four words zero) behind the matching; rule 4 has cleared its cells already.
+ * Output per item:
+ *   track_counts, int32[4]: rows = n, n_tracked = the rows with id != 0, n_live = the slots alive after the step, t;
+ *   tracks, int32[8] per rank r < n, in rank order beside A5i's table row r: id (0 = untracked), slot (-1 = untracked), age = t - born + 1,
+ *     hits (age and hits are 0 for an untracked row), sum_mx low and high word, sum_my low and high word.  Rows at and behind n are
+ *     unspecified.  sum_mx and sum_my are the int64 sums of q(cells[c].x) and q(cells[c].y) over the cells labelled r, q(v) = the
+ *     nearest-even integer of clamp(v, -64, 64) * 2^24 (exact in f32: one rintf of an exact value), q(NaN) = 0; both are 0 when cells
+ *     is NULL.  The island's mean motion is sum / area / 2^24, the caller's to compute.
+ * Consequences: a split leaves the id with the larger piece (the lower rank claims first); a merge keeps the id of the previous island
+ * with the larger pair count; an island that vanishes for at most G frames comes back under its id with hits not advanced, after G + 1
+ * frames under a new one.
+ * ofps_hip_track_islands_dev steps `batch` items in order through one state, in one launch: item j reads counts at 4 j, labels at
+ * dim * dim * j, cells at 2 * dim * dim * j and writes track_counts at 4 j and tracks at 8 * max_tracks * j; it only enqueues.
+ * ofps_hip_detect_tracks runs densify, A5i and the steps for `batch` frames of n_per_item records each from host memory; the state
+ * travels in and out, so 12 frames in one call, in 12 calls or cut 5 + 7 give the same rows and the same state bytes.
+ * OFPS_HIP_EINVAL, before anything is enqueued: T, reach, G or K outside their ranges; dim outside [1, 160]; a NULL state.
+ *
+ * The fused entry points follow ofps_hip_set_detect_tracks (options OFPS_HIP_DETECT_TRACKS, OFPS_HIP_DETECT_TRACK_REACH,
+ * OFPS_HIP_DETECT_TRACK_GAP; T = 0 is off and the default, reach 1 and gap 2 are the other defaults).  A ticket pushed with run_detector,
+ * K > 0 and T > 0 takes one step per item that yielded vectors, behind the islands launch on its stream, on the island list and the field
+ * the detector read (detect-compensation mode 1: motion relative to the camera); its rows travel in the ticket's page-locked block behind
+ * every item's A5i block and ofps_hip_frame_tracks returns them, with ofps_hip_frame_islands' rules (capacity in rows).  An item without
+ * vectors (a stream's first frame) takes no step: its track_counts are zero.  An item with vectors and no islands takes a step with n = 0.
+ * Each of the three stream forms -- ofps_hip_push_frame[_async], ofps_hip_push_frames_async, ofps_hip_lk_push_frame_fused[_async] --
+ * owns one state in context scratch; it starts from zeros after that form's reset, at the first frame of a stream, and when dim, T,
+ * reach or G differ from the push before (a push with T = 0 or K = 0 among them).  Frame k's step runs behind frame k - 1's by stream
+ * order; a batch ticket steps its items in frame order, so a frame's rows do not depend on how the frames were cut into tickets.  With
+ * T = 0 or K = 0 nothing is enqueued, reserved or copied.  The worker contexts of ofps_hip_multi_* ignore the setting. */
+size_t ofps_hip_island_tracker_bytes(int dim, int max_tracks);     /* 0: dim or max_tracks out of range */
+int ofps_hip_track_islands_dev(ofps_hip_ctx* ctx, const void* d_counts /* batch*4 */, const void* d_table /* batch*max_islands*8 */,
+                               const void* d_labels /* uint16 x batch*dim*dim */, const void* d_cells /* f32 x batch*2*dim*dim, or NULL */,
+                               int dim, int max_islands, int batch, int max_tracks, int reach, int max_gap, void* d_state,
+                               void* d_out_track_counts /* batch*4 */, void* d_out_tracks /* batch*max_tracks*8 */);
+int ofps_hip_detect_tracks(ofps_hip_ctx* ctx, const float* entries, size_t n_per_item, int batch, float min_size, size_t subdivide,
+                           float target_motion, int max_islands, int max_tracks, int reach, int max_gap, void* state /* in and out */,
+                           int32_t* out_counts /* batch*4 */, int32_t* out_table /* batch*max_islands*8 */,
+                           void* out_labels /* uint16 x batch*dim*dim, or NULL */, int32_t* out_track_counts /* batch*4 */,
+                           int32_t* out_tracks /* batch*max_tracks*8 */);
+int ofps_hip_set_detect_tracks(ofps_hip_ctx* ctx, int max_tracks, int reach, int max_gap);   /* max_tracks 0 = off (default) */
+int ofps_hip_get_detect_tracks(ofps_hip_ctx* ctx, int* max_tracks, int* reach, int* max_gap);
+int ofps_hip_frame_tracks(ofps_hip_ctx* ctx, int item, int32_t out_track_counts[4], int32_t* out_tracks, int capacity /* rows */);
+
 /* ---- A6-A12: Almeida estimator ("hip_almeida" Estimator) ----
  * out_quat = (w,i,j,k) of the returned UnitQuaternion; out_tr = translation (always 0,
  * almeida-estimator/src/lib.rs:120).  seed drives the counter-based RANSAC sampler (the reference draws from

@@ -178,6 +178,13 @@ PROTOTYPES = {
     "ofps_hip_set_detect_islands": (C.c_int, [_ctx, C.c_int]),
     "ofps_hip_get_detect_islands": (C.c_int, [_ctx]),
     "ofps_hip_frame_islands": (C.c_int, [_ctx, C.c_int, _i32p, _i32p, C.c_int, _vp]),
+    "ofps_hip_island_tracker_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ofps_hip_track_islands_dev": (C.c_int, [_ctx, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "ofps_hip_detect_tracks": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_int, C.c_float, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                         _i32p, _i32p, _vp, _i32p, _i32p]),
+    "ofps_hip_set_detect_tracks": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
+    "ofps_hip_get_detect_tracks": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ofps_hip_frame_tracks": (C.c_int, [_ctx, C.c_int, _i32p, _i32p, C.c_int]),
     "ofps_hip_almeida": (C.c_int, [_ctx, _f32p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_size_t,
                                    C.c_float, C.c_size_t, C.c_uint64, _f32p, _f32p]),
     "ofps_hip_almeida_dev": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.c_size_t,

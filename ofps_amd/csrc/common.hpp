@@ -106,8 +106,19 @@ inline size_t islands_block_bytes(int K, int dim) { return 16 + (size_t)K * 32 +
 struct IslandsTicket {
     void* pinned = nullptr; size_t cap = 0;
     int K = 0, items = 0, first = 0, dim = 0;
+    int T = 0, reach = 0, gap = 0, form = -1;     // A5t: the context's track settings at this push and the stream form whose state it steps
     void release() { free_host(pinned); }
 };
+// A5t (detect_tracks.hip): a ticket pushed with max_tracks = T > 0 as well carries [track_counts, int32 x 4][tracks, int32 x 8 x T] behind every
+// item's A5i block, whose layout does not change.  Each of the three stream forms owns one tracker state in context scratch (S_TRK_STATE +
+// form); `live` says that the state continues the settings and the grid below -- anything else starts from zeros (one memset in front of the
+// step, on its stream).  Steps of one form run in stream order: the detector's chain of ticket k + 1 lies behind ticket k's on whichever of
+// the two streams it runs (tail.hip: the side stream is forked behind and joined into the compute stream by every push)
+constexpr int kMaxTracks = 256, kMaxTrackReach = 4, kMaxTrackGap = 255;
+enum TrackFormId { TRK_PIPE = 0, TRK_BATCH = 1, TRK_DENSE = 2, kTrackForms = 3 };
+inline size_t track_block_bytes(int T) { return T > 0 ? 16 + (size_t)T * 32 : 0; }
+inline size_t ticket_block_bytes(int K, int dim, int T) { return islands_block_bytes(K, dim) + track_block_bytes(T); }
+struct TrackForm { bool live = false; int T = 0, reach = 0, gap = 0, dim = 0; uint64_t gen = 0; };
 
 // Farneback's state across calls (farneback.hip).  hip_flow in the stream forms: the pyramid + polynomial expansion of a pair's second
 // frame is the next pair's first, and the NEW frame's is made on the upload's stream beside the previous pair's flow.  Frames of the
@@ -266,6 +277,9 @@ struct ofps_hip_ctx {
         int sad_split = 0;               // OFPS_HIP_SAD_SPLIT / ofps_hip_set_sad_split: 0 one record per kept block, T in [1, 4080] (sixteenths of a grey level per pixel) a kept block whose four sub-blocks together match better by at least T yields their four records (sad_split.hip, N1s)
         int sad_batch_filter = 0;        // OFPS_HIP_SAD_BATCH_FILTER / ofps_hip_set_sad_batch_filter: 0 the batched stream forms (ofps_hip_push_frames_async, the ofps_hip_multi_* workers' pushes) ignore gate, check and median test, 1 they follow them (include/ofps_hip.h N1b)
         int sad_prefilter = 0;           // OFPS_HIP_SAD_PREFILTER / ofps_hip_set_sad_prefilter: 0 the searches read the frames as they are, r in [1, 16] their mean-removed forms, box radius r (sad_prefilter.hip, N1m)
+        // OFPS_HIP_DETECT_TRACKS, OFPS_HIP_DETECT_TRACK_REACH, OFPS_HIP_DETECT_TRACK_GAP / ofps_hip_set_detect_tracks: T = 0 off, T in [1, 256] a ticket
+        // that lists islands follows them across frames as well, with this reach in cells [0, 4] and this gap in frames [0, 255] (detect_tracks.hip, A5t)
+        int detect_tracks = 0, detect_track_reach = 1, detect_track_gap = 2;
         int detect_islands = 0;          // OFPS_HIP_DETECT_ISLANDS / ofps_hip_set_detect_islands: 0 the fused entry points' detector answers for the largest island alone, K in [1, 6400] a ticket that runs the detector lists up to K islands as well (detect.hip, A5i)
         // ofps_hip_set_klt: hip_klt's lattice cell (8 | 16 | 32), score window radius [1, 3], smallest score of a feature, smallest eigenvalue of
         // a template's structure tensor per pixel [1, 65535], residual limit in sixteenths of a grey level per pixel (0 = off) (klt.hip, N3)
@@ -303,7 +317,8 @@ struct ofps_hip_ctx {
     ofps::FarnebackState fb;
     // A5i: the islands of the most recently collected fused ticket, in host memory the context owns (detect.hip: islands_collect): `items`
     // blocks of islands_block_bytes(K, dim).  K == 0: that ticket had none
-    struct IslandsLast { char* data = nullptr; size_t cap = 0; int K = 0, items = 0, dim = 0; } isl_last;
+    struct IslandsLast { char* data = nullptr; size_t cap = 0; int K = 0, items = 0, dim = 0, T = 0; } isl_last;      // T > 0: A5t's rows behind every block
+    ofps::TrackForm trk[ofps::kTrackForms];      // A5t: what each stream form's tracker state in S_TRK_STATE + form continues
     uint32_t lk_epoch = 0;               // lk_levels_kernel: tag of the last launch in the tile flags (S_LK_FLAGS)
     uint64_t lk_flags_gen = 0;           // generation of the flag buffer the tags refer to
 
@@ -315,7 +330,7 @@ struct ofps_hip_ctx {
     // grow-only device scratch owned by the context (staging for host-pointer entry points and
     // kernel workspaces); never shrinks, freed in ofps_hip_destroy.
     struct Scratch { void* p = nullptr; size_t cap = 0; uint64_t gen = 0; };   // gen: bumped by every (re)allocation of the slot
-    static constexpr int kNumScratch = 62;
+    static constexpr int kNumScratch = 66;
     Scratch scratch[kNumScratch];
 };
 
@@ -361,9 +376,13 @@ enum ScratchSlot {
     S_KLT_WORK,             // ... [features, 3 i32 per slot][raw records per slot][keep flags, u8 per slot], in front of the compaction
     S_KLT_HOST,             // ... the host-pointer forms' device-side inputs and outputs
     S_KLT_PRED,             // N3p: the sparse stream's raw slots of the last two pairs, 6 i32 per slot each.  Compute stream only
-    S_KLT_BATCH_PRED        // N3pb: the batched stream's raw slots of the last item of the last two chained tickets, 6 i32 per slot each.  Compute stream only
+    S_KLT_BATCH_PRED,       // N3pb: the batched stream's raw slots of the last item of the last two chained tickets, 6 i32 per slot each.  Compute stream only
+    S_TRK_STATE,            // A5t (detect_tracks.hip): the tracker state of the per-frame stream form, ...
+    S_TRK_STATE_BATCH,      // ... of the batched form
+    S_TRK_STATE_DENSE,      // ... and of the dense decoders' fused form (S_TRK_STATE + TrackFormId).  Each carries state ACROSS pushes: nobody else's slot
+    S_TRK_HOST              // ... and the state of one ofps_hip_detect_tracks call, between its upload and its read-back
 };
-static_assert(S_KLT_BATCH_PRED < ofps_hip_ctx::kNumScratch, "scratch table too small");
+static_assert(S_TRK_HOST < ofps_hip_ctx::kNumScratch, "scratch table too small");
 
 // Page-locked blocks that kernels write directly and the host reads after an event (ticket result blocks, ofps_hip_host_alloc):
 // fine-grained host memory, asked for explicitly.  A/B builds (tools/read_ahead_bisect.sh) override the two constants with -D.
@@ -656,7 +675,15 @@ int frame_tail_device(ofps_hip_ctx* ctx, const float4* d_rec, size_t n, int batc
                       const ofps_hip_frame_params* prm, uint64_t seed0, bool may_compensate, int* d_result, float4* d_quat, float2* d_field,
                       const TailSide* side, int* out_dim, IslandsTicket* isl = nullptr);
 // detect.hip, A5i.  A push arms its ticket: K = the context's max_islands when the detector runs and its grid is valid, else 0; `items` frames
-void islands_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, const ofps_hip_frame_params* prm, int items);
+// form (A5t): the stream form that pushes, -1 = a ticket without tracks; restart: the ticket holds the first frame of a stream
+void islands_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, const ofps_hip_frame_params* prm, int items, int form = -1, bool restart = false);
+// densify as the detector does -> the islands of `batch` items into blocks `stride` bytes apart, each led by its A5i block
+int detect_islands_blocks_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float min_size, size_t subdivide, float target_motion,
+                                 int K, char* d_blocks, size_t stride);
+// detect_tracks.hip, A5t.  The arm step's part: T, reach and gap of the context at this push; T == 0 or a restart forget the form's state
+void tracks_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, int form, bool restart);
+// `batch` steps in item order through the form's state, one launch on ctx->stream behind the islands kernel that filled the blocks
+int tracks_ticket_device(ofps_hip_ctx* ctx, IslandsTicket* isl, int batch, int dim, char* d_blocks, size_t stride);
 // the islands of the `batch` fields detect_device has just left in S_FIELD, on ctx->stream -> isl->pinned, items isl->first ..
 int islands_ticket_device(ofps_hip_ctx* ctx, int batch, int dim, float min_size, float target_motion, IslandsTicket* isl);
 // a fused wait: the collected ticket's blocks -> the context's own host memory (what ofps_hip_frame_islands answers from)

@@ -94,6 +94,15 @@ int apply_option(ofps_hip_ctx* ctx, const char* name, const char* value, bool fr
     } else if (!strcmp(name, "OFPS_HIP_DETECT_ISLANDS")) {
         if (!unset && (iv < 0 || iv > kMaxIslands)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kMaxIslands);
         o.detect_islands = unset ? dflt.detect_islands : iv;
+    } else if (!strcmp(name, "OFPS_HIP_DETECT_TRACKS")) {
+        if (!unset && (iv < 0 || iv > kMaxTracks)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kMaxTracks);
+        o.detect_tracks = unset ? dflt.detect_tracks : iv;
+    } else if (!strcmp(name, "OFPS_HIP_DETECT_TRACK_REACH")) {
+        if (!unset && (iv < 0 || iv > kMaxTrackReach)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kMaxTrackReach);
+        o.detect_track_reach = unset ? dflt.detect_track_reach : iv;
+    } else if (!strcmp(name, "OFPS_HIP_DETECT_TRACK_GAP")) {
+        if (!unset && (iv < 0 || iv > kMaxTrackGap)) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d outside [0, %d]", name, iv, kMaxTrackGap);
+        o.detect_track_gap = unset ? dflt.detect_track_gap : iv;
     } else if (!strcmp(name, "OFPS_HIP_SAD_GATE")) {
         if (!unset && iv < 0) return set_error(ctx, OFPS_HIP_EINVAL, "%s: %d is negative", name, iv);
         o.sad_gate = unset ? dflt.sad_gate : iv;
@@ -195,6 +204,7 @@ static const char* const kOptionNames[] = {
     "OFPS_HIP_SAD_MOTION_SCALE", "OFPS_HIP_DETECT_COMPENSATE", "OFPS_HIP_SAD_GATE", "OFPS_HIP_SAD_CONSISTENCY", "OFPS_HIP_SAD_LEVELS",
     "OFPS_HIP_SAD_PREDICTORS", "OFPS_HIP_SAD_PREFILTER", "OFPS_HIP_SAD_MEDIAN", "OFPS_HIP_SAD_BATCH_FILTER",
     "OFPS_HIP_SAD_INTRA", "OFPS_HIP_SAD_CUT", "OFPS_HIP_DETECT_ISLANDS", "OFPS_HIP_SAD_SPLIT",
+    "OFPS_HIP_DETECT_TRACKS", "OFPS_HIP_DETECT_TRACK_REACH", "OFPS_HIP_DETECT_TRACK_GAP",
     "OFPS_HIP_KLT_CELL", "OFPS_HIP_KLT_SCORE_RADIUS", "OFPS_HIP_KLT_MIN_SCORE", "OFPS_HIP_KLT_MIN_EIG", "OFPS_HIP_KLT_MAX_RESIDUAL",
     "OFPS_HIP_BATCH_DECODER", "OFPS_HIP_KLT_LEVELS", "OFPS_HIP_KLT_RADIUS", "OFPS_HIP_KLT_ITERS", "OFPS_HIP_KLT_MEAN_REMOVAL",
     "OFPS_HIP_KLT_FB", "OFPS_HIP_KLT_PREDICTION", "OFPS_HIP_KLT_BATCH_PREDICTION", "OFPS_HIP_KLT_INTRA", "OFPS_HIP_KLT_CUT"};

@@ -344,7 +344,7 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
     // frame's slot is simply uploaded again by the next push) -- ADVICE r4
     const long frames_after = ds.frames + 1;
     int have_vectors = 0;
-    if (tail) ofps::islands_ticket_arm(ctx, &t.isl, tail, 1);           // A5i: the ticket follows the context's max_islands at this push
+    if (tail) ofps::islands_ticket_arm(ctx, &t.isl, tail, 1, ofps::TRK_DENSE, /*restart=*/frames_after < 2);     // A5i, A5t: the ticket follows the context's max_islands and max_tracks at this push
     else t.isl.K = 0;
     size_t tail_off = 0;
     if (frames_after >= 2) {                                        // cv-decoder/src/lib.rs:156-158: flow needs two frames
@@ -536,6 +536,7 @@ int ofps_hip_lk_reset(ofps_hip_ctx* ctx) {
     if (!ctx) return OFPS_HIP_EINVAL;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->fb.prev_flow.valid = false;                       // a new stream starts from zero flow, like a new CvDecoder
+    ctx->trk[ofps::TRK_DENSE].live = false;                // ... and from no tracks (A5t)
     return dense_stream_drain(ctx);
 }
 

@@ -332,27 +332,38 @@ static int detect_islands_device(ofps_hip_ctx* ctx, const float4* d_entries, siz
     return islands_field_device(ctx, d_field, dim, batch, min_size, target_motion, K, o);
 }
 
-static IslandsOut islands_blocks(char* base, int K, int dim) {           // `items` blocks of islands_block_bytes(K, dim)
-    const size_t bytes = islands_block_bytes(K, dim);
+// `items` blocks `bytes` apart, each led by [counts][table][labels]; bytes 0: islands_block_bytes(K, dim), nothing behind them
+static IslandsOut islands_blocks(char* base, int K, int dim, size_t bytes = 0) {
+    if (!bytes) bytes = islands_block_bytes(K, dim);
     return {reinterpret_cast<int*>(base), bytes / 4, reinterpret_cast<int*>(base + 16), bytes / 4,
             reinterpret_cast<uint16_t*>(base + 16 + (size_t)K * 32), bytes / 2, nullptr};
 }
 
-void islands_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, const ofps_hip_frame_params* prm, int items) {
+int detect_islands_blocks_device(ofps_hip_ctx* ctx, const float4* d_entries, size_t n, int batch, float min_size, size_t subdivide, float target_motion,
+                                 int K, char* d_blocks, size_t stride) {
+    const int dim = block_dim_host(min_size, subdivide);
+    OFPS_REQUIRE(ctx, dim >= 1 && dim <= kMaxDetectDim, "detect_islands: block_dim %d outside [1,160]", dim);
+    return detect_islands_device(ctx, d_entries, n, batch, min_size, subdivide, target_motion, K, islands_blocks(d_blocks, K, dim, stride));
+}
+
+void islands_ticket_arm(ofps_hip_ctx* ctx, IslandsTicket* isl, const ofps_hip_frame_params* prm, int items, int form, bool restart) {
     const int dim = prm->run_detector ? block_dim_host(prm->min_size, prm->subdivide) : 0;
     isl->K = dim >= 1 && dim <= kMaxDetectDim ? ctx->opt.detect_islands : 0;
     isl->items = items; isl->first = items; isl->dim = dim;
+    tracks_ticket_arm(ctx, isl, form, restart);                          // A5t
 }
 
 int islands_ticket_device(ofps_hip_ctx* ctx, int batch, int dim, float min_size, float target_motion, IslandsTicket* isl) {
-    const size_t bytes = islands_block_bytes(isl->K, dim);
+    const size_t bytes = ticket_block_bytes(isl->K, dim, isl->T);
     int rc = host_block_reserve(ctx, &isl->pinned, &isl->cap, bytes * isl->items);
     if (rc != OFPS_HIP_OK) return rc;
     auto* d_blocks = static_cast<char*>(scratch(ctx, S_ISL_OUT, bytes * batch));
     if (!d_blocks) return OFPS_HIP_ENOMEM;
     // detect_device has just densified these records into S_FIELD, on this stream
     rc = islands_field_device(ctx, static_cast<const float2*>(ctx->scratch[S_FIELD].p), dim, batch, min_size, target_motion, isl->K,
-                              islands_blocks(d_blocks, isl->K, dim));
+                              islands_blocks(d_blocks, isl->K, dim, bytes));
+    // A5t: a ticket armed with max_tracks > 0 steps its form's tracker through these items, behind the islands kernel on this stream
+    if (rc == OFPS_HIP_OK && isl->T > 0) rc = tracks_ticket_device(ctx, isl, batch, dim, d_blocks, bytes);
     if (rc != OFPS_HIP_OK) return rc;
     isl->first = isl->items - batch; isl->dim = dim;
     return read_back_device(ctx, static_cast<char*>(isl->pinned) + bytes * isl->first, d_blocks, bytes * batch, ctx->stream);
@@ -362,7 +373,7 @@ int islands_collect(ofps_hip_ctx* ctx, const IslandsTicket& isl) {
     auto& last = ctx->isl_last;
     last.K = 0;
     if (isl.K <= 0) return OFPS_HIP_OK;
-    const size_t bytes = islands_block_bytes(isl.K, isl.dim), total = bytes * isl.items;
+    const size_t bytes = ticket_block_bytes(isl.K, isl.dim, isl.T), total = bytes * isl.items;
     if (last.cap < total) {
         free(last.data);
         last.cap = 0;
@@ -377,7 +388,7 @@ int islands_collect(ofps_hip_ctx* ctx, const IslandsTicket& isl) {
         reinterpret_cast<int*>(dst)[2] = isl.dim;
         memset(dst + 16 + (size_t)isl.K * 32, 0xFF, (size_t)isl.dim * isl.dim * sizeof(uint16_t));
     }
-    last.K = isl.K; last.items = isl.items; last.dim = isl.dim;
+    last.K = isl.K; last.items = isl.items; last.dim = isl.dim; last.T = isl.T;
     return OFPS_HIP_OK;
 }
 
@@ -481,7 +492,7 @@ int ofps_hip_frame_islands(ofps_hip_ctx* ctx, int item, int32_t out_counts[4], i
     const auto& last = ctx->isl_last;
     OFPS_REQUIRE(ctx, last.K > 0, "frame_islands: the last collected ticket was pushed with max_islands 0 or without the detector");
     OFPS_REQUIRE(ctx, item >= 0 && item < last.items, "frame_islands: item %d outside [0, %d)", item, last.items);
-    const char* blk = last.data + ofps::islands_block_bytes(last.K, last.dim) * item;
+    const char* blk = last.data + ofps::ticket_block_bytes(last.K, last.dim, last.T) * item;
     int32_t counts[4];
     memcpy(counts, blk, sizeof(counts));
     OFPS_REQUIRE(ctx, capacity >= counts[3], "frame_islands: capacity %d is below the %d listed islands", capacity, counts[3]);

@@ -113,7 +113,7 @@ struct Push {
         t = &ctx->pipe.ring.at(tno);
         tix = (int)(tno % kTickets);
         OFPS_REQUIRE(ctx, !t->pending, "push_frame_async: ticket %ld has not been collected (at most %d frames in flight)", tno - kTickets, kTickets);
-        ofps::islands_ticket_arm(ctx, &t->isl, prm, 1);             // A5i: the ticket follows the context's max_islands at this push
+        ofps::islands_ticket_arm(ctx, &t->isl, prm, 1, ofps::TRK_PIPE);     // A5i, A5t: the ticket follows the context's max_islands and max_tracks at this push
         return f.plan(ctx, "push_frame_async");
     }
 
@@ -126,6 +126,7 @@ struct Push {
         const int rc = pipe_upload(ctx, luma, f.fr.W, f.fr.H, stride, /*overlap=*/ps.ring.other_pending(), &slots, &pitch, &dstride);
         if (rc != OFPS_HIP_OK) return rc;
         frame_no = ps.frames - 1;
+        if (frame_no == 0) ctx->trk[ofps::TRK_PIPE].live = false;      // A5t: a stream's first frame forgets the tracks of the one before
         cur_slot = (int)(frame_no % kSlots); prev_slot = (int)((frame_no + kSlots - 1) % kSlots);
         f.fr.cur_base = slots + (size_t)cur_slot * pitch; f.fr.prev_base = slots + (size_t)prev_slot * pitch;
         cur_by_event = !ps.uploaded_on_compute[cur_slot];
@@ -214,6 +215,7 @@ int ofps_hip_reset_frames(ofps_hip_ctx* ctx) {
     OFPS_HIP_TRY(ctx, ctx->batch.ring.drain());
     ctx->batch.last_frame = nullptr;
     ctx->batch.klt_pred.valid = false;
+    ctx->trk[ofps::TRK_PIPE].live = false; ctx->trk[ofps::TRK_BATCH].live = false;       // A5t: both forms' tracks start anew
     return pipe_drain(ctx);
 }
 
@@ -434,7 +436,7 @@ struct BatchPush {
         // what holds whether or not a pair follows: no slots to chain from until decode() says so, and the ticket's islands
         ctx->batch.klt_pred.valid = false;
         if (halo_mode) t->isl.K = 0;                                 // the multi-device workers list no islands (include/ofps_hip.h A5i)
-        else islands_ticket_arm(ctx, &t->isl, prm, n);
+        else islands_ticket_arm(ctx, &t->isl, prm, n, TRK_BATCH, /*restart=*/!has_prev);
         return OFPS_HIP_OK;
     }
 

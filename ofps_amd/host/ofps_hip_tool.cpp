@@ -3,7 +3,7 @@
 //                                                                               e.g. hip_sad: "Block size", "Search range", "Exact pruning", "Quarter pel"=true|false,
 //                                                                               "Split blocks"=T (then a frame holds between nblk and 4 * nblk vectors)
 //   detect  <decoder> <arg> [max_frames]                detection loop, ofps-suite/src/app/detection.rs:92-168
-//   detect  --config <saved.json> [--perf-csv <dir>] [--islands-csv <file>] [max_frames]     (--islands-csv: "Max islands" > 0 in the config)
+//   detect  --config <saved.json> [--perf-csv <dir>] [--islands-csv <file>] [max_frames]     (--islands-csv: "Max islands" > 0 in the config; "Max tracks" > 0 adds id,age,hits,mx,my)
 //                                                       the same loop from a saved MotionDetectionConfig (detection.rs:45-50):
 //                                                       plugins, their saved properties, max_frame_gap / min_frames
 //   parse-config <saved.json>                           prints what a saved configuration says (no GPU)
@@ -166,14 +166,25 @@ int main(int argc, char** argv) {
                 if (!bm || bm->max_islands == 0) throw Error("--islands-csv needs the hip_block_motion detector with \"Max islands\" above 0 in the configuration");
                 isl_out.open(islands_csv);
                 if (!isl_out) throw Error("cannot write " + islands_csv);
-                isl_out << "frame,rank,seed,area,x0,y0,x1,y1,cx,cy\n";
-                on_frame = [&isl_out, bm](size_t frame) {
+                // "Max tracks" > 0 (A5t): id, age, hits and the island's mean motion behind every row; id 0 = not followed
+                const bool with_tracks = bm->max_tracks > 0;
+                isl_out << (with_tracks ? "frame,rank,seed,area,x0,y0,x1,y1,cx,cy,id,age,hits,mx,my\n" : "frame,rank,seed,area,x0,y0,x1,y1,cx,cy\n");
+                on_frame = [&isl_out, bm, with_tracks](size_t frame) {
                     const int dim = ofps_hip_block_dim(bm->min_size, bm->subdivide);
                     size_t rank = 0;
                     char line[256];
                     for (const auto& s : bm->islands()) {
                         const double cx = ((double)s.sum_x / s.area + 0.5) / dim, cy = ((double)s.sum_y / s.area + 0.5) / dim;
-                        std::snprintf(line, sizeof(line), "%zu,%zu,%d,%d,%d,%d,%d,%d,%.6f,%.6f\n", frame, rank++, s.seed, s.area, s.x0, s.y0, s.x1, s.y1, cx, cy);
+                        if (with_tracks) {
+                            const auto& tr = bm->tracks();
+                            const HipBlockMotionDetection::Track t = rank < tr.size() ? tr[rank] : HipBlockMotionDetection::Track{0, -1, 0, 0, 0, 0};
+                            const double scale = (double)s.area * 16777216.0;
+                            std::snprintf(line, sizeof(line), "%zu,%zu,%d,%d,%d,%d,%d,%d,%.6f,%.6f,%d,%d,%d,%.8f,%.8f\n", frame, rank, s.seed, s.area, s.x0, s.y0,
+                                          s.x1, s.y1, cx, cy, t.id, t.age, t.hits, (double)t.sum_mx / scale, (double)t.sum_my / scale);
+                            ++rank;
+                        } else {
+                            std::snprintf(line, sizeof(line), "%zu,%zu,%d,%d,%d,%d,%d,%d,%.6f,%.6f\n", frame, rank++, s.seed, s.area, s.x0, s.y0, s.x1, s.y1, cx, cy);
+                        }
                         isl_out << line;
                     }
                 };

@@ -318,6 +318,22 @@ std::optional<std::pair<size_t, MotionField>> HipBlockMotionDetection::detect_mo
         const int rc = ofps_hip_detect_islands(ctx_.get(), reinterpret_cast<const float*>(mv), n, min_size, subdivide, target_motion, (int)max_islands,
                                                counts, reinterpret_cast<int32_t*>(islands_.data()), nullptr, mf.raw().data());
         islands_.resize(rc == OFPS_HIP_OK ? (size_t)counts[3] : 0);
+        tracks_.clear();
+        if (rc == OFPS_HIP_OK && max_tracks > 0) {                      // A5t: one step of this detector's tracker on the same records
+            static_assert(sizeof(Track) == 8 * sizeof(int32_t), "one track row");
+            const size_t key[5] = {(size_t)dim, max_islands, max_tracks, track_reach, track_gap};
+            const size_t bytes = ofps_hip_island_tracker_bytes(dim, (int)max_tracks);
+            if (track_state_.size() != bytes || !std::equal(key, key + 5, track_key_)) track_state_.assign(bytes, 0);
+            std::copy(key, key + 5, track_key_);
+            std::vector<Island> table(max_islands);
+            int32_t c2[4] = {0, 0, 0, 0}, tc[4] = {0, 0, 0, 0};
+            tracks_.assign(max_tracks, Track{});
+            const int rt = bytes ? ofps_hip_detect_tracks(ctx_.get(), reinterpret_cast<const float*>(mv), n, 1, min_size, subdivide, target_motion,
+                                                          (int)max_islands, (int)max_tracks, (int)track_reach, (int)track_gap, track_state_.data(), c2,
+                                                          reinterpret_cast<int32_t*>(table.data()), nullptr, tc, reinterpret_cast<int32_t*>(tracks_.data()))
+                                 : OFPS_HIP_EINVAL;
+            tracks_.resize(rt == OFPS_HIP_OK ? (size_t)tc[0] : 0);
+        }
         if (rc != OFPS_HIP_OK || counts[0] < 1) return std::nullopt;
         return std::make_pair((size_t)islands_[0].area, std::move(mf));
     }
@@ -333,7 +349,10 @@ std::vector<std::pair<std::string, PropertyMut>> HipBlockMotionDetection::props_
     return {{"Min size", PropertyMut::float_(&min_size, 0.01f, 1.0f)},
             {"Subdivisions", PropertyMut::usize(&subdivide, 1, 16)},
             {"Target motion", PropertyMut::float_(&target_motion, 0.0001f, 0.1f)},
-            {"Max islands", PropertyMut::usize(&max_islands, 0, 256)}};
+            {"Max islands", PropertyMut::usize(&max_islands, 0, 256)},
+            {"Max tracks", PropertyMut::usize(&max_tracks, 0, 256)},
+            {"Track reach", PropertyMut::usize(&track_reach, 0, 4)},
+            {"Track gap", PropertyMut::usize(&track_gap, 0, 255)}};
 }
 
 // ------------------------------------------------------------------ hip_almeida

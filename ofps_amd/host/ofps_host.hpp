@@ -256,11 +256,21 @@ public:
     size_t max_islands = 0;
     struct Island { int32_t seed, area, x0, y0, x1, y1, sum_x, sum_y; };
     const std::vector<Island>& islands() const { return islands_; }  // the last frame's listed islands, in rank order
+    // build-defined (include/ofps_hip.h A5t): with "Max islands" and "Max tracks" above 0 the detector follows the listed islands from frame
+    // to frame: tracks() holds one row per rank beside islands(), id 0 = not followed.  The tracker starts anew when one of the grid or
+    // track properties changes, and with reset_tracks()
+    size_t max_tracks = 0, track_reach = 1, track_gap = 2;
+    struct Track { int32_t id, slot, age, hits; int64_t sum_mx, sum_my; };    // mean motion of the island: sum / area / 2^24
+    const std::vector<Track>& tracks() const { return tracks_; }
+    void reset_tracks() { track_state_.clear(); }
     std::optional<std::pair<size_t, MotionField>> detect_motion(const MotionEntry* mv, size_t n) override;
     std::vector<std::pair<std::string, PropertyMut>> props_mut() override;
 private:
     HipContext ctx_;
     std::vector<Island> islands_;
+    std::vector<Track> tracks_;
+    std::vector<uint8_t> track_state_;
+    size_t track_key_[5] = {0, 0, 0, 0, 0};    // dim, K, T, reach, gap the state was made under
 };
 
 class HipAlmeidaEstimator : public Estimator {                       // almeida-estimator/src/lib.rs:57-121

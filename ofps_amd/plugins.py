@@ -347,21 +347,39 @@ class HipBlockMotionDetection(Properties):
     # returns the largest one's area with the union of the listed islands' fields, and last_islands holds the table.  props() stays the
     # reference's three names; the extension is listed by ext_props() and set through the same set_prop
     _EXT_PROPS = (("Max islands", "usize", "max_islands", 0, 256),)
+    # build-defined (include/ofps_hip.h A5t): with "Max islands" and "Max tracks" above 0 the detector follows the listed islands from frame to
+    # frame; tracks() holds the last frame's rows beside last_islands.  The three properties depend on the island list: ext_props() lists them
+    # once "Max islands" is above 0, set_prop takes them at any time
+    _TRACK_PROPS = (("Max tracks", "usize", "max_tracks", 0, 256), ("Track reach", "usize", "track_reach", 0, 4), ("Track gap", "usize", "track_gap", 0, 255))
 
     def __init__(self, device: int = 0):
         self.ctx = HipContext(device)
         self.min_size, self.subdivide, self.target_motion = 0.05, 3, 0.003
         self.max_islands = 0
         self.last_islands = None          # int32 [n_listed, 8]: seed, area, x0, y0, x1, y1, sum_x, sum_y of the last frame (Max islands > 0)
+        self.max_tracks, self.track_reach, self.track_gap = 0, 1, 2
+        self._tracks, self._track_state, self._track_key = None, None, None
 
     def ext_props(self):
-        return [(name, kind, getattr(self, attr), lo, hi) for name, kind, attr, lo, hi in self._EXT_PROPS]
+        rows = self._EXT_PROPS + (self._TRACK_PROPS if self.max_islands > 0 else ())
+        return [(name, kind, getattr(self, attr), lo, hi) for name, kind, attr, lo, hi in rows]
 
     def set_prop(self, name: str, value) -> bool:
         if name == "Max islands":
             self.max_islands = min(max(int(value), 0), 256)
             return True
+        for pname, _, attr, lo, hi in self._TRACK_PROPS:
+            if name == pname:
+                setattr(self, attr, min(max(int(value), lo), hi))
+                return True
         return super().set_prop(name, value)
+
+    def tracks(self):
+        """the last frame's tracks (HipContext.detect_tracks' dict: id, slot, age, hits, sum_motion per rank beside last_islands), or None"""
+        return self._tracks
+
+    def reset_tracks(self):
+        self._track_state = None
 
     def detect_motion(self, motion):
         """-> None | (area, MotionField)"""
@@ -369,6 +387,14 @@ class HipBlockMotionDetection(Properties):
         if self.max_islands > 0:
             r = self.ctx.detect_islands(mv, self.min_size, self.subdivide, self.target_motion, self.max_islands, want_labels=False)
             self.last_islands = r["table"]
+            self._tracks = None
+            if self.max_tracks > 0:                                      # A5t: one step of this detector's tracker on the same records
+                key = (r["dim"], self.max_islands, self.max_tracks, self.track_reach, self.track_gap)
+                if key != self._track_key:
+                    self._track_state, self._track_key = None, key
+                out, self._track_state = self.ctx.detect_tracks(mv, self.min_size, self.subdivide, self.target_motion, self.max_islands, self.max_tracks,
+                                                                self.track_reach, self.track_gap, self._track_state)
+                self._tracks = out[0]["tracks"]
             return None if r["n_islands"] == 0 else (int(r["table"][0, 1]), MotionField(r["field"]))
         r = self.ctx.detect(mv, self.min_size, self.subdivide, self.target_motion)
         return None if r is None else (r[0], MotionField(r[1]))

@@ -1045,6 +1045,8 @@ class HipContext:
                "entries": ent[:n] if (ent is not None and have) else None, "grid": grid}
         if islands:
             out["islands"] = self.frame_islands(0)
+        if islands == 2:
+            out["tracks"] = self.frame_tracks(0)
         return out
 
     def lk_push_frame_fused_async(self, frame: np.ndarray, levels=3, radius=4, iters=3, max_w=150, max_h=150, contrast_mask=False,
@@ -1246,9 +1248,84 @@ class HipContext:
         return {"n_islands": int(counts[0]), "n_components": int(counts[1]), "dim": dim, "n_listed": int(counts[3]),
                 "table": table[:int(counts[3])].copy(), "labels": labels[:dim * dim].reshape(dim, dim).copy() if want_labels else None}
 
-    def _ticket_islands(self, detector) -> bool:
-        """whether a ticket pushed now will carry islands: the context's max_islands at the push counts"""
-        return bool(detector) and self.get_detect_islands() > 0
+    def _ticket_islands(self, detector) -> int:
+        """whether a ticket pushed now will carry islands (1) and tracks as well (2): the context's max_islands and max_tracks at the push count"""
+        if not (bool(detector) and self.get_detect_islands() > 0):
+            return 0
+        return 2 if self.get_detect_tracks()["max_tracks"] > 0 else 1
+
+    # ---- A5t: island tracks (include/ofps_hip.h; csrc/detect_tracks.hip)
+    @staticmethod
+    def _tracks_dict(counts, rows) -> dict:
+        n = int(counts[0])
+        rows = np.ascontiguousarray(rows[:n], np.int32)
+        sums = rows[:, 4:8].copy().view(np.int64).reshape(n, 2)
+        return {"rows": n, "n_tracked": int(counts[1]), "n_live": int(counts[2]), "t": int(counts[3]), "id": rows[:, 0].copy(), "slot": rows[:, 1].copy(),
+                "age": rows[:, 2].copy(), "hits": rows[:, 3].copy(), "sum_motion": sums, "table": rows.copy()}
+
+    @staticmethod
+    def track_motion(tracks: dict, areas) -> np.ndarray:
+        """[n, 2] mean motion of the rows' islands: sum / area / 2^24 (areas: A5i's table column 1)"""
+        a = np.maximum(np.asarray(areas, np.float64).reshape(-1, 1)[:tracks["rows"]], 1)
+        return tracks["sum_motion"].astype(np.float64) / a / float(1 << 24)
+
+    def island_tracker_bytes(self, dim: int, max_tracks: int) -> int:
+        """the size of a tracker state; zeros are a fresh tracker.  0: dim or max_tracks out of range"""
+        return int(self._lib.ofps_hip_island_tracker_bytes(int(dim), int(max_tracks)))
+
+    def track_islands_dev(self, d_counts: int, d_table: int, d_labels: int, d_cells: int | None, dim: int, max_islands: int, batch: int,
+                          max_tracks: int, reach: int, max_gap: int, d_state: int, d_out_track_counts: int, d_out_tracks: int):
+        """Device form: `batch` items stepped in order through one state, one launch.  Per item counts int32[4], table int32[8 * max_islands],
+        labels uint16[dim * dim], cells f32[2 * dim * dim] | None -> track_counts int32[4], tracks int32[8 * max_tracks].  Enqueue only."""
+        self._check(self._lib.ofps_hip_track_islands_dev(self._h, C.c_void_p(d_counts), C.c_void_p(d_table), C.c_void_p(d_labels), C.c_void_p(d_cells or 0),
+                                                         int(dim), int(max_islands), int(batch), int(max_tracks), int(reach), int(max_gap),
+                                                         C.c_void_p(d_state or 0), C.c_void_p(d_out_track_counts), C.c_void_p(d_out_tracks)))
+
+    def detect_tracks(self, frames, min_size=0.05, subdivide=3, target_motion=0.003, max_islands=16, max_tracks=16, reach=1, max_gap=2,
+                      state: np.ndarray | None = None) -> tuple:
+        """frames: [batch, n, 4] records, one frame sequence -> (list of dict(islands=..., tracks=...) per frame, state).  state: the uint8 array a
+        call before returned, or None for a fresh tracker; it is updated in place and returned"""
+        e = np.ascontiguousarray(frames, np.float32)
+        e = e.reshape(1, -1, 4) if e.ndim == 2 else e
+        batch, n = e.shape[0], e.shape[1]
+        dim = max(self.block_dim(min_size, subdivide), 1)
+        K, T = max(int(max_islands), 1), max(int(max_tracks), 1)
+        if state is None:
+            state = np.zeros(max(self.island_tracker_bytes(dim, max_tracks), 16), np.uint8)
+        assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"]
+        counts, table = np.zeros((batch, 4), np.int32), np.zeros((batch, K, 8), np.int32)
+        labels = np.zeros((batch, dim, dim), np.uint16)
+        tcounts, rows = np.zeros((batch, 4), np.int32), np.zeros((batch, T, 8), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_detect_tracks(self._h, _fp(e), n, batch, min_size, subdivide, target_motion, int(max_islands), int(max_tracks),
+                                                     int(reach), int(max_gap), C.c_void_p(state.ctypes.data), counts.ctypes.data_as(i32),
+                                                     table.ctypes.data_as(i32), C.c_void_p(labels.ctypes.data), tcounts.ctypes.data_as(i32),
+                                                     rows.ctypes.data_as(i32)))
+        out = []
+        for j in range(batch):
+            c = counts[j]
+            isl = {"n_islands": int(c[0]), "n_components": int(c[1]), "dim": int(c[2]), "n_listed": int(c[3]), "table": table[j, :int(c[3])].copy(),
+                   "labels": labels[j].copy()}
+            out.append({"islands": isl, "tracks": self._tracks_dict(tcounts[j], rows[j])})
+        return out, state
+
+    def set_detect_tracks(self, max_tracks: int, reach: int = 1, max_gap: int = 2):
+        """max_tracks 0 = off (default); T in [1, 256]: a fused ticket that lists islands follows them across frames, read with frame_tracks"""
+        self._check(self._lib.ofps_hip_set_detect_tracks(self._h, int(max_tracks), int(reach), int(max_gap)))
+
+    def get_detect_tracks(self) -> dict:
+        t, r, g = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.ofps_hip_get_detect_tracks(self._h, C.byref(t), C.byref(r), C.byref(g)))
+        return {"max_tracks": t.value, "reach": r.value, "max_gap": g.value}
+
+    def frame_tracks(self, item: int = 0) -> dict:
+        """The tracks of `item` of the most recently collected fused ticket (pushed with max_islands > 0, max_tracks > 0 and the detector on)"""
+        counts = np.zeros(4, np.int32)
+        if getattr(self, "_trk_buf", None) is None:
+            self._trk_buf = np.zeros((256, 8), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.ofps_hip_frame_tracks(self._h, int(item), counts.ctypes.data_as(i32), self._trk_buf.ctypes.data_as(i32), 256))
+        return self._tracks_dict(counts, self._trk_buf)
 
     # ---- A6-A12
     def almeida(self, entries, aspect: float, fov_y_deg: float, use_ransac=False, num_iters=200, inlier_deg=0.05,
@@ -1373,9 +1450,12 @@ class HipContext:
         self._check(self._lib.ofps_hip_frames_wait(self._h, ticket, res))
         out = [{"have_vectors": bool(r.have_vectors), "n_vectors": int(r.n_vectors),
                 "motion": (int(r.area), int(r.dim)) if r.has_motion else None, "quat": np.array(list(r.quat), np.float32)} for r in res]
-        if getattr(self, "_batch_isl", {}).pop(ticket, False):
+        islands = getattr(self, "_batch_isl", {}).pop(ticket, 0)
+        if islands:
             for j, o in enumerate(out):
                 o["islands"] = self.frame_islands(j)
+                if islands == 2:
+                    o["tracks"] = self.frame_tracks(j)
         return out
 
     def frame_wait(self, ticket: int) -> dict:
@@ -1383,8 +1463,11 @@ class HipContext:
         self._check(self._lib.ofps_hip_frame_wait(self._h, ticket, C.byref(res)))
         out = {"have_vectors": bool(res.have_vectors), "n_vectors": int(res.n_vectors),
                "motion": (int(res.area), int(res.dim)) if res.has_motion else None, "quat": np.array(list(res.quat), np.float32)}
-        if getattr(self, "_pipe_isl", {}).pop(ticket, False):
+        islands = getattr(self, "_pipe_isl", {}).pop(ticket, 0)
+        if islands:
             out["islands"] = self.frame_islands(0)
+        if islands == 2:
+            out["tracks"] = self.frame_tracks(0)
         return out
 
     def push_frame(self, luma: np.ndarray, block=16, search_range=16, detector=True, min_size=0.05, subdivide=3,
@@ -1410,6 +1493,8 @@ class HipContext:
                "entries": ent[:min(nb, int(res.n_vectors))] if (want_entries and res.have_vectors) else None}      # (the kept records with the contrast gate on)
         if islands:
             out["islands"] = self.frame_islands(0)
+        if islands == 2:
+            out["tracks"] = self.frame_tracks(0)
         return out
 
 
