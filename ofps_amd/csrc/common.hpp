@@ -75,6 +75,24 @@ struct BatchBlock {
 static_assert(BatchBlock{1, false}.bytes() == 32 && BatchBlock{1, true}.bytes() == 36 && BatchBlock{5, true}.bytes() == 5 * 32 + 5 * 4, "batch block size");
 static_assert(BatchBlock{1, false}.quat_at() == 16 && BatchBlock{1, true}.quat_at() == 16 && BatchBlock{5, true}.quat_at() == 5 * 16, "batch block quaternions");
 static_assert(BatchBlock{1, false}.kept_at() == 32 && BatchBlock{1, true}.kept_at() == 32 && BatchBlock{5, true}.kept_at() == 5 * 32, "batch block counts");
+// A dense decoder's result block: [count, pad x 3][records x max_records] and, behind a fused ticket's records, [TailRecord][detector field
+// dim x dim].  The ticket's page-locked memory, ofps_hip_lk_decode's, and (plain) the fused push's device copy of the records; nobody else
+// spells it.  result / quat / field: null when the block is not fused
+struct DenseBlock {
+    size_t max_records; bool fused; int dim;
+    static constexpr size_t kHeader = 16;
+    constexpr size_t tail_at() const { return kHeader + max_records * sizeof(float4); }
+    constexpr size_t bytes() const { return tail_at() + (fused ? sizeof(TailRecord) + (size_t)dim * dim * sizeof(float2) : 0); }
+    uint32_t* count(char* base) const { return reinterpret_cast<uint32_t*>(base); }
+    float4* records(char* base) const { return reinterpret_cast<float4*>(base + kHeader); }
+    int* result(char* base) const { return fused ? reinterpret_cast<int*>(base + tail_at() + offsetof(TailRecord, result)) : nullptr; }
+    float4* quat(char* base) const { return fused ? reinterpret_cast<float4*>(base + tail_at() + offsetof(TailRecord, quat)) : nullptr; }
+    float2* field(char* base) const { return fused ? reinterpret_cast<float2*>(base + tail_at() + sizeof(TailRecord)) : nullptr; }
+};
+static_assert(DenseBlock::kHeader % sizeof(float4) == 0 && sizeof(TailRecord) % sizeof(float4) == 0, "records, quaternion and field stay 16-byte aligned");
+static_assert(DenseBlock{312, false, 0}.bytes() == 16 + 312 * 16 && DenseBlock{312, false, 0}.tail_at() == 16 + 312 * 16, "dense block, plain");
+static_assert(DenseBlock{312, true, 14}.bytes() == 16 + 312 * 16 + 32 + 14 * 14 * 8 && DenseBlock{312, true, 14}.tail_at() == 16 + 312 * 16, "dense block, fused");
+static_assert(DenseBlock{12600, true, 23}.bytes() == 16 + 12600 * 16 + 32 + 23 * 23 * 8 && DenseBlock{12600, true, 23}.tail_at() == 16 + 12600 * 16, "dense block, fused and reduced");
 // What every fused wait answers: zeros and the identity quaternion, then what the ticket has.  n_vectors: already clamped by the caller;
 // result (int[4]) / quat (float[4]): null for a stage that did not run or a frame without vectors; they need no alignment
 inline void fill_frame_result(ofps_hip_frame_result* out, int have_vectors, size_t n_vectors, const void* result, const void* quat) {
@@ -203,7 +221,7 @@ struct BatchStream {
 };
 
 // dense decoders, hip_lk and hip_flow (dense_decoder.hip: ofps_hip_lk_push_frame[_async] / ofps_hip_lk_frame_wait): frame k lives in
-// slot k % 3 of S_LK_FRAMES; each ticket has a page-locked block [count, pad x 3][records] that its last kernels write directly
+// slot k % 3 of S_LK_FRAMES; each ticket has a page-locked block (DenseBlock) that its last kernels write directly
 struct DenseStream {
     static constexpr int kSlots = 3, kTickets = 2;
     int w = 0, h = 0;                    // the arriving frames' size
@@ -220,12 +238,11 @@ struct DenseStream {
     struct Ticket {
         bool pending = false;
         hipEvent_t done = nullptr, uploaded = nullptr;
-        void* pinned = nullptr; size_t pinned_cap = 0;
+        void* pinned = nullptr; size_t pinned_cap = 0;       // a DenseBlock of {max_records, fused, dim}
         int have_vectors = 0, gw = 0, gh = 0;
         size_t max_records = 0;
-        // fused form (ofps_hip_lk_push_frame_fused[_async]): the tail's results sit behind the records, at tail_off of the block
+        // fused form (ofps_hip_lk_push_frame_fused[_async]): the tail's results sit behind the records
         int fused = 0, run_detector = 0, run_estimator = 0, dim = 0;
-        size_t tail_off = 0;
         IslandsTicket isl;               // A5i
     };
     TicketRing<Ticket, kTickets> ring;

@@ -120,19 +120,31 @@ __global__ __launch_bounds__(256) void dense_copy_records_kernel(const float4* _
     if (cnt_dst && blockIdx.x == 0 && threadIdx.x == 0) *cnt_dst = (uint32_t)n;
 }
 
+// One pair of a process_frame, as dense_enqueue_frame takes it
+struct DenseFrameCall {
+    const uint8_t* d_prev; const uint8_t* d_cur;      // the fw x fh frames on the device, rows dense
+    uint64_t prev_id, cur_id;                         // the stream's frame ids (farneback.hip, OFPS_HIP_FLOW_USE_PREVIOUS); 0: a pair outside a stream
+    int W, H;
+    int levels, radius, iters;
+    const DenseGrid& g;
+    float4* rec_dst; uint32_t* cnt_dst;               // device scratch, or the device address of a page-locked block
+    bool in_place;                                    // fused form: the caller reads the records where they lie -- a compaction's own output is not copied to rec_dst at all
+    const uint8_t* d_mask_ready;                      // stream forms: the mask made ahead on the upload's stream, or null
+    int* klt_slots; const int* klt_prev_slots;        // N3p: the pair's raw slots are kept in klt_slots, its tracks start from klt_prev_slots' flow
+};
+// ... and what it answers: where the records and their count lie in DEVICE memory -- rec_dst / cnt_dst, or (in_place) the compaction's own output
+struct DenseRecords {
+    int rc; const float4* rec; const uint32_t* cnt;
+    DenseRecords(int rc_, const float4* rec_ = nullptr, const uint32_t* cnt_ = nullptr) : rc(rc_), rec(rec_), cnt(cnt_) {}
+};
+
 // Enqueues everything of a process_frame that follows the uploads on ctx->stream: flow [-> contrast mask] -> output stage.
 // The record count lands at cnt_dst and the records at rec_dst -- device scratch, or the device address of a page-locked
 // block (the kernels store there directly: no read-back launch of their own).
-int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int W, int H, int levels, int radius, int iters,
-                     const DenseGrid& g, float4* rec_dst, uint32_t* cnt_dst, uint64_t prev_id = 0,
-                     uint64_t cur_id = 0, const uint8_t* d_mask_ready = nullptr, const float4** tail_rec = nullptr,
-                     const uint32_t** tail_cnt = nullptr, int* klt_slots = nullptr, const int* klt_prev_slots = nullptr) {
-    // tail_rec / tail_cnt (fused form): where a tail finds the records and their count in DEVICE memory -- rec_dst / cnt_dst, which the
-    // caller then points at device scratch, or the compaction's own output, which is then not copied to rec_dst at all
-    if (tail_rec) { *tail_rec = rec_dst; *tail_cnt = cnt_dst; }
+DenseRecords dense_enqueue_frame(ofps_hip_ctx* ctx, const DenseFrameCall& c) {
+    const auto [d_prev, d_cur, prev_id, cur_id, W, H, levels, radius, iters, g, rec_dst, cnt_dst, in_place, d_mask_ready, klt_slots, klt_prev_slots] = c;
     // hip_klt: features, pyramid, track, flags, the ordered compaction and the count, straight to rec_dst / cnt_dst
-    // (N3p, the stream forms with klt_prediction 1: the pair's raw slots are kept in klt_slots, its tracks start from klt_prev_slots' flow)
-    if (g.sparse) return ofps::klt_flow_device(ctx, d_prev, d_cur, W, H, W, levels, radius, iters, rec_dst, cnt_dst, klt_slots, klt_prev_slots);
+    if (g.sparse) return {ofps::klt_flow_device(ctx, d_prev, d_cur, W, H, W, levels, radius, iters, rec_dst, cnt_dst, klt_slots, klt_prev_slots), rec_dst, cnt_dst};
     const size_t px = (size_t)W * H, cells = g.per_pixel ? 1 : (size_t)g.gw * g.gh;
     auto* d_ent = static_cast<float4*>(ofps::scratch(ctx, ofps::S_ENTRIES, px * sizeof(float4)));
     auto* d_field = static_cast<float2*>(ofps::scratch(ctx, ofps::S_FIELD, cells * sizeof(float2)));
@@ -175,35 +187,32 @@ int dense_enqueue_frame(ofps_hip_ctx* ctx, const uint8_t* d_prev, const uint8_t*
         const float4* d_rec = d_ent;
         const uint32_t* d_n = nullptr;
         if (g.use_mask && px <= ofps::kCompactSmallMax)      // a reduced frame's records: one single-workgroup launch, straight into the block
-            return ofps::compact_small_device(ctx, d_ent, d_mask, px, rec_dst, cnt_dst);
+            return {ofps::compact_small_device(ctx, d_ent, d_mask, px, rec_dst, cnt_dst), rec_dst, cnt_dst};
         if (g.use_mask) {                                  // the masked records themselves: order-preserving compaction
             auto* d_ent2 = static_cast<float4*>(ofps::scratch(ctx, ofps::S_ENTRIES2, px * sizeof(float4)));
             if (!d_ent2) return OFPS_HIP_ENOMEM;
             rc = ofps::compact_entries_device(ctx, d_ent, d_mask, px, d_ent2, d_cnt + 1);
             if (rc != OFPS_HIP_OK) return rc;
             d_rec = d_ent2; d_n = d_cnt + 1;
-            if (tail_rec) { *tail_rec = d_ent2; *tail_cnt = d_cnt + 1; return OFPS_HIP_OK; }      // (the caller's one copy fills the block from here)
+            if (in_place) return {OFPS_HIP_OK, d_ent2, d_cnt + 1};      // (the caller's one copy fills the block from here)
         }
         hipLaunchKernelGGL(dense_copy_records_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_rec, rec_dst, d_n, px, cnt_dst);
         OFPS_HIP_TRY(ctx, hipGetLastError());
-        return OFPS_HIP_OK;
+        return {OFPS_HIP_OK, rec_dst, cnt_dst};
     }
     // down-sampled output (cv-decoder/src/lib.rs:244-291): the records are this call's own per-pixel lattice, so the
     // densifier walks each cell's rectangle of pixels (masked ones skipped in place) instead of sorting 2 M records
-    return ofps::densify_raster_entries_device(ctx, d_ent, d_mask, W, H, g.gw, g.gh, d_field, rec_dst, cnt_dst);
+    return {ofps::densify_raster_entries_device(ctx, d_ent, d_mask, W, H, g.gw, g.gh, d_field, rec_dst, cnt_dst), rec_dst, cnt_dst};
 }
 
-constexpr size_t kBlockHeader = 16;             // a page-locked result block: [count, pad x 3][records]; a fused ticket's goes on behind
-                                                // the records' capacity with [TailRecord][detector field 2 * dim * dim]
-constexpr size_t kTailResult = offsetof(ofps::TailRecord, result), kTailQuat = offsetof(ofps::TailRecord, quat), kTailField = sizeof(ofps::TailRecord);
-static_assert(kBlockHeader % sizeof(float4) == 0 && kTailField % sizeof(float4) == 0, "records, quaternion and field stay 16-byte aligned");
-
 // count + records of a finished block -> the caller's buffer
-void dense_collect(const void* pinned, size_t max_records, float* out_entries, size_t* n_out) {
+void dense_collect(void* pinned, size_t max_records, float* out_entries, size_t* n_out) {
+    const ofps::DenseBlock blk{max_records, false, 0};
+    char* base = static_cast<char*>(pinned);
     uint32_t cnt = 0;
-    memcpy(&cnt, pinned, sizeof(cnt));
+    memcpy(&cnt, blk.count(base), sizeof(cnt));
     if (cnt > max_records) cnt = (uint32_t)max_records;
-    if (cnt) memcpy(out_entries, static_cast<const char*>(pinned) + kBlockHeader, (size_t)cnt * sizeof(float4));
+    if (cnt) memcpy(out_entries, blk.records(base), (size_t)cnt * sizeof(float4));
     *n_out = cnt;
 }
 
@@ -227,11 +236,203 @@ int dense_stream_drain(ofps_hip_ctx* ctx) {
     return OFPS_HIP_OK;
 }
 
-// One frame of the dense decoders' stream.  tail == nullptr: ofps_hip_lk_push_frame_async, the records go straight to the ticket's block.
-// tail != nullptr: ofps_hip_lk_push_frame_fused_async -- the records and their count are kept in device memory (S_DENSE_REC), copied to
+// One dense_push call, step by step: claim -> reserve -> upload -> [decode -> tail] -> commit, the names of pipeline.hip's Push and BatchPush.
+// Every step enqueues or returns an error; none touches the ring (commit does, last), and none but commit writes the ticket, with one exception
+// where it always was: t.isl, armed at the end of upload() in front of the tail that takes it.  claim() refuses before anything is uploaded.
+// There is no read_back step: the kernels store into the ticket's block (its device address), the fused form's copy launch included.
+// prm == nullptr: ofps_hip_lk_push_frame_async, the records go straight to the ticket's block.
+// prm != nullptr: ofps_hip_lk_push_frame_fused_async -- the records and their count are kept in device memory (S_DENSE_REC), copied to
 // the block from there, and the detector and / or the estimator run on them behind the decoder, the count staying on the device.
 // Everything of a ticket is enqueued on the compute stream: ticket k's tail has read the records (and detect_device's / almeida's workspaces
 // are free again) before ticket k + 1's output stage writes them -- stream order is the join, no per-ticket copy of the tail's inputs.
+struct DensePush {
+    ofps_hip_ctx* ctx;
+    const uint8_t* frame; int W, H, stride, levels, radius, iters, max_w, max_h; unsigned flags;
+    const ofps_hip_frame_params* prm; int dim;           // dim: the detector's field, 0 when it does not run
+    const char* who;
+    static constexpr int kSlots = ofps::DenseStream::kSlots, kTickets = ofps::DenseStream::kTickets;
+    ofps::DenseStream& ds = ctx->dense;
+    hipStream_t s = ctx->stream;
+    const long tno = ds.ring.next;
+    ofps::DenseStream::Ticket& t = ds.ring.at(tno);
+    DenseGrid g;
+    size_t px = 0, raw_bytes = 0;        // the ring holds the frames the flow reads (reduced / converted)
+    bool other_pending = false;
+    uint8_t* d_frames = nullptr; uint8_t* d_raw_all = nullptr;
+    int slot = 0;
+    const uint8_t* d_mask_ready = nullptr;
+    long frames_after = 0;
+    ofps::DenseBlock blk{0, false, 0};   // the ticket's block ...
+    char* base = nullptr;                // ... and its device address
+    const float4* d_rec = nullptr;       // the records and their count in device memory: what the fused form's copy and tail read
+    const uint32_t* d_cnt = nullptr;
+
+    int claim() {
+        // (a stream's first frame runs no flow: the flow's parameters -- Farneback's own limits included -- are refused here, not one frame later)
+        int rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, who, &g);
+        if (rc != OFPS_HIP_OK) return rc;
+        OFPS_REQUIRE(ctx, !t.pending, "%s: ticket %ld has not been collected (at most %d frames in flight)", who,
+                     tno - kTickets, kTickets);
+        px = (size_t)g.fw * g.fh; raw_bytes = g.raw_row * (size_t)H;
+        // A new geometry restarts the stream and may reallocate the ring.  With a ticket in flight that would throw its records away
+        // (draining marks it collected: the caller's later lk_frame_wait would fail with "already collected"): refused, like the
+        // multi-device form does -- collect first, or ofps_hip_lk_reset.
+        other_pending = ds.ring.other_pending();
+        // (so does a change of the front-end -- "Process Fullres" flipped, another pixel format: the ring's frames are the other mode's; cv-decoder
+        // returns Ok(false) for that frame because gray and old_gray differ in size, cv-decoder/src/lib.rs:156-158)
+        const bool restart = ds.w != W || ds.h != H || ds.fw != g.fw || ds.fh != g.fh || ds.fmt != g.fmt ||
+                             ctx->scratch[ofps::S_LK_FRAMES].cap < kSlots * px ||
+                             (g.frontend && ctx->scratch[ofps::S_FE_RAW].cap < kTickets * raw_bytes);
+        OFPS_REQUIRE(ctx, !(restart && other_pending), "%s: geometry change %dx%d -> %dx%d with a ticket in flight "
+                     "(collect it with ofps_hip_lk_frame_wait first)", who, ds.w, ds.h, W, H);
+        // hip_flow expands a new frame ahead of its pair, into the plane slot of the oldest frame of THIS parameter set: other Farneback parameters
+        // re-plan the workspace (other layers), which a flow still in flight would be reading -- refused like a geometry change
+        const bool fb_params_changed = g.farneback && ds.fb_params_valid && (ds.fb_levels != levels || ds.fb_radius != radius);
+        OFPS_REQUIRE(ctx, !(fb_params_changed && other_pending), "%s: Farneback parameters changed (levels %d -> %d, radius %d -> %d) with a "
+                     "ticket in flight (collect it with ofps_hip_lk_frame_wait first)", who, ds.fb_levels, levels, ds.fb_radius, radius);
+        if (g.farneback) { ds.fb_params_valid = true; ds.fb_levels = levels; ds.fb_radius = radius; }
+        if (restart) {
+            rc = dense_stream_drain(ctx);
+            if (rc != OFPS_HIP_OK) return rc;
+            ds.w = W; ds.h = H; ds.fw = g.fw; ds.fh = g.fh; ds.fmt = g.fmt;
+            ctx->fb.prev_flow.valid = false;
+        }
+        return OFPS_HIP_OK;
+    }
+
+    // only these two scratch() calls: a reallocation synchronises, so none may move across an enqueue
+    int reserve() {
+        // the stream's frames have slots of their own: no other entry point (lk_decode, lk_flow, sad_flow, contrast_mask stage
+        // their frames in S_FRAMES) can overwrite or reallocate a previous frame behind the stream's back.  Three slots: frame
+        // k + 1 is uploaded (copy stream) into the slot of frame k - 2, whose last reader -- ticket k - 1 -- has been collected
+        // by the time a third push is accepted.
+        d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_LK_FRAMES, kSlots * px));
+        // the arriving frame of a stream with a front-end is staged per ticket in flight (the ticket's upload + front-end run on one stream; the
+        // buffer's previous user, ticket tno - 2, has been collected)
+        d_raw_all = g.frontend ? static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FE_RAW, kTickets * raw_bytes)) : nullptr;
+        if (!d_frames || (g.frontend && !d_raw_all)) return OFPS_HIP_ENOMEM;
+        if (ds.frames_gen != ctx->scratch[ofps::S_LK_FRAMES].gen) {         // (re)allocated: whatever was there is gone
+            ds.frames_gen = ctx->scratch[ofps::S_LK_FRAMES].gen;
+            ds.frames = 0;
+        }
+        return OFPS_HIP_OK;
+    }
+
+    int upload() {
+        // with another ticket in flight the upload goes to the copy stream and overlaps that ticket's flow; a lone frame is
+        // copied on the compute stream itself (no cross-stream event on the latency path of the synchronous call)
+        const bool overlap = other_pending;
+        slot = (int)(ds.frames % kSlots);
+        hipStream_t up = overlap ? ds.copy_stream : s;
+        ds.slot_id[slot] = ++ds.frame_serial;               // (a new id for whatever is in the slot now, also if the push fails below)
+        int rc = dense_upload_frame(ctx, g, frame, W, H, stride, d_raw_all ? d_raw_all + (size_t)(tno % kTickets) * raw_bytes : nullptr,
+                                    d_frames + (size_t)slot * px, up);
+        if (rc != OFPS_HIP_OK) return rc;
+        // cv-decoder's contrast mask depends on the new frame only: it is made right behind the upload, on the upload's stream -- with
+        // another ticket in flight that is beside that ticket's flow instead of after this one's (one mask buffer per ticket in flight)
+        if (g.use_mask && ds.frames + 1 >= 2) {
+            auto* masks = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_LK_MASKS, (size_t)kTickets * px));
+            if (!masks) return OFPS_HIP_ENOMEM;
+            uint8_t* m = masks + (size_t)(tno % kTickets) * px;
+            rc = ofps::contrast_mask_device(ctx, d_frames + (size_t)slot * px, g.fw, g.fh, g.fw, m, up);
+            if (rc != OFPS_HIP_OK) return rc;
+            d_mask_ready = m;
+        }
+        // hip_flow: the new frame's pyramid + polynomial expansion depend on that frame only, like the mask: made here, behind the upload on the
+        // upload's stream -- with another ticket in flight beside that ticket's flow, whose coarse layers (a chain of dependent round trips) leave
+        // most of the device idle (farneback.hip: farneback_prepare_device; the pair's flow below finds the planes by the frame's id)
+        if (g.farneback && ctx->opt.fb_prepare_ahead) {
+            rc = ofps::farneback_prepare_device(ctx, d_frames + (size_t)slot * px, g.fw, g.fh, g.fw, levels, 2 * radius + 1, 7, 1.5, ds.slot_id[slot], up);
+            if (rc != OFPS_HIP_OK) return rc;
+        }
+        if (overlap) {
+            OFPS_HIP_TRY(ctx, hipEventRecord(t.uploaded, up));
+            OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, t.uploaded, 0));       // everything of this ticket on the compute stream comes after the upload
+            if (g.farneback) ofps::farneback_mark_ordered(ctx, s);         // ... the new frame's pyramid + expansion included
+        }
+        // the stream position and the ticket change only once everything is enqueued: a failure below leaves both as they were (the
+        // frame's slot is simply uploaded again by the next push) -- ADVICE r4
+        frames_after = ds.frames + 1;
+        // ... but for what holds whether or not a pair follows, the ticket's islands
+        if (prm) ofps::islands_ticket_arm(ctx, &t.isl, prm, 1, ofps::TRK_DENSE, /*restart=*/frames_after < 2);     // A5i, A5t: the ticket follows the context's max_islands and max_tracks at this push
+        else t.isl.K = 0;
+        return OFPS_HIP_OK;
+    }
+
+    // the pair (frame k - 1, frame k) -> the records and their count in the ticket's block; fused: in device memory (d_rec, d_cnt) and from there,
+    // by one copy launch in front of the tail, in the block
+    int decode() {
+        blk = {g.max_records, prm != nullptr, dim};
+        int rc = ofps::host_block_reserve(ctx, &t.pinned, &t.pinned_cap, blk.bytes());
+        if (rc != OFPS_HIP_OK) return rc;
+        void* mapped = nullptr;
+        OFPS_REQUIRE(ctx, ofps::device_address_of(t.pinned, &mapped), "%s: page-locked block is not device-addressable", who);
+        base = static_cast<char*>(mapped);
+        const int prev_slot = (int)((frames_after - 2) % kSlots);
+        float4* rec_dst = blk.records(base);
+        uint32_t* cnt_dst = blk.count(base);
+        if (prm) {
+            // the tail reads records and count from DEVICE memory, not back over PCIe: the output stage stores there, and one copy kernel
+            // (bounded by the count it reads on the device) fills the block
+            const ofps::DenseBlock dev{g.max_records, false, 0};
+            char* d_rec_blk = static_cast<char*>(ofps::scratch(ctx, ofps::S_DENSE_REC, dev.bytes()));
+            if (!d_rec_blk) return OFPS_HIP_ENOMEM;
+            rec_dst = dev.records(d_rec_blk);
+            cnt_dst = dev.count(d_rec_blk);
+        }
+        // N3p: with the setting on the stream keeps each pair's raw slots, two buffers that alternate by pair (per stream, not per ticket: the
+        // track launches of two tickets in flight run on the one compute stream, in order).  Pair k reads pair k - 1's if that pair wrote them
+        // on this lattice under these flags; a pair pushed with the setting off writes none, so its successor starts from zero
+        ofps::DenseStream::KltPred& kp = ds.klt_pred;
+        int* klt_slots = nullptr;
+        const int* klt_prev_slots = nullptr;
+        const bool predict = g.sparse && ctx->opt.klt_prediction;
+        if (predict) {
+            const size_t half = (g.max_records * 6 * sizeof(int) + 255) & ~(size_t)255;
+            auto* d_pred = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_PRED, 2 * half));
+            if (!d_pred) return OFPS_HIP_ENOMEM;
+            const uint64_t gen = ctx->scratch[ofps::S_KLT_PRED].gen;
+            if (kp.valid && kp.pair == frames_after - 1 && kp.fw == g.fw && kp.fh == g.fh && kp.cell == ctx->opt.klt_cell && kp.flags == flags && kp.gen == gen)
+                klt_prev_slots = reinterpret_cast<const int*>(d_pred + (size_t)(kp.pair & 1) * half);
+            klt_slots = reinterpret_cast<int*>(d_pred + (size_t)(frames_after & 1) * half);
+        }
+        kp.valid = false;                                    // (until this pair has enqueued everything)
+        const DenseRecords at = dense_enqueue_frame(ctx, {d_frames + (size_t)prev_slot * px, d_frames + (size_t)slot * px, ds.slot_id[prev_slot], ds.slot_id[slot],
+                                                          g.fw, g.fh, levels, radius, iters, g, rec_dst, cnt_dst, /*in_place=*/prm != nullptr, d_mask_ready,
+                                                          klt_slots, klt_prev_slots});
+        if (at.rc != OFPS_HIP_OK) return at.rc;
+        if (predict) kp = {true, frames_after, g.fw, g.fh, ctx->opt.klt_cell, flags, ctx->scratch[ofps::S_KLT_PRED].gen};
+        d_rec = at.rec; d_cnt = at.cnt;
+        if (prm) {
+            const unsigned copy_blocks = (unsigned)((g.max_records + 255) / 256 < 1024 ? (g.max_records + 255) / 256 : 1024);
+            hipLaunchKernelGGL(dense_copy_records_kernel, dim3(copy_blocks ? copy_blocks : 1), dim3(256), 0, s, d_rec,
+                               blk.records(base), d_cnt, g.max_records, blk.count(base));
+            OFPS_HIP_TRY(ctx, hipGetLastError());
+        }
+        return OFPS_HIP_OK;
+    }
+
+    // the 32 bytes the caller waits for -- island result, quaternion -- and the island's field are stored by the detector's and the
+    // estimator's last kernels straight into the ticket's block, as pipeline.hip does.  The tail (tail.hip) in its device-count form,
+    // sized from the capacity, on this one stream; with detect-compensation 1 its detector reads compensated records in a slot of
+    // their own: d_rec is what decode()'s copy reads
+    int tail() {
+        return ofps::frame_tail_device(ctx, d_rec, g.max_records, 1, d_cnt, /*lsq_min_n=*/0, prm, prm->seed, /*may_compensate=*/true,
+                                       blk.result(base), blk.quat(base), blk.field(base), nullptr, nullptr, &t.isl);
+    }
+
+    int commit(int* ticket) {
+        OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
+        ds.frames = frames_after;
+        t.have_vectors = frames_after >= 2; t.gw = g.gw; t.gh = g.gh; t.max_records = g.max_records;       // cv-decoder/src/lib.rs:156-158: flow needs two frames
+        t.fused = prm ? 1 : 0; t.run_detector = prm ? prm->run_detector : 0; t.run_estimator = prm ? prm->run_estimator : 0;
+        t.dim = dim;
+        *ticket = ds.ring.commit();
+        return OFPS_HIP_OK;
+    }
+};
+
+// One frame of the dense decoders' stream, ofps_hip_lk_push_frame[_fused][_async]: the refusals that need no stream, then DensePush's steps
 int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride, int levels, int radius, int iters, int max_w, int max_h,
                unsigned flags, const ofps_hip_frame_params* tail, int* ticket, const char* who) {
     if (!ctx) return OFPS_HIP_EINVAL;
@@ -260,160 +461,15 @@ int dense_push(ofps_hip_ctx* ctx, const uint8_t* frame, int W, int H, int stride
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = dense_stream_setup(ctx);
     if (rc != OFPS_HIP_OK) return rc;
-    ofps::DenseStream& ds = ctx->dense;
-    constexpr int kSlots = ofps::DenseStream::kSlots, kTickets = ofps::DenseStream::kTickets;
-    DenseGrid g;
-    // (a stream's first frame runs no flow: the flow's parameters -- Farneback's own limits included -- are refused here, not one frame later)
-    rc = dense_grid_of(ctx, W, H, stride, max_w, max_h, flags, levels, radius, iters, who, &g);
-    if (rc != OFPS_HIP_OK) return rc;
-    const long tno = ds.ring.next;
-    auto& t = ds.ring.at(tno);
-    OFPS_REQUIRE(ctx, !t.pending, "%s: ticket %ld has not been collected (at most %d frames in flight)", who,
-                 tno - kTickets, kTickets);
-    const size_t px = (size_t)g.fw * g.fh, raw_bytes = g.raw_row * (size_t)H;      // the ring holds the frames the flow reads (reduced / converted)
-    // A new geometry restarts the stream and may reallocate the ring.  With a ticket in flight that would throw its records away
-    // (draining marks it collected: the caller's later lk_frame_wait would fail with "already collected"): refused, like the
-    // multi-device form does -- collect first, or ofps_hip_lk_reset.
-    const bool other_pending = ds.ring.other_pending();
-    // (so does a change of the front-end -- "Process Fullres" flipped, another pixel format: the ring's frames are the other mode's; cv-decoder
-    // returns Ok(false) for that frame because gray and old_gray differ in size, cv-decoder/src/lib.rs:156-158)
-    const bool restart = ds.w != W || ds.h != H || ds.fw != g.fw || ds.fh != g.fh || ds.fmt != g.fmt ||
-                         ctx->scratch[ofps::S_LK_FRAMES].cap < kSlots * px ||
-                         (g.frontend && ctx->scratch[ofps::S_FE_RAW].cap < kTickets * raw_bytes);
-    OFPS_REQUIRE(ctx, !(restart && other_pending), "%s: geometry change %dx%d -> %dx%d with a ticket in flight "
-                 "(collect it with ofps_hip_lk_frame_wait first)", who, ds.w, ds.h, W, H);
-    // hip_flow expands a new frame ahead of its pair, into the plane slot of the oldest frame of THIS parameter set: other Farneback parameters
-    // re-plan the workspace (other layers), which a flow still in flight would be reading -- refused like a geometry change
-    const bool fb_params_changed = g.farneback && ds.fb_params_valid && (ds.fb_levels != levels || ds.fb_radius != radius);
-    OFPS_REQUIRE(ctx, !(fb_params_changed && other_pending), "%s: Farneback parameters changed (levels %d -> %d, radius %d -> %d) with a "
-                 "ticket in flight (collect it with ofps_hip_lk_frame_wait first)", who, ds.fb_levels, levels, ds.fb_radius, radius);
-    if (g.farneback) { ds.fb_params_valid = true; ds.fb_levels = levels; ds.fb_radius = radius; }
-    if (restart) {
-        rc = dense_stream_drain(ctx);
-        if (rc != OFPS_HIP_OK) return rc;
-        ds.w = W; ds.h = H; ds.fw = g.fw; ds.fh = g.fh; ds.fmt = g.fmt;
-        ctx->fb.prev_flow.valid = false;
+    DensePush p{ctx, frame, W, H, stride, levels, radius, iters, max_w, max_h, flags, tail, dim, who};
+    rc = p.claim();                                     // refused before anything is uploaded
+    if (rc == OFPS_HIP_OK) rc = p.reserve();
+    if (rc == OFPS_HIP_OK) rc = p.upload();
+    if (rc == OFPS_HIP_OK && p.frames_after >= 2) {     // cv-decoder/src/lib.rs:156-158: flow needs two frames
+        rc = p.decode();
+        if (rc == OFPS_HIP_OK && tail) rc = p.tail();
     }
-    // the stream's frames have slots of their own: no other entry point (lk_decode, lk_flow, sad_flow, contrast_mask stage
-    // their frames in S_FRAMES) can overwrite or reallocate a previous frame behind the stream's back.  Three slots: frame
-    // k + 1 is uploaded (copy stream) into the slot of frame k - 2, whose last reader -- ticket k - 1 -- has been collected
-    // by the time a third push is accepted.
-    auto* d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_LK_FRAMES, kSlots * px));
-    // the arriving frame of a stream with a front-end is staged per ticket in flight (the ticket's upload + front-end run on one stream; the
-    // buffer's previous user, ticket tno - 2, has been collected)
-    auto* d_raw_all = g.frontend ? static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FE_RAW, kTickets * raw_bytes)) : nullptr;
-    if (!d_frames || (g.frontend && !d_raw_all)) return OFPS_HIP_ENOMEM;
-    if (ds.frames_gen != ctx->scratch[ofps::S_LK_FRAMES].gen) {         // (re)allocated: whatever was there is gone
-        ds.frames_gen = ctx->scratch[ofps::S_LK_FRAMES].gen;
-        ds.frames = 0;
-    }
-    hipStream_t s = ctx->stream;
-    // with another ticket in flight the upload goes to the copy stream and overlaps that ticket's flow; a lone frame is
-    // copied on the compute stream itself (no cross-stream event on the latency path of the synchronous call)
-    const bool overlap = other_pending;
-    const int slot = (int)(ds.frames % kSlots);
-    hipStream_t up = overlap ? ds.copy_stream : s;
-    ds.slot_id[slot] = ++ds.frame_serial;               // (a new id for whatever is in the slot now, also if the push fails below)
-    rc = dense_upload_frame(ctx, g, frame, W, H, stride, d_raw_all ? d_raw_all + (size_t)(tno % kTickets) * raw_bytes : nullptr,
-                            d_frames + (size_t)slot * px, up);
-    if (rc != OFPS_HIP_OK) return rc;
-    // cv-decoder's contrast mask depends on the new frame only: it is made right behind the upload, on the upload's stream -- with
-    // another ticket in flight that is beside that ticket's flow instead of after this one's (one mask buffer per ticket in flight)
-    const uint8_t* d_mask_ready = nullptr;
-    if (g.use_mask && ds.frames + 1 >= 2) {
-        auto* masks = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_LK_MASKS, (size_t)kTickets * px));
-        if (!masks) return OFPS_HIP_ENOMEM;
-        uint8_t* m = masks + (size_t)(tno % kTickets) * px;
-        rc = ofps::contrast_mask_device(ctx, d_frames + (size_t)slot * px, g.fw, g.fh, g.fw, m, up);
-        if (rc != OFPS_HIP_OK) return rc;
-        d_mask_ready = m;
-    }
-    // hip_flow: the new frame's pyramid + polynomial expansion depend on that frame only, like the mask: made here, behind the upload on the
-    // upload's stream -- with another ticket in flight beside that ticket's flow, whose coarse layers (a chain of dependent round trips) leave
-    // most of the device idle (farneback.hip: farneback_prepare_device; the pair's flow below finds the planes by the frame's id)
-    if (g.farneback && ctx->opt.fb_prepare_ahead) {
-        rc = ofps::farneback_prepare_device(ctx, d_frames + (size_t)slot * px, g.fw, g.fh, g.fw, levels, 2 * radius + 1, 7, 1.5, ds.slot_id[slot], up);
-        if (rc != OFPS_HIP_OK) return rc;
-    }
-    if (overlap) {
-        OFPS_HIP_TRY(ctx, hipEventRecord(t.uploaded, up));
-        OFPS_HIP_TRY(ctx, hipStreamWaitEvent(s, t.uploaded, 0));       // everything of this ticket on the compute stream comes after the upload
-        if (g.farneback) ofps::farneback_mark_ordered(ctx, s);         // ... the new frame's pyramid + expansion included
-    }
-    // the stream position and the ticket change only once everything is enqueued: a failure below leaves both as they were (the
-    // frame's slot is simply uploaded again by the next push) -- ADVICE r4
-    const long frames_after = ds.frames + 1;
-    int have_vectors = 0;
-    if (tail) ofps::islands_ticket_arm(ctx, &t.isl, tail, 1, ofps::TRK_DENSE, /*restart=*/frames_after < 2);     // A5i, A5t: the ticket follows the context's max_islands and max_tracks at this push
-    else t.isl.K = 0;
-    size_t tail_off = 0;
-    if (frames_after >= 2) {                                        // cv-decoder/src/lib.rs:156-158: flow needs two frames
-        const size_t rec_bytes = kBlockHeader + g.max_records * sizeof(float4);
-        tail_off = rec_bytes;
-        rc = ofps::host_block_reserve(ctx, &t.pinned, &t.pinned_cap, rec_bytes + (tail ? kTailField + (size_t)dim * dim * sizeof(float2) : 0));
-        if (rc != OFPS_HIP_OK) return rc;
-        void* mapped = nullptr;
-        OFPS_REQUIRE(ctx, ofps::device_address_of(t.pinned, &mapped), "%s: page-locked block is not device-addressable", who);
-        char* blk = static_cast<char*>(mapped);
-        const int prev_slot = (int)((frames_after - 2) % kSlots);
-        float4* rec_dst = reinterpret_cast<float4*>(blk + kBlockHeader);
-        uint32_t* cnt_dst = reinterpret_cast<uint32_t*>(blk);
-        char* d_rec_blk = nullptr;
-        if (tail) {
-            // the tail reads records and count from DEVICE memory, not back over PCIe: the output stage stores there, and one copy kernel
-            // (bounded by the count it reads on the device) fills the block
-            d_rec_blk = static_cast<char*>(ofps::scratch(ctx, ofps::S_DENSE_REC, rec_bytes));
-            if (!d_rec_blk) return OFPS_HIP_ENOMEM;
-            rec_dst = reinterpret_cast<float4*>(d_rec_blk + kBlockHeader);
-            cnt_dst = reinterpret_cast<uint32_t*>(d_rec_blk);
-        }
-        const float4* d_rec = nullptr;                       // fused form: the records and their count in device memory
-        const uint32_t* d_cnt = nullptr;
-        // N3p: with the setting on the stream keeps each pair's raw slots, two buffers that alternate by pair (per stream, not per ticket: the
-        // track launches of two tickets in flight run on the one compute stream, in order).  Pair k reads pair k - 1's if that pair wrote them
-        // on this lattice under these flags; a pair pushed with the setting off writes none, so its successor starts from zero
-        ofps::DenseStream::KltPred& kp = ds.klt_pred;
-        int* klt_slots = nullptr;
-        const int* klt_prev_slots = nullptr;
-        const bool predict = g.sparse && ctx->opt.klt_prediction;
-        if (predict) {
-            const size_t half = (g.max_records * 6 * sizeof(int) + 255) & ~(size_t)255;
-            auto* d_pred = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_PRED, 2 * half));
-            if (!d_pred) return OFPS_HIP_ENOMEM;
-            const uint64_t gen = ctx->scratch[ofps::S_KLT_PRED].gen;
-            if (kp.valid && kp.pair == frames_after - 1 && kp.fw == g.fw && kp.fh == g.fh && kp.cell == ctx->opt.klt_cell && kp.flags == flags && kp.gen == gen)
-                klt_prev_slots = reinterpret_cast<const int*>(d_pred + (size_t)(kp.pair & 1) * half);
-            klt_slots = reinterpret_cast<int*>(d_pred + (size_t)(frames_after & 1) * half);
-        }
-        kp.valid = false;                                    // (until this pair has enqueued everything)
-        rc = dense_enqueue_frame(ctx, d_frames + (size_t)prev_slot * px, d_frames + (size_t)slot * px, g.fw, g.fh, levels, radius, iters, g,
-                                 rec_dst, cnt_dst, ds.slot_id[prev_slot], ds.slot_id[slot], d_mask_ready, tail ? &d_rec : nullptr,
-                                 tail ? &d_cnt : nullptr, klt_slots, klt_prev_slots);
-        if (rc != OFPS_HIP_OK) return rc;
-        if (predict) kp = {true, frames_after, g.fw, g.fh, ctx->opt.klt_cell, flags, ctx->scratch[ofps::S_KLT_PRED].gen};
-        if (tail) {
-            const unsigned copy_blocks = (unsigned)((g.max_records + 255) / 256 < 1024 ? (g.max_records + 255) / 256 : 1024);
-            hipLaunchKernelGGL(dense_copy_records_kernel, dim3(copy_blocks ? copy_blocks : 1), dim3(256), 0, s, d_rec,
-                               reinterpret_cast<float4*>(blk + kBlockHeader), d_cnt, g.max_records, reinterpret_cast<uint32_t*>(blk));
-            OFPS_HIP_TRY(ctx, hipGetLastError());
-            // the 32 bytes the caller waits for -- island result, quaternion -- and the island's field are stored by the detector's and the
-            // estimator's last kernels straight into the ticket's block, as pipeline.hip does.  The tail (tail.hip) in its device-count form,
-            // sized from the capacity, on this one stream; with detect-compensation 1 its detector reads compensated records in a slot of
-            // their own: d_rec is what the copy above reads
-            rc = ofps::frame_tail_device(ctx, d_rec, g.max_records, 1, d_cnt, /*lsq_min_n=*/0, tail, tail->seed, /*may_compensate=*/true,
-                                         reinterpret_cast<int*>(blk + tail_off + kTailResult), reinterpret_cast<float4*>(blk + tail_off + kTailQuat),
-                                         reinterpret_cast<float2*>(blk + tail_off + kTailField), nullptr, nullptr, &t.isl);
-            if (rc != OFPS_HIP_OK) return rc;
-        }
-        have_vectors = 1;
-    }
-    OFPS_HIP_TRY(ctx, hipEventRecord(t.done, s));
-    ds.frames = frames_after;
-    t.have_vectors = have_vectors; t.gw = g.gw; t.gh = g.gh; t.max_records = g.max_records;
-    t.fused = tail ? 1 : 0; t.run_detector = tail ? tail->run_detector : 0; t.run_estimator = tail ? tail->run_estimator : 0;
-    t.dim = dim; t.tail_off = tail_off;
-    *ticket = ds.ring.commit();
-    return OFPS_HIP_OK;
+    return rc == OFPS_HIP_OK ? p.commit(ticket) : rc;
 }
 
 }  // namespace
@@ -441,12 +497,14 @@ int ofps_hip_lk_decode(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t* cu
     if (rc != OFPS_HIP_OK) return rc;
     // the count and the records come back in ONE page-locked block and one wait; only the visited cells' records reach the
     // caller's buffer
-    rc = ofps::host_block_reserve(ctx, &ctx->dense.decode_pinned, &ctx->dense.decode_pinned_cap, kBlockHeader + g.max_records * sizeof(float4));
+    const ofps::DenseBlock blk{g.max_records, false, 0};
+    rc = ofps::host_block_reserve(ctx, &ctx->dense.decode_pinned, &ctx->dense.decode_pinned_cap, blk.bytes());
     if (rc != OFPS_HIP_OK) return rc;
     void* mapped = nullptr;
     OFPS_REQUIRE(ctx, ofps::device_address_of(ctx->dense.decode_pinned, &mapped), "lk_decode: page-locked block is not device-addressable");
-    rc = dense_enqueue_frame(ctx, d_frames, d_frames + px, g.fw, g.fh, levels, radius, iters, g, reinterpret_cast<float4*>(static_cast<char*>(mapped) + kBlockHeader),
-                             static_cast<uint32_t*>(mapped));
+    char* base = static_cast<char*>(mapped);
+    rc = dense_enqueue_frame(ctx, {d_frames, d_frames + px, 0, 0, g.fw, g.fh, levels, radius, iters, g, blk.records(base), blk.count(base), /*in_place=*/false,
+                                   nullptr, nullptr, nullptr}).rc;
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     dense_collect(ctx->dense.decode_pinned, g.max_records, out_entries, n_out);
@@ -505,18 +563,18 @@ int ofps_hip_lk_frame_fused_wait(ofps_hip_ctx* ctx, int ticket, ofps_hip_frame_r
     OFPS_HIP_TRY(ctx, hipEventSynchronize(t->done));
     t->pending = false;
     // identity / no motion: a stream's first frame, a plain ticket, a stage that did not run
-    const char* blk = static_cast<const char*>(t->pinned);
-    const char* tail = t->have_vectors && t->fused ? blk + t->tail_off : nullptr;
+    const ofps::DenseBlock blk{t->max_records, t->have_vectors && t->fused, t->dim};
+    char* base = static_cast<char*>(t->pinned);
     uint32_t cnt = 0;
-    if (t->have_vectors) memcpy(&cnt, blk, sizeof(cnt));
+    if (t->have_vectors) memcpy(&cnt, blk.count(base), sizeof(cnt));
     if (cnt > t->max_records) cnt = (uint32_t)t->max_records;
-    ofps::fill_frame_result(out, t->have_vectors, cnt, tail && t->run_detector ? tail + kTailResult : nullptr, tail && t->run_estimator ? tail + kTailQuat : nullptr);
+    ofps::fill_frame_result(out, t->have_vectors, cnt, t->run_detector ? blk.result(base) : nullptr, t->run_estimator ? blk.quat(base) : nullptr);
     if (out_w) *out_w = t->gw;
     if (out_h) *out_h = t->gh;
     const int isl_rc = ofps::islands_collect(ctx, t->isl);             // (a plain ticket: none)
     if (isl_rc != OFPS_HIP_OK) return isl_rc;
-    if (out_entries && cnt) memcpy(out_entries, blk + kBlockHeader, (size_t)cnt * sizeof(float4));
-    if (tail && t->run_detector && out_field) memcpy(out_field, tail + kTailField, (size_t)t->dim * t->dim * sizeof(float2));
+    if (out_entries && cnt) memcpy(out_entries, blk.records(base), (size_t)cnt * sizeof(float4));
+    if (blk.fused && t->run_detector && out_field) memcpy(out_field, blk.field(base), (size_t)t->dim * t->dim * sizeof(float2));
     return OFPS_HIP_OK;
 }
 

@@ -715,7 +715,7 @@ int klt_pyramid_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int lev
         b->prev_pitch[l] = b->cur_pitch[l] = 0;
         if (l >= levels) continue;
         lv->W[l] = lv->W[l - 1] >> 1; lv->H[l] = lv->H[l - 1] >> 1;
-        lv->stride[l] = (lv->W[l] + 63) & ~63;
+        lv->stride[l] = ofps::padded_stride(lv->W[l]);
         off[l] = bytes; bytes += (size_t)total * lv->stride[l] * lv->H[l];
     }
     if (levels == 1) return OFPS_HIP_OK;
@@ -947,7 +947,7 @@ int ofps_hip_klt_features(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, 
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const KltSettings s = klt_settings(ctx);
     const size_t ns = klt_slots(W, H, s.cell);
-    const int ss = (W + 63) & ~63;
+    const int ss = ofps::padded_stride(W);
     auto* d_img = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)ss * H));
     auto* d_out = static_cast<int*>(ofps::scratch(ctx, ofps::S_KLT_HOST, ns * 3 * sizeof(int)));
     if (!d_img || !d_out) return OFPS_HIP_ENOMEM;
@@ -996,7 +996,7 @@ static int klt_track_host_impl(ofps_hip_ctx* ctx, const uint8_t* prev, const uin
                      "klt_track_from: guess %zu = (%d, %d) lies beyond +-2^23", k, guesses[2 * k], guesses[2 * k + 1]);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return OFPS_HIP_OK;
-    const int ss = (W + 63) & ~63;
+    const int ss = ofps::padded_stride(W);
     const size_t fb = (size_t)ss * H, o_quad = pad16(n * 2 * sizeof(int)), o_guess = o_quad + n * 4 * sizeof(int);
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
     auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_guess + (guesses ? n * 2 * sizeof(int) : 0)));
@@ -1128,7 +1128,7 @@ int ofps_hip_klt_flow_from(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8_t
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
-    const int ss = (W + 63) & ~63;
+    const int ss = ofps::padded_stride(W);
     const size_t fb = (size_t)ss * H;
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * fb));
     const KltHostIo io(ctx, 1, ns, prev_slots != nullptr);
@@ -1198,7 +1198,7 @@ static int klt_flow_batch_host_impl(ofps_hip_ctx* ctx, const uint8_t* frames, in
     const size_t ns = klt_slots(W, H, ctx->opt.klt_cell);
     OFPS_REQUIRE(ctx, (unsigned long long)pairs * ns < (1ull << 31), "klt_flow_batch: %d pairs of %zu slots (pairs * slots must stay below 2^31)", pairs, ns);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int ss = (W + 63) & ~63;
+    const int ss = ofps::padded_stride(W);
     const size_t fb = (size_t)ss * H;
     auto* d_fr = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)n_frames * fb));
     const KltHostIo io(ctx, pairs, ns, prev_slots != nullptr);

@@ -261,7 +261,7 @@ int ofps_hip_klt_activity(ofps_hip_ctx* ctx, const uint8_t* luma, int W, int H, 
                      "klt_activity: point %zu = (%d, %d) lies outside the %d x %d frame", k, points[2 * k], points[2 * k + 1], W, H);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return OFPS_HIP_OK;
-    const int ss = (W + 63) & ~63;
+    const int ss = ofps::padded_stride(W);
     const size_t o_out = (n * 2 * sizeof(int) + 15) & ~size_t(15);
     auto* d_img = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)ss * H));
     auto* d_io = static_cast<char*>(ofps::scratch(ctx, ofps::S_KLT_HOST, o_out + n * sizeof(uint32_t)));

@@ -473,7 +473,7 @@ int sad_hier_pairs_device(ofps_hip_ctx* ctx, const SadFrames& f, int pairs, int 
     lv[0] = f;
     for (int l = 1; l < levels; ++l) {                       // the geometry; the bases follow the reservation
         lv[l].W = lv[l - 1].W >> 1; lv[l].H = lv[l - 1].H >> 1;
-        lv[l].stride = (lv[l].W + 63) & ~63;                 // 64-byte rows, so 16-byte frame pitches: the top search gets the strip kernel
+        lv[l].stride = ofps::padded_stride(lv[l].W);         // 64-byte rows, so 16-byte frame pitches: the top search gets the strip kernel
         pyr_off[l] = pyr_bytes; pyr_bytes += (size_t)(sets.nprev + sets.ncur) * lv[l].stride * lv[l].H;
         best_off[l] = best_bytes;
         best_bytes += (((size_t)pairs * (lv[l].W / block) * (lv[l].H / block) * 3 * sizeof(int)) + 255) & ~size_t(255);
@@ -550,7 +550,7 @@ int ofps_hip_sad_down2(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, int 
     OFPS_REQUIRE(ctx, W >= 2 && H >= 2 && stride >= W && dst_stride >= (W >> 1), "sad_down2: bad geometry W=%d H=%d stride=%d dst_stride=%d", W, H,
                  stride, dst_stride);
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int Wo = W >> 1, Ho = H >> 1, ss = (W + 63) & ~63, ds = (Wo + 63) & ~63;
+    const int Wo = W >> 1, Ho = H >> 1, ss = ofps::padded_stride(W), ds = ofps::padded_stride(Wo);
     auto* d_src = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)ss * H));
     auto* d_dst = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_HIER_PYR, (size_t)ds * Ho));
     if (!d_src || !d_dst) return OFPS_HIP_ENOMEM;
@@ -590,7 +590,7 @@ int ofps_hip_sad_refine_pred(ofps_hip_ctx* ctx, const uint8_t* prev, const uint8
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // repack to a 64-byte-multiple device stride so any host stride is accepted (as ofps_hip_sad_flow does)
-    const int dstride = (W + 63) & ~63;
+    const int dstride = ofps::padded_stride(W);
     const size_t pitch = (size_t)dstride * H, nblk = ofps_hip_sad_block_count(W, H, block), npar = (size_t)nbx_parent * nby_parent;
     auto* d_frames = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, 2 * pitch));
     auto* d_ent = static_cast<float*>(ofps::scratch(ctx, ofps::S_ENTRIES, nblk * 4 * sizeof(float)));

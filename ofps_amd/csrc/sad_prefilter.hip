@@ -189,7 +189,7 @@ int sad_prefilter_device(ofps_hip_ctx* ctx, const uint8_t* src, size_t src_pitch
 // written and read on ctx->stream only, anew by every search, which that stream orders.
 int sad_prefilter_pairs_device(ofps_hip_ctx* ctx, int radius, const SadFrames& f, int pairs, SadFrames* filtered) {
     const SadFrames::Sets sets = f.sets(pairs);
-    const int fstride = (f.W + 63) & ~63;
+    const int fstride = ofps::padded_stride(f.W);
     const size_t fpitch = (size_t)fstride * f.H;
     auto* buf = static_cast<uint8_t*>(scratch(ctx, S_SAD_PREF, (size_t)(sets.nprev + sets.ncur) * fpitch));
     if (!buf) return OFPS_HIP_ENOMEM;
@@ -226,7 +226,7 @@ int ofps_hip_sad_prefilter(ofps_hip_ctx* ctx, const uint8_t* src, int W, int H, 
     int rc = prefilter_check(ctx, src, dst, W, H, stride, radius, dst_stride);
     if (rc != OFPS_HIP_OK) return rc;
     OFPS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int ds = (W + 63) & ~63;                               // both sides repacked to 64-byte rows, so any host stride is accepted
+    const int ds = ofps::padded_stride(W);                       // both sides repacked to 64-byte rows, so any host stride is accepted
     auto* d_src = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_FRAMES, (size_t)ds * H));
     auto* d_dst = static_cast<uint8_t*>(ofps::scratch(ctx, ofps::S_SAD_PREF, (size_t)ds * H));
     if (!d_src || !d_dst) return OFPS_HIP_ENOMEM;

@@ -80,6 +80,23 @@ def test_the_motion_pairs_constrain_detector_and_estimators_at_every_cap(cap, re
     assert len(half) < len(fc.records(*fc.MOTION_PAIRS[0], cap, reduced)[0])
 
 
+def test_the_refusal_stream_frames_give_counts_between_zero_and_capacity():
+    """tests/test_stream_refusal_gpu.py's dense forms push texture, halfflat, move0, move1, movehalf, halfflat: the oracle's record counts of
+    the five pairs, so that three of five items lie strictly between 0 and the capacity and none is empty"""
+    kinds = ("texture", "halfflat", "move0", "move1", "movehalf", "halfflat")
+    pairs = list(zip(kinds, kinds[1:]))
+    for cap, reduced, farneback, params, capacity, want in (((24, 24), False, False, fc.LK, 312, (149, 312, 311, 169, 149)),
+                                                           ((24, 24), False, True, fc.FB, 312, (149, 312, 311, 169, 149)),
+                                                           ((150, 150), True, False, fc.LK, 12600, (6179, 12600, 12600, 6853, 6179))):
+        got = []
+        for a, b in pairs:
+            rec, grid = fc.records(a, b, cap, reduced, farneback, params)
+            assert grid[0] * grid[1] == capacity
+            got.append(len(rec))
+        assert tuple(got) == want, (cap, reduced, farneback, got)
+        assert sum(0 < n < capacity for n in got) >= 3 and min(got) > 0
+
+
 def test_a_large_refit_set_behind_more_than_8192_samples():
     """the device-count refit route of RANSAC (more than 8,192 samples -> cluster / stepped solver with the inlier count on the device) is
     compared on refit sets of thousands of records with an answer that is not the identity"""
